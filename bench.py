@@ -153,6 +153,36 @@ def n50_of(fasta_bytes):
     return None
 
 
+DUMP_SAMPLE = 4 << 20      # --dump-outputs: values kept of an output kind longer than this (three kinds as float32: 48 MB, under the 64 MB the dump may take)
+DUMP_BLOCK = 1 << 16       # --dump-outputs: bytes per block sum
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: outputs = {kind: {unit: uint8 buffer}}, what the last timed step delivered.  Per kind, the units' bytes in unit order are
+    written as float32 to <kind>.npy (longer than DUMP_SAMPLE: the bytes at DUMP_SAMPLE sorted positions drawn by numpy's default_rng(<kind's index>)
+    over the whole length), and the float64 sums of their DUMP_BLOCK-byte blocks to <kind>_block_sums.npy, so that no byte goes unseen.  lengths.npy
+    (float64, one row per unit: unit, then the byte length of every kind in the order of `outputs`, -1 where this rank does not hold it)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    units = sorted(set().union(*outputs.values()))
+    lengths = np.full((len(units), 1 + len(outputs)), -1.0)
+    lengths[:, 0] = units
+    for i, (kind, per_unit) in enumerate(outputs.items()):
+        parts = [np.frombuffer(memoryview(per_unit[uu]), dtype=np.uint8) for uu in units if uu in per_unit]
+        for r, uu in enumerate(units):
+            if uu in per_unit:
+                lengths[r, 1 + i] = len(memoryview(per_unit[uu]))
+        b = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+        if len(b) > DUMP_SAMPLE:
+            sample = b[np.sort(np.random.default_rng(i).integers(0, len(b), DUMP_SAMPLE))]
+        else:
+            sample = b
+        np.save(os.path.join(out_dir, kind + ".npy"), sample.astype(np.float32))
+        pad = np.zeros(-len(b) % DUMP_BLOCK, np.uint8)
+        np.save(os.path.join(out_dir, kind + "_block_sums.npy"), np.concatenate([b, pad]).reshape(-1, DUMP_BLOCK).sum(axis=1, dtype=np.int64).astype(np.float64))
+    np.save(os.path.join(out_dir, "lengths.npy"), lengths)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -197,7 +227,12 @@ def main():
     ap.add_argument("--cpu-sample-pairs", type=int, default=200000, help="pairs in the bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--workdir", default=os.environ.get("AGX_BENCH_DIR", "/tmp/agx_bench"))
     ap.add_argument("--keep", action="store_true", help="keep the generated inputs (a later run with the same configuration re-uses them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one delivered as DIR/<kind>.npy (bench.py dump_outputs): the extended contigs of every unit, and the "
+                         "initial and pre-extended contigs of rank 0's units (at N = 1 all of them).  The inputs are seeded: two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import aligngraph_amd as A
@@ -484,6 +519,10 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     cpu_s_per_step = (time.process_time() - cpu0) / max(1, args.steps)      # every thread of this process (walkers, helpers, the runtime's), user + system
+    last_step = None
+    if args.dump_outputs and rank == 0:      # what the last timed step delivered, copied now (the same-configuration leg below runs the units again)
+        last_step = {"initial": {uu: r.bytes("initial") for uu, r in held.items()}, "pre_extended": {uu: r.bytes("pre") for uu, r in held.items()},
+                     "extended": {uu: bytes(v) for uu, v in gathered.items()}}
     if thr0 is not None and rank == 0:
         by_name = {}
         for tid, (name, sec) in thread_cpu().items():
@@ -601,6 +640,8 @@ def main():
         outs = {uu: bytes(v) for uu, v in gathered.items()}
         assert sorted(outs) == (sorted(mine) if emu else list(range(n_units))), "the gather did not deliver every unit"
         all_ext = b"".join(outs[uu] for uu in sorted(outs))
+        if last_step is not None:
+            dump_outputs(args.dump_outputs, last_step)
         reads_per_step = 2.0 * (sam_pairs_total if emu else pairs)
         sec_per_step = elapsed / args.steps
         value = reads_per_step / sec_per_step

@@ -16,15 +16,27 @@ def test_oracle_reproduces_reference_outputs(golden, built):
                 assert got[key] == exp[key], "%s cov=%d unit=%d %s differs from the reference" % (golden.name, cov, u, key)
 
 
-@pytest.mark.skipif(not H.have_reference(), reason="oracle/_ref not built (no /root/reference on this machine)")
+FRESH_SEED = dict(seed=4242, chroms="30000,20000", part=2, pairs=8000, coverage=5, contig_min=800, contig_max=4000, read_indel=0.2, read_clip=0.2, multi=0.2, sam_seq=0)
+
+
 def test_oracle_matches_live_reference_on_fresh_seed(built, tmp_path):
-    run = H.synth(str(tmp_path / "run"), seed=4242, chroms="30000,20000", part=2, pairs=8000, coverage=5, contig_min=800, contig_max=4000,
-                  read_indel=0.2, read_clip=0.2, multi=0.2, sam_seq=0)
-    ref, _ = H.run_reference(run)
-    assert len(ref) == 4
-    for u, exp in enumerate(ref):
-        got = H.run_oracle(os.path.join(run, "tmp"), u, 5, 50, 5)
-        assert got["initial"] == exp["initial"] and got["pre"] == exp["pre"] and got["extended"] == exp["extended"]
+    """Against the md5s of what the reference wrote for these inputs (tests/golden/reference_runs.json), and against the reference itself where oracle/_ref is built."""
+    import hashlib
+    from golden import reference_runs
+    rec = reference_runs.load()["fresh_seed"]
+    assert rec["synth"] == FRESH_SEED
+    run = H.synth(str(tmp_path / "run"), **FRESH_SEED)
+    assert reference_runs.tree_md5(run) == rec["inputs_md5"], "the generator no longer reproduces the inputs the reference was run on: regenerate tests/golden/reference_runs.json"
+    got = [H.run_oracle(os.path.join(run, "tmp"), u, 5, 50, 5) for u in range(4)]
+    assert len(rec["expected"]) == 4
+    for u, exp in enumerate(rec["expected"]):
+        for key in ("initial", "pre", "extended"):
+            assert (hashlib.md5(got[u][key]).hexdigest(), len(got[u][key])) == (exp[key]["md5"], exp[key]["bytes"]), "unit %d: %s differs from the reference" % (u, key)
+    if H.have_reference():
+        ref, _ = H.run_reference(run)
+        assert len(ref) == 4
+        for u, exp in enumerate(ref):
+            assert got[u]["initial"] == exp["initial"] and got[u]["pre"] == exp["pre"] and got[u]["extended"] == exp["extended"]
 
 
 def test_batch_boundary_unit_matches_the_reference_md5(built, tmp_path):

@@ -3,8 +3,9 @@
 Every class below is something bowtie2 / BLAT / formalizeGenome never produce, and on which the reference has no defined behaviour: it
 indexes vectors out of bounds or carries state from one record into the next.  The product refuses each with a return code instead of
 reproducing an accident.  The first half of every case runs everywhere (the loader is host code: the serial test executor links it); the
-second half runs where the real reference binary was built (this container) and pins what the reference does — `crash` (killed by a signal),
-`exit` (its own error exit) or `finishes` — so that a change of these expectations is a conscious edit of this table, and DESIGN.md can cite it.
+second half pins what the reference does — `crash` (killed by a signal), `exit` (its own error exit) or `finishes` — against the record of
+the reference's runs on these very inputs (tests/golden/reference_runs.json), and against the reference binary itself where oracle/_ref is
+built, so that a change of these expectations is a conscious edit of this table, and DESIGN.md can cite it.
 """
 import os
 import shutil
@@ -13,6 +14,7 @@ import subprocess
 import pytest
 
 import harness as H
+from golden import reference_runs
 from hostsim import sim
 
 E_FORMAT, E_UNSUPPORTED = -2, -3
@@ -110,16 +112,25 @@ def test_the_loader_refuses_with_a_code(built, tmp_path, name):
     assert e.value.code == code and msg in e.value.msg, (e.value.code, e.value.msg)
 
 
-@pytest.mark.skipif(not H.have_reference(), reason="oracle/_ref not built (no /root/reference on this machine)")
-@pytest.mark.parametrize("name", sorted(CASES))
-def test_what_the_reference_does_with_them(built, tmp_path, name):
-    run = _run(tmp_path, name)
+def reference_outcome(run):
+    """Replays a copy of `run` through the reference binary: "crash", "exit", "finishes" or "hangs", and the tail of its stdout."""
     work = run + ".ref"
     shutil.copytree(run, work)
     env = dict(os.environ, PATH=H.STUBS + os.pathsep + os.environ.get("PATH", ""))
     try:
         p = subprocess.run([H.REF_O2, "--resume"], cwd=work, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
-        got = "crash" if p.returncode < 0 else "finishes" if p.returncode == 0 and b"FINISHED SUCCESSFULLY" in p.stdout else "exit"
+        return "crash" if p.returncode < 0 else "finishes" if p.returncode == 0 and b"FINISHED SUCCESSFULLY" in p.stdout else "exit", p.stdout[-200:]
     except subprocess.TimeoutExpired:
-        got = "hangs"
-    assert got == CASES[name][3], "%s: the reference %s (stdout tail: %r)" % (name, got, p.stdout[-200:] if got != "hangs" else b"")
+        return "hangs", b""
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_what_the_reference_does_with_them(built, tmp_path, name):
+    """Against what the reference did with these very inputs (tests/golden/reference_runs.json), and against the reference itself where oracle/_ref is built."""
+    run = _run(tmp_path, name)
+    rec = reference_runs.load()["rejected_inputs"][name]
+    assert reference_runs.tree_md5(run) == rec["inputs_md5"], "the generator no longer reproduces the inputs the reference was run on: regenerate tests/golden/reference_runs.json"
+    assert rec["reference"] == CASES[name][3], "%s: the reference %s" % (name, rec["reference"])
+    if H.have_reference():
+        got, tail = reference_outcome(run)
+        assert got == CASES[name][3], "%s: the reference %s (stdout tail: %r)" % (name, got, tail)
