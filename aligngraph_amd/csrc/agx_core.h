@@ -157,6 +157,8 @@ AGX_HD agx_u32 agx_uload(const agx_u32 *p, size_t i) { return p[i]; }
 // leaves the tile to the next pass, whose buckets are not packed.  Counters are only reached through agx_cnt_*; agx_b serves the other fields in both layouts.
 struct agx_bucket { agx_u32 *base; agx_u32 stride; agx_u32 maxv; agx_u32 packed; };
 #define AGX_NFP 10u
+static_assert(AGX_F_COV == AGX_F_OFF0 + 1 && AGX_F_A == AGX_F_COV + 1 && AGX_F_S0 == AGX_F_N + 1 && AGX_NFP == AGX_NF - 3,
+              "packed buckets: the six counters from AGX_F_COV on pair up into three words, and agx_b maps S0 / S1 three words down");
 AGX_HD agx_u32 &agx_b(const agx_bucket &b, agx_u32 v, agx_u32 f) { return b.base[(b.packed ? v * AGX_NFP + (f >= (agx_u32)AGX_F_S0 ? f - 3u : f) : v * AGX_NF + f) * b.stride]; }
 AGX_HD agx_u32 &agx_cnt_word(const agx_bucket &b, agx_u32 v, agx_u32 f) { return b.base[(v * AGX_NFP + (agx_u32)AGX_F_COV + ((f - (agx_u32)AGX_F_COV) >> 1)) * b.stride]; }      // (packed layout: the word that holds counter f)
 // counter update of a bucket word.  In the LDS node sweep it is a wave-private LDS add (one ds_add_u32 instead of

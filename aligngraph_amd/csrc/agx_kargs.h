@@ -94,6 +94,7 @@ void agx_launch_compact(const agx_compact_args *, const agx_u32 *chain_end, agx_
 // main ids), cut_out[AGX_DL_PIECES + 1 ..] = side ids.
 #define AGX_DL_PIECES 16u
 struct agx_cut_args { agx_u32 n; agx_u32 word[AGX_DL_PIECES + 1]; agx_u32 *cut_out; };
+static_assert(AGX_TILE == 64, "a cut's word of the special-id bitmap (64 ids) is also a tile of the side-id prefix: agx_collect_block and stream_cuts count positions in 64s");
 void agx_launch_special(const agx_compact_args *, agx_u32 n_words, agx_u32 *sp_rank, agx_u32 *scan_tmp, unsigned long long *desc,
                         agx_u32 *out, const agx_u32 *a, const agx_u32 *b, const agx_u32 *pool_cnt, agx_u32 regions, agx_u32 *sum, const agx_cut_args *cuts, hipStream_t);
 #define AGX_MID_WAVES 3072u     // wavefronts of pass 1 (3 per SIMD fit its LDS buckets); they stride over the list of tiles pass 0 gave up on

@@ -39,7 +39,13 @@ struct SimGraph {
     }
 };
 
-void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage, agx_u32 maxv_first, SimGraph &S, int &n_big_tiles) {
+// What a test may ask of the executor besides the graph: the lean record of every list entry (what pass 0 of the device's node sweep reads, made by the
+// same agx_lean_make_v from the same hits), and pass 0 on packed buckets (agx_bucket::packed: the device's layout, counters as 16-bit halves).
+struct SimOptions { bool packed = false, records = false; };
+struct SimRecords { std::vector<agx_u32> tile_len, recs; };      // recs: per list entry tile, geo, qoff1, boff1, qoff2, boff2, lenjs
+enum { AGX_SIM_REC_WORDS = 7 };
+
+void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage, agx_u32 maxv_first, SimGraph &S, int &n_big_tiles, const SimOptions &opt, SimRecords &R) {
     const agx_u32 n_pos = (agx_u32)T.ref.size();
     const agx_u32 n_tiles = (n_pos + AGX_TILE - 1) / AGX_TILE;
     // hit_prep
@@ -72,6 +78,7 @@ void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage,
             // the lean record of the entry (what pass 0 of the device's node sweep reads): wherever it is not kind GENERAL it must give the same arrival on every lane
             const agx_lrec lr = agx_lean_make(dh[h], P.runs.data(), t, k, h);
             lean_kinds[lr.geo >> 30]++;
+            if (opt.records) { const agx_u32 w[AGX_SIM_REC_WORDS] = {t, lr.geo, lr.qoff1, lr.boff1, lr.qoff2, lr.boff2, lr.lenjs}; R.recs.insert(R.recs.end(), w, w + AGX_SIM_REC_WORDS); }
             if (lr.slot != dh[h].a_slot || lr.hit != h || lr.lenjs != ((agx_u32)dh[h].len | ((agx_u32)dh[h].jstar << 16)) || (((lr.geo & AGX_LF_AREV) != 0) != ((dh[h].flags & AGX_HF_AREV) != 0)))
                 throw Error{E_ARG, "a lean tile record names another read"};
             if ((lr.geo >> 30) == AGX_LK_ONE && (lr.qoff2 != ((dh[h].flags & AGX_HF_AREV) ? (agx_u32)dh[h].len - lr.qoff1 : lr.qoff1) || lr.boff2 != (agx_u32)dh[h].jstar - lr.qoff1 || (lr.geo & (AGX_LF_BN1 | AGX_LF_JUMP1))))
@@ -101,6 +108,7 @@ void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage,
         }
     }
     tile_off[n_tiles] = (agx_u32)tile_hits.size();
+    if (opt.records) for (agx_u32 t = 0; t < n_tiles; t++) R.tile_len.push_back(tile_off[t + 1] - tile_off[t]);
     if (getenv("AGX_SIM_STATS")) fprintf(stderr, "[hostsim] lean records: %zu general, %zu one piece, %zu one piece with a jump or without mate positions, %zu two pieces\n", lean_kinds[0], lean_kinds[1], lean_kinds[2], lean_kinds[3]);
     if (getenv("AGX_SIM_STATS")) { size_t lin = 0, cx = 0, cx_hits = 0; for (const agx_dhit &r : tile_recs) (r.a_nruns | r.b_nruns) ? cx++ : lin++; for (const agx_dhit &r : dh) if (!(r.flags & AGX_HF_SKIP) && (r.a_nruns | r.b_nruns)) cx_hits++;
         fprintf(stderr, "[hostsim] tile-list entries: %zu linear pieces, %zu general records (%.1f %%); hits with a multi-run mate: %zu of %zu\n", lin, cx, 100.0 * cx / (lin + cx + 1e-9), cx_hits, dh.size()); }
@@ -159,21 +167,23 @@ void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage,
     n_big_tiles = 0;
     agx_u32 pool = 0;
     auto get = [&](agx_u32 i) { return tile_recs[i]; };
-    std::vector<agx_u32> lds((size_t)AGX_NF * maxv_first * AGX_TILE), big;
+    const agx_u32 pk = opt.packed ? 1u : 0u;         // (packed: AGX_NFP words per variant, as pass 0 of the device holds them; the fallback's buckets are not packed)
+    std::vector<agx_u32> lds((size_t)(pk ? AGX_NFP : (agx_u32)AGX_NF) * maxv_first * AGX_TILE), big;
     for (agx_u32 t = 0; t < n_tiles; t++) {
         agx_u32 cnt[AGX_TILE], pflag[AGX_TILE]; bool ok = true;
         // what every lane hands to its left neighbour per hit (the kernel does it with a wave shuffle inside the sweep's loop)
         struct Touch { agx_u32 vm, sp; };
         std::vector<Touch> touched[AGX_TILE];
-        agx_bucket b{nullptr, AGX_TILE, maxv_first, 0u};
-        for (agx_u32 lane = 0; lane < AGX_TILE; lane++) {
+        agx_bucket b{nullptr, AGX_TILE, maxv_first, pk};
+        if (pk && tile_off[t + 1] - tile_off[t] > 65535u) ok = false;      // (the device's pass 0 leaves such a list to the next pass: no counter of a packed bucket may pass 16 bits)
+        else for (agx_u32 lane = 0; lane < AGX_TILE; lane++) {
             b.base = lds.data() + lane;
             ok &= agx_node_sweep_lane<false>(A, t, t * AGX_TILE + lane, b, cnt[lane], pflag[lane], get, [&](agx_u32 vm, agx_u32 sp) { touched[lane].push_back(Touch{vm, sp}); });
         }
-        agx_u32 *store = lds.data(); agx_u32 maxv = maxv_first;
+        agx_u32 *store = lds.data(); agx_u32 maxv = maxv_first, wpk = pk;
         if (!ok) {                                     // the fallback the engine runs for overflowed tiles
             n_big_tiles++;
-            big.assign((size_t)AGX_NF * AGX_MAXV_HUGE * AGX_TILE, 0); store = big.data(); maxv = AGX_MAXV_HUGE;      // (the engine: 4, then 64, then 1024 variants)
+            big.assign((size_t)AGX_NF * AGX_MAXV_HUGE * AGX_TILE, 0); store = big.data(); maxv = AGX_MAXV_HUGE; wpk = 0u;      // (the engine: 4, then 64, then 1024 variants)
             agx_bucket bb{nullptr, AGX_TILE, maxv, 0u};
             for (agx_u32 lane = 0; lane < AGX_TILE; lane++) {
                 bb.base = store + lane;
@@ -182,7 +192,7 @@ void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage,
         }
         agx_u32 total = 0; for (agx_u32 lane = 0; lane < AGX_TILE; lane++) total += cnt[lane];
         if (pool + total > S.cid.size()) { S.reserve((pool + total) * 2); bind(); }
-        agx_bucket wb{nullptr, AGX_TILE, maxv, 0u}, wn{nullptr, AGX_TILE, maxv, 0u};
+        agx_bucket wb{nullptr, AGX_TILE, maxv, wpk}, wn{nullptr, AGX_TILE, maxv, wpk};
         agx_u32 side_before = 0;                       // the kernel's wave scan
         for (agx_u32 lane = 0; lane < AGX_TILE; lane++) {
             const agx_u32 X = t * AGX_TILE + lane;
@@ -275,9 +285,13 @@ typedef struct {
     uint32_t *node_start;   // canonical (position-ordered) numbering, same layout as the oracle's dump
     uint32_t *node_key; int32_t *node_cnt; uint32_t *node_slen; uint32_t *edge_start; uint32_t *edge_dst;   // edge_dst sorted per node
     uint64_t n_walk_ids, n_special, n_fetched;   // walk graph: ids, records in the sparse table, records read through the fetch hook
+    uint32_t n_tiles; uint32_t *tile_len;        // AGX_SIM_RECORDS: each tile's list length,
+    uint64_t n_recs; uint32_t *recs;             // and per list entry (in list order) AGX_SIM_REC_WORDS words: tile, geo, qoff1, boff1, qoff2, boff2, lenjs
 } agx_hostsim_result;
 
-int agx_hostsim_run_unit(const char *tmp_dir, int unit, int k, int iv, int coverage, long batch, int maxv_first, int want_graph, agx_hostsim_result *out) {
+enum { AGX_SIM_GRAPH = 1, AGX_SIM_PACKED = 2, AGX_SIM_RECORDS = 4 };
+
+int agx_hostsim_run_unit(const char *tmp_dir, int unit, int k, int iv, int coverage, long batch, int maxv_first, int options, agx_hostsim_result *out) {
     memset(out, 0, sizeof *out);
     try {
         const std::string d = tmp_dir, u = std::to_string(unit);
@@ -289,8 +303,14 @@ int agx_hostsim_run_unit(const char *tmp_dir, int unit, int k, int iv, int cover
             try { load_pairs_from_files(d + "/_reads.fa", d + "/_reads_genome." + u + ".bowtie", batch, (agx_u32)k, P, ri); } catch (...) { reads_index_close(ri); throw; }
             reads_index_close(ri);
         } else load_pairs_from_files(d + "/_reads.fa", d + "/_reads_genome." + u + ".bowtie", batch, (agx_u32)k, P);
-        SimGraph S; int nbig = 0;
-        simulate(T, P, (agx_u32)k, iv, coverage, maxv_first > 0 ? (agx_u32)maxv_first : AGX_MAXV_LDS, S, nbig);
+        const bool want_graph = (options & AGX_SIM_GRAPH) != 0;
+        SimGraph S; int nbig = 0; SimOptions opt; SimRecords R;
+        opt.packed = (options & AGX_SIM_PACKED) != 0; opt.records = (options & AGX_SIM_RECORDS) != 0;
+        simulate(T, P, (agx_u32)k, iv, coverage, maxv_first > 0 ? (agx_u32)maxv_first : AGX_MAXV_LDS, S, nbig, opt, R);
+        if (opt.records) {
+            out->n_tiles = (uint32_t)R.tile_len.size(); out->tile_len = (uint32_t *)malloc(4 * (R.tile_len.size() + 1)); memcpy(out->tile_len, R.tile_len.data(), 4 * R.tile_len.size());
+            out->n_recs = R.recs.size() / AGX_SIM_REC_WORDS; out->recs = (uint32_t *)malloc(4 * (R.recs.size() + 1)); memcpy(out->recs, R.recs.data(), 4 * R.recs.size());
+        }
         GraphView G; G.n_pos = (agx_u32)T.ref.size(); G.n_ids = S.n_ids;
         G.meta = S.a_meta.data(); G.str = S.a_str.data(); G.side_xpos = S.side_xpos.data();
         G.sp_bits = S.sp_bits.data(); G.sp_rank = S.sp_rank.data(); G.sp_node = S.sp_node.data(); G.sp_hop = S.sp_hop.data(); G.n_special = S.n_special;
@@ -405,7 +425,7 @@ int agx_hostsim_run_unit(const char *tmp_dir, int unit, int k, int iv, int cover
 
 void agx_hostsim_free(agx_hostsim_result *r) {
     free(r->initial_contigs); free(r->pre_extended); free(r->extended);
-    free(r->node_start); free(r->node_key); free(r->node_cnt); free(r->node_slen); free(r->edge_start); free(r->edge_dst);
+    free(r->node_start); free(r->node_key); free(r->node_cnt); free(r->node_slen); free(r->edge_start); free(r->edge_dst); free(r->tile_len); free(r->recs);
     memset(r, 0, sizeof *r);
 }
 

@@ -30,7 +30,11 @@ class _Result(ctypes.Structure):
         ("node_cnt", ctypes.POINTER(ctypes.c_int32)), ("node_slen", ctypes.POINTER(ctypes.c_uint32)),
         ("edge_start", ctypes.POINTER(ctypes.c_uint32)), ("edge_dst", ctypes.POINTER(ctypes.c_uint32)),
         ("n_walk_ids", ctypes.c_uint64), ("n_special", ctypes.c_uint64), ("n_fetched", ctypes.c_uint64),
+        ("n_tiles", ctypes.c_uint32), ("tile_len", ctypes.POINTER(ctypes.c_uint32)), ("n_recs", ctypes.c_uint64), ("recs", ctypes.POINTER(ctypes.c_uint32)),
     ]
+
+
+REC_FIELDS = ("tile", "geo", "qoff1", "boff1", "qoff2", "boff2", "lenjs")      # the words of one entry of run(..., records=True)["records"]
 
 
 _lib = None
@@ -43,7 +47,10 @@ class SimError(RuntimeError):
         self.msg = msg
 
 
-def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, maxv_first=0, graph=False):
+def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, maxv_first=0, graph=False, packed=False, records=False):
+    """One unit through the serial executor.  packed: pass 0 of the node sweep on packed buckets (AGX_NFP words per variant, the device's layout; a list of more
+    than 65 535 entries goes to the next pass).  records: also returns "records", the lean record of every tile-list entry in list order as a structured
+    numpy array with the fields REC_FIELDS, and "tile_len", each tile's list length."""
     global _lib
     if _lib is None:
         build()
@@ -51,7 +58,8 @@ def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, max
         _lib.agx_hostsim_run_unit.argtypes = [ctypes.c_char_p] + [ctypes.c_int] * 4 + [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_Result)]
         _lib.agx_hostsim_free.argtypes = [ctypes.POINTER(_Result)]
     r = _Result()
-    rc = _lib.agx_hostsim_run_unit(tmp_dir.encode(), unit, k, insert_variation, coverage, batch, maxv_first, 1 if graph else 0, ctypes.byref(r))
+    options = (1 if graph else 0) | (2 if packed else 0) | (4 if records else 0)
+    rc = _lib.agx_hostsim_run_unit(tmp_dir.encode(), unit, k, insert_variation, coverage, batch, maxv_first, options, ctypes.byref(r))
     if rc != 0:
         msg = r.error.decode()
         _lib.agx_hostsim_free(ctypes.byref(r))
@@ -59,9 +67,12 @@ def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, max
     out = {"initial": ctypes.string_at(r.initial_contigs, r.initial_len), "pre": ctypes.string_at(r.pre_extended, r.pre_len),
            "extended": ctypes.string_at(r.extended, r.extended_len), "n_big_tiles": r.n_big_tiles,
            "n_walk_ids": r.n_walk_ids, "n_special": r.n_special, "n_fetched": r.n_fetched}
+    import numpy as np
+    if records:
+        flat = np.ctypeslib.as_array(r.recs, shape=(r.n_recs * len(REC_FIELDS),)).copy() if r.n_recs else np.zeros(0, "uint32")
+        out["records"] = flat.view([(f, "uint32") for f in REC_FIELDS]).reshape(-1)
+        out["tile_len"] = np.ctypeslib.as_array(r.tile_len, shape=(r.n_tiles,)).copy() if r.n_tiles else np.zeros(0, "uint32")
     if graph:
-        import numpy as np
-
         def arr(p, n, dt):
             return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
         out["graph"] = {
