@@ -23,7 +23,7 @@ EXPORTS = [
     "agx_unit_finish", "agx_result_free", "agx_unit_stats", "agx_unit_graph", "agx_graph_free", "agx_run_unit",
     "agx_reads_open", "agx_reads_close", "agx_unit_load_files_shared", "agx_run_unit_shared",
     "agx_unit_stage", "agx_unit_release", "agx_pool_trim", "agx_unit_cache_build", "agx_unit_cache_save", "agx_unit_hbm_needed",
-    "agx_unit_trim",
+    "agx_unit_trim", "agx_unit_unitigs", "agx_unitigs_free", "agx_unitigs_gfa", "agx_text_free",
 ]
 
 
@@ -77,6 +77,13 @@ class Graph(ctypes.Structure):
                 ("edge_start", ctypes.POINTER(ctypes.c_uint32)), ("edge_dst", ctypes.POINTER(ctypes.c_uint32))]
 
 
+class Unitigs(ctypes.Structure):
+    _fields_ = [("n_segs", ctypes.c_uint32), ("n_links", ctypes.c_uint32), ("n_bases", ctypes.c_uint64),
+                ("head_pos", ctypes.POINTER(ctypes.c_uint32)), ("head_var", ctypes.POINTER(ctypes.c_uint32)), ("n_nodes", ctypes.POINTER(ctypes.c_uint32)),
+                ("last_pos", ctypes.POINTER(ctypes.c_uint32)), ("coverage", ctypes.POINTER(ctypes.c_uint64)), ("seq_off", ctypes.POINTER(ctypes.c_uint64)),
+                ("seq", ctypes.c_void_p), ("link_from", ctypes.POINTER(ctypes.c_uint32)), ("link_to", ctypes.POINTER(ctypes.c_uint32))]
+
+
 class AgxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("agx error %d: %s" % (code, msg))
@@ -127,6 +134,12 @@ def lib():
         L.agx_unit_graph.argtypes = [ctypes.c_void_p, ctypes.POINTER(Graph)]
         L.agx_graph_free.argtypes = [ctypes.POINTER(Graph)]
         L.agx_graph_free.restype = None
+        L.agx_unit_unitigs.argtypes = [ctypes.c_void_p, ctypes.POINTER(Unitigs)]
+        L.agx_unitigs_free.argtypes = [ctypes.POINTER(Unitigs)]
+        L.agx_unitigs_free.restype = None
+        L.agx_unitigs_gfa.argtypes = [ctypes.POINTER(Unitigs), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+        L.agx_text_free.argtypes = [ctypes.c_void_p]
+        L.agx_text_free.restype = None
         L.agx_run_unit.argtypes = [ctypes.POINTER(Params), ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Result), ctypes.c_char_p, ctypes.c_size_t]
         _lib = L
     return _lib
@@ -315,6 +328,69 @@ class Unit:
                "edge_start": arr(g.edge_start, g.n_nodes + 1, "uint32"), "edge_dst": arr(g.edge_dst, g.n_edges, "uint32")}
         lib().agx_graph_free(ctypes.byref(g))
         return out
+
+    def unitigs(self):
+        """The unit's pruned graph compacted into unitigs on the device (agx_unit_unitigs; needs keep_counts): numpy arrays per segment and link, the
+        bases as bytes."""
+        t = Unitigs()
+        self._check(lib().agx_unit_unitigs(self._h, ctypes.byref(t)))
+        try:
+            return _unitigs_arrays(t)
+        finally:
+            lib().agx_unitigs_free(ctypes.byref(t))
+
+    def gfa(self, unit=0):
+        """GFA 1.0 S and L lines of the unit's unitigs, segments named u<unit>_<pos>_<var> (no header line)."""
+        t = Unitigs()
+        self._check(lib().agx_unit_unitigs(self._h, ctypes.byref(t)))
+        try:
+            return _gfa_text(t, unit)
+        finally:
+            lib().agx_unitigs_free(ctypes.byref(t))
+
+
+def _unitigs_arrays(t):
+    import numpy as np
+
+    def arr(p, n, dt):
+        return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
+    ns, nl = t.n_segs, t.n_links
+    return {"head_pos": arr(t.head_pos, ns, "uint32"), "head_var": arr(t.head_var, ns, "uint32"), "n_nodes": arr(t.n_nodes, ns, "uint32"),
+            "last_pos": arr(t.last_pos, ns, "uint32"), "coverage": arr(t.coverage, ns, "uint64"),
+            "seq_off": arr(t.seq_off, ns + 1, "uint64") if ns else np.zeros(1, "uint64"),
+            "seq": ctypes.string_at(t.seq, t.n_bases) if t.seq and t.n_bases else b"",
+            "link_from": arr(t.link_from, nl, "uint32"), "link_to": arr(t.link_to, nl, "uint32")}
+
+
+def _gfa_text(t, unit):
+    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
+    rc = lib().agx_unitigs_gfa(ctypes.byref(t), unit, ctypes.byref(p), ctypes.byref(n))
+    if rc != AGX_OK:
+        raise AgxError(rc, "agx_unitigs_gfa: the unitig table is inconsistent")
+    try:
+        return ctypes.string_at(p, n.value) if n.value else b""
+    finally:
+        lib().agx_text_free(p)
+
+
+def _unitigs_struct(u):
+    """An agx_unitigs over the arrays of a dict like Unit.unitigs() returns; returns (struct, the buffers it points into)."""
+    import numpy as np
+    keep = {k: np.ascontiguousarray(u[k], dtype=dt) for k, dt in (("head_pos", "uint32"), ("head_var", "uint32"), ("n_nodes", "uint32"), ("last_pos", "uint32"),
+                                                                   ("coverage", "uint64"), ("seq_off", "uint64"), ("link_from", "uint32"), ("link_to", "uint32"))}
+    seq = ctypes.create_string_buffer(bytes(u["seq"]), max(1, len(u["seq"])))
+    t = Unitigs()
+    t.n_segs, t.n_links, t.n_bases = len(keep["head_pos"]), len(keep["link_from"]), len(u["seq"])
+    for k, a in keep.items():
+        setattr(t, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64 if a.dtype == np.uint64 else ctypes.c_uint32)))
+    t.seq = ctypes.cast(seq, ctypes.c_void_p).value
+    return t, (keep, seq)
+
+
+def unitigs_gfa(u, unit=0):
+    """GFA S/L lines (no header) of a unitig table given as the dict Unit.unitigs() returns (agx_unitigs_gfa; host only, needs no device)."""
+    t, _keep = _unitigs_struct(u)
+    return _gfa_text(t, unit)
 
 
 def cache_build(tmp_dir, unit, batch=0, device=0, reads=None, k=5):

@@ -39,8 +39,9 @@ using std::cout; using std::endl; using std::string; using std::vector;
 namespace {
 
 struct Options {
-    string read1, read2, contig, genome, ext, rmn;
+    string read1, read2, contig, genome, ext, rmn, graph;
     int tagRead1 = 0, tagRead2 = 0, tagContig = 0, tagGenome = 0, tagExt = 0, tagRmn = 0, tagK = 0, tagLow = 0, tagHigh = 0, tagIV = 0, tagCov = 0, tagPart = 0;
+    int tagGraph = 0;                   // --graphOut: each unit's pruned graph as GFA (not an option of the reference; its usage text stays as it is)
     int fastMap = 0, ratioCheck = 0, uniqueExtension = 0, iterativeMap = 0, misassemblyRemoval = 0, resume = 0;
     int k = 5, distanceLow = 0, distanceHigh = 99999, coverage = 20, insertVariation = 50, part = 1;      // defaults of AG:4701
 };
@@ -106,6 +107,7 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--distanceHigh") integer(i, o.tagHigh, o.distanceHigh);
         else if (b == "--extendedContig") outfile(i, o.tagExt, o.ext);          // opening truncates the file right away, like ofstream::open (AG:4477)
         else if (b == "--remainingContig") outfile(i, o.tagRmn, o.rmn);
+        else if (b == "--graphOut") outfile(i, o.tagGraph, o.graph);
         else if (b == "--kMer") integer(i, o.tagK, o.k);
         else if (b == "--insertVariation") integer(i, o.tagIV, o.insertVariation);
         else if (b == "--coverage") integer(i, o.tagCov, o.coverage);
@@ -1138,7 +1140,7 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                 if (at >= order.size() || failed.load()) return;
                 const int u = order[at];
                 // the five calls of the unit loop (AG:4768-4776) through the split entry points of agx_run_unit, with the admission between load and upload
-                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, AGX_FLAG_ONE_SHOT};
+                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, AGX_FLAG_ONE_SHOT | (o.tagGraph ? AGX_FLAG_KEEP_COUNTS : 0u)};
                 agx_result r; memset(&r, 0, sizeof r); char err[512]; err[0] = 0;
                 agx_unit *un = nullptr;
                 int rc = agx_unit_create(&p, &un);
@@ -1149,6 +1151,19 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                 if (rc == AGX_OK) { std::unique_lock<std::mutex> g(mem_mu); waiting[d]++; mem_cv.wait(g, [&] { return used[d] == 0.0 || used[d] + est <= budget[d]; }); waiting[d]--; used[d] += est; admitted = true; }
                 if (rc == AGX_OK) rc = agx_unit_upload(un);
                 if (rc == AGX_OK) rc = agx_unit_build(un);
+                if (rc == AGX_OK && o.tagGraph) {      // --graphOut: the unit's GFA lines, exported before the download (one-shot units) into tmp/_graph.<u>.gfa
+                    agx_unitigs ut; char *text = nullptr; size_t len = 0;
+                    rc = agx_unit_unitigs(un, &ut);
+                    if (rc == AGX_OK) { rc = agx_unitigs_gfa(&ut, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "GFA FORMATTING FAILED"); }
+                    agx_unitigs_free(&ut);
+                    if (rc == AGX_OK) {
+                        const string path = "tmp/_graph." + itoa(u) + ".gfa";
+                        FILE *f = fopen(path.c_str(), "wb"); bool ok = f != nullptr;
+                        if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
+                        if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
+                    }
+                    agx_text_free(text);
+                }
                 bool wanted = false; if (rc == AGX_OK) { std::lock_guard<std::mutex> g(mem_mu); wanted = waiting[d] > 0; }
                 if (rc == AGX_OK && wanted) {      // r05: somebody waits for room on this device — the whole download first, then what the walk cannot ask the device for goes back: the next unit is admitted while this one is walked on the host
                     rc = agx_unit_download(un);
@@ -1240,6 +1255,20 @@ int main(int argc, char **argv) {
     stage("resume / ratio check");
     if (cp < units) run_units(o, cp, units, wcp);
     stage("unit loop");
+    if (o.tagGraph) {                                                         // --graphOut: the header and every unit's lines, in unit order (a --resume run finds the earlier units' files in tmp/)
+        FILE *g = fopen(o.graph.c_str(), "wb");
+        bool ok = g != nullptr && fputs("H\tVN:Z:1.0\n", g) >= 0;
+        for (int u = 0; ok && u < units; u++) {
+            FILE *f = fopen(("tmp/_graph." + itoa(u) + ".gfa").c_str(), "rb");
+            if (!f) { ok = false; break; }
+            char buf[1 << 16]; size_t n;
+            while (ok && (n = fread(buf, 1, sizeof buf, f)) > 0) ok = fwrite(buf, 1, n, g) == n;
+            fclose(f);
+        }
+        if (g) ok = (fclose(g) == 0) && ok;
+        if (!ok) die("CANNOT OPEN FILE!");
+        stage("graph output");
+    }
     refinement(o, units, genomeIds, contigIds);
     stage("refinement");
     if (o.misassemblyRemoval == 1) {                                          // AG:4787-4792

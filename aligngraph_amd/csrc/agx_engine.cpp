@@ -28,6 +28,7 @@
 #include <mutex>
 #include <system_error>
 #include <thread>
+#include <type_traits>
 #include <pthread.h>
 #include <atomic>
 #include <condition_variable>
@@ -246,6 +247,7 @@ struct agx_unit {
     bool have_ref = false, have_threads = false, staged = false, uploaded = false, built = false, downloaded = false;
     bool consumed = false;             // AGX_FLAG_ONE_SHOT: the download has overwritten the staged inputs
     bool pending_walk = false;         // counted in g_walks_pending: uploaded, not yet walked (or released)
+    bool trimmed = false;              // agx_unit_trim since the last build: the node table may be gone (agx_unit_unitigs refuses)
     bool expanded = false;             // the conti-mer tables and vote codes have been made from what was uploaded (opens the unit's first build)
     hipEvent_t ev_built = nullptr;     // this unit's build commands are done (waited for on the host; ev_dl: its download)
     UnitOutput out; OutBuf out_initial; bool out_ready = false;      // output buffers of the next finish, reserved and touched by a helper thread while the unit is uploaded and built (prepare_outputs)
@@ -291,6 +293,7 @@ struct agx_unit {
     DBuf<agx_u32> d_pool_cnt, d_region_off; agx_u32 n_regions = 0;      // the node pool's slices (AGX_REGION_TILES tiles each) and their counters
     DBuf<agx_u32> d_node_start, d_slow_list, d_perm, d_tfirst, d_ckey, d_long; DBuf<agx_u16> d_node_cnt; DBuf<agx_u8> d_pos_succ;
     DBuf<agx_u32> d_cid, d_coff, d_cid0, d_coff0, d_off0, d_next; DBuf<agx_u8> d_base, d_flags; DBuf<agx_sref> d_sref; DBuf<int> d_counts;
+    DBuf<char> d_ut;                   // the unitig export's scratch (unitig_layout): reserved with the unit's block when it keeps counts, reused by every export
     DBuf<agx_edge_ovf> d_ovf; DBuf<agx_u32> d_mid_list, d_big_list, d_scratch, d_huge_list, d_scratch_huge; bool huge = false, dense = false;      // dense: the scatter fallback of the tile lists is queued (a build met more than AGX_LONG_MAX long hits); huge: pass 3 of the node sweep is queued (a build met a position beyond AGX_MAXV_BIG variants)
     // walk graph (agx_core.h "walk preparation")
     agx_u32 n_ids = 0;
@@ -891,6 +894,32 @@ void alloc_sparse(agx_unit *u, agx_u32 cap) { u->sp_cap = cap; u->d_sp_node.rele
 
 void do_release(agx_unit *u);
 
+// The unitig export's scratch (agx_unit_unitigs, agx_unitig.hip) as one buffer carved in this order; base == nullptr: only the size.  Sized for the worst case — every
+// node slot a piece and a segment — since a unit that keeps counts has it reserved with its block (plan_capacities): an export never asks the device for memory.
+// Phase 3 reuses what phases 1-2 are done with: the links lie over pos_of | outs | oout | p_len | p_next, the bases over succ.
+size_t unitig_layout(size_t cap, size_t n_pos, size_t n_ovf, char *base, agx_unitig_args *A, agx_u32 **words) {
+    size_t at = 0;
+    auto take = [&](auto *&p, size_t n) { at = (at + 255) & ~(size_t)255; p = base ? (std::remove_reference_t<decltype(*p)> *)(base + at) : nullptr; at += (n ? n : 1) * sizeof(*p); };
+    agx_unitig_args T{}; agx_unitig_args &X = A ? *A : T; agx_u32 *w = nullptr, *R = nullptr;
+    size_t hash_n = 64; while (hash_n < 2 * n_ovf) hash_n *= 2;
+    const size_t nwin = (cap + 63) / 64, nmax = std::max(std::max(cap, n_pos), nwin) + 1;
+    take(w, 8); take(R, 5 * cap + n_ovf);
+    take(X.indeg, cap); take(X.succ, cap); take(X.osucc, cap); take(X.nxt, cap); take(X.haspred, cap);
+    take(X.ovf_hash, hash_n); take(X.ovf_first, n_ovf); take(X.wcnt, nwin + 1); take(X.woff, nwin + 1);
+    for (int i = 0; i < 2; i++) { take(X.anc[i], cap); take(X.off[i], cap); }
+    take(X.p_seg, cap); take(X.hcnt, n_pos + 1); take(X.hoff, n_pos + 1);
+    take(X.s_len, cap + 1); take(X.s_links, cap + 1); take(X.s_hpos, cap); take(X.s_hvar, cap); take(X.s_last, cap); take(X.s_cov, cap);
+    take(X.s_off, cap + 1); take(X.l_off, cap + 1); take(X.l_cur, cap + 1);
+    take(X.scan_tmp, 2 * ((nmax + 4095) / 4096 + 1) + 2 * ((nmax + 4096ull * 4096 - 1) / (4096ull * 4096) + 1) + 8);
+    if (base) {
+        X.pos_of = R; X.outs = R + cap; X.oout = R + 2 * cap; X.p_len = R + 3 * cap; X.p_next = R + 4 * cap;
+        X.l_to = R; X.link_cap = (agx_u32)std::min<size_t>(5 * cap + n_ovf, 0xFFFFFFFFull); X.seq = (char *)X.succ; X.seq_cap = (agx_u32)std::min<size_t>(4 * cap, 0xFFFFFFFFull);
+        X.hash_mask = (agx_u32)(hash_n - 1);
+        if (words) *words = w;
+    }
+    return at + 256;
+}
+
 // Capacities of a unit's first build and the HBM they add up to (what do_upload reserves as one block; AlignGraph_amd admits a unit to a device by it:
 // agx_unit_hbm_needed).  From the staged counts: positions, hits, runs, conti-mers, read rows.
 struct Plan { agx_u32 pool_cap, list_cap, ovf_cap, sp_cap; size_t total; };
@@ -921,7 +950,7 @@ Plan plan_capacities(const agx_unit *u) {
     const size_t total = wire + n_pos * per_pos + n_tiles * per_tile + nh * per_hit_b + u->n_runs * sizeof(agx_run) + u->n_cm * sizeof(agx_cmkey) + (u->rows_diffed ? u->n_units * 2 + u->n_rowcnt + (u->n_blockoff + u->n_blockfirst + u->n_anchor) * 4 : codes_bytes(u)) + n_bases + others_up(u) * 8 +
                          (size_t)P.pool_cap * per_slot + ids_cap * per_id + (size_t)P.list_cap * 36 + (size_t)P.ovf_cap * 16 + (size_t)P.sp_cap * (sizeof(agx_walknode) + sizeof(agx_hop)) +
                          (size_t)AGX_BIG_WAVES * AGX_NF * AGX_MAXV_BIG * 64 * 4 + (size_t)n_regions * AGX_REGION_PAD * 4 + (64u << 10) * 100;
-    P.total = total + total / 64;
+    P.total = total + total / 64 + ((u->prm.flags & AGX_FLAG_KEEP_COUNTS) ? unitig_layout(P.pool_cap, n_pos, P.ovf_cap, nullptr, nullptr, nullptr) : 0);      // (counts are kept for the unitig export)
     return P;
 }
 
@@ -1301,7 +1330,7 @@ void do_build(agx_unit *u) {
 #endif
         break;
     }
-    u->built = true; u->downloaded = false;
+    u->built = true; u->downloaded = false; u->trimmed = false;
     u->stats.ms_build_span = u->ev.all ? u->ev.span() : 0.0;
     u->stats.ms_prep = u->ev.ms(B_PREP); u->stats.ms_bin = u->ev.ms(B_BIN); u->stats.ms_node_sweep = u->ev.ms(B_NODE);
     if (swept_windows >= 1 && swept_timed) {      // a windowed first build: the sweep's time is the sum over its windows (between them the stream may have waited for rows that were still travelling)
@@ -1498,7 +1527,7 @@ void do_release(agx_unit *u) {
     u->d_units.release(); u->d_rowcnt.release(); u->d_blockoff.release(); u->d_blockfirst.release(); u->d_anchor.release();
     u->d_other.release(); u->d_whits.release(); u->d_wsides.release(); u->d_wruns.release(); u->d_wref.release(); u->d_refx.release();
     u->d_cm.release(); u->d_cm_head.release(); u->d_ref.release(); u->d_cm_cnt.release(); u->d_segs.release(); u->d_up_desc.release(); u->d_cntruns.release(); u->d_cntchunks.release(); u->d_segchunks.release(); u->d_jump.release(); u->d_segindex.release(); u->d_sp_hop.release(); u->d_runs.release(); u->d_dhit.release(); u->d_scan_desc.release(); u->d_sref.release(); u->d_counts.release();
-    u->d_ovf.release(); u->d_a_ovf.release(); u->d_huge_list.release(); u->d_scratch_huge.release(); u->huge = false; u->dense = false; u->d_a_str.release(); u->d_fetch.release(); u->d_sp_node.release(); u->d_sp_bits.release();
+    u->d_ut.release(); u->d_ovf.release(); u->d_a_ovf.release(); u->d_huge_list.release(); u->d_scratch_huge.release(); u->huge = false; u->dense = false; u->d_a_str.release(); u->d_fetch.release(); u->d_sp_node.release(); u->d_sp_bits.release();
     u->arena.reset();
     u->h_a_str.release(); u->h_a_meta.release(); u->h_side_xpos.release(); u->h_sp_rank.release(); u->h_sp_bits.release(); u->h_sp_node.release(); u->h_fetch.release(); u->h_a_ovf.release();
     u->h_sp_hop.release();
@@ -1759,7 +1788,7 @@ int agx_unit_hbm_needed(agx_unit *u, uint64_t *bytes) {
 int agx_unit_stage(agx_unit *u) { if (!u) return AGX_E_ARG; return guarded(u, [&] { stage_inputs(u); }); }
 int agx_unit_upload(agx_unit *u) { if (!u) return AGX_E_ARG; return guarded(u, [&] { do_upload(u); }); }
 int agx_unit_release(agx_unit *u) { if (!u) return AGX_E_ARG; return guarded(u, [&] { do_release(u); }); }
-int agx_unit_trim(agx_unit *u, uint64_t *freed) { if (!u) return AGX_E_ARG; if (freed) *freed = 0; return guarded(u, [&] { const size_t f = do_trim(u); if (freed) *freed = f; }); }
+int agx_unit_trim(agx_unit *u, uint64_t *freed) { if (!u) return AGX_E_ARG; if (freed) *freed = 0; return guarded(u, [&] { const size_t f = do_trim(u); u->trimmed = true; if (freed) *freed = f; }); }
 void agx_pool_trim(int device) { if (device >= 0) dev_trim(device); else if (device == -1) { host_trim(); scratch_trim(); out_cache_trim(); } else host_retire(); }      // (-1 also unmaps the loaders' cached scratch memory: up to 16 GB of touched pages per process otherwise stay until exit)
 int agx_unit_build(agx_unit *u) { if (!u) return AGX_E_ARG; return guarded(u, [&] { do_build(u); }); }
 int agx_unit_download(agx_unit *u) { if (!u) return AGX_E_ARG; return guarded(u, [&] { do_download(u); }); }
@@ -1877,6 +1906,79 @@ int agx_unit_graph(agx_unit *u, agx_graph *g) {
 void agx_graph_free(agx_graph *g) {
     if (!g) return;
     free(g->node_start); free(g->node_key); free(g->node_cnt); free(g->node_slen); free(g->edge_start); free(g->edge_dst); memset(g, 0, sizeof *g);
+}
+
+// Unitig export: the kernels of agx_unitig.hip on a stream of the export's own, scratch from an arena of its own (given back to the device's
+// caches on return).  Three host round trips: the piece count (the pointer jumping's rounds and arrays), the totals (segments, bases, links), the download.
+int agx_unit_unitigs(agx_unit *u, agx_unitigs *t) {
+    if (!u || !t) return AGX_E_ARG;
+    memset(t, 0, sizeof *t);
+    const int rc = guarded(u, [&] {
+        if (!(u->prm.flags & AGX_FLAG_KEEP_COUNTS)) throw Error{E_ARG, "unitigs: the unit was created without AGX_FLAG_KEEP_COUNTS (the segments' coverage needs the counts)"};
+        if (!u->built || u->trimmed) throw Error{E_ARG, "unitigs: the unit is not built (call agx_unit_build; not after agx_unit_trim or agx_unit_release)"};
+        if ((u->prm.flags & AGX_FLAG_ONE_SHOT) && (u->consumed || u->downloaded)) throw Error{E_ARG, "unitigs: a one-shot unit exports before its download or finish"};
+        HIP_OK(hipSetDevice(u->prm.device));
+        HIP_OK(wait_event(u->ev_built));
+        const agx_u32 n_pos = (agx_u32)u->V.n_pos, cap = u->pool_cap, n_ovf = std::min(u->n_ovf, u->ovf_cap);
+        if (!n_pos || !cap || !u->n_nodes) return;
+        const size_t bytes = unitig_layout(cap, n_pos, n_ovf, nullptr, nullptr, nullptr);
+        u->d_ut.alloc(u->arena, bytes);                  // (from the room the upload reserved for it; a unit whose pool or overflow list grew takes the difference)
+        u->stats.device_bytes = u->arena.capacity();
+        struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;      // (the export's work is done before the call returns, also on an error)
+        HIP_OK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+        auto fill = [&](void *p, int v, size_t b) { HIP_OK(hipMemsetAsync(p, v, b ? b : 1, st.s)); };
+        agx_unitig_args A{}; agx_u32 *words = nullptr;
+        unitig_layout(cap, n_pos, n_ovf, u->d_ut.p, &A, &words);
+        A.node_start = u->d_node_start.p; A.node_cnt = u->d_node_cnt.p; A.n_flags = u->d_flags.p; A.n_base = u->d_base.p; A.n_next = u->d_next.p;
+        A.n_counts = u->d_counts.p; A.ref = u->d_ref.p; A.ovf = u->d_ovf.p; A.n_ovf = n_ovf; A.n_pos = n_pos; A.pool_cap = cap; A.piece_cap = cap; A.err = words;
+        const size_t nwin = ((size_t)cap + 63) / 64;
+        fill(words, 0, 32); fill(A.pos_of, 0xFF, (size_t)cap * 4); fill(A.indeg, 0, (size_t)cap * 4); fill(A.oout, 0, (size_t)cap * 4); fill(A.haspred, 0, cap);
+        fill(A.ovf_hash, 0xFF, ((size_t)A.hash_mask + 1) * 8); fill(A.wcnt, 0, (nwin + 1) * 4);
+        agx_launch_unitig_phase1(&A, st.s);
+        agx_u32 h[4] = {0, 0, 0, 0};
+        HIP_OK(hipMemcpyAsync(h, words, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipMemcpyAsync(h + 1, A.woff + nwin, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
+        if (h[0] & 1u) throw Error{E_DEVICE, "unitigs: an edge of the node table does not lead to a later position (the graph is not a DAG)"};
+        if (h[0]) throw Error{E_DEVICE, "unitigs: the node table is inconsistent (error word " + std::to_string(h[0]) + ")"};
+        const agx_u32 np = h[1];
+        if (np > cap) throw Error{E_DEVICE, "unitigs: more pieces than node slots"};
+        A.piece_cap = np;
+        agx_u32 rounds = 1; while (rounds < 32 && (1ull << (rounds - 1)) < np) rounds++;      // ceil(log2 np) + 1
+        fill(A.p_seg, 0xFF, (size_t)np * 4); fill(A.hcnt, 0, ((size_t)n_pos + 1) * 4);
+        fill(A.s_len, 0, ((size_t)np + 1) * 4); fill(A.s_links, 0, ((size_t)np + 1) * 4); fill(A.s_cov, 0, (size_t)np * 8); fill(A.l_cur, 0, ((size_t)np + 1) * 4);
+        agx_launch_unitig_phase2(&A, rounds, st.s);
+        agx_launch_unitig_totals(&A, words + 4, st.s);
+        HIP_OK(hipMemcpyAsync(h, words + 4, 16, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
+        if (h[3]) throw Error{E_DEVICE, "unitigs: the unitig ranks are inconsistent (error word " + std::to_string(h[3]) + ")"};
+        const agx_u32 ns = h[0], nb = h[1], nl = h[2];
+        if (ns > np || nb > u->n_nodes || nb > A.seq_cap || nl > A.link_cap) throw Error{E_DEVICE, "unitigs: segment totals out of range"};
+        A.seq_cap = nb; A.link_cap = nl;
+        agx_launch_unitig_phase3(&A, st.s);
+        // the compact arrays (per-node arrays never leave the device) into pinned memory, then into the caller's malloc'd table
+        const size_t o_hp = 0, o_hv = o_hp + 4 * (size_t)ns, o_ln = o_hv + 4 * (size_t)ns, o_lp = o_ln + 4 * (size_t)ns, o_cov = (o_lp + 4 * (size_t)ns + 7) & ~(size_t)7,
+                     o_so = o_cov + 8 * (size_t)ns, o_lo = o_so + 4 * ((size_t)ns + 1), o_lt = o_lo + 4 * ((size_t)ns + 1), o_seq = o_lt + 4 * (size_t)nl, o_end = o_seq + nb;
+        PBuf<char> pin; pin.alloc(o_end + 8);
+        auto down = [&](size_t o, const void *src, size_t b) { if (b) HIP_OK(hipMemcpyAsync(pin.p + o, src, b, hipMemcpyDeviceToHost, st.s)); };
+        down(o_hp, A.s_hpos, 4 * (size_t)ns); down(o_hv, A.s_hvar, 4 * (size_t)ns); down(o_ln, A.s_len, 4 * (size_t)ns); down(o_lp, A.s_last, 4 * (size_t)ns);
+        down(o_cov, A.s_cov, 8 * (size_t)ns); down(o_so, A.s_off, 4 * ((size_t)ns + 1)); down(o_lo, A.l_off, 4 * ((size_t)ns + 1)); down(o_lt, A.l_to, 4 * (size_t)nl); down(o_seq, A.seq, nb);
+        HIP_OK(hipMemcpyAsync(h, words, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
+        if (h[0]) throw Error{E_DEVICE, "unitigs: the segments are inconsistent (error word " + std::to_string(h[0]) + ")"};
+        t->n_segs = ns; t->n_links = nl; t->n_bases = nb;
+        t->head_pos = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->head_var = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->n_nodes = (uint32_t *)malloc(4 * ((size_t)ns + 1));
+        t->last_pos = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->coverage = (uint64_t *)malloc(8 * ((size_t)ns + 1)); t->seq_off = (uint64_t *)malloc(8 * ((size_t)ns + 1));
+        t->seq = (char *)malloc((size_t)nb + 1); t->link_from = (uint32_t *)malloc(4 * ((size_t)nl + 1)); t->link_to = (uint32_t *)malloc(4 * ((size_t)nl + 1));
+        if (!t->head_pos || !t->head_var || !t->n_nodes || !t->last_pos || !t->coverage || !t->seq_off || !t->seq || !t->link_from || !t->link_to) throw Error{E_ARG, "out of host memory"};
+        memcpy(t->head_pos, pin.p + o_hp, 4 * (size_t)ns); memcpy(t->head_var, pin.p + o_hv, 4 * (size_t)ns); memcpy(t->n_nodes, pin.p + o_ln, 4 * (size_t)ns);
+        memcpy(t->last_pos, pin.p + o_lp, 4 * (size_t)ns); memcpy(t->coverage, pin.p + o_cov, 8 * (size_t)ns); memcpy(t->link_to, pin.p + o_lt, 4 * (size_t)nl); memcpy(t->seq, pin.p + o_seq, nb);
+        t->seq[nb] = 0;
+        const agx_u32 *so = (const agx_u32 *)(pin.p + o_so), *lo = (const agx_u32 *)(pin.p + o_lo);
+        for (size_t g = 0; g <= ns; g++) t->seq_off[g] = so[g];      // (a unit's nodes are counted in 32 bits, so are its bases)
+        for (size_t g = 0; g < ns; g++) {
+            if (lo[g] > lo[g + 1] || lo[g + 1] > nl) throw Error{E_DEVICE, "unitigs: link offsets out of range"};
+            for (agx_u32 i = lo[g]; i < lo[g + 1]; i++) t->link_from[i] = (uint32_t)g;
+        }
+    });
+    if (rc != AGX_OK) agx_unitigs_free(t);
+    return rc;
 }
 
 int agx_run_unit(const agx_params *p, const char *tmp_dir, int unit, int write_files, agx_result *r, char *err, size_t err_len) {

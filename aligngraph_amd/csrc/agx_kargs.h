@@ -47,6 +47,37 @@ struct agx_edge_kargs {
     const agx_u32 *abort;                      // the node sweeps' status word: non-zero = the node table is incomplete, do nothing
     const agx_u32 *big_list; const agx_u32 *big_n;   // tiles the fallback pass wrote (their edges are all pass A/B's)
 };
+// Unitig export (agx_unitig.hip): reads the node table a build left in HBM, writes only its own scratch.  Slot arrays are [pool_cap], piece arrays
+// [piece_cap], segment arrays [piece_cap + 1] (every unitig head is a piece start, so there are never more segments than pieces).
+struct agx_unitig_args {
+    const agx_u32 *node_start; const agx_u16 *node_cnt; const agx_u8 *n_flags; const agx_u8 *n_base; const agx_u32 *n_next; const int *n_counts; const char *ref;
+    const agx_edge_ovf *ovf; agx_u32 n_ovf; agx_u32 n_pos, pool_cap;
+    agx_u32 *err;                   // bit 0: an edge that does not lead to a later position; bit 1: a slot index outside the pool; bit 2: the piece lists disagree
+    // per slot
+    agx_u32 *pos_of;                // position of every used slot (NONE: not a node)
+    agx_u32 *indeg;                 // alive in-degree (distinct predecessors), reused as the slot's segment once heads are known
+    agx_u32 *outs;                  // alive successors among the four inline slots, then the whole alive out-degree
+    agx_u32 *succ;                  // the last alive inline successor, reused as the piece id of piece starts
+    agx_u32 *oout, *osucc;          // distinct alive successors on the overflow list / the last of them (osucc reused as the node's rank in its unitig)
+    agx_u32 *nxt;                   // the internal edge out of the node, or NONE
+    agx_u8 *haspred;                // 1: the node has an internal predecessor
+    // overflow list
+    unsigned long long *ovf_hash; agx_u32 hash_mask; agx_u8 *ovf_first;      // open-addressing set of (src, dst): ovf_first[i] = entry i is the first of its edge
+    // pieces (runs of slot+1 internal edges inside a 64-slot window)
+    agx_u32 piece_cap;
+    agx_u32 *wcnt, *woff;  // [pool_cap / 64 + 1] pieces per 64-slot window and their exclusive scan (a piece's id: its window's offset + its rank there)
+    agx_u32 *p_len, *p_next;                           // nodes, the piece its last node's internal edge enters (slot, then piece id)
+    agx_u32 *anc[2], *off[2];                          // pointer jumping: ancestor piece and the nodes in between (ping-pong)
+    agx_u32 *p_seg;                                    // segment of a head piece
+    // heads and segments
+    agx_u32 *hcnt, *hoff;                              // [n_pos + 1] heads per position, exclusive scan
+    agx_u32 *s_len, *s_links, *s_hpos, *s_hvar, *s_last; unsigned long long *s_cov;
+    agx_u32 *s_off, *l_off, *l_cur;                    // scans of s_len / s_links, cursor of each segment's links
+    char *seq; agx_u32 seq_cap;
+    agx_u32 *l_to; agx_u32 link_cap;
+    agx_u32 *scan_tmp;                                 // the multi-launch scans' block sums (the export's scans run one after another on its stream)
+};
+
 #define AGX_SLOW_WAVES 8192u    // wavefronts of the per-hit edge pass if the occupancy query fails (normally: as many as are resident at once)
 
 extern "C" {
@@ -100,5 +131,10 @@ void agx_launch_special(const agx_compact_args *, agx_u32 n_words, agx_u32 *sp_r
 #define AGX_MID_WAVES 3072u     // wavefronts of pass 1 (3 per SIMD fit its LDS buckets); they stride over the list of tiles pass 0 gave up on
 #define AGX_BIG_WAVES 256u      // resident wavefronts of the global-scratch fallback pass
 #define AGX_HUGE_WAVES 32u      // wavefronts of pass 3 (0.85 MB of scratch each)
+// unitig export: phase 1 (degrees, internal edges, pieces), phase 2 (piece ranks, heads, segments, links).  The host reads the piece count between them.
+void agx_launch_unitig_phase1(const agx_unitig_args *, hipStream_t);
+void agx_launch_unitig_phase2(const agx_unitig_args *, agx_u32 rounds, hipStream_t);
+void agx_launch_unitig_phase3(const agx_unitig_args *, hipStream_t);      // bases and links, once the scans are in (the host sized seq / links from them)
+void agx_launch_unitig_totals(const agx_unitig_args *, agx_u32 *tot, hipStream_t);      // tot[0..3] = segments, bases, links, error word
 void agx_launch_node_sweep_huge(const agx_node_kargs *, hipStream_t);
 }

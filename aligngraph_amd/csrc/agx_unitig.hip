@@ -1,0 +1,304 @@
+// agx_unitig.hip — gfx950 kernels of the unitig export (agx_unit_unitigs).
+//
+// They read the node table a build leaves in HBM (node_start / node_cnt, n_flags, n_next with the overflow list, n_base, the counts, ref) and write
+// only their own scratch.  A node is alive when the build did not prune it (AGX_NF_DEAD clear); an alive edge joins two alive nodes; an edge u -> v is
+// INTERNAL when u has one alive successor, v one alive predecessor and u != v; a unitig is a maximal path of internal edges.  Every edge the build
+// makes goes from a position to a later one, so the alive graph is a DAG and every unitig has one head; the degree kernels check that where they
+// look at the edges anyway and set a bit of the error word instead of trusting it.
+//
+// Shape: one pass over positions for degrees and internal edges; the nodes in slot order, a wavefront per 64 slots, cut into PIECES (runs of
+// u -> u+1 internal edges inside the window: the common case, since a position's single variant sits one slot behind its predecessor's); the
+// pieces ranked by pointer jumping in ceil(log2 pieces) + 1 rounds (no spins, no grid-wide barrier); heads compacted in (position, variant) order
+// by a scan over positions; segment lengths and link counts scanned for the offsets; then every node writes its base and every tail its links.
+// Every loop is bounded by a count the kernel read, and every store is checked against the capacity of what it writes.  The scans are the multi-launch
+// form (agx_launch_exclusive_scan): nothing here spins, whatever builds run beside an export on the same device.
+#include <hip/hip_runtime.h>
+#include "agx_kargs.h"
+
+namespace {
+
+__device__ __forceinline__ bool ut_alive(const agx_unitig_args &A, agx_u32 slot) { return !(A.n_flags[slot] & AGX_NF_DEAD); }
+
+// pos_of[slot] for every used slot (pos_of was set to NONE before)
+__global__ void __launch_bounds__(256) agx_k_ut_pos(agx_unitig_args A) {
+    const agx_u32 X = blockIdx.x * 256u + threadIdx.x;
+    if (X >= A.n_pos) return;
+    const agx_u32 s = A.node_start[X], n = A.node_cnt[X];
+    for (agx_u32 v = 0; v < n; v++) {
+        if (s + v >= A.pool_cap) { atomicOr(A.err, 2u); return; }
+        A.pos_of[s + v] = X;
+    }
+}
+
+// alive successors among the inline slots (distinct by construction: the build inserts into them as a set) and the in-degree they give
+__global__ void __launch_bounds__(256) agx_k_ut_degrees(agx_unitig_args A) {
+    const agx_u32 X = blockIdx.x * 256u + threadIdx.x;
+    if (X >= A.n_pos) return;
+    const agx_u32 s = A.node_start[X], n = A.node_cnt[X];
+    for (agx_u32 v = 0; v < n && s + v < A.pool_cap; v++) {
+        const agx_u32 u = s + v;
+        if (!ut_alive(A, u)) continue;
+        const uint4 nx = *reinterpret_cast<const uint4 *>(A.n_next + (size_t)u * AGX_MAXE);
+        const agx_u32 t[AGX_MAXE] = {nx.x, nx.y, nx.z, nx.w};
+        agx_u32 cnt = 0, last = AGX_NONE;
+        for (agx_u32 e = 0; e < AGX_MAXE; e++) {
+            if (t[e] == AGX_NONE) continue;
+            if (t[e] >= A.pool_cap) { atomicOr(A.err, 2u); continue; }
+            if (!ut_alive(A, t[e])) continue;
+            const agx_u32 tp = A.pos_of[t[e]];
+            if (tp == AGX_NONE || tp <= X) { atomicOr(A.err, 1u); continue; }
+            cnt++; last = t[e];
+            atomicAdd(A.indeg + t[e], 1u);
+        }
+        A.outs[u] = cnt; A.succ[u] = last;
+    }
+}
+
+// the overflow list: an edge may be listed more than once (two lanes that inserted it at the same time); the first to enter the hash set counts it
+__global__ void __launch_bounds__(256) agx_k_ut_ovf(agx_unitig_args A) {
+    const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= A.n_ovf) return;
+    A.ovf_first[i] = 0;
+    const agx_u32 s = A.ovf[i].src, d = A.ovf[i].dst;
+    if (s == AGX_NONE || d == AGX_NONE) return;
+    if (s >= A.pool_cap || d >= A.pool_cap) { atomicOr(A.err, 2u); return; }
+    if (!ut_alive(A, s) || !ut_alive(A, d)) return;
+    const agx_u32 sp = A.pos_of[s], dp = A.pos_of[d];
+    if (sp == AGX_NONE || dp == AGX_NONE || dp <= sp) { atomicOr(A.err, 1u); return; }
+    const unsigned long long key = ((unsigned long long)s << 32) | d;
+    agx_u32 h = (agx_u32)((key * 0x9E3779B97F4A7C15ull) >> 32) & A.hash_mask;
+    for (agx_u32 probe = 0; probe <= A.hash_mask; probe++) {          // (the set holds twice the list: a free cell is always found)
+        const unsigned long long old = atomicCAS(A.ovf_hash + h, ~0ull, key);
+        if (old == key) return;
+        if (old == ~0ull) {
+            A.ovf_first[i] = 1;
+            atomicAdd(A.indeg + d, 1u); atomicAdd(A.oout + s, 1u); A.osucc[s] = d;      // (osucc is only read where oout == 1)
+            return;
+        }
+        h = (h + 1u) & A.hash_mask;
+    }
+}
+
+// internal edges: nxt[u] = the one alive successor if it has one alive predecessor; outs[u] becomes the whole alive out-degree
+__global__ void __launch_bounds__(256) agx_k_ut_internal(agx_unitig_args A) {
+    const agx_u32 X = blockIdx.x * 256u + threadIdx.x;
+    if (X >= A.n_pos) return;
+    const agx_u32 s = A.node_start[X], n = A.node_cnt[X];
+    for (agx_u32 v = 0; v < n && s + v < A.pool_cap; v++) {
+        const agx_u32 u = s + v;
+        agx_u32 nx = AGX_NONE;
+        if (ut_alive(A, u)) {
+            const agx_u32 a = A.outs[u], b = A.oout[u], d = a + b;
+            const agx_u32 t = d != 1u ? AGX_NONE : a == 1u ? A.succ[u] : A.osucc[u];
+            if (t != AGX_NONE && t < A.pool_cap && A.indeg[t] == 1u) { nx = t; A.haspred[t] = 1; }
+            A.outs[u] = d;
+        }
+        A.nxt[u] = nx; A.succ[u] = AGX_NONE;          // (succ becomes the piece id of piece starts)
+    }
+}
+
+// a 64-slot window: which lanes are alive nodes, which continue into the next slot (internal edge u -> u+1), which start a piece
+struct ut_window { agx_u32 u, lane, nx; bool valid, link; unsigned long long lm, sm; };
+__device__ __forceinline__ ut_window ut_window_of(const agx_unitig_args &A) {
+    ut_window w;
+    w.u = blockIdx.x * 256u + threadIdx.x; w.lane = threadIdx.x & 63u;
+    w.valid = w.u < A.pool_cap && A.pos_of[w.u] != AGX_NONE && ut_alive(A, w.u);
+    w.nx = w.valid ? A.nxt[w.u] : AGX_NONE;
+    w.link = w.valid && w.lane < 63u && w.nx == w.u + 1u;
+    w.lm = __ballot(w.link);
+    const bool prev = w.lane > 0 && ((w.lm >> (w.lane - 1u)) & 1ull);
+    w.sm = __ballot(w.valid && !prev);
+    return w;
+}
+
+__global__ void __launch_bounds__(256) agx_k_ut_piece_count(agx_unitig_args A) {
+    const ut_window w = ut_window_of(A);
+    if (w.lane == 0 && w.u < A.pool_cap) A.wcnt[w.u / 64u] = (agx_u32)__popcll(w.sm);
+}
+// (the ids come from a scan of the windows' counts: one atomic counter per wavefront cost 5.6 ms on a 30 Mb unit, every wavefront waiting for the same address)
+__global__ void __launch_bounds__(256) agx_k_ut_pieces(agx_unitig_args A) {
+    const ut_window w = ut_window_of(A);
+    const bool start = (w.sm >> w.lane) & 1ull;
+    const agx_u32 end = w.lane + (agx_u32)__builtin_ctzll(~w.lm >> w.lane);      // (bit 63 of ~lm is always set)
+    const agx_u32 nx_end = __shfl(w.nx, (int)end, 64);
+    if (!start) return;
+    const agx_u32 pid = A.woff[w.u / 64u] + (agx_u32)__popcll(w.sm & ((1ull << w.lane) - 1ull));
+    if (pid >= A.piece_cap) { atomicOr(A.err, 4u); return; }
+    A.p_len[pid] = end - w.lane + 1u; A.p_next[pid] = nx_end; A.succ[w.u] = pid;
+}
+
+// pointer jumping over the pieces: anc = predecessor piece (self for a head), off = nodes of the predecessor
+__global__ void __launch_bounds__(256) agx_k_ut_jump_init(agx_unitig_args A, agx_u32 np) {
+    const agx_u32 p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= np) return;
+    A.anc[0][p] = p; A.off[0][p] = 0;
+}
+__global__ void __launch_bounds__(256) agx_k_ut_jump_link(agx_unitig_args A, agx_u32 np) {
+    const agx_u32 p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= np) return;
+    const agx_u32 t = A.p_next[p];
+    if (t == AGX_NONE) return;
+    const agx_u32 q = t < A.pool_cap ? A.succ[t] : AGX_NONE;       // (the target of an internal edge that leaves a piece always starts one)
+    if (q >= np) { atomicOr(A.err, 4u); return; }
+    A.anc[0][q] = p; A.off[0][q] = A.p_len[p];
+}
+__global__ void __launch_bounds__(256) agx_k_ut_jump(agx_unitig_args A, agx_u32 np, agx_u32 r) {
+    const agx_u32 p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= np) return;
+    const agx_u32 *ai = A.anc[r & 1u], *oi = A.off[r & 1u];
+    agx_u32 *ao = A.anc[(r & 1u) ^ 1u], *oo = A.off[(r & 1u) ^ 1u];
+    const agx_u32 a = ai[p];
+    if (a == p || a >= np) { ao[p] = a; oo[p] = oi[p]; return; }
+    ao[p] = ai[a]; oo[p] = oi[p] + oi[a];
+}
+
+// heads: alive nodes without an internal predecessor, counted per position and numbered in (position, variant) order
+__global__ void __launch_bounds__(256) agx_k_ut_head_count(agx_unitig_args A) {
+    const agx_u32 X = blockIdx.x * 256u + threadIdx.x;
+    if (X >= A.n_pos) return;
+    const agx_u32 s = A.node_start[X], n = A.node_cnt[X];
+    agx_u32 c = 0;
+    for (agx_u32 v = 0; v < n && s + v < A.pool_cap; v++) c += (ut_alive(A, s + v) && !A.haspred[s + v]) ? 1u : 0u;
+    A.hcnt[X] = c;
+}
+__global__ void __launch_bounds__(256) agx_k_ut_head_assign(agx_unitig_args A, agx_u32 np) {
+    const agx_u32 X = blockIdx.x * 256u + threadIdx.x;
+    if (X >= A.n_pos) return;
+    const agx_u32 s = A.node_start[X], n = A.node_cnt[X];
+    agx_u32 seg = A.hoff[X];
+    for (agx_u32 v = 0; v < n && s + v < A.pool_cap; v++) {
+        const agx_u32 u = s + v;
+        if (!ut_alive(A, u) || A.haspred[u]) continue;
+        const agx_u32 p = A.succ[u];
+        if (p >= np || seg >= A.piece_cap) { atomicOr(A.err, 4u); return; }
+        A.p_seg[p] = seg; A.s_hpos[seg] = X; A.s_hvar[seg] = v;
+        seg++;
+    }
+}
+
+// every node: its segment and rank; every tail: its segment's length, last position and link count; coverage summed per piece, one atomic per piece
+__global__ void __launch_bounds__(256) agx_k_ut_rank(agx_unitig_args A, agx_u32 np, agx_u32 fin) {
+    const ut_window w = ut_window_of(A);
+    const unsigned long long below = w.sm & ((2ull << w.lane) - 1ull);
+    const agx_u32 ps = below ? 63u - (agx_u32)__builtin_clzll(below) : 0u;
+    const bool start = (w.sm >> w.lane) & 1ull;
+    const agx_u32 pid_here = start ? A.succ[w.u] : AGX_NONE;
+    const agx_u32 pid = __shfl(pid_here, (int)ps, 64);
+    unsigned long long cov = w.valid ? (unsigned long long)(agx_u32)A.n_counts[(size_t)w.u * 6] : 0ull, incl = cov;
+    for (agx_u32 d = 1; d < 64u; d <<= 1) { const unsigned long long o = __shfl_up(incl, d, 64); if (w.lane >= d) incl += o; }
+    const unsigned long long excl_ps = __shfl(incl - cov, (int)ps, 64);
+    if (!w.valid) return;
+    if (pid >= np) { atomicOr(A.err, 4u); return; }
+    const agx_u32 h = A.anc[fin][pid];
+    if (h >= np || A.anc[fin][h] != h) { atomicOr(A.err, 4u); return; }       // (not converged: impossible on a DAG)
+    const agx_u32 seg = A.p_seg[h];
+    if (seg >= A.piece_cap) { atomicOr(A.err, 4u); return; }
+    const agx_u32 rank = A.off[fin][pid] + (w.lane - ps);
+    A.indeg[w.u] = seg; A.osucc[w.u] = rank;
+    if (!w.link) atomicAdd(A.s_cov + seg, incl - excl_ps);            // the piece's last node
+    if (w.nx == AGX_NONE) { A.s_len[seg] = rank + 1u; A.s_last[seg] = A.pos_of[w.u]; A.s_links[seg] = A.outs[w.u]; }
+}
+
+__global__ void agx_k_ut_totals(agx_unitig_args A, agx_u32 *tot) {
+    if (threadIdx.x || blockIdx.x) return;
+    const agx_u32 ns = A.hoff[A.n_pos];
+    tot[0] = ns; tot[1] = ns <= A.piece_cap ? A.s_off[ns] : 0u; tot[2] = ns <= A.piece_cap ? A.l_off[ns] : 0u; tot[3] = *A.err;
+}
+
+// bases at s_off[seg] + rank; a tail's inline links (the overflow list's follow in agx_k_ut_links_ovf)
+__global__ void __launch_bounds__(256) agx_k_ut_emit(agx_unitig_args A) {
+    const agx_u32 X = blockIdx.x * 256u + threadIdx.x;
+    if (X >= A.n_pos) return;
+    const agx_u32 s = A.node_start[X], n = A.node_cnt[X];
+    const agx_u32 ns = A.hoff[A.n_pos];
+    for (agx_u32 v = 0; v < n && s + v < A.pool_cap; v++) {
+        const agx_u32 u = s + v;
+        if (!ut_alive(A, u)) continue;
+        const agx_u32 seg = A.indeg[u], rank = A.osucc[u];
+        if (seg >= ns) { atomicOr(A.err, 4u); continue; }
+        const agx_u32 at = A.s_off[seg] + rank;
+        const char c = (char)A.n_base[u];
+        if (at < A.s_off[seg + 1] && at < A.seq_cap) A.seq[at] = c != 'X' ? c : A.ref[X];       // consensus, else the reference base (AG:1997-2001)
+        else atomicOr(A.err, 4u);
+        if (A.nxt[u] != AGX_NONE) continue;
+        const agx_u32 lo = A.l_off[seg], hi = A.l_off[seg + 1];
+        const uint4 nx = *reinterpret_cast<const uint4 *>(A.n_next + (size_t)u * AGX_MAXE);
+        const agx_u32 t[AGX_MAXE] = {nx.x, nx.y, nx.z, nx.w};
+        agx_u32 k = 0;
+        for (agx_u32 e = 0; e < AGX_MAXE; e++) {
+            if (t[e] == AGX_NONE || t[e] >= A.pool_cap || !ut_alive(A, t[e])) continue;
+            if (lo + k < hi && lo + k < A.link_cap) A.l_to[lo + k] = A.indeg[t[e]]; else atomicOr(A.err, 4u);
+            k++;
+        }
+        A.l_cur[seg] = k;
+    }
+}
+__global__ void __launch_bounds__(256) agx_k_ut_links_ovf(agx_unitig_args A) {
+    const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= A.n_ovf || !A.ovf_first[i]) return;
+    const agx_u32 s = A.ovf[i].src, d = A.ovf[i].dst;                 // (both alive and in the pool: agx_k_ut_ovf)
+    if (A.nxt[s] == d) return;                                          // the internal edge of a node whose only successor is on the list
+    const agx_u32 seg = A.indeg[s], ns = A.hoff[A.n_pos];
+    if (seg >= ns) { atomicOr(A.err, 4u); return; }
+    const agx_u32 at = A.l_off[seg] + atomicAdd(A.l_cur + seg, 1u);
+    if (at < A.l_off[seg + 1] && at < A.link_cap) A.l_to[at] = A.indeg[d]; else atomicOr(A.err, 4u);
+}
+// each segment's links by target segment (link_from is filled on the host from the offsets) (a few per tail; the overflow list's nodes have more), insertion sort in the segment's own range
+__global__ void __launch_bounds__(256) agx_k_ut_links_sort(agx_unitig_args A) {
+    const agx_u32 g = blockIdx.x * 256u + threadIdx.x;
+    const agx_u32 ns = A.hoff[A.n_pos];
+    if (g >= ns) return;
+    const agx_u32 lo = A.l_off[g], hi = A.l_off[g + 1] < A.link_cap ? A.l_off[g + 1] : A.link_cap;
+    for (agx_u32 i = lo; i < hi; i++) {
+        const agx_u32 x = A.l_to[i];
+        agx_u32 j = i;
+        while (j > lo && A.l_to[j - 1] > x) { A.l_to[j] = A.l_to[j - 1]; j--; }
+        A.l_to[j] = x;
+    }
+}
+
+inline dim3 ut_grid(agx_u32 n) { return dim3((n + 255u) / 256u); }
+
+}  // namespace
+
+extern "C" void agx_launch_unitig_phase1(const agx_unitig_args *A, hipStream_t st) {
+    if (A->n_pos) {
+        hipLaunchKernelGGL(agx_k_ut_pos, ut_grid(A->n_pos), dim3(256), 0, st, *A);
+        hipLaunchKernelGGL(agx_k_ut_degrees, ut_grid(A->n_pos), dim3(256), 0, st, *A);
+    }
+    if (A->n_ovf) hipLaunchKernelGGL(agx_k_ut_ovf, ut_grid(A->n_ovf), dim3(256), 0, st, *A);
+    if (A->n_pos) hipLaunchKernelGGL(agx_k_ut_internal, ut_grid(A->n_pos), dim3(256), 0, st, *A);
+    if (A->pool_cap) {
+        const agx_u32 nwin = (A->pool_cap + 63u) / 64u;
+        hipLaunchKernelGGL(agx_k_ut_piece_count, ut_grid(nwin * 64u), dim3(256), 0, st, *A);
+        agx_launch_exclusive_scan(A->wcnt, A->woff, nwin, A->scan_tmp, st);
+        hipLaunchKernelGGL(agx_k_ut_pieces, ut_grid(nwin * 64u), dim3(256), 0, st, *A);
+    }
+}
+
+extern "C" void agx_launch_unitig_phase2(const agx_unitig_args *A, agx_u32 rounds, hipStream_t st) {
+    const agx_u32 np = A->piece_cap;
+    if (np) {
+        hipLaunchKernelGGL(agx_k_ut_jump_init, ut_grid(np), dim3(256), 0, st, *A, np);
+        hipLaunchKernelGGL(agx_k_ut_jump_link, ut_grid(np), dim3(256), 0, st, *A, np);
+        for (agx_u32 r = 0; r < rounds; r++) hipLaunchKernelGGL(agx_k_ut_jump, ut_grid(np), dim3(256), 0, st, *A, np, r);
+    }
+    if (A->n_pos) {
+        hipLaunchKernelGGL(agx_k_ut_head_count, ut_grid(A->n_pos), dim3(256), 0, st, *A);
+        agx_launch_exclusive_scan(A->hcnt, A->hoff, A->n_pos, A->scan_tmp, st);
+        hipLaunchKernelGGL(agx_k_ut_head_assign, ut_grid(A->n_pos), dim3(256), 0, st, *A, np);
+    }
+    if (np) hipLaunchKernelGGL(agx_k_ut_rank, ut_grid((A->pool_cap + 63u) / 64u * 64u), dim3(256), 0, st, *A, np, rounds & 1u);
+    agx_launch_exclusive_scan(A->s_len, A->s_off, np, A->scan_tmp, st);
+    agx_launch_exclusive_scan(A->s_links, A->l_off, np, A->scan_tmp, st);
+}
+
+extern "C" void agx_launch_unitig_phase3(const agx_unitig_args *A, hipStream_t st) {
+    if (A->n_pos) hipLaunchKernelGGL(agx_k_ut_emit, ut_grid(A->n_pos), dim3(256), 0, st, *A);
+    if (A->n_ovf) hipLaunchKernelGGL(agx_k_ut_links_ovf, ut_grid(A->n_ovf), dim3(256), 0, st, *A);
+    if (A->piece_cap) hipLaunchKernelGGL(agx_k_ut_links_sort, ut_grid(A->piece_cap), dim3(256), 0, st, *A);
+}
+
+extern "C" void agx_launch_unitig_totals(const agx_unitig_args *A, agx_u32 *tot, hipStream_t st) {
+    hipLaunchKernelGGL(agx_k_ut_totals, dim3(1), dim3(64), 0, st, *A, tot);
+}

@@ -133,6 +133,22 @@ typedef struct {
     uint32_t *edge_dst;     /* [n_edges] sorted per node */
 } agx_graph;
 
+/* A unit's pruned graph compacted into unitigs (maximal paths of internal edges: u -> v with one alive successor of u, one alive
+ * predecessor of v), for GFA export.  Segments are in the order of their head nodes (position, then variant in agx_unit_graph's
+ * order); links are the alive edges that are not internal, by (from, to) segment.  malloc'd; free with agx_unitigs_free. */
+typedef struct {
+    uint32_t n_segs, n_links;
+    uint64_t n_bases;       /* = seq_off[n_segs] */
+    uint32_t *head_pos;     /* [n_segs] position of the head node */
+    uint32_t *head_var;     /* [n_segs] its variant index at that position */
+    uint32_t *n_nodes;      /* [n_segs] nodes (= bases) of the segment */
+    uint32_t *last_pos;     /* [n_segs] position of the last node */
+    uint64_t *coverage;     /* [n_segs] sum of the nodes' coverage */
+    uint64_t *seq_off;      /* [n_segs + 1] segment s is seq[seq_off[s] .. seq_off[s+1]) */
+    char *seq;              /* [n_bases] one base per node: the consensus, or the reference base where the node has no votes */
+    uint32_t *link_from, *link_to;   /* [n_links] segment indexes */
+} agx_unitigs;
+
 /* ---- entry points ------------------------------------------------------------------------------------ */
 
 const char *agx_version(void);
@@ -193,6 +209,13 @@ void agx_pool_trim(int device);                  /* device >= 0: frees the cache
 int agx_unit_stats(const agx_unit *u, agx_stats *s);
 int agx_unit_graph(agx_unit *u, agx_graph *g);   /* after agx_unit_build */
 void agx_graph_free(agx_graph *g);
+/* After agx_unit_build of a unit created with AGX_FLAG_KEEP_COUNTS, before agx_unit_trim / agx_unit_release (AGX_FLAG_ONE_SHOT units: before their download
+ * or finish).  Runs on the device over the node table the build left there and changes nothing the walk reads.  AGX_E_ARG otherwise. */
+int agx_unit_unitigs(agx_unit *u, agx_unitigs *t);
+void agx_unitigs_free(agx_unitigs *t);
+/* Host only: the S and L lines of GFA 1.0 for unit `unit` (no header line), as DESIGN.md §11 defines them; *text is malloc'd, free it with agx_text_free. */
+int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len);
+void agx_text_free(char *text);
 
 /* The five-call seam in one call.  write_files != 0 also writes the three files under tmp_dir like the reference does. */
 int agx_run_unit(const agx_params *p, const char *tmp_dir, int unit, int write_files, agx_result *r, char *err, size_t err_len);
