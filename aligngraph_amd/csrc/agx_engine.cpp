@@ -305,7 +305,7 @@ struct agx_unit {
     PBuf<char> h_a_str; PBuf<agx_u8> h_a_meta; PBuf<agx_u32> h_side_xpos, h_sp_rank; PBuf<unsigned long long> h_sp_bits;
     PBuf<agx_walknode> h_sp_node, h_fetch; PBuf<agx_edge_ovf> h_a_ovf; PBuf<agx_hop> h_sp_hop; DBuf<agx_hop> d_sp_hop;
     PBuf<agx_u32> h_words;
-    agx_u32 n_nodes = 0, n_ovf = 0, n_tiles = 0, n_tile_entries = 0, n_big = 0, n_mid = 0;
+    agx_u32 n_nodes = 0, n_ovf = 0, n_tiles = 0, n_tile_entries = 0, n_big = 0, n_mid = 0, n_slow = 0;
     Boundaries ev; hipEvent_t ev_front = nullptr, ev_passA = nullptr, ev_passJ = nullptr, ev_up0 = nullptr, ev_uploaded = nullptr, ev_dl = nullptr, ev_hits = nullptr;      // ev_hits: everything but the read bases is in HBM
     bool up_timed = false;
     agx_stats stats{};
@@ -1317,7 +1317,7 @@ void do_build(agx_unit *u) {
             else if (w[W_N + 2] > u->sp_cap) { alloc_sparse(u, w[W_N + 2] + w[W_N + 2] / 8 + 1024); again = true; }
         }
         if (again) { HIP_OK(hipEventRecord(u->ev_uploaded, turn.down)); continue; }
-        u->n_nodes = w[W_POOL]; u->n_big = w[W_BIGCOUNT]; u->n_mid = w[W_MIDCOUNT]; u->n_ovf = w[W_OVFCOUNT];
+        u->n_nodes = w[W_POOL]; u->n_big = w[W_BIGCOUNT]; u->n_mid = w[W_MIDCOUNT]; u->n_ovf = w[W_OVFCOUNT]; u->n_slow = w[W_SLOWCOUNT];
         const unsigned long long ids = (unsigned long long)n_pos + w[W_N + 1];
         if (ids >= 0xFFFFFF00ull) throw Error{E_OVERFLOW, "walk graph exceeds 2^32 ids"};
         u->n_ids = (agx_u32)ids; u->n_special = w[W_N + 2];
@@ -1847,7 +1847,7 @@ int agx_unit_stats(const agx_unit *u, agx_stats *s) {
     *s = u->stats;
     const bool st = u->staged || u->consumed;      // (a one-shot unit's staged inputs are gone after its download; their counts are not)
     s->n_pos = st ? u->V.n_pos : u->T.ref.size(); s->n_ref = st ? u->V.n_ref : u->T.n_ref; s->n_hits = st ? u->nh : u->P.hits.size(); s->n_runs = st ? u->n_runs : u->P.runs.size(); s->pinned_bytes_cached = host_cache().held(); s->device_bytes_cached = dev_cache(u->prm.device).held(); s->n_nodes = u->n_nodes;
-    s->n_tiles = u->n_tiles; s->n_tile_entries = u->n_tile_entries; s->n_big_tiles = u->n_big; s->n_mid_tiles = u->n_mid; s->n_edge_overflow = u->n_ovf;
+    s->n_tiles = u->n_tiles; s->n_tile_entries = u->n_tile_entries; s->n_big_tiles = u->n_big; s->n_mid_tiles = u->n_mid; s->n_edge_overflow = u->n_ovf; s->n_edge_slow = u->n_slow;
     s->pairs_in_file = u->pairs_in_file; s->sam_line_pairs = u->sam_pairs;
     return AGX_OK;
 }

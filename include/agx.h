@@ -120,6 +120,8 @@ typedef struct {
                                                                     1024 such hits: every list of the unit was made by scatter (agx_k_bin_fill + agx_k_tile_sort).
                                                                     rows_by_reference: read rows the upload sent as their differences from the reference under their first hit's
                                                                     alignment (AGX_ROW_DIFF, engine: stage_rows; 0: all rows crossed as 2-bit classes) */
+    uint64_t n_edge_slow;                                        /* positions the edge build's pass B resolved hit by hit: multi-variant positions with a step elsewhere, listed by the
+                                                                    node sweep, and the positions pass A found with several variants there or at x+1 */
 } agx_stats;
 
 /* Node/edge tables in canonical numbering (position-major, variant order), for parity tests. malloc'd; free with agx_graph_free. */

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <set>
 #include <string>
 #include <thread>
 #include <vector>
@@ -41,11 +42,27 @@ struct SimGraph {
 
 // What a test may ask of the executor besides the graph: the lean record of every list entry (what pass 0 of the device's node sweep reads, made by the
 // same agx_lean_make_v from the same hits), and pass 0 on packed buckets (agx_bucket::packed: the device's layout, counters as 16-bit halves).
-struct SimOptions { bool packed = false, records = false; };
+// edges: which path of the edge build made each edge (SimEdges), with the slow list as the device makes it.
+struct SimOptions { bool packed = false, records = false, edges = false; };
 struct SimRecords { std::vector<agx_u32> tile_len, recs; };      // recs: per list entry tile, geo, qoff1, boff1, qoff2, boff2, lenjs
 enum { AGX_SIM_REC_WORDS = 7 };
+// The edge build's paths, counted around the serial loop (tests/edge_units.py names them).  Every counter but the slow ones counts what the executor does; the
+// slow positions follow the DEVICE's rule (agx_k_node_sweep lists a multi-variant position of lanes 0..62 with a step elsewhere; agx_k_edge_sweep runs
+// agx_edge_fast_lane for lane 63 of every tile and for lanes 0..62 of the tiles pass 2 or 3 swept): the executor also runs the lane function for the last
+// position of a partial tile, and it sweeps a tile of 3 or 4 variants without the merge, where the device's pass 1 writes its x -> x+1 edges itself.
+enum { SE_MERGE, SE_A_WRITTEN, SE_A_REFUSED, SE_SLOW_SWEEP, SE_SLOW_A, SE_J_INSERTS, SE_B_REG_PAIRS, SE_B_HIT_INSERTS, SE_OVF_APPENDS, SE_OVF_DUP_APPENDS,
+       SE_SLOW_TILE_LEN_MAX, SE_OVF_RUN_MAX, SE_OVF_DISTINCT, SE_A_NOSTEP, SE_N = 16 };
+enum { AGX_SIM_SLOW_WORDS = 9, AGX_SIM_JSTEP_WORDS = 6, AGX_SIM_OVF_WORDS = 4 };
+struct SimEdges {
+    unsigned long long ctr[SE_N] = {};
+    std::vector<agx_u32> slow;      // per slow position (device rule, ascending): X, who (0: the node sweep, 1: pass A), n, n1, register path, tile-list length, pairs the register path found,
+                                    // pairs agx_edge_allowed lets through (register path), inserts through agx_edge_slow_hit
+    std::vector<agx_u32> jsteps;    // per step of a hit that does not go to x+1 (agx_edge_jump_hit's run ends): hit, a runs, X, xs, variants at X, variants at xs
+    std::vector<agx_u32> jins;      // per pass-J insert: position of the source, of the target
+    std::vector<agx_u32> ovf;       // per overflow append, in order: position of the source, of the target, source's variant, 1 if the pair was listed before
+};
 
-void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage, agx_u32 maxv_first, SimGraph &S, int &n_big_tiles, const SimOptions &opt, SimRecords &R) {
+void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage, agx_u32 maxv_first, SimGraph &S, int &n_big_tiles, const SimOptions &opt, SimRecords &R, SimEdges &E) {
     const agx_u32 n_pos = (agx_u32)T.ref.size();
     const agx_u32 n_tiles = (n_pos + AGX_TILE - 1) / AGX_TILE;
     // hit_prep
@@ -211,23 +228,81 @@ void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage,
     S.n_nodes = pool;
     // edge build: pass A (lanes = positions) writes the x -> x+1 edges of single-variant positions and collects the slow positions,
     // pass J (lanes = hits) adds the steps that do not go to x+1, pass B resolves every hit of the slow positions' tiles
+    std::vector<agx_u32> pos_of;                       // (opt.edges: a node's position)
+    if (opt.edges) {
+        pos_of.assign(S.n_nodes, AGX_NONE);
+        for (agx_u32 X = 0; X < n_pos; X++) for (agx_u32 v = 0; v < S.node_cnt[X]; v++) pos_of[S.node_start[X] + v] = X;
+        for (agx_u32 X = 0; X < n_pos; X++) if (S.pos_succ[X] & 0x80u)
+            for (agx_u32 v = 0; v < S.node_cnt[X]; v++) for (agx_u32 e = 0; e < AGX_MAXE; e++) E.ctr[SE_MERGE] += S.next[(size_t)(S.node_start[X] + v) * AGX_MAXE + e] != AGX_NONE;
+    }
+    std::set<std::pair<agx_u32, agx_u32> > listed;     // (opt.edges: every overflow pair so far)
     auto ins = [&](agx_u32 src, agx_u32 dst) {
         agx_u32 *slots = S.next.data() + (size_t)src * AGX_MAXE;
         for (agx_u32 e = 0; e < AGX_MAXE; e++) { if (slots[e] == AGX_NONE) slots[e] = dst; if (slots[e] == dst) return; }
         S.flags[src] |= AGX_NF_EOVF; S.ovf.push_back(agx_edge_ovf{src, dst});
+        if (opt.edges) {
+            const bool again = !listed.insert(std::make_pair(src, dst)).second;
+            E.ctr[SE_OVF_APPENDS]++; E.ctr[SE_OVF_DUP_APPENDS] += again; E.ctr[SE_OVF_DISTINCT] += !again;
+            const agx_u32 w[AGX_SIM_OVF_WORDS] = {pos_of[src], pos_of[dst], src - S.node_start[pos_of[src]], again ? 1u : 0u}; E.ovf.insert(E.ovf.end(), w, w + AGX_SIM_OVF_WORDS);
+        }
     };
     std::vector<agx_u32> slow;
     for (agx_u32 X = 0; X < n_pos; X++) {
         const agx_u32 nbs = X + 1 < n_pos ? S.node_start[X + 1] : 0, nbc = X + 1 < n_pos ? S.node_cnt[X + 1] : 0;
-        if (agx_edge_fast_lane(A, X, S.node_start[X], S.node_cnt[X], nbs, nbc)) slow.push_back(X);
+        const agx_u32 ps = S.pos_succ[X], own = S.node_cnt[X];
+        if (opt.edges && !(ps & 0x80u) && own == 1 && nbc == 1) E.ctr[!(ps & 1u) ? SE_A_NOSTEP : agx_edge_allowed(A, S.node_start[X], nbs) ? SE_A_WRITTEN : SE_A_REFUSED]++;
+        if (agx_edge_fast_lane(A, X, S.node_start[X], own, nbs, nbc)) slow.push_back(X);
     }
-    for (size_t h = 0; h < dh.size(); h++) agx_edge_jump_hit(A, dh[h], ins);
+    std::vector<agx_u32> slow_dev;
+    if (opt.edges) {                                   // the slow list as the device makes it
+        std::vector<agx_u32> tile_max(n_tiles, 0);
+        for (agx_u32 X = 0; X < n_pos; X++) tile_max[X / AGX_TILE] = std::max<agx_u32>(tile_max[X / AGX_TILE], S.node_cnt[X]);
+        for (agx_u32 X = 0; X < n_pos; X++) {
+            const agx_u32 t = X / AGX_TILE, lane = X % AGX_TILE, own = S.node_cnt[X], nbc = X + 1 < n_pos ? S.node_cnt[X + 1] : 0;
+            int who = -1;
+            if (lane == AGX_TILE - 1u || tile_max[t] > AGX_MAXV_MID) { if (own != 0 && (own >= 2 || nbc >= 2)) who = 1; }      // pass A (bit 7 is never set there)
+            else if (X + 1 < n_pos && own >= 2 && (S.pos_succ[X] & 2u)) who = 0;                                               // the node sweep (pass 0 or 1)
+            if (who < 0) continue;
+            agx_slow_ctx c; agx_edge_slow_ctx(A, X, c);
+            const agx_u32 tl = tile_off[t + 1] - tile_off[t];
+            const agx_u32 w[AGX_SIM_SLOW_WORDS] = {X, (agx_u32)who, c.n, c.n1, c.reg, tl, 0u, c.allowed, 0u};
+            E.slow.insert(E.slow.end(), w, w + AGX_SIM_SLOW_WORDS); slow_dev.push_back(X);
+            E.ctr[who ? SE_SLOW_A : SE_SLOW_SWEEP]++; E.ctr[SE_SLOW_TILE_LEN_MAX] = std::max<unsigned long long>(E.ctr[SE_SLOW_TILE_LEN_MAX], tl);
+        }
+        for (size_t h = 0; h < dh.size(); h++) {       // the steps pass J looks at (agx_edge_jump_hit's loop, whatever the node counts)
+            const agx_dhit &d = dh[h];
+            if ((d.flags & AGX_HF_SKIP) || d.a_nruns < 2) continue;
+            for (agx_u32 i = 0; i + 1 < d.a_nruns; i++) {
+                const agx_run r = P.runs[d.a_runs + i];
+                if (r.n == 0 || r.t + r.n - 1 >= n_pos) continue;
+                const agx_u32 X = r.t + r.n - 1;
+                const agx_arrival a = agx_decode_arrival(d, P.runs.data(), X, k);
+                if (!a.has || !a.has_succ || a.xs >= n_pos || a.xs == X + 1) continue;
+                const agx_u32 w[AGX_SIM_JSTEP_WORDS] = {(agx_u32)h, d.a_nruns, X, a.xs, S.node_cnt[X], S.node_cnt[a.xs]};
+                E.jsteps.insert(E.jsteps.end(), w, w + AGX_SIM_JSTEP_WORDS);
+            }
+        }
+    }
+    for (size_t h = 0; h < dh.size(); h++) agx_edge_jump_hit(A, dh[h], [&](agx_u32 src, agx_u32 dst) {
+        if (opt.edges) { E.ctr[SE_J_INSERTS]++; E.jins.push_back(pos_of[src]); E.jins.push_back(pos_of[dst]); }
+        ins(src, dst);
+    });
     for (agx_u32 X : slow) {
         const agx_u32 t = X / AGX_TILE;
         agx_slow_ctx c; agx_edge_slow_ctx(A, X, c);
         agx_u32 pairs = 0;
-        for (agx_u32 i = tile_off[t]; i < tile_off[t + 1]; i++) pairs |= agx_edge_slow_pair(A, c, X, tile_recs[i], true, ins);
-        for (agx_u32 b = 0; b < AGX_SLOW_V * AGX_SLOW_V; b++) if ((pairs >> b) & 1u) ins(c.s + b / AGX_SLOW_V, c.s1 + b % AGX_SLOW_V);
+        agx_u32 hit_ins = 0;
+        for (agx_u32 i = tile_off[t]; i < tile_off[t + 1]; i++) pairs |= agx_edge_slow_pair(A, c, X, tile_recs[i], true, [&](agx_u32 src, agx_u32 dst) { E.ctr[SE_B_HIT_INSERTS]++; hit_ins++; ins(src, dst); });
+        for (agx_u32 b = 0; b < AGX_SLOW_V * AGX_SLOW_V; b++) if ((pairs >> b) & 1u) { E.ctr[SE_B_REG_PAIRS]++; ins(c.s + b / AGX_SLOW_V, c.s1 + b % AGX_SLOW_V); }
+        if (opt.edges) { const auto at = std::lower_bound(slow_dev.begin(), slow_dev.end(), X); if (at != slow_dev.end() && *at == X) { E.slow[(size_t)(at - slow_dev.begin()) * AGX_SIM_SLOW_WORDS + 6] = pairs; E.slow[(size_t)(at - slow_dev.begin()) * AGX_SIM_SLOW_WORDS + 8] = hit_ins; } }
+    }
+    if (opt.edges) {                                   // the longest run of overflowing single-variant sources at consecutive positions of one tile
+        agx_u32 run = 0;
+        for (agx_u32 X = 0; X < n_pos; X++) {
+            const bool o = S.node_cnt[X] == 1 && (S.flags[S.node_start[X]] & AGX_NF_EOVF);
+            run = o ? (X % AGX_TILE && run ? run + 1 : 1) : 0;
+            E.ctr[SE_OVF_RUN_MAX] = std::max<unsigned long long>(E.ctr[SE_OVF_RUN_MAX], run);
+        }
     }
 
     // walk preparation, the same per-element functions the compaction kernels run
@@ -287,9 +362,11 @@ typedef struct {
     uint64_t n_walk_ids, n_special, n_fetched;   // walk graph: ids, records in the sparse table, records read through the fetch hook
     uint32_t n_tiles; uint32_t *tile_len;        // AGX_SIM_RECORDS: each tile's list length,
     uint64_t n_recs; uint32_t *recs;             // and per list entry (in list order) AGX_SIM_REC_WORDS words: tile, geo, qoff1, boff1, qoff2, boff2, lenjs
+    uint64_t edge_ctr[SE_N];                     // AGX_SIM_EDGES: SimEdges
+    uint32_t n_slow, n_jsteps, n_jins, n_ovf; uint32_t *slow, *jsteps, *jins, *ovf;
 } agx_hostsim_result;
 
-enum { AGX_SIM_GRAPH = 1, AGX_SIM_PACKED = 2, AGX_SIM_RECORDS = 4 };
+enum { AGX_SIM_GRAPH = 1, AGX_SIM_PACKED = 2, AGX_SIM_RECORDS = 4, AGX_SIM_EDGES = 8 };
 
 int agx_hostsim_run_unit(const char *tmp_dir, int unit, int k, int iv, int coverage, long batch, int maxv_first, int options, agx_hostsim_result *out) {
     memset(out, 0, sizeof *out);
@@ -304,9 +381,15 @@ int agx_hostsim_run_unit(const char *tmp_dir, int unit, int k, int iv, int cover
             reads_index_close(ri);
         } else load_pairs_from_files(d + "/_reads.fa", d + "/_reads_genome." + u + ".bowtie", batch, (agx_u32)k, P);
         const bool want_graph = (options & AGX_SIM_GRAPH) != 0;
-        SimGraph S; int nbig = 0; SimOptions opt; SimRecords R;
-        opt.packed = (options & AGX_SIM_PACKED) != 0; opt.records = (options & AGX_SIM_RECORDS) != 0;
-        simulate(T, P, (agx_u32)k, iv, coverage, maxv_first > 0 ? (agx_u32)maxv_first : AGX_MAXV_LDS, S, nbig, opt, R);
+        SimGraph S; int nbig = 0; SimOptions opt; SimRecords R; SimEdges E;
+        opt.packed = (options & AGX_SIM_PACKED) != 0; opt.records = (options & AGX_SIM_RECORDS) != 0; opt.edges = (options & AGX_SIM_EDGES) != 0;
+        simulate(T, P, (agx_u32)k, iv, coverage, maxv_first > 0 ? (agx_u32)maxv_first : AGX_MAXV_LDS, S, nbig, opt, R, E);
+        if (opt.edges) {
+            memcpy(out->edge_ctr, E.ctr, sizeof E.ctr);
+            auto give = [](const std::vector<agx_u32> &v, agx_u32 words, uint32_t &n, uint32_t *&p) { n = (uint32_t)(v.size() / words); p = (uint32_t *)malloc(4 * (v.size() + 1)); if (!v.empty()) memcpy(p, v.data(), 4 * v.size()); };
+            give(E.slow, AGX_SIM_SLOW_WORDS, out->n_slow, out->slow); give(E.jsteps, AGX_SIM_JSTEP_WORDS, out->n_jsteps, out->jsteps);
+            give(E.jins, 2, out->n_jins, out->jins); give(E.ovf, AGX_SIM_OVF_WORDS, out->n_ovf, out->ovf);
+        }
         if (opt.records) {
             out->n_tiles = (uint32_t)R.tile_len.size(); out->tile_len = (uint32_t *)malloc(4 * (R.tile_len.size() + 1)); memcpy(out->tile_len, R.tile_len.data(), 4 * R.tile_len.size());
             out->n_recs = R.recs.size() / AGX_SIM_REC_WORDS; out->recs = (uint32_t *)malloc(4 * (R.recs.size() + 1)); memcpy(out->recs, R.recs.data(), 4 * R.recs.size());
@@ -426,6 +509,7 @@ int agx_hostsim_run_unit(const char *tmp_dir, int unit, int k, int iv, int cover
 void agx_hostsim_free(agx_hostsim_result *r) {
     free(r->initial_contigs); free(r->pre_extended); free(r->extended);
     free(r->node_start); free(r->node_key); free(r->node_cnt); free(r->node_slen); free(r->edge_start); free(r->edge_dst); free(r->tile_len); free(r->recs);
+    free(r->slow); free(r->jsteps); free(r->jins); free(r->ovf);
     memset(r, 0, sizeof *r);
 }
 

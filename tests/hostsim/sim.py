@@ -31,10 +31,22 @@ class _Result(ctypes.Structure):
         ("edge_start", ctypes.POINTER(ctypes.c_uint32)), ("edge_dst", ctypes.POINTER(ctypes.c_uint32)),
         ("n_walk_ids", ctypes.c_uint64), ("n_special", ctypes.c_uint64), ("n_fetched", ctypes.c_uint64),
         ("n_tiles", ctypes.c_uint32), ("tile_len", ctypes.POINTER(ctypes.c_uint32)), ("n_recs", ctypes.c_uint64), ("recs", ctypes.POINTER(ctypes.c_uint32)),
+        ("edge_ctr", ctypes.c_uint64 * 16),
+        ("n_slow", ctypes.c_uint32), ("n_jsteps", ctypes.c_uint32), ("n_jins", ctypes.c_uint32), ("n_ovf", ctypes.c_uint32),
+        ("slow", ctypes.POINTER(ctypes.c_uint32)), ("jsteps", ctypes.POINTER(ctypes.c_uint32)), ("jins", ctypes.POINTER(ctypes.c_uint32)), ("ovf", ctypes.POINTER(ctypes.c_uint32)),
     ]
 
 
 REC_FIELDS = ("tile", "geo", "qoff1", "boff1", "qoff2", "boff2", "lenjs")      # the words of one entry of run(..., records=True)["records"]
+# run(..., edges=True): the edge build's counters (SimEdges, agx_hostsim.cpp) and its lists as structured arrays.  Only the slow list and its two counters
+# follow the device's rule; the others count the executor's passes, which sweep a tile of 3 or 4 variants without the merge and so run pass A and
+# pass B over positions whose x -> x + 1 edges the device's pass 1 writes itself (merge, a_written and b_reg_pairs differ from the device's there)
+EDGE_COUNTERS = ("merge", "a_written", "a_refused", "slow_sweep", "slow_a", "j_inserts", "b_reg_pairs", "b_hit_inserts", "ovf_appends", "ovf_dup_appends",
+                 "slow_tile_len_max", "ovf_run_max", "ovf_distinct", "a_nostep")
+SLOW_FIELDS = ("x", "who", "n", "n1", "reg", "tile_len", "pairs", "allowed", "hit_ins")      # who: 0 the node sweep listed it, 1 pass A
+JSTEP_FIELDS = ("hit", "a_nruns", "x", "xs", "cnt_x", "cnt_xs")
+JINS_FIELDS = ("x", "xs")
+OVF_FIELDS = ("x", "xs", "v", "again")
 
 
 _lib = None
@@ -47,10 +59,12 @@ class SimError(RuntimeError):
         self.msg = msg
 
 
-def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, maxv_first=0, graph=False, packed=False, records=False):
+def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, maxv_first=0, graph=False, packed=False, records=False, edges=False):
     """One unit through the serial executor.  packed: pass 0 of the node sweep on packed buckets (AGX_NFP words per variant, the device's layout; a list of more
     than 65 535 entries goes to the next pass).  records: also returns "records", the lean record of every tile-list entry in list order as a structured
-    numpy array with the fields REC_FIELDS, and "tile_len", each tile's list length."""
+    numpy array with the fields REC_FIELDS, and "tile_len", each tile's list length.  edges: also returns "edges", the counters EDGE_COUNTERS of the edge
+    build's paths, "slow" (the slow positions the device lists, ascending; SLOW_FIELDS), "jsteps" (the steps pass J looks at; JSTEP_FIELDS), "jins" (pass J's
+    inserts; JINS_FIELDS) and "ovf" (every overflow append in order; OVF_FIELDS); positions, not node ids."""
     global _lib
     if _lib is None:
         build()
@@ -58,7 +72,7 @@ def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, max
         _lib.agx_hostsim_run_unit.argtypes = [ctypes.c_char_p] + [ctypes.c_int] * 4 + [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_Result)]
         _lib.agx_hostsim_free.argtypes = [ctypes.POINTER(_Result)]
     r = _Result()
-    options = (1 if graph else 0) | (2 if packed else 0) | (4 if records else 0)
+    options = (1 if graph else 0) | (2 if packed else 0) | (4 if records else 0) | (8 if edges else 0)
     rc = _lib.agx_hostsim_run_unit(tmp_dir.encode(), unit, k, insert_variation, coverage, batch, maxv_first, options, ctypes.byref(r))
     if rc != 0:
         msg = r.error.decode()
@@ -72,6 +86,12 @@ def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, max
         flat = np.ctypeslib.as_array(r.recs, shape=(r.n_recs * len(REC_FIELDS),)).copy() if r.n_recs else np.zeros(0, "uint32")
         out["records"] = flat.view([(f, "uint32") for f in REC_FIELDS]).reshape(-1)
         out["tile_len"] = np.ctypeslib.as_array(r.tile_len, shape=(r.n_tiles,)).copy() if r.n_tiles else np.zeros(0, "uint32")
+    if edges:
+        out["edges"] = {n: int(r.edge_ctr[i]) for i, n in enumerate(EDGE_COUNTERS)}
+        for key, names in (("slow", SLOW_FIELDS), ("jsteps", JSTEP_FIELDS), ("jins", JINS_FIELDS), ("ovf", OVF_FIELDS)):
+            n = getattr(r, "n_" + key)
+            flat = np.ctypeslib.as_array(getattr(r, key), shape=(n * len(names),)).copy() if n else np.zeros(0, "uint32")
+            out[key] = flat.view([(f, "uint32") for f in names]).reshape(-1)
     if graph:
         def arr(p, n, dt):
             return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
