@@ -17,7 +17,12 @@ Text parsing of the five per-unit files (T_unit = parse + T_core: the scope of t
 once while the inputs are loaded (a rank's units side by side, each on its share of the CPUs the process can keep busy) and reported beside it
 (`t_unit_s`, `value_t_unit`, `load_ms_per_unit`), and so is loading the units from their binary caches.  `roofline` carries `frac` (bytes the dominant
 kernel cannot avoid / its time / HBM peak), `frac_hbm` (counter traffic), `job_frac` (SURVEY 8(d)'s algorithmic bytes / T_core / peak)
-and a `pcie` block; `cpu_baseline` the reference binary on one CPU and, under `parallel`, one process per usable CPU.
+and a `pcie` block, all from the timed steps' own figures.
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.
+--full adds what takes runs of its own after the timed steps: the kernel sections of the largest unit (`breakdown_ms_largest_unit`,
+`graph_largest_unit`), `cpu_baseline` (the reference binary on one CPU and, under `parallel`, one process per usable CPU; the engine's bytes
+asserted equal to the reference's on that sample) and, at N > 1, the same job on one GPU (below).
 
 Configurations (--config; BASELINE.json `configs`, synthetic data of that shape from tools/agx_synth, seeded):
     cfg3 (default)  A. thaliana shape: 5 units of 30.4 / 19.7 / 23.5 / 18.6 / 27.0 Mb, 20 M 2x100 bp pairs, k=5      <- the north-star 1-GPU target
@@ -29,8 +34,8 @@ Configurations (--config; BASELINE.json `configs`, synthetic data of that shape 
 
 Multi-GPU (driver: torch.distributed.run, one rank per GPU): units are the shard — assigned longest-first to the least
 loaded rank (shard.assign_units), each rank runs its own list, and ONE gather of the extended-contig bytes to rank 0 ends the step
-(RCCL: sizes by all_gather, then exact-size point-to-point sends to the root).  Total work is fixed: "scaling": "strong".  After the timed N-rank steps rank 0 runs the
-same job alone on its GPU (`single_gpu_ms_same_config`, `speedup_vs_1gpu`).
+(RCCL: sizes by all_gather, then exact-size point-to-point sends to the root).  Total work is fixed: "scaling": "strong".  With --full, after the timed N-rank steps
+rank 0 runs the same job alone on its GPU (`single_gpu_ms_same_config`, `speedup_vs_1gpu`).
 
 Prints ONE JSON line on rank 0.
 """
@@ -191,7 +196,11 @@ def main():
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS) + ["custom"],
                     help="default: cfg3 on one GPU (the north-star 1-GPU configuration); with --gpus N > 1: cfg5s, the 24-unit whole-human shard shape (cfg3 has five units: "
                          "three of eight ranks would idle)")
-    ap.add_argument("--same-config-steps", type=int, default=4, help="N > 1: after the timed N-rank steps rank 0 runs the SAME job alone on its GPU for this many steps "
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in runs of their own after the timed steps: the kernel sections of the largest unit, "
+                         "the CPU baseline (--cpu-sample-pairs) and, at N > 1, the same job on one GPU (--same-config-steps).  Off: set up, warm up, time the steps, "
+                         "write --dump-outputs, print the line")
+    ap.add_argument("--same-config-steps", type=int, default=4, help="--full, N > 1: after the timed N-rank steps rank 0 runs the SAME job alone on its GPU for this many steps "
                                                                       "(single_gpu_ms_same_config, speedup_vs_1gpu in the JSON line); 0 = skip")
     ap.add_argument("--host-gb", type=float, default=0.0, help="host memory a rank may hold in staged unit sets; more steps than fit re-upload the same unit objects (as --reupload).  "
                                                                "0 (default): 160 GB or 40 %% of the control group's memory limit, whichever is less, divided by the ranks on this host")
@@ -224,7 +233,7 @@ def main():
                          "buffers).  Default: every step gets its own set of units, loaded from the unit caches before the clock starts and used once "
                          "(AGX_FLAG_ONE_SHOT, what agx_run_unit and AlignGraph_amd do: a unit's download lands in the pinned memory of its dead inputs)")
     ap.add_argument("--inflight", type=int, default=0, help="units in flight per GPU = worker threads (0: all of the rank's units, at most 8)")
-    ap.add_argument("--cpu-sample-pairs", type=int, default=200000, help="pairs in the bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-sample-pairs", type=int, default=200000, help="--full: pairs in the bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--workdir", default=os.environ.get("AGX_BENCH_DIR", "/tmp/agx_bench"))
     ap.add_argument("--keep", action="store_true", help="keep the generated inputs (a later run with the same configuration re-uses them)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -549,7 +558,7 @@ def main():
     single_ms = None
     if dist:
         dist.barrier()
-        if rank == 0 and args.same_config_steps > 0:
+        if rank == 0 and args.full and args.same_config_steps > 0:
             everything = shard.plan(unit_len, 0, 1)
             ms = []
             for it in range(args.same_config_steps + 1):                 # (the first one is a warm-up)
@@ -569,9 +578,9 @@ def main():
                     un.close()
             single_ms = sum(ms) / len(ms)
         dist.barrier()
-    # ---- after the timed region, rank 0: kernel sections of the largest unit (exclusive builds with section events) ----
+    # ---- --full, after the timed region, rank 0: kernel sections of the largest unit (exclusive builds with section events) ----
     kern, big_stats = {}, None
-    if rank == 0 and mine:
+    if rank == 0 and mine and args.full:
         big = max(mine, key=lambda uu: (unit_len[uu], -uu))
         with A.Unit(k=k, insert_variation=50, coverage=args.coverage, device=local_rank, flags=A.AGX_FLAG_TIME_SECTIONS) as ub:
             ub.load_files(tmp, big)
@@ -590,9 +599,9 @@ def main():
                 ub.build()
             kern["ms_resident_rebuild"] = 1e3 * (time.perf_counter() - t1) / 16
 
-    # ---- parity spot-check of what was timed + CPU baseline on rank 0 at N=1: the real reference binary (oracle/_ref, -O2, 1 thread) ----
+    # ---- --full: parity spot-check of what was timed + CPU baseline on rank 0 at N=1: the real reference binary (oracle/_ref, -O2, 1 thread) ----
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_sample_pairs > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_sample_pairs > 0:
         total_len = sum(chroms)
         frac = args.cpu_sample_pairs / float(pairs)
         sg = max(20000, int(total_len * frac))
@@ -683,7 +692,7 @@ def main():
         line = {
             "metric": "aligned reads/sec through graph build+extend", "value": round(value, 1), "unit": "reads/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * sec_per_step, 3),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u32",
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u32", "full": args.full,
             "data": "synthetic" if not share else "synthetic (AGX_BENCH_SHARE_GPU plumbing test: ranks share a GPU, gloo gather)",
             "config": {"workload": label + ", k=%d, --coverage %d, synthetic target at 1%% SNP + 0.1%% indel" % (k, args.coverage)
                        + (" [NON-STANDARD generator options: %s]" % os.environ["AGX_BENCH_SYNTH"] if extra else ""),
@@ -725,7 +734,7 @@ def main():
                                   "note": "host -> HBM and HBM -> host bytes of rank 0's units per job over T_core over 64 GB/s (PCIe 5 x16, one direction): how much of the job the link would be busy if nothing else ran; upload_GBs_largest_unit = the rate of the largest unit's copies alone on the device's upload stream"}},
             "cpu_baseline": cpu,
             "emulated_rank": emu_note,
-            "breakdown_ms_largest_unit": {k2: round(v, 3) for k2, v in kern.items()},
+            "breakdown_ms_largest_unit": {k2: round(v, 3) for k2, v in kern.items()} if args.full else None,
             "breakdown_note": "largest unit of rank 0, exclusive builds with section events after the timed region (4 uploads + first builds); ms_resident_rebuild = r01's headline quantity (rebuild of a resident unit, kernels only)",
             "units": per_unit,
             "host": numa_note,

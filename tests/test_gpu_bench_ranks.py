@@ -1,7 +1,7 @@
 """bench.py's N > 1 code path on the one-GPU box (-m gpu): two ranks that share the device (AGX_BENCH_SHARE_GPU=1: the gather then runs over gloo with
 CPU tensors — RCCL refuses two ranks on one device), launched exactly as the driver launches it (torch.distributed.run, one rank per "GPU").  What the
-job delivers to rank 0 must be, unit by unit, what a one-rank run of the same configuration delivers; the line must carry the same-configuration
-single-GPU time measured in the same run."""
+job delivers to rank 0 must be, unit by unit, what a one-rank run of the same configuration delivers; the line of a --full run must carry the
+same-configuration single-GPU time measured in the same run."""
 import json
 import os
 import socket
@@ -32,7 +32,7 @@ def test_two_ranks_deliver_what_one_rank_delivers(tmp_path, staged, monkeypatch)
               "--cpu-sample-pairs", "0", "--workdir", str(tmp_path / "work")]
     env = dict(os.environ, AGX_BENCH_SHARE_GPU="1", AGX_BENCH_DIGEST=str(tmp_path / "two.json"))
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-config-steps", "2"] + common, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--same-config-steps", "2"] + common, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["units"] == 5

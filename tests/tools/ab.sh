@@ -2,7 +2,7 @@
 # kernel A/B on the GPU box: bench.py once per library variant given (paths relative to the repo root), prints the per-kernel times
 for lib in "$@"; do
   if [ "$lib" = base ]; then unset AGX_LIB_PATH; else export AGX_LIB_PATH=$PWD/$lib; fi
-  timeout 120 python bench.py --steps 96 --cpu-sample-pairs 0 2>/dev/null | python -c "
+  timeout 120 python bench.py --full --steps 96 --cpu-sample-pairs 0 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Copy / kernel overlap from a rocprofv3 trace of bench.py (run on the GPU box):
-    rocprofv3 --kernel-trace --memory-copy-trace -d gpurun_out/ovl -o r --output-format csv -- python bench.py --steps 3 --warmup 1 --cpu-sample-pairs 0 --keep
-    python tests/tools/overlap.py gpurun_out/ovl > profiles/<tag>_overlap.txt
+    rocprofv3 --kernel-trace --memory-copy-trace -d <trace dir> -o r --output-format csv -- python bench.py --full --steps 3 --warmup 1 --cpu-sample-pairs 0 --keep
+    python tests/tools/overlap.py <trace dir> > profiles/<tag>_overlap.txt
 Reports, for the last job of the run: the host-to-device copies (the units' uploads), the kernels, how much of the copy time had a kernel of
 ANOTHER unit's build running beside it, and the busy fractions of the job."""
 import csv

@@ -24,7 +24,7 @@ units = line["units"]
 big = line["graph_largest_unit"]
 per_hit = big["tile_entries"] / big["hits"]
 jobs = 5                                   # profile.sh: --steps 4 --warmup 1
-section_builds = 21                        # bench.py's section pass on the largest unit
+section_builds = 21                        # bench.py --full's section pass on the largest unit
 entries = jobs * sum(u["hits"] for u in units.values()) * per_hit + section_builds * big["tile_entries"]
 builds = jobs * len(units) + section_builds
 out_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")

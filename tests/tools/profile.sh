@@ -6,8 +6,8 @@
 set -u
 tag=${1:-prof}; cfg=${2:-cfg2}; out=$PWD/gpurun_out/$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-B="python bench.py --config $cfg --steps 4 --warmup 1 --cpu-sample-pairs 0 --keep"
-timeout 400 python bench.py --config $cfg --keep > $out/${tag}_bench.json 2> $out/bench.err
+B="python bench.py --full --config $cfg --steps 4 --warmup 1 --cpu-sample-pairs 0 --keep"
+timeout 400 python bench.py --full --config $cfg --keep > $out/${tag}_bench.json 2> $out/bench.err
 timeout 300 rocprofv3 --kernel-trace --stats -d $out/trace -o r --output-format csv -- $B > $out/trace.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $out/fetch -o r --output-format csv -- $B > $out/fetch.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $out/write -o r --output-format csv -- $B > $out/write.log 2>&1

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device timeline of the last timed job of a rocprofv3 trace of bench.py (kernels and copies in start order, offsets from the job's first upload copy):
-    rocprofv3 --kernel-trace --memory-copy-trace -d gpurun_out/tl -o r --output-format csv -- python bench.py --steps 3 --warmup 1 --cpu-sample-pairs 0 --keep
-    python tests/tools/timeline.py gpurun_out/tl [n_units] > profiles/<tag>_timeline.txt"""
+    rocprofv3 --kernel-trace --memory-copy-trace -d <trace dir> -o r --output-format csv -- python bench.py --full --steps 3 --warmup 1 --cpu-sample-pairs 0 --keep
+    python tests/tools/timeline.py <trace dir> [n_units] > profiles/<tag>_timeline.txt"""
 import csv, glob, os, sys
 out = sys.argv[1]; n_units = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 
