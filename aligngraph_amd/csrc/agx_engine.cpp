@@ -281,7 +281,7 @@ struct agx_unit {
     bool pairs_staged = false;          // the fast loader has written hits, runs, codes and the list of other bases straight into the staged buffers
     agx::PairsFile pairs_file;          // the unit's read alignments were handed over staged (tmp/_agx_pairs.<u>.bin, agx_host.h): the mapped file, which the walk takes its k-mer tails from
     // inputs on the device
-    DBuf<agx_u32> d_cm_start, d_cm_cnt; DBuf<agx_cmkey> d_cm; DBuf<agx_cmhead> d_cm_head; DBuf<char> d_ref; DBuf<agx_cmseg> d_segs; DBuf<unsigned long long> d_up_desc;
+    DBuf<agx_u32> d_cm_start; DBuf<agx_cmkey> d_cm; DBuf<agx_cmhead> d_cm_head; DBuf<char> d_ref; DBuf<agx_cmseg> d_segs;
     DBuf<agx_run> d_runs; DBuf<agx_u8> d_codes, d_vcodes; DBuf<unsigned long long> d_other;
     DBuf<agx_u16> d_units; DBuf<agx_u8> d_rowcnt; DBuf<agx_u32> d_blockoff, d_blockfirst, d_anchor;
     DBuf<agx_cntrun> d_cntruns; DBuf<agx_chunk> d_cntchunks, d_segchunks; DBuf<agx_u32> d_jump, d_segindex;
@@ -301,6 +301,7 @@ struct agx_unit {
     DBuf<agx_u8> d_a_meta, d_a_mark; DBuf<agx_walknode> d_fetch, d_sp_node; DBuf<agx_u32> d_a_nid; DBuf<agx_edge_ovf> d_a_ovf; agx_compact_args walk_args{};      // walk_args: the last build's, for record fetches
     DBuf<agx_u32> d_chain_end, d_side_xpos, d_sp_cnt, d_sp_rank; DBuf<unsigned long long> d_sp_bits;
     agx_u32 n_chain_end = 0, n_special = 0, n_words = 0;
+    size_t keep_end = 0;               // where the arrays that outlive the download end in the arena's first block (pool_bufs, fetch_records; do_trim gives back what lies behind)
     // downloaded: the walk graph with its sparse record table (agx_core.h); the full record table stays on the device
     PBuf<char> h_a_str; PBuf<agx_u8> h_a_meta; PBuf<agx_u32> h_side_xpos, h_sp_rank; PBuf<unsigned long long> h_sp_bits;
     PBuf<agx_walknode> h_sp_node, h_fetch; PBuf<agx_edge_ovf> h_a_ovf; PBuf<agx_hop> h_sp_hop; DBuf<agx_hop> d_sp_hop;
@@ -310,6 +311,7 @@ struct agx_unit {
     bool up_timed = false;
     agx_stats stats{};
     ~agx_unit() {
+        arena.reset();                  // (while the views it empties are still there)
         if (pending_walk) g_walks_pending.fetch_sub(1);
         ev.destroy();
         for (hipEvent_t e : {ev_front, ev_passA, ev_passJ, ev_up0, ev_uploaded, ev_dl, ev_built, ev_hits}) if (e) (void)hipEventDestroy(e);
@@ -863,34 +865,68 @@ unsigned long long layout_regions(agx_unit *u, const agx_u32 *demand, agx_u32 ma
     return need;
 }
 
-void alloc_pool(agx_unit *u, agx_u32 cap) {
-    u->pool_cap = cap;
-    DevArena &a = u->arena;
+// ---- a unit's device buffers ---------------------------------------------------------------------------------------------------------
+// Every buffer a unit takes with its block is named ONCE, with its element count, in one of five groups: the groups are what regrows separately.  A group is a function
+// that shows its buffers, in the order they lie in the block, to a Take.  On a const unit that only adds up their bytes (plan_capacities: what the block must hold,
+// whatever the views hold now); with an arena, on a unit that is uploaded or regrown, it also takes them from it (the arena keeps what a regrown group leaves behind until
+// the unit is released) and notes in the unit what the group was sized by.  A new buffer is one line in its group, plus the member.
+struct Take {
+    DevArena *arena = nullptr; size_t bytes = 0;
+    template <class B> void operator()(B &b, size_t count) {
+        bytes += (count * sizeof(*b.p) + 255) & ~(size_t)255;      // (DevArena::take's alignment)
+        if constexpr (!std::is_const_v<B>) if (arena) { b.release(); b.alloc(*arena, count); }
+    }
+    template <class M> void note(M &member, size_t v) { if constexpr (!std::is_const_v<M>) if (arena) member = (M)v; }
+};
+inline size_t codes_bytes(const agx_unit *u) { return u->tiled ? u->nh * (u->stride / 4) : u->n_codes; }      // packed read rows as they are uploaded (tile-ordered: one row per hit)
+inline size_t others_up(const agx_unit *u) { return u->tiled ? u->n_other_t : u->n_other; }
+inline agx_u32 tiles_of(const agx_unit *u) { return (agx_u32)((u->V.n_pos + AGX_TILE - 1) / AGX_TILE); }
+inline agx_u32 regions_of(const agx_unit *u) { return (tiles_of(u) + AGX_REGION_TILES - 1) / AGX_REGION_TILES; }
+inline agx_u32 words_of(const agx_unit *u, agx_u32 pool_cap) { return (agx_u32)((u->V.n_pos + pool_cap) / 64 + 1); }      // 64 walk ids per word of the sparse table's bit vector
+inline size_t scan_desc_of(const agx_unit *u, agx_u32 pool_cap) { return (std::max<size_t>(tiles_of(u), words_of(u, pool_cap)) + 1) / 4096 + 2; }
+
+// the node pool and what is indexed by walk id (side variants <= nodes <= pool_cap)
+template <class U> void pool_bufs(U *u, agx_u32 cap, Take &t) {
+    const size_t n_pos = u->V.n_pos, ids_cap = n_pos + cap, n_words = words_of(u, cap);
+    t.note(u->pool_cap, cap); t.note(u->n_words, n_words); t.note(u->scan_desc_n, scan_desc_of(u, cap));
     const size_t kcap = (size_t)cap + AGX_SLOW_V;      // slack: the edge pass reads whole AGX_SLOW_V-row batches of keys (agx_edge_slow_ctx)
     // First what the host walk may still ask the device for after the download (agx_walk_record through fetch_records: the records of ids outside the sparse table): the walk id
     // and node of every id, and four node arrays — 40 bytes per node slot + 4 per id, a quarter of the unit's block.  They lie at the FRONT of the block so that everything
     // behind them can go back to the device when the download is done (agx_unit_trim), not when the walk is (r05: on the whole-human job a unit's walk takes longer than its
     // upload and build, and the units waiting for room on the device were waiting for walks).
-    const size_t n_pos = u->V.n_pos, ids_cap = n_pos + cap;
-    u->d_aid_of.release(); u->d_aid_of.alloc(a, (size_t)cap + 1); u->d_a_nid.release(); u->d_a_nid.alloc(a, ids_cap + 1);
-    u->d_off0.release(); u->d_off0.alloc(a, kcap); u->d_sref.release(); u->d_sref.alloc(a, cap); u->d_next.release(); u->d_next.alloc(a, (size_t)cap * AGX_MAXE);
-    u->d_fetch.release(); u->d_fetch.alloc(a, 65536);
-    for (auto *b : {&u->d_cid, &u->d_coff, &u->d_cid0, &u->d_coff0}) { b->release(); b->alloc(a, kcap); }
-    u->d_base.release(); u->d_base.alloc(a, cap); u->d_flags.release(); u->d_flags.alloc(a, cap);
-    if (u->prm.flags & AGX_FLAG_KEEP_COUNTS) { u->d_counts.release(); u->d_counts.alloc(a, (size_t)cap * 6); }
-    // walk-graph arrays indexed by walk id: side variants <= nodes <= pool_cap
-    u->d_a_str.release(); u->d_a_str.alloc(a, ids_cap + 1); u->d_a_meta.release(); u->d_a_meta.alloc(a, ids_cap + 16);
-    u->d_a_mark.release(); u->d_a_mark.alloc(a, ids_cap + 2); u->d_side_xpos.release(); u->d_side_xpos.alloc(a, (size_t)cap + 1);
-    u->n_words = (agx_u32)(ids_cap / 64 + 1);
-    u->d_sp_bits.release(); u->d_sp_bits.alloc(a, (size_t)u->n_words + 1); u->d_sp_cnt.release(); u->d_sp_cnt.alloc(a, (size_t)u->n_words + 1);
-    u->d_sp_rank.release(); u->d_sp_rank.alloc(a, (size_t)u->n_words + 2);
-    const size_t nb = ((size_t)std::max<size_t>(n_pos, u->n_words) + 1 + 1023) / 1024;
-    u->d_scan_tmp.release(); u->d_scan_tmp.alloc(a, 2 * (nb + 1) + 2 * ((nb + 1023) / 1024 + 1) + 16);
-    u->scan_desc_n = (std::max<size_t>(u->n_tiles, u->n_words) + 1) / 4096 + 2; u->d_scan_desc.release(); u->d_scan_desc.alloc(a, 3 * u->scan_desc_n);
+    t(u->d_aid_of, (size_t)cap + 1); t(u->d_a_nid, ids_cap + 1); t(u->d_off0, kcap); t(u->d_sref, cap); t(u->d_next, (size_t)cap * AGX_MAXE); t(u->d_fetch, 65536);
+    t.note(u->keep_end, t.arena ? t.arena->first_block_at() : 0);      // (do_trim; ~0: this pool is a regrown one in a later block)
+    t(u->d_cid, kcap); t(u->d_coff, kcap); t(u->d_cid0, kcap); t(u->d_coff0, kcap); t(u->d_base, cap); t(u->d_flags, cap);
+    if (u->prm.flags & AGX_FLAG_KEEP_COUNTS) t(u->d_counts, (size_t)cap * 6);
+    t(u->d_a_str, ids_cap + 1); t(u->d_a_meta, ids_cap + 16); t(u->d_a_mark, ids_cap + 2); t(u->d_side_xpos, (size_t)cap + 1);
+    t(u->d_sp_bits, n_words + 1); t(u->d_sp_cnt, n_words + 1); t(u->d_sp_rank, n_words + 2);
+    const size_t nb = (std::max<size_t>(n_pos, n_words) + 1 + 1023) / 1024;
+    t(u->d_scan_tmp, 2 * (nb + 1) + 2 * ((nb + 1023) / 1024 + 1) + 16); t(u->d_scan_desc, 3 * scan_desc_of(u, cap));      // (descriptors of the three one-launch scans)
 }
-void alloc_lists(agx_unit *u, agx_u32 cap) { u->list_cap = cap; u->d_unsorted.release(); u->d_unsorted.alloc(u->arena, (size_t)cap + 1); u->d_tile_recs.release(); u->d_tile_recs.alloc(u->arena, ((size_t)cap + 4) * 8); }
-void alloc_ovf(agx_unit *u, agx_u32 cap) { u->ovf_cap = cap; u->d_ovf.release(); u->d_ovf.alloc(u->arena, cap); u->d_a_ovf.release(); u->d_a_ovf.alloc(u->arena, (size_t)cap + 1); }
-void alloc_sparse(agx_unit *u, agx_u32 cap) { u->sp_cap = cap; u->d_sp_node.release(); u->d_sp_node.alloc(u->arena, (size_t)cap + 1); u->d_sp_hop.release(); u->d_sp_hop.alloc(u->arena, (size_t)cap + 2); }
+// what never regrows: the inputs in their upload forms, the arrays derived from them per position, tile and hit, scratch, counters
+template <class U> void fixed_bufs(U *u, Take &t) {
+    const size_t n_pos = u->V.n_pos, nh = u->nh, n_tiles = tiles_of(u), n_regions = regions_of(u);
+    t(u->d_cm_start, n_pos + 2); t(u->d_cm, u->n_cm + 1); t(u->d_ref, n_pos + 16); t(u->d_cm_head, n_pos + 1);
+    t(u->d_segs, u->n_segs + 1); t(u->d_cntruns, u->n_cntruns + 1); t(u->d_cntchunks, u->n_cntchunks + 1); t(u->d_segchunks, u->n_segchunks + 1); t(u->d_segindex, u->n_segindex + 1);
+    t(u->d_runs, u->n_runs + 1); t(u->d_vcodes, codes_bytes(u) * 4 + 16); t(u->d_other, others_up(u) + 1);
+    if (u->rows_diffed) { t(u->d_units, u->n_units + 2); t(u->d_rowcnt, u->n_rowcnt); t(u->d_blockoff, u->n_blockoff); t(u->d_blockfirst, u->n_blockfirst); t(u->d_anchor, u->n_anchor); }
+    else t(u->d_codes, codes_bytes(u) + 16);
+    t(u->d_whits, nh + 1); t(u->d_wsides, u->n_sides + 1); t(u->d_wruns, u->n_runs + 1); t(u->d_jump, u->n_jump + 1);
+    if (u->ref_packed) { t(u->d_wref, (n_pos + 3) / 4 + 32); t(u->d_refx, u->n_refx + 1); }
+    t(u->d_dhit, nh + 1);
+    t(u->d_perm, nh + 1); t(u->d_tfirst, n_tiles + 2); t(u->d_ckey, nh + 1); t(u->d_long, AGX_LONG_MAX);
+    t(u->d_tile_cnt, n_tiles + 1); t(u->d_tile_off, n_tiles + 2); t(u->d_cursor, n_tiles + 1);
+    t(u->d_words, W_TOTAL);
+    t(u->d_chain_end, (size_t)u->n_chain_end + 1);
+    t(u->d_node_start, n_pos); t(u->d_node_cnt, n_pos); t(u->d_pos_succ, n_pos); t(u->d_slow_list, n_pos + 64);
+    t(u->d_side_pk, n_pos + 2); t(u->d_tile_side, n_tiles + 2); t(u->d_tile_side_start, n_tiles + 2);
+    t(u->d_big_list, n_tiles + 1); t(u->d_mid_list, n_tiles + 1);
+    t(u->d_scratch, (size_t)AGX_BIG_WAVES * AGX_NF * AGX_MAXV_BIG * 64);
+    t(u->d_region_off, n_regions + 1); t(u->d_pool_cnt, n_regions * AGX_REGION_PAD);
+}
+template <class U> void list_bufs(U *u, agx_u32 cap, Take &t) { t.note(u->list_cap, cap); t(u->d_unsorted, (size_t)cap + 1); t(u->d_tile_recs, ((size_t)cap + 4) * 8); }      // the tile lists
+template <class U> void ovf_bufs(U *u, agx_u32 cap, Take &t) { t.note(u->ovf_cap, cap); t(u->d_ovf, cap); t(u->d_a_ovf, (size_t)cap + 1); }                                  // the edge overflow list
+template <class U> void sparse_bufs(U *u, agx_u32 cap, Take &t) { t.note(u->sp_cap, cap); t(u->d_sp_node, (size_t)cap + 1); t(u->d_sp_hop, (size_t)cap + 2); }               // the sparse record table
 
 void do_release(agx_unit *u);
 
@@ -922,18 +958,18 @@ size_t unitig_layout(size_t cap, size_t n_pos, size_t n_ovf, char *base, agx_uni
 
 // Capacities of a unit's first build and the HBM they add up to (what do_upload reserves as one block; AlignGraph_amd admits a unit to a device by it:
 // agx_unit_hbm_needed).  From the staged counts: positions, hits, runs, conti-mers, read rows.
-struct Plan { agx_u32 pool_cap, list_cap, ovf_cap, sp_cap; size_t total; };
+struct Plan { agx_u32 pool_cap, list_cap, ovf_cap, sp_cap; size_t exact, total; };      // exact: what the five groups take; total: with the room to regrow in and the export's scratch
 // first row of window w's piece of a tile-ordered upload (w = n_win: all rows): the place in the tile order of the first hit of the window's first tile, rounded up to 16 rows —
 // a piece then begins on a 16-byte boundary of the packed classes and on a multiple of 16 bases (agx_k_expand_codes takes 16 bases per thread); the few rows of the next window's
 // hits that ride in this piece only arrive early
 inline size_t win_row(const agx_unit *u, agx_u32 w) { const size_t a = u->rows_diffed ? 63 : 15;      // (rows as differences: whole 64-row blocks of the stream)
     return w == 0 ? 0 : w >= u->n_win ? u->nh : std::min<size_t>(u->nh, ((size_t)u->s_tfirst.p[u->win_tile[w]] + a) & ~a); }
-inline size_t codes_bytes(const agx_unit *u) { return u->tiled ? u->nh * (u->stride / 4) : u->n_codes; }      // packed read rows as they are uploaded (tile-ordered: one row per hit)
-inline size_t others_up(const agx_unit *u) { return u->tiled ? u->n_other_t : u->n_other; }
+// Room behind the exact sum, in the same block: a group that proves too small on the device is taken again at its larger size, and while that fits here the unit stays
+// in ONE block — it holds no more HBM than it was admitted with, and agx_unit_trim can still give its tail back.  A 64th of the unit; the constant is what small units
+// (AGX_TEST_SMALL_CAPS ones above all) regrow in.
+inline size_t regrow_slack(size_t exact) { return exact / 64 + (64u << 10) * 100; }
 Plan plan_capacities(const agx_unit *u) {
     const size_t n_pos = u->V.n_pos, nh = u->nh;
-    const agx_u32 n_tiles = (agx_u32)((n_pos + AGX_TILE - 1) / AGX_TILE), n_regions = (n_tiles + AGX_REGION_TILES - 1) / AGX_REGION_TILES;
-    const size_t n_bases = codes_bytes(u) * 4;
     Plan P;
     const agx_u32 main_cap = (agx_u32)std::min<size_t>(g_tiny ? n_pos / 8 + 64 : n_pos + n_pos / 4 + 4096, 0xE0000000ull);
     P.pool_cap = u->pool_cap ? u->pool_cap : main_cap + spill_min(u);
@@ -943,14 +979,9 @@ Plan plan_capacities(const agx_unit *u) {
     P.ovf_cap = u->ovf_cap ? u->ovf_cap : (g_tiny ? 4u : 1u << 16);
     const size_t ids_cap = n_pos + P.pool_cap;
     P.sp_cap = u->sp_cap ? u->sp_cap : (agx_u32)std::min<size_t>(g_tiny ? 32 : ids_cap / 4 + 4096, 0xFFFFFF00ull);      // special ids: 8 % on the bench unit
-    // what the takes of do_upload add up to, plus the alignment of ~90 buffers
-    const size_t per_pos = 4 + 16 + 1 + 4 + 2 + 1 + 4 + 4, per_tile = 4 * 4 + 4 * 2 + 4 * 2, per_hit_b = sizeof(agx_dhit) + 4 + 4 + 4;      // per hit: derived record, order, last-tile key, (pass J / long list)
-    const size_t per_slot = 5 * 4 + 4 + 4 * AGX_MAXE + 1 + 1 + sizeof(agx_sref) + ((u->prm.flags & AGX_FLAG_KEEP_COUNTS) ? 24 : 0) + 4 + 4, per_id = 1 + 1 + 4 + 1 + 3.0 * 8 / 64 + 1;
-    const size_t wire = nh * sizeof(agx_whit) + u->n_sides * sizeof(agx_wside) + u->n_runs * sizeof(agx_wrun) + u->n_jump * 4 + (u->ref_packed ? n_pos / 4 + u->n_refx * sizeof(agx_refx) : 0) + 4096;
-    const size_t total = wire + n_pos * per_pos + n_tiles * per_tile + nh * per_hit_b + u->n_runs * sizeof(agx_run) + u->n_cm * sizeof(agx_cmkey) + (u->rows_diffed ? u->n_units * 2 + u->n_rowcnt + (u->n_blockoff + u->n_blockfirst + u->n_anchor) * 4 : codes_bytes(u)) + n_bases + others_up(u) * 8 +
-                         (size_t)P.pool_cap * per_slot + ids_cap * per_id + (size_t)P.list_cap * 36 + (size_t)P.ovf_cap * 16 + (size_t)P.sp_cap * (sizeof(agx_walknode) + sizeof(agx_hop)) +
-                         (size_t)AGX_BIG_WAVES * AGX_NF * AGX_MAXV_BIG * 64 * 4 + (size_t)n_regions * AGX_REGION_PAD * 4 + (64u << 10) * 100;
-    P.total = total + total / 64 + ((u->prm.flags & AGX_FLAG_KEEP_COUNTS) ? unitig_layout(P.pool_cap, n_pos, P.ovf_cap, nullptr, nullptr, nullptr) : 0);      // (counts are kept for the unitig export)
+    Take m; pool_bufs(u, P.pool_cap, m); fixed_bufs(u, m); list_bufs(u, P.list_cap, m); ovf_bufs(u, P.ovf_cap, m); sparse_bufs(u, P.sp_cap, m);
+    P.exact = m.bytes;
+    P.total = P.exact + regrow_slack(P.exact) + ((u->prm.flags & AGX_FLAG_KEEP_COUNTS) ? unitig_layout(P.pool_cap, n_pos, P.ovf_cap, nullptr, nullptr, nullptr) : 0);      // (counts are kept for the unitig export)
     return P;
 }
 
@@ -966,32 +997,17 @@ void do_upload(agx_unit *u) {
     HIP_OK(hipSetDevice(u->prm.device));
     const size_t n_pos = u->V.n_pos, nh = u->nh;
     u->arena.device = u->prm.device;
-    u->n_tiles = (agx_u32)((n_pos + AGX_TILE - 1) / AGX_TILE);
-    u->n_regions = (u->n_tiles + AGX_REGION_TILES - 1) / AGX_REGION_TILES;
-    const size_t n_bases = codes_bytes(u) * 4;
+    u->n_tiles = tiles_of(u); u->n_regions = regions_of(u);
     const Plan plan = plan_capacities(u);
-    const agx_u32 pool_cap = plan.pool_cap, list_cap = plan.list_cap, ovf_cap = plan.ovf_cap, sp_cap = plan.sp_cap;
     u->arena.reserve(plan.total);                        // one block for all of it
-    DevArena &a = u->arena;
-    alloc_pool(u, pool_cap);                             // (first: what outlives the download lies at the front of the block, agx_unit_trim)
-    u->d_cm_start.alloc(a, n_pos + 2); u->d_cm.alloc(a, u->n_cm + 1); u->d_ref.alloc(a, n_pos + 16); u->d_cm_head.alloc(a, n_pos + 1);
-    u->d_segs.alloc(a, u->n_segs + 1); u->d_cntruns.alloc(a, u->n_cntruns + 1); u->d_cntchunks.alloc(a, u->n_cntchunks + 1); u->d_segchunks.alloc(a, u->n_segchunks + 1); u->d_segindex.alloc(a, u->n_segindex + 1);
-    u->d_runs.alloc(a, u->n_runs + 1); u->d_vcodes.alloc(a, n_bases + 16); u->d_other.alloc(a, others_up(u) + 1);
-    if (u->rows_diffed) { u->d_units.alloc(a, u->n_units + 2); u->d_rowcnt.alloc(a, u->n_rowcnt); u->d_blockoff.alloc(a, u->n_blockoff); u->d_blockfirst.alloc(a, u->n_blockfirst); u->d_anchor.alloc(a, u->n_anchor); }
-    else u->d_codes.alloc(a, codes_bytes(u) + 16);
-    u->d_whits.alloc(a, nh + 1); u->d_wsides.alloc(a, u->n_sides + 1); u->d_wruns.alloc(a, u->n_runs + 1); u->d_jump.alloc(a, u->n_jump + 1);
-    if (u->ref_packed) { u->d_wref.alloc(a, (n_pos + 3) / 4 + 32); u->d_refx.alloc(a, u->n_refx + 1); }
-    u->d_dhit.alloc(a, nh + 1);
-    u->d_perm.alloc(a, nh + 1); u->d_tfirst.alloc(a, (size_t)u->n_tiles + 2); u->d_ckey.alloc(a, nh + 1); u->d_long.alloc(a, AGX_LONG_MAX);
-    u->d_tile_cnt.alloc(a, (size_t)u->n_tiles + 1); u->d_tile_off.alloc(a, (size_t)u->n_tiles + 2); u->d_cursor.alloc(a, (size_t)u->n_tiles + 1);
-    u->d_words.alloc(a, W_TOTAL); u->h_words.alloc(W_TOTAL);
-    u->d_chain_end.alloc(a, (size_t)u->n_chain_end + 1);
-    u->d_node_start.alloc(a, n_pos); u->d_node_cnt.alloc(a, n_pos); u->d_pos_succ.alloc(a, n_pos); u->d_slow_list.alloc(a, n_pos + 64);
-    u->d_side_pk.alloc(a, n_pos + 2); u->d_tile_side.alloc(a, (size_t)u->n_tiles + 2); u->d_tile_side_start.alloc(a, (size_t)u->n_tiles + 2);
-    u->d_big_list.alloc(a, (size_t)u->n_tiles + 1); u->d_mid_list.alloc(a, (size_t)u->n_tiles + 1);
-    u->d_scratch.alloc(a, (size_t)AGX_BIG_WAVES * AGX_NF * AGX_MAXV_BIG * 64);
-    u->d_region_off.alloc(a, (size_t)u->n_regions + 1); u->d_pool_cnt.alloc(a, (size_t)u->n_regions * AGX_REGION_PAD);
-    alloc_lists(u, list_cap); alloc_ovf(u, ovf_cap); alloc_sparse(u, sp_cap);
+    Take t{&u->arena};
+    pool_bufs(u, plan.pool_cap, t);                      // (first: what outlives the download lies at the front of the block, agx_unit_trim)
+    fixed_bufs(u, t); list_bufs(u, plan.list_cap, t); ovf_bufs(u, plan.ovf_cap, t); sparse_bufs(u, plan.sp_cap, t);
+    // the groups took what they were measured to take: a buffer allocated outside them fails here, not later as a silent second block.  Taken later, by design, and not part
+    // of the sum: d_huge_list / d_scratch_huge (do_build: a unit that needs pass 3), d_fetch beyond its first 65536 records (fetch_records) — out of the regrowth room or a
+    // later block — and d_ut (agx_unit_unitigs), out of the part of `total` that is reserved for it.
+    if (u->arena.used() != plan.exact) throw Error{E_DEVICE, "internal: the unit's buffers take " + std::to_string(u->arena.used()) + " bytes, its layout measured " + std::to_string(plan.exact)};
+    u->h_words.alloc(W_TOTAL);
     // copies: all of them on the device's upload stream, behind those of the units queued before.  The kernels that expand what was copied
     // (conti-mer tables, vote codes) open the unit's first build instead of following the copies here: a kernel on this stream would wait for
     // CUs while another unit's node sweep holds them all, and every later unit's copies with it.
@@ -1019,7 +1035,7 @@ void do_upload(agx_unit *u) {
             up(u->d_other.p, u->s_other_t.p, u->n_other_t * 8);
             if (u->ref_packed) { up(u->d_wref.p, u->s_ref.p, (n_pos + 3) / 4); up(u->d_refx.p, u->s_refx.p, u->n_refx * sizeof(agx_refx)); } else up(u->d_ref.p, u->s_ref.p, n_pos);
             up(u->d_chain_end.p, u->s_chain_end.p, (size_t)u->n_chain_end * 4);
-            layout_regions(u, nullptr, pool_cap - spill_min(u), true, st);
+            layout_regions(u, nullptr, u->pool_cap - spill_min(u), true, st);
             const size_t s4 = u->stride / 4;
             if (u->rows_diffed) { up(u->d_blockoff.p, u->s_blockoff.p, u->n_blockoff * 4); up(u->d_blockfirst.p, u->s_blockfirst.p, u->n_blockfirst * 4); up(u->d_anchor.p, u->s_anchor.p, u->n_anchor * 4); }
             for (agx_u32 w = 0; w < u->n_win; w++) {      // rows of the hits whose first tile lies in window w (a tile's list also names hits that begin in earlier tiles: earlier pieces)
@@ -1037,7 +1053,7 @@ void do_upload(agx_unit *u) {
             up(u->d_other.p, u->s_other.p, u->n_other * 8);      // first needed by the sweep
             if (u->ref_packed) { up(u->d_wref.p, u->s_ref.p, (n_pos + 3) / 4); up(u->d_refx.p, u->s_refx.p, u->n_refx * sizeof(agx_refx)); } else up(u->d_ref.p, u->s_ref.p, n_pos);
             up(u->d_chain_end.p, u->s_chain_end.p, (size_t)u->n_chain_end * 4);      // first needed by the walk preparation
-            layout_regions(u, nullptr, pool_cap - spill_min(u), true, st);
+            layout_regions(u, nullptr, u->pool_cap - spill_min(u), true, st);
         }
         HIP_OK(hipEventRecord(u->ev_uploaded, st));
     } catch (...) { (void)hipStreamSynchronize(st); throw; }      // (copies that were queued before the failure must not outlive the unit's HBM block)
@@ -1295,9 +1311,9 @@ void do_build(agx_unit *u) {
         u->n_tile_entries = w[W_N];
         // a capacity that was too small: take a larger buffer (the arena keeps the old one until the unit is released) and build again.
         // Whatever a retry changes on the device goes through the download stream and a fresh ev_uploaded, which the next attempt waits for.
-        bool again = false;
+        bool again = false; Take grow{&u->arena};
         if ((w[W_STATUS] & 16u) && !u->dense) { u->dense = true; HIP_OK(hipEventRecord(u->ev_uploaded, turn.down)); continue; }      // more long hits than the window scan takes: again, with the scatter fallback queued
-        if (u->n_tile_entries > u->list_cap) { alloc_lists(u, u->n_tile_entries + u->n_tile_entries / 8 + 1024); again = true; }
+        if (u->n_tile_entries > u->list_cap) { list_bufs(u, u->n_tile_entries + u->n_tile_entries / 8 + 1024, grow); again = true; }
         else {
             if ((w[W_STATUS] & 2u) && !u->huge) {     // a position beyond the 64 variants of pass 2 (deep repeats under a wide --distanceHigh): queue pass 3 and build again
                 u->huge = true; u->d_huge_list.alloc(u->arena, (size_t)u->n_tiles + 1); u->d_scratch_huge.alloc(u->arena, (size_t)AGX_HUGE_WAVES * AGX_NF * AGX_MAXV_HUGE * 64);
@@ -1310,11 +1326,11 @@ void do_build(agx_unit *u) {
                 for (agx_u32 r = 0; r < u->n_regions; r++) demand[r] = padded[(size_t)r * AGX_REGION_PAD];
                 const unsigned long long need = layout_regions(u, demand.data(), 0, false, turn.down);
                 if (need >= 0xFFFFFF00ull) throw Error{E_OVERFLOW, "node table exceeds 2^32 entries"};
-                if (need > u->pool_cap) alloc_pool(u, (agx_u32)need);
+                if (need > u->pool_cap) pool_bufs(u, (agx_u32)need, grow);
                 layout_regions(u, demand.data(), 0, true, turn.down);
                 again = true;
-            } else if (w[W_OVFCOUNT] > u->ovf_cap) { alloc_ovf(u, w[W_OVFCOUNT] + w[W_OVFCOUNT] / 2 + 1024); again = true; }
-            else if (w[W_N + 2] > u->sp_cap) { alloc_sparse(u, w[W_N + 2] + w[W_N + 2] / 8 + 1024); again = true; }
+            } else if (w[W_OVFCOUNT] > u->ovf_cap) { ovf_bufs(u, w[W_OVFCOUNT] + w[W_OVFCOUNT] / 2 + 1024, grow); again = true; }
+            else if (w[W_N + 2] > u->sp_cap) { sparse_bufs(u, w[W_N + 2] + w[W_N + 2] / 8 + 1024, grow); again = true; }
         }
         if (again) { HIP_OK(hipEventRecord(u->ev_uploaded, turn.down)); continue; }
         u->n_nodes = w[W_POOL]; u->n_big = w[W_BIGCOUNT]; u->n_mid = w[W_MIDCOUNT]; u->n_ovf = w[W_OVFCOUNT]; u->n_slow = w[W_SLOWCOUNT];
@@ -1492,20 +1508,17 @@ bool begin_streamed_download(agx_unit *u) {
     return true;
 }
 
-// After the download: everything on the device that the walk cannot ask for (all but the arrays agx_walk_record reads, which lie at the front of the unit's block: alloc_pool)
+// After the download: everything on the device that the walk cannot ask for (all but the arrays agx_walk_record reads, which lie at the front of the unit's block: pool_bufs)
 // goes back to the device's memory region.  The unit is no longer built: another build uploads it again.  Returns the bytes given back (0: the block is not the region's — a
 // unit below the region's threshold on a device without one —, or a capacity grew during the build and the arrays are no longer at the front).
 size_t do_trim(agx_unit *u) {
     if (!u->downloaded) throw Error{E_ARG, "trim: the unit's walk graph has not been downloaded"};
     HIP_OK(hipSetDevice(u->prm.device));
-    const char *base = (const char *)u->arena.base();
-    if (!base) return 0;
-    size_t keep = 0;
-    auto end_of = [&](const void *p, size_t bytes) { if (p) { const size_t e = (size_t)((const char *)p - base) + bytes; if (e > keep) keep = e; } };
-    end_of(u->d_aid_of.p, u->d_aid_of.n * 4); end_of(u->d_a_nid.p, u->d_a_nid.n * 4); end_of(u->d_off0.p, u->d_off0.n * 4);
-    end_of(u->d_sref.p, u->d_sref.n * sizeof(agx_sref)); end_of(u->d_next.p, u->d_next.n * 4); end_of(u->d_fetch.p, u->d_fetch.n * sizeof(agx_walknode));
-    if (keep > u->arena.capacity()) return 0;            // (an array in a later block: nothing is given back)
-    const size_t freed = u->arena.shrink_to(keep);
+    if (!u->arena.base()) return 0;
+    // keep_end is where the kept front of the pool group ends in the arena's first block: as uploaded; or, after a pool regrow inside that block, the end of the new front (the old
+    // one lies before it); or, after fetch_records regrew d_fetch inside it, the end of that.  ~0: the pool or d_fetch was regrown into a later block — nothing is given back.
+    if (u->keep_end > u->arena.capacity()) return 0;
+    const size_t freed = u->arena.shrink_to(u->keep_end);
     if (freed) { u->built = false; u->uploaded = false; }      // what lay behind the kept arrays is gone: the build's buffers, the uploaded inputs
     return freed;
 }
@@ -1519,16 +1532,8 @@ void do_release(agx_unit *u) {
     join_dl_helper(u);                                 // (it fills the download buffers released below)
     stream_wait_all(u);
     if (u->uploaded) { (void)hipSetDevice(u->prm.device); (void)hipEventSynchronize(u->ev_uploaded); (void)hipEventSynchronize(u->ev_built); (void)hipEventSynchronize(u->ev_dl); }      // (its commands are done before its memory goes)
-    for (auto *b : {&u->d_cm_start, &u->d_tile_cnt, &u->d_tile_off, &u->d_cursor, &u->d_unsorted, &u->d_tile_recs, &u->d_scan_tmp, &u->d_words, &u->d_pool_cnt, &u->d_region_off, &u->d_node_start,
-                    &u->d_slow_list, &u->d_perm, &u->d_tfirst, &u->d_ckey, &u->d_long, &u->d_cid, &u->d_coff, &u->d_cid0, &u->d_coff0, &u->d_off0, &u->d_next, &u->d_mid_list, &u->d_big_list, &u->d_scratch,
-                    &u->d_side_pk, &u->d_tile_side, &u->d_tile_side_start, &u->d_aid_of, &u->d_a_nid, &u->d_chain_end, &u->d_side_xpos, &u->d_sp_cnt, &u->d_sp_rank}) b->release();
-    u->d_node_cnt.release();
-    for (auto *b : {&u->d_pos_succ, &u->d_base, &u->d_flags, &u->d_a_meta, &u->d_a_mark, &u->d_codes, &u->d_vcodes}) b->release();
-    u->d_units.release(); u->d_rowcnt.release(); u->d_blockoff.release(); u->d_blockfirst.release(); u->d_anchor.release();
-    u->d_other.release(); u->d_whits.release(); u->d_wsides.release(); u->d_wruns.release(); u->d_wref.release(); u->d_refx.release();
-    u->d_cm.release(); u->d_cm_head.release(); u->d_ref.release(); u->d_cm_cnt.release(); u->d_segs.release(); u->d_up_desc.release(); u->d_cntruns.release(); u->d_cntchunks.release(); u->d_segchunks.release(); u->d_jump.release(); u->d_segindex.release(); u->d_sp_hop.release(); u->d_runs.release(); u->d_dhit.release(); u->d_scan_desc.release(); u->d_sref.release(); u->d_counts.release();
-    u->d_ut.release(); u->d_ovf.release(); u->d_a_ovf.release(); u->d_huge_list.release(); u->d_scratch_huge.release(); u->huge = false; u->dense = false; u->d_a_str.release(); u->d_fetch.release(); u->d_sp_node.release(); u->d_sp_bits.release();
-    u->arena.reset();
+    u->huge = false; u->dense = false;
+    u->arena.reset();                                  // (empties every d_* view with it)
     u->h_a_str.release(); u->h_a_meta.release(); u->h_side_xpos.release(); u->h_sp_rank.release(); u->h_sp_bits.release(); u->h_sp_node.release(); u->h_fetch.release(); u->h_a_ovf.release();
     u->h_sp_hop.release();
     u->pool_cap = u->spill_lo = u->ovf_cap = u->list_cap = u->sp_cap = 0;
@@ -1546,7 +1551,8 @@ void fetch_records(void *ctx, agx_u32 first, agx_u32 stride, agx_u32 rows, agx_u
     HIP_OK(hipSetDevice(u->prm.device));
     DeviceTurn &turn = turn_of(u->prm.device);
     std::lock_guard<std::mutex> l(turn.down_m);      // (also: the walkers of a large unit share the unit's fetch buffers)
-    u->h_fetch.alloc(n); u->d_fetch.alloc(u->arena, n);
+    u->h_fetch.alloc(n);
+    if (n > u->d_fetch.n) { u->d_fetch.alloc(u->arena, n); u->keep_end = u->arena.first_block_at(); }      // (it outlives the download: do_trim)
     agx_compact_args C = u->walk_args; C.n_ids = u->n_ids;
     agx_launch_fetch_records(&C, first, stride, rows, width, u->d_fetch.p, turn.down);
     HIP_OK(hipMemcpyAsync(u->h_fetch.p, u->d_fetch.p, n * sizeof(agx_walknode), hipMemcpyDeviceToHost, turn.down));
@@ -1593,8 +1599,8 @@ int agx_selftest_scan(int device, uint32_t n, uint32_t seed) {
         for (uint32_t i = 0; i < n; i++) { x ^= x << 13; x ^= x >> 17; x ^= x << 5; in[i] = (x % 5u == 0) ? x % 97u : 0u; }       // mostly zeros, like the side-id counts
         for (uint32_t i = 0; i <= n; i++) { want[i] = acc; acc += in[i]; }
         const size_t nb = ((size_t)n + 1 + 4095) / 4096;
-        DevArena arena; arena.device = device;
         DBuf<agx_u32> d_in, d_out; DBuf<unsigned long long> d_desc;
+        DevArena arena; arena.device = device;
         d_in.alloc(arena, (size_t)n + 1); d_out.alloc(arena, (size_t)n + 1); d_desc.alloc(arena, nb + 1);
         HIP_OK(hipMemcpy(d_in.p, in.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
         HIP_OK(hipMemset(d_desc.p, 0, (nb + 1) * 8)); HIP_OK(hipMemset(d_out.p, 0xFF, ((size_t)n + 1) * 4));

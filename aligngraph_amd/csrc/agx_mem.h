@@ -163,8 +163,11 @@ public:
         void *p = (char *)blocks_.back().p + at_; at_ += bytes; used_ += bytes;
         return p;
     }
-    void reset() { for (const MemBlock &b : blocks_) dev_give(device, b); blocks_.clear(); at_ = 0; used_ = 0; }
+    // the views filled from this arena (DBuf::alloc) are emptied with it: none keeps a pointer into a block that went back to the device's cache
+    void reset() { for (const View &v : views_) v.clear(v.buf); views_.clear(); for (const MemBlock &b : blocks_) dev_give(device, b); blocks_.clear(); at_ = 0; used_ = 0; }
+    void filled(void *buf, void (*clear)(void *)) { views_.push_back(View{buf, clear}); }      // (the view must stay where it is until the next reset: agx_unit is neither copied nor moved)
     size_t used() const { return used_; }
+    size_t first_block_at() const { return blocks_.size() == 1 ? at_ : ~(size_t)0; }      // where the next take lands in the first block; ~0: the arena has gone on to a later one
     size_t capacity() const { size_t s = 0; for (const MemBlock &b : blocks_) s += b.n; return s; }
     // Everything behind the first `keep` bytes of the arena's only block goes back to the device's region (the caller no longer uses what lies there); what is taken from
     // the arena afterwards comes from a new block.  Returns the bytes given back: 0 if the arena holds several blocks, or its block is not the region's.
@@ -177,16 +180,23 @@ public:
     }
     const void *base() const { return blocks_.empty() ? nullptr : blocks_[0].p; }
 private:
-    std::vector<MemBlock> blocks_; size_t at_ = 0, used_ = 0;
+    struct View { void *buf; void (*clear)(void *); };
+    std::vector<MemBlock> blocks_; std::vector<View> views_; size_t at_ = 0, used_ = 0;
     size_t room() const { return blocks_.empty() ? 0 : blocks_.back().n - at_; }
     void add(size_t bytes) { blocks_.push_back(dev_block(device, bytes, blocks_.empty())); at_ = 0; }
 };
 
-// typed view of arena memory.  alloc() only ever grows; memory that a regrow leaves behind stays in the arena until the unit is released.
+// typed view of arena memory.  alloc() only ever grows; memory that a regrow leaves behind stays in the arena until the unit is released, and the arena's reset()
+// empties every view it filled: there is no list of a unit's buffers to keep for that.  A view is declared before its arena where both are locals (it must outlive the reset).
 template <class T> struct DBuf {
     T *p = nullptr; size_t n = 0;
-    void alloc(DevArena &a, size_t count) { if (count <= n && p) return; p = count ? (T *)a.take(count * sizeof(T)) : nullptr; n = count; }
+    void alloc(DevArena &a, size_t count) {
+        if (count <= n && p) return;
+        p = count ? (T *)a.take(count * sizeof(T)) : nullptr; n = count;
+        if (p) a.filled(this, [](void *b) { ((DBuf *)b)->release(); });
+    }
     void release() { p = nullptr; n = 0; }
+    DBuf() = default; DBuf(const DBuf &) = delete; DBuf &operator=(const DBuf &) = delete;
 };
 
 // ---- pinned host memory -----------------------------------------------------------------------------------------------------------
