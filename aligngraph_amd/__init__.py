@@ -24,6 +24,7 @@ EXPORTS = [
     "agx_reads_open", "agx_reads_close", "agx_unit_load_files_shared", "agx_run_unit_shared",
     "agx_unit_stage", "agx_unit_release", "agx_pool_trim", "agx_unit_cache_build", "agx_unit_cache_save", "agx_unit_hbm_needed",
     "agx_unit_trim", "agx_unit_unitigs", "agx_unitigs_free", "agx_unitigs_gfa", "agx_text_free",
+    "agx_unit_walk_graph", "agx_walk_graph_free",
 ]
 
 
@@ -85,6 +86,32 @@ class Unitigs(ctypes.Structure):
                 ("seq", ctypes.c_void_p), ("link_from", ctypes.POINTER(ctypes.c_uint32)), ("link_to", ctypes.POINTER(ctypes.c_uint32))]
 
 
+class WalkGraph(ctypes.Structure):
+    _fields_ = [("want_all_node", ctypes.c_uint32), ("n_pos", ctypes.c_uint32), ("n_ids", ctypes.c_uint32), ("n_special", ctypes.c_uint32), ("n_ovf", ctypes.c_uint32),
+                ("n_chain_str", ctypes.c_uint64), ("meta", ctypes.c_void_p), ("str", ctypes.c_void_p), ("side_xpos", ctypes.c_void_p), ("sp_bits", ctypes.c_void_p),
+                ("sp_rank", ctypes.c_void_p), ("sp_node", ctypes.c_void_p), ("sp_hop", ctypes.c_void_p), ("ovf", ctypes.c_void_p), ("chain_str", ctypes.c_void_p),
+                ("all_node", ctypes.c_void_p)]
+
+
+# numpy layouts of agx_walk_rec and agx_walk_hop
+WALK_RECORD = [("next", "<u4", (4,)), ("off0", "<u4"), ("xpos", "<u4"), ("sref_slot", "<u4"), ("sref_qlen", "<u4")]
+WALK_HOP = [("str_off", "<u4"), ("len", "<u4"), ("end_pos", "<u4")]
+
+
+def walk_graph_arrays(g):
+    """An agx_walk_graph-shaped ctypes struct (this library's, or the test executor's) as a dict of numpy arrays; str and chain_str as bytes."""
+    import numpy as np
+
+    def arr(p, n, dt):
+        return np.frombuffer(ctypes.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy() if p and n else np.zeros(0, dt)
+    ni, nw = g.n_ids, g.n_ids // 64 + 1
+    return {"n_pos": g.n_pos, "n_ids": ni, "n_special": g.n_special, "meta": arr(g.meta, ni, "u1"), "str": ctypes.string_at(g.str, ni) if g.str else b"",
+            "side_xpos": arr(g.side_xpos, ni - g.n_pos, "<u4"), "sp_bits": arr(g.sp_bits, nw, "<u8"), "sp_rank": arr(g.sp_rank, nw, "<u4"),
+            "sp_node": arr(g.sp_node, g.n_special, WALK_RECORD), "sp_hop": arr(g.sp_hop, g.n_special, WALK_HOP), "ovf": arr(g.ovf, g.n_ovf * 2, "<u4").reshape(-1, 2),
+            "chain_str": ctypes.string_at(g.chain_str, g.n_chain_str) if g.chain_str else b"",
+            "all_node": arr(g.all_node, ni, WALK_RECORD) if g.all_node else None}
+
+
 class AgxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("agx error %d: %s" % (code, msg))
@@ -135,6 +162,9 @@ def lib():
         L.agx_unit_graph.argtypes = [ctypes.c_void_p, ctypes.POINTER(Graph)]
         L.agx_graph_free.argtypes = [ctypes.POINTER(Graph)]
         L.agx_graph_free.restype = None
+        L.agx_unit_walk_graph.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(WalkGraph)]
+        L.agx_walk_graph_free.argtypes = [ctypes.POINTER(WalkGraph)]
+        L.agx_walk_graph_free.restype = None
         L.agx_unit_unitigs.argtypes = [ctypes.c_void_p, ctypes.POINTER(Unitigs)]
         L.agx_unitigs_free.argtypes = [ctypes.POINTER(Unitigs)]
         L.agx_unitigs_free.restype = None
@@ -329,6 +359,17 @@ class Unit:
                "edge_start": arr(g.edge_start, g.n_nodes + 1, "uint32"), "edge_dst": arr(g.edge_dst, g.n_edges, "uint32")}
         lib().agx_graph_free(ctypes.byref(g))
         return out
+
+    def walk_graph(self, streamed=False, all_node=False):
+        """Test and inspection hook (agx_unit_walk_graph): the walk graph as the walk would be handed it, after a whole download in the one-piece form
+        (streamed=False) or the windowed one (streamed=True); all_node: every id's record through the fetch path as well.  The unit stays usable."""
+        g = WalkGraph()
+        g.want_all_node = 1 if all_node else 0
+        self._check(lib().agx_unit_walk_graph(self._h, 1 if streamed else 0, ctypes.byref(g)))
+        try:
+            return walk_graph_arrays(g)
+        finally:
+            lib().agx_walk_graph_free(ctypes.byref(g))
 
     def unitigs(self):
         """The unit's pruned graph compacted into unitigs on the device (agx_unit_unitigs; needs keep_counts): numpy arrays per segment and link, the

@@ -1227,7 +1227,8 @@ enum { AGX_WM_CONT = 1, AGX_WM_CONTIG = 2, AGX_WM_SIDE = 4, AGX_WM_ANY = 8, AGX_
 //     places the position scan of AG:1972-1978 can start a walk, since a cont predecessor drags its successor along),
 //   - every edge target of an id without the cont bit, and the id just before such a target (a run stops in front of a node that a
 //     jump has already visited),
-//   - every main id of a position where a conti-mer chain ends (the hop back onto the k-mer graph, AG:2093-2136, reads the node there).
+//   - every main id of a position where a conti-mer chain ends (the hop back onto the k-mer graph, AG:2093-2136, reads the node there), and the id just
+//     before it (the hop marks that node visited like a jump marks its target: a run stops in front of it).
 // The one place a walk stands anywhere else is after the reference's +1000 position skip inside long records (AG:2194-2202), which
 // can start a walk in the middle of a forced run; the host then fetches that record from the full table that stays on the device.
 struct agx_compact_args {

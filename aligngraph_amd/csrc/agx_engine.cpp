@@ -242,6 +242,7 @@ struct agx_unit {
     std::string err;
     Threads T; Pairs P;                 // what the loaders / the packed-array calls filled (empty when the unit came out of a cache file)
     UnitView V;                         // what everything downstream reads: into T / P, or into the mapped cache file
+    size_t n_chain_str = 0;             // bytes behind V.chain_str (agx_unit_walk_graph hands them out)
     struct Mapped { void *p = nullptr; size_t n = 0; void reset() { if (p) munmap(p, n); p = nullptr; n = 0; } ~Mapped() { reset(); } } cache_map;
     agx_u32 n_seg0 = 0, stride = 0, n_slots = 0, n_rows = 0; unsigned long long pairs_in_file = 0, sam_pairs = 0;
     bool have_ref = false, have_threads = false, staged = false, uploaded = false, built = false, downloaded = false;
@@ -610,7 +611,7 @@ void stage_inputs(agx_unit *u) {
         V.bases = nullptr; V.row_off = nullptr; V.stride = u->stride; V.codes2 = (const agx_u8 *)F.sec(pairsfile::S_CODES);
         V.other_idx = (const unsigned long long *)F.sec(pairsfile::S_OTHER); V.other_byte = (const agx_u8 *)F.sec(pairsfile::S_OTHERB); V.n_other = (size_t)F.H.n_other;
     } else if (u->pairs_staged) { V.bases = u->reads_keep ? u->reads_keep->fv.p : nullptr; V.stride = u->stride; V.row_off = u->row_off.data(); }
-    u->V = V;
+    u->V = V; u->n_chain_str = u->T.chain_str.size();
     stage_rows(u, threads);
     stage_order(u, threads);
     stage_tiled(u, threads);
@@ -829,7 +830,7 @@ bool load_cache(agx_unit *u, const std::string &dir, int unit) {
     if (from_codes) { V.bases = nullptr; V.codes2 = (const agx_u8 *)(base + H.off[S_CODES]); V.other_idx = (const unsigned long long *)(base + H.off[S_OTHER]); V.other_byte = (const agx_u8 *)(base + H.off[S_OTHERB]); V.n_other = u->n_other; }
     else if (in_reads) { u->reads_map = std::move(reads_map); V.bases = u->reads_map->p; V.row_off = (const uint64_t *)(base + H.off[S_ROWS]); }
     else { V.bases = base + H.off[S_BASES]; u->row_slot.assign((const agx_u32 *)(base + H.off[S_ROWS]), (const agx_u32 *)(base + H.off[S_ROWS]) + H.n_rows); }
-    u->V = V; u->pairs_staged = false;
+    u->V = V; u->n_chain_str = (size_t)H.len[S_CHAIN_STR]; u->pairs_staged = false;
     stage_rows(u, std::max(threads, std::min(8u, usable_cpus())));
     stage_order(u, std::max(threads, std::min(16u, usable_cpus())));
     stage_tiled(u, std::max(threads, std::min(16u, usable_cpus())));
@@ -1912,6 +1913,45 @@ int agx_unit_graph(agx_unit *u, agx_graph *g) {
 void agx_graph_free(agx_graph *g) {
     if (!g) return;
     free(g->node_start); free(g->node_key); free(g->node_cnt); free(g->node_slen); free(g->edge_start); free(g->edge_dst); memset(g, 0, sizeof *g);
+}
+
+// Test and inspection hook: the walk graph exactly as view_of() hands it to the walk, copied out before any walk has marked a_meta.
+int agx_unit_walk_graph(agx_unit *u, int streamed, agx_walk_graph *g) {
+    if (!u || !g) return AGX_E_ARG;
+    const bool want_all = g->want_all_node != 0;
+    memset(g, 0, sizeof *g);
+    const int rc = guarded(u, [&] {
+        static_assert(sizeof(agx_walk_rec) == sizeof(agx_walknode) && sizeof(agx_walk_hop) == sizeof(agx_hop), "include/agx.h mirrors the walk graph's records");
+        if (u->prm.flags & AGX_FLAG_ONE_SHOT) throw Error{E_ARG, "walk graph: a one-shot unit's download lands in its staged inputs and cannot be repeated for the walk"};
+        if (streamed) {
+            if (!begin_streamed_download(u)) throw Error{E_ARG, "walk graph: this unit's download cannot be streamed (no window cuts, or no copy engines)"};
+            stream_wait_all(u);           // every window and the bases
+        } else do_download(u);
+        const GraphView G = view_of(u);
+        const size_t ni = G.n_ids, nw = ni / 64 + 1, ns = G.n_special, nside = ni - G.n_pos;
+        auto dup = [](const void *p, size_t bytes) { void *q = malloc(bytes + 1); if (!q) throw Error{E_ARG, "out of host memory"}; if (bytes) memcpy(q, p, bytes); return q; };
+        g->n_pos = G.n_pos; g->n_ids = G.n_ids; g->n_special = G.n_special; g->n_ovf = (uint32_t)G.n_ovf; g->n_chain_str = u->n_chain_str;
+        g->meta = (uint8_t *)dup(G.meta, ni); g->str = (char *)dup(G.str, ni); g->side_xpos = (uint32_t *)dup(G.side_xpos, nside * 4);
+        g->sp_bits = (uint64_t *)dup(G.sp_bits, nw * 8); g->sp_rank = (uint32_t *)dup(G.sp_rank, nw * 4);
+        g->sp_node = (agx_walk_rec *)dup(G.sp_node, ns * sizeof(agx_walknode)); g->sp_hop = (agx_walk_hop *)dup(G.sp_hop, ns * sizeof(agx_hop));
+        g->ovf = (uint32_t *)dup(G.ovf, G.n_ovf * sizeof(agx_edge_ovf)); g->chain_str = (char *)dup(u->V.chain_str, u->n_chain_str);
+        if (want_all) {                   // every id's record through the fetch path: whole rows of 64 ids a stride apart, then the rest as one row
+            g->all_node = (agx_walk_rec *)malloc((ni + 1) * sizeof(agx_walknode));
+            if (!g->all_node) throw Error{E_ARG, "out of host memory"};
+            const agx_u32 rows = (agx_u32)(ni / 64);
+            if (rows) G.fetch(G.fetch_ctx, 0, 64, rows, 64, (agx_walknode *)g->all_node);
+            if (ni % 64) G.fetch(G.fetch_ctx, rows * 64u, 0, 1, (agx_u32)(ni % 64), (agx_walknode *)g->all_node + (size_t)rows * 64);
+        }
+        if (streamed) u->downloaded = false;      // (as agx_unit_finish leaves a streamed unit: the next finish downloads again)
+    });
+    if (rc != AGX_OK) agx_walk_graph_free(g);
+    return rc;
+}
+
+void agx_walk_graph_free(agx_walk_graph *g) {
+    if (!g) return;
+    free(g->meta); free(g->str); free(g->side_xpos); free(g->sp_bits); free(g->sp_rank); free(g->sp_node); free(g->sp_hop); free(g->ovf); free(g->chain_str); free(g->all_node);
+    memset(g, 0, sizeof *g);
 }
 
 // Unitig export: the kernels of agx_unitig.hip on a stream of the export's own, scratch from an arena of its own (given back to the device's

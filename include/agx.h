@@ -151,6 +151,26 @@ typedef struct {
     uint32_t *link_from, *link_to;   /* [n_links] segment indexes */
 } agx_unitigs;
 
+/* The walk graph: what the walk preparation (csrc/agx_core.h "walk preparation") leaves on the device and the download carries to the host walk (GraphView, csrc/agx_host.h).
+ * Walk ids [0, n_pos) are the first alive variant of each position, [n_pos, n_ids) the further ones.  malloc'd; free with agx_walk_graph_free. */
+typedef struct { uint32_t next[4]; uint32_t off0, xpos, sref_slot, sref_qlen; } agx_walk_rec;   /* successors (walk ids, 0xFFFFFFFF = none), mate offset, position, k-mer string (length: bits 16..30 of sref_qlen) */
+typedef struct { uint32_t str_off, len, end_pos; } agx_walk_hop;                                  /* leave the k-mer graph: append chain_str[str_off, str_off + len), land on end_pos; len 0 = no hop */
+typedef struct {
+    uint32_t want_all_node;    /* IN: non-zero = also fill all_node (set it in a zeroed struct before the call) */
+    uint32_t n_pos, n_ids, n_special, n_ovf;
+    uint64_t n_chain_str;
+    uint8_t *meta;             /* [n_ids] AGX_WM_* bits: 1 forced step to id + 1, 2 on a contig, 4 side ids at the position, 8 a variant at the position, 128 no node */
+    char *str;                 /* [n_ids] the base a node emits */
+    uint32_t *side_xpos;       /* [n_ids - n_pos] position of each side id */
+    uint64_t *sp_bits;         /* [n_ids / 64 + 1] special-id bitmap */
+    uint32_t *sp_rank;         /* [n_ids / 64 + 1] special ids before each 64-id word */
+    agx_walk_rec *sp_node;  /* [n_special] records of the special ids, id order */
+    agx_walk_hop *sp_hop;      /* [n_special] hop entry of each special id's position */
+    uint32_t *ovf;             /* [n_ovf * 2] overflow edges (source, target) in walk ids; 0xFFFFFFFF pairs and duplicates are to be ignored */
+    char *chain_str;           /* [n_chain_str] the unit's conti-mer chain bases (agx_walk_hop::str_off points in here) */
+    agx_walk_rec *all_node; /* [n_ids] (want_all_node) every id's record, read through the path the walk fetches single records by */
+} agx_walk_graph;
+
 /* ---- entry points ------------------------------------------------------------------------------------ */
 
 const char *agx_version(void);
@@ -211,6 +231,15 @@ void agx_pool_trim(int device);                  /* device >= 0: frees the cache
 int agx_unit_stats(const agx_unit *u, agx_stats *s);
 int agx_unit_graph(agx_unit *u, agx_graph *g);   /* after agx_unit_build */
 void agx_graph_free(agx_graph *g);
+/* Test and inspection hook, like agx_unit_graph: builds the unit if need be, then does a WHOLE download (streamed == 0: the one-piece form of agx_unit_download, which a trimmed unit's
+ * walk reads; streamed != 0: the window-by-window form agx_unit_finish uses, waited for to its last piece; AGX_E_ARG where that form does not apply) and copies out what the walk
+ * would be handed, before any walk has marked it.  Costs a download and a host copy of every array.  With want_all_node it also fetches the WHOLE record table in two calls of
+ * the path the walk fetches single records by (rows of 64 ids, then the rest): that grows the unit's device fetch buffer to n_ids records (32 bytes per id of HBM, kept until
+ * agx_unit_release) and moves the end of what agx_unit_trim keeps behind it, so a later trim gives back that much less, or nothing if the buffer fell into a later block.  The unit
+ * stays usable: agx_unit_finish afterwards gives what it gives without this call.  Refused (AGX_E_ARG) for AGX_FLAG_ONE_SHOT units: their download lands in the staged
+ * inputs and cannot be made twice. */
+int agx_unit_walk_graph(agx_unit *u, int streamed, agx_walk_graph *g);
+void agx_walk_graph_free(agx_walk_graph *g);
 /* After agx_unit_build of a unit created with AGX_FLAG_KEEP_COUNTS, before agx_unit_trim / agx_unit_release (AGX_FLAG_ONE_SHOT units: before their download
  * or finish).  Runs on the device over the node table the build left there and changes nothing the walk reads.  AGX_E_ARG otherwise. */
 int agx_unit_unitigs(agx_unit *u, agx_unitigs *t);

@@ -89,6 +89,9 @@ class _Result(ctypes.Structure):
         ("node_start", ctypes.POINTER(ctypes.c_uint32)), ("node_key", ctypes.POINTER(ctypes.c_uint32)),
         ("node_cnt", ctypes.POINTER(ctypes.c_int32)), ("node_slen", ctypes.POINTER(ctypes.c_uint32)),
         ("edge_start", ctypes.POINTER(ctypes.c_uint32)), ("edge_dst", ctypes.POINTER(ctypes.c_uint32)),
+        ("pos_nuc", ctypes.c_void_p), ("cm_count", ctypes.POINTER(ctypes.c_uint32)), ("chain_end", ctypes.POINTER(ctypes.c_uint8)),
+        ("hop_off", ctypes.POINTER(ctypes.c_uint32)), ("hop_len", ctypes.POINTER(ctypes.c_uint32)), ("hop_end", ctypes.POINTER(ctypes.c_uint32)),
+        ("hop_str", ctypes.c_void_p), ("n_hop_str", ctypes.c_uint64),
     ]
 
 
@@ -139,6 +142,10 @@ def run_oracle(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=10000
             "node_slen": arr(r.node_slen, r.n_nodes, "uint32"),
             "edge_start": arr(r.edge_start, r.n_nodes + 1, "uint32"),
             "edge_dst": arr(r.edge_dst, r.n_edges, "uint32"),
+            # per position: its own base, its conti-mers, whether a chain ends there, and the hop of AG:2047-2057 in the reference's terms (hop_len 0: none)
+            "pos_nuc": ctypes.string_at(r.pos_nuc, r.n_pos), "cm_count": arr(r.cm_count, r.n_pos, "uint32"), "chain_end": arr(r.chain_end, r.n_pos, "uint8"),
+            "hop_off": arr(r.hop_off, r.n_pos, "uint32"), "hop_len": arr(r.hop_len, r.n_pos, "uint32"), "hop_end": arr(r.hop_end, r.n_pos, "uint32"),
+            "hop_str": ctypes.string_at(r.hop_str, r.n_hop_str),
         }
     lib.agx_oracle_free(ctypes.byref(r))
     return out

@@ -345,6 +345,10 @@ void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage,
     S.walk_args = C;
 }
 
+void agx_walk_graph_free_sim(agx_walk_graph *g) {      // (agx_walk_graph_free lives in libagx.so, which the executor is never linked with)
+    free(g->meta); free(g->str); free(g->side_xpos); free(g->sp_bits); free(g->sp_rank); free(g->sp_node); free(g->sp_hop); free(g->ovf); free(g->chain_str); free(g->all_node);
+}
+
 char *dup_buf(const std::string &s) { char *p = (char *)malloc(s.size() + 1); memcpy(p, s.data(), s.size()); p[s.size()] = 0; return p; }
 
 }  // namespace
@@ -364,9 +368,14 @@ typedef struct {
     uint64_t n_recs; uint32_t *recs;             // and per list entry (in list order) AGX_SIM_REC_WORDS words: tile, geo, qoff1, boff1, qoff2, boff2, lenjs
     uint64_t edge_ctr[SE_N];                     // AGX_SIM_EDGES: SimEdges
     uint32_t n_slow, n_jsteps, n_jins, n_ovf; uint32_t *slow, *jsteps, *jins, *ovf;
+    // AGX_SIM_WALK: the walk graph in the layout of agx_unit_walk_graph (all_node filled), copied before the walk; the conti-mer chains as runs (AGX_SIM_SEG_WORDS words
+    // each, the first n_seg0 of rank 0), the device's index of the rank-0 runs and the chain-end positions: what the device's hop search and chain-end marks start from
+    agx_walk_graph walk;
+    uint32_t n_segs, n_seg0, n_seg_index, n_chain_end; uint32_t *segs, *seg_index, *chain_end;
 } agx_hostsim_result;
 
-enum { AGX_SIM_GRAPH = 1, AGX_SIM_PACKED = 2, AGX_SIM_RECORDS = 4, AGX_SIM_EDGES = 8 };
+enum { AGX_SIM_GRAPH = 1, AGX_SIM_PACKED = 2, AGX_SIM_RECORDS = 4, AGX_SIM_EDGES = 8, AGX_SIM_WALK = 16 };
+enum { AGX_SIM_SEG_WORDS = 6 };      // pos0, len, rank, hop_str0, hop_len0, hop_end
 
 int agx_hostsim_run_unit(const char *tmp_dir, int unit, int k, int iv, int coverage, long batch, int maxv_first, int options, agx_hostsim_result *out) {
     memset(out, 0, sizeof *out);
@@ -401,6 +410,23 @@ int agx_hostsim_run_unit(const char *tmp_dir, int unit, int k, int iv, int cover
             for (agx_u32 r = 0; r < rows; r++) for (agx_u32 c = 0; c < width; c++) { const SimGraph *g = (const SimGraph *)ctx; const size_t a = (size_t)first + (size_t)r * stride + c; if (a >= g->n_ids) throw Error{E_ARG, "record fetch beyond the walk graph"}; o[(size_t)r * width + c] = agx_walk_record(g->walk_args, (agx_u32)a); }
         }; G.fetch_ctx = &S;
         G.ovf = S.a_ovf.data(); G.n_ovf = S.ovf.size();
+        if (options & AGX_SIM_WALK) {
+            static_assert(sizeof(agx_walk_rec) == sizeof(agx_walknode) && sizeof(agx_walk_hop) == sizeof(agx_hop), "include/agx.h mirrors the walk graph's records");
+            auto dup = [](const void *p, size_t bytes) { void *q = malloc(bytes + 1); if (bytes) memcpy(q, p, bytes); return q; };
+            agx_walk_graph &W = out->walk; const size_t ni = S.n_ids, nw = ni / 64 + 1, ns = S.n_special;
+            W.n_pos = G.n_pos; W.n_ids = S.n_ids; W.n_special = S.n_special; W.n_ovf = (uint32_t)S.ovf.size(); W.n_chain_str = T.chain_str.size();
+            W.meta = (uint8_t *)dup(S.a_meta.data(), ni); W.str = (char *)dup(S.a_str.data(), ni); W.side_xpos = (uint32_t *)dup(S.side_xpos.data(), (ni - G.n_pos) * 4);
+            W.sp_bits = (uint64_t *)dup(S.sp_bits.data(), nw * 8); W.sp_rank = (uint32_t *)dup(S.sp_rank.data(), nw * 4);
+            W.sp_node = (agx_walk_rec *)dup(S.sp_node.data(), ns * sizeof(agx_walknode)); W.sp_hop = (agx_walk_hop *)dup(S.sp_hop.data(), ns * sizeof(agx_hop));
+            W.ovf = (uint32_t *)dup(S.a_ovf.data(), S.ovf.size() * sizeof(agx_edge_ovf)); W.chain_str = (char *)dup(T.chain_str.data(), T.chain_str.size());
+            std::vector<agx_walknode> all(ni + 1); for (size_t a = 0; a < ni; a++) all[a] = agx_walk_record(S.walk_args, (agx_u32)a);
+            W.all_node = (agx_walk_rec *)dup(all.data(), ni * sizeof(agx_walknode));
+            std::vector<agx_u32> sw; for (const agx_cmseg &g : T.segs) { const agx_u32 w[AGX_SIM_SEG_WORDS] = {g.pos0, g.len, g.rank, g.hop_str0, g.hop_len0, g.hop_end}; sw.insert(sw.end(), w, w + AGX_SIM_SEG_WORDS); }
+            std::vector<agx_u32> index; build_seg_index(T.segs.data(), T.n_seg0, G.n_pos, index);
+            out->n_segs = (uint32_t)T.segs.size(); out->n_seg0 = T.n_seg0; out->segs = (uint32_t *)dup(sw.data(), sw.size() * 4);
+            out->n_seg_index = (uint32_t)index.size(); out->seg_index = (uint32_t *)dup(index.data(), index.size() * 4);
+            out->n_chain_end = (uint32_t)T.chain_end_pos.size(); out->chain_end = (uint32_t *)dup(T.chain_end_pos.data(), T.chain_end_pos.size() * 4);
+        }
         if (const char *rep = getenv("AGX_WALK_REPEAT")) {           // walk micro-benchmark: best of N on an already built graph
             double best = 1e30;
             for (int i = 0; i < atoi(rep); i++) { UnitOutput Q; const auto t0 = std::chrono::steady_clock::now(); walk_join_scaffold(view_of(T, P), G, Q); const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); if (ms < best) best = ms; }
@@ -510,6 +536,7 @@ void agx_hostsim_free(agx_hostsim_result *r) {
     free(r->initial_contigs); free(r->pre_extended); free(r->extended);
     free(r->node_start); free(r->node_key); free(r->node_cnt); free(r->node_slen); free(r->edge_start); free(r->edge_dst); free(r->tile_len); free(r->recs);
     free(r->slow); free(r->jsteps); free(r->jins); free(r->ovf);
+    agx_walk_graph_free_sim(&r->walk); free(r->segs); free(r->seg_index); free(r->chain_end);
     memset(r, 0, sizeof *r);
 }
 

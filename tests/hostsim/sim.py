@@ -2,13 +2,17 @@
 import ctypes
 import os
 import subprocess
+import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.environ.get("AGX_HOSTSIM_LIB", os.path.join(HERE, "libagx_hostsim.so"))      # (override: a variant build, e.g. -DAGX_WALK_CHECK, made by hand)
 SRC = [os.path.join(HERE, "agx_hostsim.cpp"), os.path.join(ROOT, "aligngraph_amd", "csrc", "agx_host.cpp"),
        os.path.join(ROOT, "aligngraph_amd", "csrc", "agx_walk.cpp"), os.path.join(ROOT, "aligngraph_amd", "csrc", "agx_load.cpp")]
-DEPS = SRC + [os.path.join(ROOT, "aligngraph_amd", "csrc", h) for h in ("agx_core.h", "agx_host.h", "agx_parse.h")]
+DEPS = SRC + [os.path.join(ROOT, "aligngraph_amd", "csrc", h) for h in ("agx_core.h", "agx_host.h", "agx_parse.h")] + [os.path.join(ROOT, "include", "agx.h")]
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+import aligngraph_amd as _agx  # noqa: E402  (the ctypes mirror of agx_walk_graph only: the executor never loads libagx.so)
 
 
 def build():
@@ -34,6 +38,9 @@ class _Result(ctypes.Structure):
         ("edge_ctr", ctypes.c_uint64 * 16),
         ("n_slow", ctypes.c_uint32), ("n_jsteps", ctypes.c_uint32), ("n_jins", ctypes.c_uint32), ("n_ovf", ctypes.c_uint32),
         ("slow", ctypes.POINTER(ctypes.c_uint32)), ("jsteps", ctypes.POINTER(ctypes.c_uint32)), ("jins", ctypes.POINTER(ctypes.c_uint32)), ("ovf", ctypes.POINTER(ctypes.c_uint32)),
+        ("walk", _agx.WalkGraph),
+        ("n_segs", ctypes.c_uint32), ("n_seg0", ctypes.c_uint32), ("n_seg_index", ctypes.c_uint32), ("n_chain_end", ctypes.c_uint32),
+        ("segs", ctypes.POINTER(ctypes.c_uint32)), ("seg_index", ctypes.POINTER(ctypes.c_uint32)), ("chain_end", ctypes.POINTER(ctypes.c_uint32)),
     ]
 
 
@@ -47,6 +54,7 @@ SLOW_FIELDS = ("x", "who", "n", "n1", "reg", "tile_len", "pairs", "allowed", "hi
 JSTEP_FIELDS = ("hit", "a_nruns", "x", "xs", "cnt_x", "cnt_xs")
 JINS_FIELDS = ("x", "xs")
 OVF_FIELDS = ("x", "xs", "v", "again")
+SEG_FIELDS = ("pos0", "len", "rank", "hop_str0", "hop_len0", "hop_end")      # run(..., walk=True)["walk"]["segs"]: the conti-mer chains as runs, the first n_seg0 of rank 0
 
 
 _lib = None
@@ -59,12 +67,14 @@ class SimError(RuntimeError):
         self.msg = msg
 
 
-def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, maxv_first=0, graph=False, packed=False, records=False, edges=False):
+def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, maxv_first=0, graph=False, packed=False, records=False, edges=False, walk=False):
     """One unit through the serial executor.  packed: pass 0 of the node sweep on packed buckets (AGX_NFP words per variant, the device's layout; a list of more
     than 65 535 entries goes to the next pass).  records: also returns "records", the lean record of every tile-list entry in list order as a structured
     numpy array with the fields REC_FIELDS, and "tile_len", each tile's list length.  edges: also returns "edges", the counters EDGE_COUNTERS of the edge
     build's paths, "slow" (the slow positions the device lists, ascending; SLOW_FIELDS), "jsteps" (the steps pass J looks at; JSTEP_FIELDS), "jins" (pass J's
-    inserts; JINS_FIELDS) and "ovf" (every overflow append in order; OVF_FIELDS); positions, not node ids."""
+    inserts; JINS_FIELDS) and "ovf" (every overflow append in order; OVF_FIELDS); positions, not node ids.  walk: also returns "walk", the walk graph the executor hands to
+    the host walk in the layout of aligngraph_amd.Unit.walk_graph(all_node=True), plus "segs" (SEG_FIELDS), "n_seg0", "seg_index" and "chain_end": what the device's
+    hop search and chain-end marks start from."""
     global _lib
     if _lib is None:
         build()
@@ -72,7 +82,7 @@ def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, max
         _lib.agx_hostsim_run_unit.argtypes = [ctypes.c_char_p] + [ctypes.c_int] * 4 + [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_Result)]
         _lib.agx_hostsim_free.argtypes = [ctypes.POINTER(_Result)]
     r = _Result()
-    options = (1 if graph else 0) | (2 if packed else 0) | (4 if records else 0) | (8 if edges else 0)
+    options = (1 if graph else 0) | (2 if packed else 0) | (4 if records else 0) | (8 if edges else 0) | (16 if walk else 0)
     rc = _lib.agx_hostsim_run_unit(tmp_dir.encode(), unit, k, insert_variation, coverage, batch, maxv_first, options, ctypes.byref(r))
     if rc != 0:
         msg = r.error.decode()
@@ -92,6 +102,14 @@ def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, max
             n = getattr(r, "n_" + key)
             flat = np.ctypeslib.as_array(getattr(r, key), shape=(n * len(names),)).copy() if n else np.zeros(0, "uint32")
             out[key] = flat.view([(f, "uint32") for f in names]).reshape(-1)
+    if walk:
+        w = _agx.walk_graph_arrays(r.walk)
+        flat = np.ctypeslib.as_array(r.segs, shape=(r.n_segs * len(SEG_FIELDS),)).copy() if r.n_segs else np.zeros(0, "uint32")
+        w["segs"] = flat.view([(f, "uint32") for f in SEG_FIELDS]).reshape(-1)
+        w["n_seg0"] = r.n_seg0
+        w["seg_index"] = np.ctypeslib.as_array(r.seg_index, shape=(r.n_seg_index,)).copy() if r.n_seg_index else np.zeros(0, "uint32")
+        w["chain_end"] = np.ctypeslib.as_array(r.chain_end, shape=(r.n_chain_end,)).copy() if r.n_chain_end else np.zeros(0, "uint32")
+        out["walk"] = w
     if graph:
         def arr(p, n, dt):
             return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)

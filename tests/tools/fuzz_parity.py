@@ -3,7 +3,9 @@
 coverage threshold, units), each compared byte for byte (three output files + node/edge tables) between the oracle and
   --engine hostsim : the kernels' per-lane functions on the CPU serial executor (tests/hostsim; no GPU needed), or
   --engine gpu     : the HIP engine through the C-ABI.
-Usage: python tests/tools/fuzz_parity.py [--n 40] [--seed 1] [--engine hostsim|gpu]"""
+--walk-graph adds, per unit, the engine's walk graph (the executor's dump, or Unit.walk_graph in the download form the draw picked, every record through the fetch path)
+against the model of tests/walk_model.py; one-shot units cannot give it and are then drawn as ordinary ones, and units below 4 096 positions have no streamed form.
+Usage: python tests/tools/fuzz_parity.py [--n 40] [--seed 1] [--engine hostsim|gpu] [--walk-graph]"""
 import argparse
 import os
 import random
@@ -23,6 +25,7 @@ ap.add_argument("--n", type=int, default=40)
 ap.add_argument("--seed", type=int, default=1)
 ap.add_argument("--engine", default="hostsim", choices=["hostsim", "gpu"])
 ap.add_argument("--workdir", default="/tmp/agx_fuzz")
+ap.add_argument("--walk-graph", action="store_true", help="also compare each unit's walk graph with tests/walk_model.py")
 a = ap.parse_args()
 
 if a.engine == "hostsim":
@@ -42,7 +45,7 @@ if a.engine == "hostsim":
             os.environ["AGX_SIM_ASSISTANT"] = "1"; os.environ["AGX_WALK_SPLIT_MIN"] = "0"; os.environ["AGX_WALK_SPLIT_WALKERS"] = str(r.choice([2, 3, 5, 8, 16])); os.environ["AGX_WALK_SPLIT_WARMUP"] = str(r.choice([200, 2000, 20000])); os.environ["AGX_WALK_POISON"] = "1"
             if r.random() < 0.3:
                 os.environ["AGX_WALK_EVEN_CUTS"] = "1"
-        return sim.run(tmp, u, k, iv, cov, graph=True)
+        return sim.run(tmp, u, k, iv, cov, graph=True, walk=a.walk_graph)
 else:
     import aligngraph_amd as A
     knob_rng = random.Random(a.seed * 7919 + 13)
@@ -67,13 +70,18 @@ else:
             os.environ["AGX_ROW_DIFF"] = "1"
         if r.random() < 0.15:
             os.environ["AGX_NO_TILED_UPLOAD"] = "1"
-        one_shot = r.random() < 0.4
+        one_shot = r.random() < 0.4 and not a.walk_graph
         with A.Unit(k=k, insert_variation=iv, coverage=cov, keep_counts=True, flags=A.AGX_FLAG_ONE_SHOT if one_shot else 0) as un:
             un.load_files(tmp, u); un.upload(); un.build()
             graph = un.graph()
+            walk = None
+            if a.walk_graph:
+                walk = un.walk_graph(streamed=stream and graph["n_pos"] >= 4096, all_node=True)      # (no window cuts below 4 096 positions: the one-piece form; any error is a finding)
             if not stream and r.random() < 0.5:
                 un.download()
             out = un.finish(); out["graph"] = graph
+            if walk is not None:
+                out["walk"] = walk
         return out
 
 rng = random.Random(a.seed)
@@ -108,6 +116,10 @@ for it in range(a.n):
         bad = graph_mismatch(o["graph"], g["graph"])
         if bad is None:
             bad = next((key for key in ("initial", "pre", "extended") if o[key] != g[key]), None)
+        if bad is None and a.walk_graph:
+            import walk_model as WM
+            bad = WM.mismatch(WM.build(o["graph"], meta["coverage"]), g["walk"])
+            bad = bad and "walk graph: " + bad
         if bad is not None:
             keep = os.path.join(a.workdir, "FAILED_%d" % it)
             shutil.rmtree(keep, ignore_errors=True); shutil.copytree(runp, keep)
