@@ -86,16 +86,6 @@ struct Boundaries {
     double ms(int b) const { if (!at[b - 1] || !at[b]) return 0; float f = 0; (void)hipEventElapsedTime(&f, e[b - 1], e[b]); return f; }      // section that ends at boundary b
 };
 
-template <class F> void on_threads(unsigned threads, F fn) {      // (as in agx_host.cpp: nothing leaves a worker thread as an exception)
-    std::vector<std::thread> th; std::vector<std::exception_ptr> ex(threads);
-    auto guarded = [&](unsigned t) { try { fn(t); } catch (...) { ex[t] = std::current_exception(); } };
-    std::vector<unsigned> mine{0u};
-    for (unsigned t = 1; t < threads; t++) { try { th.emplace_back(guarded, t); } catch (const std::system_error &) { mine.push_back(t); } }
-    for (unsigned t : mine) guarded(t);
-    for (auto &x : th) x.join();
-    for (auto &e : ex) if (e) std::rethrow_exception(e);
-}
-
 }  // namespace
 
 // Downloads through the HSA runtime's asynchronous copy, i.e. the SDMA engines.  hipMemcpyAsync does a device-to-host copy into registered
@@ -407,18 +397,24 @@ void fill_sweep_args(agx_unit *u, agx_sweep_args &S) {
 // from them and keep them pinned.
 inline bool want_tiled() { return !getenv("AGX_NO_TILED_UPLOAD"); }
 template <class B> inline void alloc_file_order(B &buf, size_t count) { if (want_tiled()) buf.alloc_plain(count); else buf.alloc(count); }
+// One of the six arrays of a unit's staged read alignments, for `bytes` of content: an element of slack each; the packed rows are asked for with their 16 bytes of slack.
+void *alloc_pair_array(agx_unit *u, int which, size_t bytes) {
+    switch (which) {
+    case SA_HITS:  alloc_file_order(u->s_hits, bytes / sizeof(agx_whit) + 1); return u->s_hits.p;
+    case SA_SIDES: u->s_sides.alloc(bytes / sizeof(agx_wside) + 1); return u->s_sides.p;
+    case SA_RUNS:  u->s_runs.alloc(bytes / sizeof(agx_wrun) + 1); return u->s_runs.p;
+    case SA_CODES: alloc_file_order(u->s_codes, bytes); return u->s_codes.p;
+    case SA_JUMP:  u->s_jump.alloc(bytes / 4 + 1); return u->s_jump.p;
+    default:       u->s_other.alloc(bytes / 8 + 1); return u->s_other.p;
+    }
+}
+void alloc_pair_arrays(agx_unit *u) {      // all six, from the unit's counts (a staged-pairs file, a cache file)
+    alloc_pair_array(u, SA_HITS, u->nh * sizeof(agx_whit)); alloc_pair_array(u, SA_SIDES, u->n_sides * sizeof(agx_wside)); alloc_pair_array(u, SA_JUMP, u->n_jump * 4);
+    alloc_pair_array(u, SA_RUNS, u->n_runs * sizeof(agx_wrun)); alloc_pair_array(u, SA_CODES, u->n_codes + 16); alloc_pair_array(u, SA_OTHER, u->n_other * 8);
+}
 struct UnitSink : StageSink {
     agx_unit *u; explicit UnitSink(agx_unit *x) : u(x) {}
-    void *take(int which, size_t bytes) override {
-        switch (which) {
-        case SA_HITS:  alloc_file_order(u->s_hits, bytes / sizeof(agx_whit) + 1); return u->s_hits.p;
-        case SA_SIDES: u->s_sides.alloc(bytes / sizeof(agx_wside) + 1); return u->s_sides.p;
-        case SA_RUNS:  u->s_runs.alloc(bytes / sizeof(agx_wrun) + 1); return u->s_runs.p;
-        case SA_CODES: alloc_file_order(u->s_codes, bytes); return u->s_codes.p;
-        case SA_JUMP:  u->s_jump.alloc(bytes / 4 + 1); return u->s_jump.p;
-        default:       u->s_other.alloc(bytes / 8 + 1); return u->s_other.p;
-        }
-    }
+    void *take(int which, size_t bytes) override { return alloc_pair_array(u, which, bytes); }
 };
 void adopt_pairs(agx_unit *u, StagedPairs &S) {      // the staged read alignments' counts and the host-side row table
     u->nh = S.nh; u->n_runs = S.n_runs; u->n_sides = S.n_sides; u->n_jump = S.n_jump; u->n_codes = S.n_codes; u->n_other = S.n_other; u->stride = S.stride; u->maxlen = S.maxlen;
@@ -445,16 +441,60 @@ void stage_reference(agx_unit *u, const char *ref, size_t n_pos, unsigned thread
     const unsigned T = std::max(1u, std::min(threads, 8u));
     on_threads(T, [&](unsigned t) { const size_t lo = n_pos * t / T, hi = n_pos * (t + 1) / T; memcpy(u->s_ref.p + lo, ref + lo, hi - lo); });
 }
+// ---- the walk graph's way to the host ------------------------------------------------------------------------------------------------
+// Every array of the walk graph that is downloaded is named ONCE, here: its pinned buffer, its source on the device, how many elements are copied — a function of the
+// graph's four counts — and how many more the buffer holds behind them (the walk reads a little past some ends; the 64 bytes behind the meta bytes are zeroed).  The
+// function shows them to a visitor, in the order a one-piece download copies them.  Buffers by estimate and exactly, the borrowed ones of a one-shot unit, the copy lists of
+// both download forms, the release, download_bytes and what agx_unit_walk_graph hands out all work from it: a new array is one line here, plus the members.
+struct GraphCounts { size_t n_pos, n_ids, n_special, n_ovf; };
+enum { GA_BITS = 0, GA_RANK, GA_STR, GA_META, GA_XPOS, GA_NODE, GA_HOP, GA_OVF, GA_N };
+template <class F> void graph_arrays(agx_unit *u, const GraphCounts &c, F f) {
+    const size_t words = c.n_ids / 64 + 1, sides = c.n_ids - c.n_pos;
+    f(GA_BITS, u->h_sp_bits, u->d_sp_bits, words, 1); f(GA_RANK, u->h_sp_rank, u->d_sp_rank, words, 1);      // the special ids: a bit per id, the records in front of every word
+    f(GA_STR, u->h_a_str, u->d_a_str, c.n_ids, 1); f(GA_META, u->h_a_meta, u->d_a_meta, c.n_ids, 64);         // a base and a meta byte per id
+    f(GA_XPOS, u->h_side_xpos, u->d_side_xpos, sides, 1);                                                    // the position of every side id
+    f(GA_NODE, u->h_sp_node, u->d_sp_node, c.n_special, 1); f(GA_HOP, u->h_sp_hop, u->d_sp_hop, c.n_special, 2);      // the sparse record table
+    f(GA_OVF, u->h_a_ovf, u->d_a_ovf, c.n_ovf, 1);                                                           // the edges that did not fit their records
+}
+// the one-shot download cuts its buffers from the dead staged blocks in this order: the largest arrays first, so that what does not fit any block is small
+const int GRAPH_CUT_ORDER[GA_N] = {GA_NODE, GA_META, GA_STR, GA_HOP, GA_XPOS, GA_BITS, GA_RANK, GA_OVF};
+inline GraphCounts graph_counts(const agx_unit *u) { return GraphCounts{u->V.n_pos, u->n_ids, u->n_special, u->n_ovf}; }
+inline size_t graph_bytes(agx_unit *u, const GraphCounts &c) {      // what a download moves (stats.download_bytes, either form)
+    size_t sum = 0; graph_arrays(u, c, [&](int, auto &h, auto &, size_t n, size_t) { sum += n * sizeof(*h.p); }); return sum;
+}
+// What a unit of n_pos positions is expected to download, where buffers are made before the build has counted:
+// for the helper thread's pinned buffers (do_upload): walk ids ~ 1.05 x positions — an eighth of room —, special ids ~ 8 % of them; do_download re-sizes what is too small
+inline GraphCounts helper_estimate(size_t n_pos) { const size_t ni = n_pos + n_pos / 8 + 4096; return GraphCounts{n_pos, ni, ni / 8 + 4096, 63}; }
+// for the landing room of a one-shot unit (reserve_landing), which stays pinned as long as the staged unit does: a sixteenth of room, a tenth of the ids special
+inline GraphCounts landing_estimate(size_t n_pos) { const size_t ni = n_pos + n_pos / 16 + 4096; return GraphCounts{n_pos, ni, ni / 10 + 4096, 0}; }
+
+// The staged blocks that a one-shot unit's download may land in, in the order download_buffers cuts from them, the largest first: its inputs, dead once they are in HBM
+// (`input`), and the landing block that reserve_landing sizes by what the inputs lack.
+const int LANDING_ROOMS = 8;
+template <class F> void landing_rooms(agx_unit *u, F f) {
+    f(u->s_codes, true); f(u->s_hits, true); f(u->s_landing, false); f(u->s_codes_t, true); f(u->s_hits_t, true); f(u->s_runs, true); f(u->s_sides, true); f(u->s_other, true);
+}
+
 // A one-shot unit's download lands in the pinned memory of its staged inputs, which are dead once they are in HBM (do_download).  Since r03 those are packed
-// (wire formats) and can be smaller than the walk graph: what is missing is pinned here, by estimate (walk ids ~ 1.06 x positions, special
-// ids ~ 8 % of them), while the unit is staged — inside T_core mapping and registering it cost 1 ms per unit.
+// (wire formats) and can be smaller than the walk graph: what is missing is pinned here, by estimate (landing_estimate), while the unit is staged — inside T_core
+// mapping and registering it cost 1 ms per unit.  (`need` is a bound with slack of its own — 2 bytes per id, a record and a hop entry per special id, a quarter byte
+// per id and 4 MB for the rest — not a sum over the arrays: it is left as it was, so that a unit pins what it pinned.)
 void reserve_landing(agx_unit *u) {
     if (!(u->prm.flags & AGX_FLAG_ONE_SHOT)) { u->s_landing.release(); return; }
-    const size_t n_pos = u->V.n_pos, ni = n_pos + n_pos / 16 + 4096, ns = ni / 10 + 4096;
+    const GraphCounts c = landing_estimate(u->V.n_pos); const size_t ni = c.n_ids, ns = c.n_special;
     const size_t need = 2 * (ni + 512) + ns * (sizeof(agx_walknode) + sizeof(agx_hop)) + ni / 4 + (4u << 20);
-    const size_t have = u->s_codes.block_bytes() + u->s_hits.block_bytes() + u->s_runs.block_bytes() + u->s_sides.block_bytes() + u->s_other.block_bytes() + u->s_codes_t.block_bytes() + u->s_hits_t.block_bytes();
+    size_t have = 0; landing_rooms(u, [&](auto &b, bool input) { if (input) have += b.block_bytes(); });
     // (a buffer must fit one block: count the blocks at 85 %)
     if (need > have * 85 / 100) u->s_landing.alloc(need - have * 85 / 100 + (ni + 512)); else u->s_landing.release();
+}
+// What the encoder of the read rows made (build_row_diffs), into the unit's pinned buffers: the rows cross as differences from now on.  For both stagers below.
+void adopt_row_diffs(agx_unit *u, const RowDiffs &D, unsigned threads) {
+    u->n_units = D.n_units; u->n_rowcnt = D.cnt.size(); u->n_blockoff = D.block_off.size(); u->n_blockfirst = D.block_first.size(); u->n_anchor = D.anchor_bits.size(); u->n_rows_explicit = D.n_explicit;
+    u->s_units.alloc(u->n_units + 2); u->s_rowcnt.alloc(u->n_rowcnt); u->s_blockoff.alloc(u->n_blockoff); u->s_blockfirst.alloc(u->n_blockfirst); u->s_anchor.alloc(u->n_anchor);
+    const unsigned T = std::max(1u, std::min(threads, 8u));
+    on_threads(T, [&](unsigned t) { const size_t lo = u->n_units * t / T, hi = u->n_units * (t + 1) / T; if (hi > lo) memcpy(u->s_units.p + lo, D.units.data() + lo, (hi - lo) * 2); });
+    memcpy(u->s_rowcnt.p, D.cnt.data(), u->n_rowcnt); memcpy(u->s_blockoff.p, D.block_off.data(), u->n_blockoff * 4); memcpy(u->s_blockfirst.p, D.block_first.data(), u->n_blockfirst * 4); memcpy(u->s_anchor.p, D.anchor_bits.data(), u->n_anchor * 4);
+    u->rows_diffed = true;
 }
 // The read rows for the upload as differences against the reference (agx_core.h; build_row_diffs in agx_load.cpp): AGX_ROW_DIFF=1 asks for it.  It is NOT the default:
 // it takes 36-44 % off a unit's upload (66 -> 36 bytes per pair at 2x150) but no measured job is bound by its uploads — cfg3 36.4 against 36.5 ms, the 24-unit human
@@ -470,12 +510,7 @@ void stage_rows(agx_unit *u, unsigned threads) {
     RowDiffs D;
     if (!build_row_diffs(u->s_hits.p, u->nh, u->s_sides.p, u->n_sides, u->s_runs.p, u->n_runs, u->s_codes.p, u->n_rows, u->stride, (const agx_u32 *)u->s_ref.p, u->V.n_pos ? u->V.n_pos : u->T.ref.size(), threads, D)) return;
     if (D.n_units * 2 + D.cnt.size() + (D.block_off.size() + D.block_first.size() + D.anchor_bits.size()) * 4 >= u->n_codes) return;      // nothing gained (reads that do not resemble the reference)
-    u->n_units = D.n_units; u->n_rowcnt = D.cnt.size(); u->n_blockoff = D.block_off.size(); u->n_blockfirst = D.block_first.size(); u->n_anchor = D.anchor_bits.size(); u->n_rows_explicit = D.n_explicit;
-    u->s_units.alloc(u->n_units + 2); u->s_rowcnt.alloc(u->n_rowcnt); u->s_blockoff.alloc(u->n_blockoff); u->s_blockfirst.alloc(u->n_blockfirst); u->s_anchor.alloc(u->n_anchor);
-    const unsigned T = std::max(1u, std::min(threads, 8u));
-    on_threads(T, [&](unsigned t) { const size_t lo = u->n_units * t / T, hi = u->n_units * (t + 1) / T; if (hi > lo) memcpy(u->s_units.p + lo, D.units.data() + lo, (hi - lo) * 2); });
-    memcpy(u->s_rowcnt.p, D.cnt.data(), u->n_rowcnt); memcpy(u->s_blockoff.p, D.block_off.data(), u->n_blockoff * 4); memcpy(u->s_blockfirst.p, D.block_first.data(), u->n_blockfirst * 4); memcpy(u->s_anchor.p, D.anchor_bits.data(), u->n_anchor * 4);
-    u->rows_diffed = true;
+    adopt_row_diffs(u, D, threads);
     if (getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] read rows against the reference: %.1f ms, %zu rows (%zu as they are), %.1f -> %.1f bytes per row\n", now_ms() - t0, (size_t)u->n_rows, u->n_rows_explicit,
                                           (double)u->n_codes / u->n_rows, (double)(u->n_units * 2 + u->n_rowcnt + (u->n_blockoff + u->n_blockfirst + u->n_anchor) * 4) / u->n_rows);
 }
@@ -567,14 +602,21 @@ void stage_rows_tiled(agx_unit *u, unsigned threads) {
     RowDiffs D;
     if (!build_row_diffs(u->s_hits_t.p, u->nh, u->s_sides.p, u->n_sides, u->s_runs.p, u->n_runs, u->s_codes_t.p, u->nh, u->stride, (const agx_u32 *)u->s_ref.p, n_pos, threads, D, true)) return;
     if (D.n_units * 2 + D.cnt.size() + (D.block_off.size() + D.block_first.size() + D.anchor_bits.size()) * 4 >= u->nh * (u->stride / 4)) return;      // nothing gained (reads that do not resemble the reference)
-    u->n_units = D.n_units; u->n_rowcnt = D.cnt.size(); u->n_blockoff = D.block_off.size(); u->n_blockfirst = D.block_first.size(); u->n_anchor = D.anchor_bits.size(); u->n_rows_explicit = D.n_explicit;
-    u->s_units.alloc(u->n_units + 2); u->s_rowcnt.alloc(u->n_rowcnt); u->s_blockoff.alloc(u->n_blockoff); u->s_blockfirst.alloc(u->n_blockfirst); u->s_anchor.alloc(u->n_anchor);
-    const unsigned T = std::max(1u, std::min(threads, 8u));
-    on_threads(T, [&](unsigned t) { const size_t lo = u->n_units * t / T, hi = u->n_units * (t + 1) / T; if (hi > lo) memcpy(u->s_units.p + lo, D.units.data() + lo, (hi - lo) * 2); });
-    memcpy(u->s_rowcnt.p, D.cnt.data(), u->n_rowcnt); memcpy(u->s_blockoff.p, D.block_off.data(), u->n_blockoff * 4); memcpy(u->s_blockfirst.p, D.block_first.data(), u->n_blockfirst * 4); memcpy(u->s_anchor.p, D.anchor_bits.data(), u->n_anchor * 4);
-    u->rows_diffed = true;
+    adopt_row_diffs(u, D, threads);
     if (getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] tile-ordered rows against the reference: %.1f ms, %zu rows (%zu as they are), %.1f -> %.1f bytes per row\n", now_ms() - t0, u->nh, u->n_rows_explicit,
                                           (double)(u->stride / 4), (double)(u->n_units * 2 + u->n_rowcnt + (u->n_blockoff + u->n_blockfirst + u->n_anchor) * 4) / u->nh);
+}
+
+// The tail of staging, from the text (stage_inputs) and from the cache file (load_cache) alike, once the unit's view and its file-order arrays are there: the upload forms
+// of the rows and the hits, the landing room of a one-shot download; the unit is staged and nothing of an earlier upload counts any more.
+void finish_staging(agx_unit *u, unsigned threads_rows, unsigned threads) {
+    stage_rows(u, threads_rows);
+    stage_order(u, threads);
+    stage_tiled(u, threads);
+    stage_rows_tiled(u, threads);
+    u->V.slot_row = u->tiled ? u->slot_row.data() : nullptr;
+    reserve_landing(u);
+    u->staged = true; u->consumed = false; u->uploaded = false; u->built = false; u->downloaded = false;
 }
 
 void stage_inputs(agx_unit *u) {
@@ -612,13 +654,7 @@ void stage_inputs(agx_unit *u) {
         V.other_idx = (const unsigned long long *)F.sec(pairsfile::S_OTHER); V.other_byte = (const agx_u8 *)F.sec(pairsfile::S_OTHERB); V.n_other = (size_t)F.H.n_other;
     } else if (u->pairs_staged) { V.bases = u->reads_keep ? u->reads_keep->fv.p : nullptr; V.stride = u->stride; V.row_off = u->row_off.data(); }
     u->V = V; u->n_chain_str = u->T.chain_str.size();
-    stage_rows(u, threads);
-    stage_order(u, threads);
-    stage_tiled(u, threads);
-    stage_rows_tiled(u, threads);
-    u->V.slot_row = u->tiled ? u->slot_row.data() : nullptr;
-    reserve_landing(u);
-    u->staged = true; u->consumed = false; u->uploaded = false; u->built = false; u->downloaded = false;
+    finish_staging(u, threads, threads);
     u->stats.ms_stage = now_ms() - t0;
 }
 
@@ -652,6 +688,21 @@ void stamps(const std::string &d, int unit, unsigned long long st[6][2]) {
 std::string path_of(const std::string &d, int unit) { return d + "/_agx_unit." + std::to_string(unit) + ".bin"; }
 }  // namespace cache
 
+// Large arrays between memory and a file or a mapping, in pieces of 32 MB on a few threads.  A piece names its memory and the other side's offset; step(memory, offset, bytes)
+// moves up to that many bytes and returns how many it did (memcpy, pread, pwrite; <= 0: failed).  false: some piece failed.
+struct Piece { char *mem; unsigned long long off, len; };
+void cut_pieces(std::vector<Piece> &pieces, const void *mem, unsigned long long off, unsigned long long len) {
+    for (unsigned long long a = 0; a < len; a += 32ull << 20) pieces.push_back(Piece{(char *)mem + a, off + a, std::min<unsigned long long>(32ull << 20, len - a)});
+}
+template <class Step> bool move_pieces(const std::vector<Piece> &pieces, unsigned threads, Step step) {
+    std::vector<int> bad(threads, 0);
+    on_threads(threads, [&](unsigned t) {
+        for (size_t i = t; i < pieces.size(); i += threads)
+            for (size_t done = 0; done < pieces[i].len;) { const ssize_t r = step(pieces[i].mem + done, pieces[i].off + done, (size_t)(pieces[i].len - done)); if (r <= 0) { bad[t] = 1; return; } done += (size_t)r; }
+    });
+    return std::find(bad.begin(), bad.end(), 1) == bad.end();
+}
+
 void save_cache(agx_unit *u, const std::string &dir, int unit) {
     using namespace cache;
     if (!u->staged || u->cache_map.p) throw Error{E_ARG, "nothing staged from text"};
@@ -674,18 +725,9 @@ void save_cache(agx_unit *u, const std::string &dir, int unit) {
     if (fd < 0) throw Error{E_IO, "CANNOT OPEN FILE! (" + part + ")"};
     bool ok = ftruncate(fd, (off_t)at) == 0 && pwrite(fd, &H, sizeof H, 0) == (ssize_t)sizeof H;
     if (ok) {      // the sections, large pieces on a few threads
-        struct Piece { const char *src; unsigned long long off, len; };
         std::vector<Piece> pieces;
-        for (int i = 0; i < S_N; i++) for (unsigned long long a = 0; a < len[i]; a += 32ull << 20) pieces.push_back(Piece{(const char *)ptr[i] + a, H.off[i] + a, std::min<unsigned long long>(32ull << 20, len[i] - a)});
-        const unsigned threads = (unsigned)std::min<size_t>(8, pieces.size() ? pieces.size() : 1);
-        std::vector<int> bad(threads, 0);
-        on_threads(threads, [&](unsigned t) {
-            for (size_t i = t; i < pieces.size(); i += threads) {
-                size_t done = 0;
-                while (done < pieces[i].len) { const ssize_t w = pwrite(fd, pieces[i].src + done, pieces[i].len - done, (off_t)(pieces[i].off + done)); if (w <= 0) { bad[t] = 1; return; } done += (size_t)w; }
-            }
-        });
-        for (int b : bad) ok = ok && !b;
+        for (int i = 0; i < S_N; i++) cut_pieces(pieces, ptr[i], H.off[i], len[i]);
+        ok = move_pieces(pieces, (unsigned)std::min<size_t>(8, pieces.size() ? pieces.size() : 1), [&](char *mem, unsigned long long off, size_t n) { return pwrite(fd, mem, n, (off_t)off); });
     }
     ok = (close(fd) == 0) && ok;
     if (!ok || rename(part.c_str(), path.c_str()) != 0) { (void)remove(part.c_str()); throw Error{E_IO, "cannot write " + path}; }
@@ -732,13 +774,12 @@ void load_staged_pairs(agx_unit *u, agx::PairsFile &F) {
     if (H.k != u->prm.k || H.batch != u->prm.batch) throw Error{E_ARG, "tmp/_agx_pairs: staged for another k or another BATCH than this unit's"};
     u->nh = H.nh; u->n_runs = H.n_runs; u->n_sides = H.n_sides; u->n_jump = H.n_jump; u->n_codes = H.n_codes; u->n_other = H.n_other; u->stride = H.stride; u->maxlen = H.maxlen; u->n_rows = H.n_rows;
     u->pairs_in_file = H.pairs_in_file; u->sam_pairs = H.sam_pairs; u->n_slots = 0; u->row_off.clear(); u->row_slot.clear(); u->reads_keep.reset(); u->reads_map.reset();
-    alloc_file_order(u->s_hits, u->nh + 1); u->s_sides.alloc(u->n_sides + 1); u->s_jump.alloc(u->n_jump + 1); u->s_runs.alloc(u->n_runs + 1); alloc_file_order(u->s_codes, u->n_codes + 16); u->s_other.alloc(u->n_other + 1);
-    struct Piece { void *dst; const char *src; size_t len; };
+    alloc_pair_arrays(u);
     std::vector<Piece> pieces;
-    auto cut = [&](void *dst, int sec) { for (unsigned long long a = 0; a < H.len[sec]; a += 32ull << 20) pieces.push_back(Piece{(char *)dst + a, F.sec(sec) + a, (size_t)std::min<unsigned long long>(32ull << 20, H.len[sec] - a)}); };
+    auto cut = [&](void *dst, int sec) { cut_pieces(pieces, dst, H.off[sec], H.len[sec]); };
     cut(u->s_hits.p, S_HITS); cut(u->s_sides.p, S_SIDES); cut(u->s_jump.p, S_JUMP); cut(u->s_runs.p, S_RUNS); cut(u->s_codes.p, S_CODES); cut(u->s_other.p, S_OTHER);
     const unsigned threads = (unsigned)std::min<size_t>(std::min<unsigned>(8u, std::max(1u, usable_cpus())), pieces.size() ? pieces.size() : 1);
-    on_threads(threads, [&](unsigned t) { for (size_t i = t; i < pieces.size(); i += threads) memcpy(pieces[i].dst, pieces[i].src, pieces[i].len); });
+    move_pieces(pieces, threads, [&](char *mem, unsigned long long off, size_t n) { memcpy(mem, F.fv->p + off, n); return (ssize_t)n; });
     bool fine = staged_pairs_fine(u, H.n_rows, H.stride, H.maxlen, H.n_runs, H.n_sides, threads);
     for (size_t i = 1; i < u->n_other && fine; i++) fine = u->s_other.p[i - 1] < u->s_other.p[i];      // (the walk bisects the list)
     if (!fine) throw Error{E_FORMAT, "tmp/_agx_pairs: the staged arrays are inconsistent"};
@@ -777,22 +818,13 @@ bool load_cache(agx_unit *u, const std::string &dir, int unit) {
     const char *base = (const char *)m;
     u->nh = H.nh; u->n_runs = H.n_runs; u->n_sides = H.n_sides; u->n_jump = H.n_jump; u->n_cm = H.n_cm; u->n_segs = H.n_segs; u->n_seg0 = (agx_u32)H.n_seg0; u->n_chain_end = (agx_u32)H.n_chain_end; u->n_codes = H.n_codes; u->n_other = H.len[S_OTHER] / 8;
     u->pairs_in_file = H.pairs_in_file; u->sam_pairs = H.sam_pairs; u->stride = H.stride; u->maxlen = H.maxlen; u->n_slots = H.n_slots; u->n_rows = (agx_u32)H.n_rows;
-    alloc_file_order(u->s_hits, u->nh + 1); u->s_sides.alloc(u->n_sides + 1); u->s_jump.alloc(u->n_jump + 1); u->s_runs.alloc(u->n_runs + 1); alloc_file_order(u->s_codes, u->n_codes + 16); u->s_other.alloc(u->n_other + 1); u->s_segs.alloc(u->n_segs + 1); u->s_chain_end.alloc((size_t)u->n_chain_end + 1);
+    alloc_pair_arrays(u); u->s_segs.alloc(u->n_segs + 1); u->s_chain_end.alloc((size_t)u->n_chain_end + 1);
     // the staged arrays: read into the pinned buffers, a few threads, large pieces
-    struct Piece { void *dst; unsigned long long off, len; };
     std::vector<Piece> pieces;
-    auto cut = [&](void *dst, int sec) { for (unsigned long long a = 0; a < H.len[sec]; a += 32ull << 20) pieces.push_back(Piece{(char *)dst + a, H.off[sec] + a, std::min<unsigned long long>(32ull << 20, H.len[sec] - a)}); };
+    auto cut = [&](void *dst, int sec) { cut_pieces(pieces, dst, H.off[sec], H.len[sec]); };
     cut(u->s_hits.p, S_HITS); cut(u->s_sides.p, S_SIDES); cut(u->s_jump.p, S_JUMP); cut(u->s_runs.p, S_RUNS); cut(u->s_codes.p, S_CODES); cut(u->s_other.p, S_OTHER); cut(u->s_segs.p, S_SEGS); cut(u->s_chain_end.p, S_CHAIN_END);
     const unsigned threads = (unsigned)std::min<size_t>(std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency())), pieces.size() ? pieces.size() : 1);
-    std::vector<int> bad(threads, 0);
-    on_threads(threads, [&](unsigned t) {
-        for (size_t i = t; i < pieces.size(); i += threads) {
-            size_t done = 0;
-            while (done < pieces[i].len) { const ssize_t r = pread(fd, (char *)pieces[i].dst + done, pieces[i].len - done, (off_t)(pieces[i].off + done)); if (r <= 0) { bad[t] = 1; return; } done += (size_t)r; }
-        }
-    });
-    bool fine = true;
-    for (int b : bad) fine = fine && !b;
+    bool fine = move_pieces(pieces, threads, [&](char *mem, unsigned long long off, size_t n) { return pread(fd, mem, n, (off_t)off); });
     // what the device and the walk index with must be in range: a file whose lengths are intact but whose content is not is a reason to parse the text again, not to read out of bounds
     if (fine) {
         fine = staged_pairs_fine(u, H.n_rows, H.stride, H.maxlen, H.n_runs, H.n_sides, threads);
@@ -831,13 +863,8 @@ bool load_cache(agx_unit *u, const std::string &dir, int unit) {
     else if (in_reads) { u->reads_map = std::move(reads_map); V.bases = u->reads_map->p; V.row_off = (const uint64_t *)(base + H.off[S_ROWS]); }
     else { V.bases = base + H.off[S_BASES]; u->row_slot.assign((const agx_u32 *)(base + H.off[S_ROWS]), (const agx_u32 *)(base + H.off[S_ROWS]) + H.n_rows); }
     u->V = V; u->n_chain_str = (size_t)H.len[S_CHAIN_STR]; u->pairs_staged = false;
-    stage_rows(u, std::max(threads, std::min(8u, usable_cpus())));
-    stage_order(u, std::max(threads, std::min(16u, usable_cpus())));
-    stage_tiled(u, std::max(threads, std::min(16u, usable_cpus())));
-    stage_rows_tiled(u, std::max(threads, std::min(16u, usable_cpus())));
-    u->V.slot_row = u->tiled ? u->slot_row.data() : nullptr;
-    reserve_landing(u);
-    u->have_ref = u->have_threads = true; u->staged = true; u->consumed = false; u->uploaded = false; u->built = false; u->downloaded = false;
+    finish_staging(u, std::max(threads, std::min(8u, usable_cpus())), std::max(threads, std::min(16u, usable_cpus())));
+    u->have_ref = u->have_threads = true;
     u->stats.ms_stage = now_ms() - t0; u->stats.ms_parse = 0; u->stats.ms_thread = 0; u->stats.from_cache = 1;
     return true;
 }
@@ -849,8 +876,8 @@ agx_u32 spill_min(const agx_unit *u) { const size_t n_pos = u->V.n_pos; return (
 
 // Slices of the node pool, one per region, and the spill area behind them.  Without a measurement every region gets the same share of
 // `main_cap` ids; after a build in which the pool ran out, `demand` holds what every region asked for (the counters keep counting) and the
-// slices are cut to that plus slack.  Returns the ids the layout needs; applies it (queues the copy on `st`) if they fit.
-unsigned long long layout_regions(agx_unit *u, const agx_u32 *demand, agx_u32 main_cap, bool apply, hipStream_t st) {
+// slices are cut to that plus slack.  Returns the ids the layout needs; applies it (queues the copy on `st`, and adds its bytes to `sent`) if they fit.
+unsigned long long layout_regions(agx_unit *u, const agx_u32 *demand, agx_u32 main_cap, bool apply, hipStream_t st, size_t *sent = nullptr) {
     const agx_u32 R = u->n_regions;
     u->s_region_off.alloc((size_t)R + 1);
     agx_u32 *off = u->s_region_off.p;
@@ -863,6 +890,7 @@ unsigned long long layout_regions(agx_unit *u, const agx_u32 *demand, agx_u32 ma
     if (!apply || need > u->pool_cap) return need;
     off[R] = (agx_u32)at; u->spill_lo = (agx_u32)at;
     HIP_OK(hipMemcpyAsync(u->d_region_off.p, off, ((size_t)R + 1) * 4, hipMemcpyHostToDevice, st));
+    if (sent) *sent += ((size_t)R + 1) * 4;
     return need;
 }
 
@@ -1023,8 +1051,10 @@ void do_upload(agx_unit *u) {
         if (u->up_timed) HIP_OK(hipEventRecord(u->ev_up0, st));
         // (AGX_UP_CHUNK_MB: experiment knob — copies cut into pieces of that size)
         static const size_t chunk = getenv("AGX_UP_CHUNK_MB") ? (size_t)atoi(getenv("AGX_UP_CHUNK_MB")) << 20 : 0;
+        size_t sent = 0;      // stats.upload_bytes: what the copies below carry
         auto up = [&](void *dst, const void *src, size_t bytes) {
             for (size_t at = 0; at < bytes;) { const size_t m = chunk ? std::min(chunk, bytes - at) : bytes; HIP_OK(hipMemcpyAsync((char *)dst + at, (const char *)src + at, m, hipMemcpyHostToDevice, st)); at += m; }
+            sent += bytes;
         };
         up(u->d_segs.p, u->s_segs.p, u->n_segs * sizeof(agx_cmseg)); up(u->d_cntruns.p, u->s_cntruns.p, u->n_cntruns * sizeof(agx_cntrun));
         up(u->d_cntchunks.p, u->s_cntchunks.p, u->n_cntchunks * sizeof(agx_chunk)); up(u->d_segchunks.p, u->s_segchunks.p, u->n_segchunks * sizeof(agx_chunk)); up(u->d_segindex.p, u->s_segindex.p, u->n_segindex * 4);
@@ -1032,13 +1062,19 @@ void do_upload(agx_unit *u) {
         if (!u->tiled) up(u->d_perm.p, u->s_perm.p, nh * 4);      // (tile-ordered records carry their hit numbers: agx_k_hit_prep writes the array)
         up(u->d_tfirst.p, u->s_tfirst.p, ((size_t)u->n_tiles + 2) * 4);
         HIP_OK(hipEventRecord(u->ev_hits, st));         // what the front of the build needs (conti-mer tables, hit preparation, binning) is there: it starts while the rest still travels
-        if (u->tiled) {      // the small things first, the read rows last and window by window: a window's sweep starts when its rows are in (do_build)
-            up(u->d_other.p, u->s_other_t.p, u->n_other_t * 8);
+        // The two forms send the same things behind this point and differ in where the read rows go: tile-ordered, the small things first and the rows last, window by window — a
+        // window's sweep starts when its rows are in (do_build); in file order the rows first, whole.
+        auto small = [&] {      // the listed bases (first needed by the sweep), the unit sequence, the chain ends (first needed by the walk preparation), the region layout
+            up(u->d_other.p, u->tiled ? u->s_other_t.p : u->s_other.p, others_up(u) * 8);
             if (u->ref_packed) { up(u->d_wref.p, u->s_ref.p, (n_pos + 3) / 4); up(u->d_refx.p, u->s_refx.p, u->n_refx * sizeof(agx_refx)); } else up(u->d_ref.p, u->s_ref.p, n_pos);
             up(u->d_chain_end.p, u->s_chain_end.p, (size_t)u->n_chain_end * 4);
-            layout_regions(u, nullptr, u->pool_cap - spill_min(u), true, st);
+            layout_regions(u, nullptr, u->pool_cap - spill_min(u), true, st, &sent);      // (equal shares always fit)
+        };
+        auto tables = [&] { up(u->d_blockoff.p, u->s_blockoff.p, u->n_blockoff * 4); up(u->d_blockfirst.p, u->s_blockfirst.p, u->n_blockfirst * 4); up(u->d_anchor.p, u->s_anchor.p, u->n_anchor * 4); };      // of rows that cross as differences
+        if (u->tiled) {
+            small();
+            if (u->rows_diffed) tables();
             const size_t s4 = u->stride / 4;
-            if (u->rows_diffed) { up(u->d_blockoff.p, u->s_blockoff.p, u->n_blockoff * 4); up(u->d_blockfirst.p, u->s_blockfirst.p, u->n_blockfirst * 4); up(u->d_anchor.p, u->s_anchor.p, u->n_anchor * 4); }
             for (agx_u32 w = 0; w < u->n_win; w++) {      // rows of the hits whose first tile lies in window w (a tile's list also names hits that begin in earlier tiles: earlier pieces)
                 const size_t r_lo = win_row(u, w), r_hi = win_row(u, w + 1);
                 if (u->rows_diffed) {                     // the window's count bytes and its piece of the stream of differences (whole 64-row blocks)
@@ -1049,18 +1085,16 @@ void do_upload(agx_unit *u) {
                 HIP_OK(hipEventRecord(u->ev_rows[w], st));
             }
         } else {
-            if (u->rows_diffed) { up(u->d_units.p, u->s_units.p, u->n_units * 2); up(u->d_rowcnt.p, u->s_rowcnt.p, u->n_rowcnt); up(u->d_blockoff.p, u->s_blockoff.p, u->n_blockoff * 4); up(u->d_blockfirst.p, u->s_blockfirst.p, u->n_blockfirst * 4); up(u->d_anchor.p, u->s_anchor.p, u->n_anchor * 4); }
+            if (u->rows_diffed) { up(u->d_units.p, u->s_units.p, u->n_units * 2); up(u->d_rowcnt.p, u->s_rowcnt.p, u->n_rowcnt); tables(); }
             else up(u->d_codes.p, u->s_codes.p, u->n_codes);
-            up(u->d_other.p, u->s_other.p, u->n_other * 8);      // first needed by the sweep
-            if (u->ref_packed) { up(u->d_wref.p, u->s_ref.p, (n_pos + 3) / 4); up(u->d_refx.p, u->s_refx.p, u->n_refx * sizeof(agx_refx)); } else up(u->d_ref.p, u->s_ref.p, n_pos);
-            up(u->d_chain_end.p, u->s_chain_end.p, (size_t)u->n_chain_end * 4);      // first needed by the walk preparation
-            layout_regions(u, nullptr, u->pool_cap - spill_min(u), true, st);
+            small();
         }
         HIP_OK(hipEventRecord(u->ev_uploaded, st));
+        u->stats.upload_bytes = sent;
     } catch (...) { (void)hipStreamSynchronize(st); throw; }      // (copies that were queued before the failure must not outlive the unit's HBM block)
     u->expanded = false;
     trace(u, "upload: queue copies", tq, n_pos);
-    // While the copies run: the download's pinned buffers, by estimate (walk ids ~ 1.05 x positions, special ids ~ 8 % of them), on a helper
+    // While the copies run: the download's pinned buffers, by estimate (helper_estimate), on a helper
     // thread.  Mapping and registering them costs 5-13 ms for a cold cache.  Between the build and the download that was on the unit's critical
     // path; on the unit's worker right here it kept the NEXT unit's upload from starting (a job hands its units out one at a time); beside the
     // build's kernels, or at the start of do_build, it held up the other units' HIP calls.  do_download joins the helper and re-sizes what is too small.
@@ -1070,9 +1104,7 @@ void do_upload(agx_unit *u) {
         const double th0 = now_ms();
         try {
             if (hipSetDevice(u->prm.device) != hipSuccess) return;
-            const size_t ni = n_pos + n_pos / 8 + 4096, nw = ni / 64 + 1, ns = ni / 8 + 4096;
-            u->h_a_str.alloc(ni + 1); u->h_a_meta.alloc(ni + 64); u->h_side_xpos.alloc(n_pos / 8 + 4097);
-            u->h_sp_bits.alloc(nw + 1); u->h_sp_rank.alloc(nw + 1); u->h_sp_node.alloc(ns + 1); u->h_sp_hop.alloc(ns + 2); u->h_a_ovf.alloc(64);
+            graph_arrays(u, helper_estimate(n_pos), [](int, auto &h, auto &, size_t n, size_t pad) { h.alloc(n + pad); });
         } catch (...) { }                               // do_download allocates what is missing and reports
         trace(u, "helper: download buffers", th0, n_pos);
     };
@@ -1082,8 +1114,6 @@ void do_upload(agx_unit *u) {
     u->uploaded = true; u->built = false; u->downloaded = false;
     if (!u->pending_walk) { u->pending_walk = true; g_walks_pending.fetch_add(1); }
     u->stats.ms_upload = now_ms() - t0;
-    u->stats.upload_bytes = u->n_segs * sizeof(agx_cmseg) + u->n_cntruns * sizeof(agx_cntrun) + (u->n_cntchunks + u->n_segchunks) * sizeof(agx_chunk) + (u->ref_packed ? (n_pos + 3) / 4 + u->n_refx * sizeof(agx_refx) : n_pos) + nh * sizeof(agx_whit) + u->n_sides * sizeof(agx_wside) + u->n_runs * sizeof(agx_wrun) + u->n_jump * 4 + nh * 4 + ((size_t)u->n_tiles + 2) * 4 +
-                            (size_t)u->n_chain_end * 4 + (u->rows_diffed ? u->n_units * 2 + u->n_rowcnt + (u->n_blockoff + u->n_blockfirst + u->n_anchor) * 4 : codes_bytes(u)) + others_up(u) * 8 + ((size_t)u->n_regions + 1) * 4 - (u->tiled ? nh * 4 : 0);
     u->stats.device_bytes = u->arena.capacity();
     u->stats.rows_by_reference = u->rows_diffed ? (uint32_t)((u->tiled ? u->nh : u->n_rows) - u->n_rows_explicit) : 0u;
 }
@@ -1360,38 +1390,29 @@ void do_build(agx_unit *u) {
 
 // the pinned buffers a download lands in (a one-shot unit: cut from its dead staged inputs)
 void download_buffers(agx_unit *u) {
-    const size_t n_pos = u->V.n_pos, ni = u->n_ids;
-    const size_t nw = ni / 64 + 1, ns = u->n_special, nside = ni - n_pos;
+    const GraphCounts c = graph_counts(u);
     join_dl_helper(u);
     if (u->prm.flags & AGX_FLAG_ONE_SHOT) {
         // The inputs are in HBM and will not be uploaded again: their staged copies are dead pinned memory.  The download's arrays are cut
         // from the largest of those blocks, largest array first; what does not fit (thin read sets) gets a buffer of its own below.
-        struct Room { char *at; size_t left; } room[8] = {{(char *)u->s_codes.p, u->s_codes.block_bytes()}, {(char *)u->s_hits.p, u->s_hits.block_bytes()}, {(char *)u->s_landing.p, u->s_landing.block_bytes()},
-                                                          {(char *)u->s_codes_t.p, u->s_codes_t.block_bytes()}, {(char *)u->s_hits_t.p, u->s_hits_t.block_bytes()},
-                                                          {(char *)u->s_runs.p, u->s_runs.block_bytes()}, {(char *)u->s_sides.p, u->s_sides.block_bytes()}, {(char *)u->s_other.p, u->s_other.block_bytes()}};
-        // (a loan from an earlier download of this unit object must not survive into alloc() below: the memory it names has been handed out again)
-        u->h_sp_node.release(); u->h_a_meta.release(); u->h_a_str.release(); u->h_sp_hop.release(); u->h_side_xpos.release(); u->h_sp_bits.release(); u->h_sp_rank.release(); u->h_a_ovf.release();
-        auto cut = [&](auto &buf, size_t count) {
-            using T = typename std::remove_reference<decltype(*buf.p)>::type;
-            const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-            for (Room &r : room) if (r.at && r.left >= bytes) { buf.borrow((T *)r.at, count); r.at += bytes; r.left -= bytes; return; }
-        };
+        struct Room { char *at; size_t left; } room[LANDING_ROOMS]; int rooms = 0;
+        landing_rooms(u, [&](auto &b, bool) { room[rooms++] = Room{(char *)b.p, b.block_bytes()}; });
         u->consumed = true; u->staged = false;
-        cut(u->h_sp_node, ns + 1); cut(u->h_a_meta, ni + 64); cut(u->h_a_str, ni + 1); cut(u->h_sp_hop, ns + 2); cut(u->h_side_xpos, nside + 1);
-        cut(u->h_sp_bits, nw + 1); cut(u->h_sp_rank, nw + 1); cut(u->h_a_ovf, (size_t)u->n_ovf + 1);
+        size_t want[GA_N]; char *at[GA_N] = {};
+        // (a loan from an earlier download of this unit object must not survive into alloc() below: the memory it names has been handed out again)
+        graph_arrays(u, c, [&](int which, auto &h, auto &, size_t n, size_t pad) { h.release(); want[which] = ((n + pad) * sizeof(*h.p) + 255) & ~(size_t)255; });
+        for (const int which : GRAPH_CUT_ORDER) for (Room &r : room) if (r.at && r.left >= want[which]) { at[which] = r.at; r.at += want[which]; r.left -= want[which]; break; }
+        graph_arrays(u, c, [&](int which, auto &h, auto &, size_t n, size_t pad) { if (at[which]) h.borrow((decltype(h.p))at[which], n + pad); });
     }
-    u->h_a_str.alloc(ni + 1); u->h_a_meta.alloc(ni + 64); u->h_side_xpos.alloc(nside + 1);
-    u->h_sp_bits.alloc(nw + 1); u->h_sp_rank.alloc(nw + 1); u->h_sp_node.alloc(ns + 1); u->h_sp_hop.alloc(ns + 2);
-    u->h_a_ovf.alloc((size_t)u->n_ovf + 1);
+    graph_arrays(u, c, [](int, auto &h, auto &, size_t n, size_t pad) { h.alloc(n + pad); });      // (keeps a loan, or a helper's buffer, that is large enough)
 }
 
 void do_download(agx_unit *u) {
     if (!u->built) do_build(u);
     HIP_OK(hipSetDevice(u->prm.device));             // the calling thread may never have touched this device
     const double t0 = now_ms();
-    const size_t n_pos = u->V.n_pos, ni = u->n_ids;
+    const GraphCounts c = graph_counts(u); const size_t n_pos = c.n_pos, ni = c.n_ids, ns = c.n_special;
     DeviceTurn &turn = turn_of(u->prm.device);
-    const size_t nw = ni / 64 + 1, ns = u->n_special, nside = ni - n_pos;
     download_buffers(u);
     u->dl_streaming = false;
     // the walk graph into the pinned buffers: plain copy commands on the device's download stream.  (r02 first used a kernel of its own for
@@ -1399,11 +1420,8 @@ void do_download(agx_unit *u) {
     // memory slowed whatever ran beside it, the next unit's binning most of all: the five builds of a cfg3 job ended at 45 ms with it, at
     // 42-45 ms with grids of 16-128 blocks, at 35 ms with the runtime's copies.)
     {
-        void *dst[24]; const void *src[24]; size_t bytes[24]; int n = 0;
-        auto add = [&](void *h, const void *d, size_t b) { if (b) { dst[n] = h; src[n] = d; bytes[n] = b; n++; } };
-        if (ni) { add(u->h_sp_bits.p, u->d_sp_bits.p, nw * 8); add(u->h_sp_rank.p, u->d_sp_rank.p, nw * 4); add(u->h_a_str.p, u->d_a_str.p, ni); add(u->h_a_meta.p, u->d_a_meta.p, ni); }
-        add(u->h_side_xpos.p, u->d_side_xpos.p, nside * 4);
-        add(u->h_sp_node.p, u->d_sp_node.p, ns * sizeof(agx_walknode)); add(u->h_sp_hop.p, u->d_sp_hop.p, ns * sizeof(agx_hop)); add(u->h_a_ovf.p, u->d_a_ovf.p, (size_t)u->n_ovf * sizeof(agx_edge_ovf));
+        void *dst[GA_N]; const void *src[GA_N]; size_t bytes[GA_N]; int n = 0;
+        graph_arrays(u, c, [&](int, auto &h, auto &d, size_t count, size_t) { if (ni && count) { dst[n] = h.p; src[n] = d.p; bytes[n] = count * sizeof(*h.p); n++; } });      // (a unit without ids copies nothing, not even the one word its bitmap always has)
         bool by_engines = u->dl_sdma && n > 0;
         if (by_engines) {                            // (the build is complete and visible: this thread has waited for its last command)
             hsa_signal_store_relaxed(u->dl_signal, n);
@@ -1425,7 +1443,7 @@ void do_download(agx_unit *u) {
     if (getenv("AGX_DL_TIMING")) fprintf(stderr, "[agx download] buffers %.2f ms, copies %.2f ms (%zu ids, %zu records)\n", t1 - t0, now_ms() - t1, ni, ns);
     memset(u->h_a_meta.p + ni, 0, 64);
     u->stats.n_walk_ids = ni; u->stats.n_special = ns;
-    u->stats.download_bytes = 2 * ni + nw * 12 + nside * 4 + ns * (sizeof(agx_walknode) + sizeof(agx_hop)) + (size_t)u->n_ovf * sizeof(agx_edge_ovf);
+    u->stats.download_bytes = graph_bytes(u, c);
     u->downloaded = true;
     u->stats.ms_download = now_ms() - t0;
     trace(u, u->dl_sdma ? "download (copy engines)" : "download (hipMemcpyAsync)", t0, n_pos);
@@ -1466,7 +1484,7 @@ bool begin_streamed_download(agx_unit *u) {
     if (!M || !u->dl_sdma || getenv("AGX_NO_STREAM_DOWNLOAD")) return false;
     HIP_OK(hipSetDevice(u->prm.device));
     const double t0 = now_ms();
-    const size_t n_pos = u->V.n_pos, ni = u->n_ids, ns = u->n_special, nside = ni - n_pos;
+    const GraphCounts c = graph_counts(u); const size_t n_pos = c.n_pos, ni = c.n_ids, ns = c.n_special, nside = ni - n_pos;
     const agx_u32 *rank = u->h_words.p + W_CUT, *side = rank + (AGX_DL_PIECES + 1);
     // the cuts must be what the tables say: ranks and side counts ascending, every side id special, the last cut the whole table
     if (rank[0] != 0 || side[0] != 0 || side[M] != nside || (size_t)rank[M] + nside != ns) return false;
@@ -1477,34 +1495,36 @@ bool begin_streamed_download(agx_unit *u) {
     for (agx_u32 w = 0; w <= M; w++) { u->cut_main[w] = w == M ? (agx_u32)n_pos : u->cuts.word[w] * 64u; u->cut_side[w] = (agx_u32)n_pos + side[w]; }
     struct Copy { void *dst; const void *src; size_t bytes; int piece; };
     std::vector<Copy> copies; copies.reserve(12 * (size_t)M + 4);
-    auto add = [&](int piece, void *h, const void *d, size_t b) { if (b) copies.push_back(Copy{h, d, b, piece}); };
-    add(0, u->h_side_xpos.p, u->d_side_xpos.p, nside * 4); add(0, u->h_a_ovf.p, u->d_a_ovf.p, (size_t)u->n_ovf * sizeof(agx_edge_ovf));
-    add(0, u->h_sp_bits.p, u->d_sp_bits.p, (ni / 64 + 1) * 8); add(0, u->h_sp_rank.p, u->d_sp_rank.p, (ni / 64 + 1) * 4);      // (the bitmap and its ranks whole: 0.2 bytes per id, and two copies instead of four per window — a copy command costs the engines ~10 us)
+    // the buffers, the sources, the counts and the element sizes are the declaration's (graph_arrays); which piece a range of an array travels in is decided here
+    struct Arr { char *h; const char *d; size_t n, elem; } a[GA_N];
+    graph_arrays(u, c, [&](int which, auto &h, auto &d, size_t n, size_t) { a[which] = Arr{(char *)h.p, (const char *)d.p, n, sizeof(*h.p)}; });
+    auto add = [&](int piece, int which, size_t lo, size_t hi) { const Arr &x = a[which]; if (lo < hi) copies.push_back(Copy{x.h + lo * x.elem, x.d + lo * x.elem, (hi - lo) * x.elem, piece}); };
+    add(0, GA_XPOS, 0, a[GA_XPOS].n); add(0, GA_OVF, 0, a[GA_OVF].n);
+    add(0, GA_BITS, 0, a[GA_BITS].n); add(0, GA_RANK, 0, a[GA_RANK].n);      // (the bitmap and its ranks whole: 0.2 bytes per id, and two copies instead of four per window — a copy command costs the engines ~10 us)
     size_t main_bytes = 0;
     auto ids = [&](int piece, size_t lo, size_t hi, size_t r_lo, size_t r_hi) {      // everything about walk ids [lo, hi), whose records are [r_lo, r_hi) of the sparse table
         if (lo >= hi) return;
-        add(piece, u->h_a_meta.p + lo, u->d_a_meta.p + lo, hi - lo);
-        add(piece, u->h_sp_node.p + r_lo, u->d_sp_node.p + r_lo, (r_hi - r_lo) * sizeof(agx_walknode)); add(piece, u->h_sp_hop.p + r_lo, u->d_sp_hop.p + r_lo, (r_hi - r_lo) * sizeof(agx_hop));
-        main_bytes += (hi - lo) + (r_hi - r_lo) * (sizeof(agx_walknode) + sizeof(agx_hop));
+        add(piece, GA_META, lo, hi); add(piece, GA_NODE, r_lo, r_hi); add(piece, GA_HOP, r_lo, r_hi);
+        main_bytes += (hi - lo) * a[GA_META].elem + (r_hi - r_lo) * (a[GA_NODE].elem + a[GA_HOP].elem);
     };
     for (agx_u32 w = 0; w < M; w++) {
         ids(1 + (int)w, u->cut_main[w], u->cut_main[w + 1], rank[w], rank[w + 1]);
         ids(1 + (int)w, u->cut_side[w], u->cut_side[w + 1], (size_t)rank[M] + side[w], (size_t)rank[M] + side[w + 1]);
     }
-    add((int)M + 1, u->h_a_str.p, u->d_a_str.p, ni);
+    add((int)M + 1, GA_STR, 0, a[GA_STR].n);      // the bases last: the walk only takes byte ranges of them
     int count[agx_unit::DL_SIGNALS] = {};
-    for (const Copy &c : copies) count[c.piece]++;
+    for (const Copy &k : copies) count[k.piece]++;
     for (agx_u32 p = 0; p <= M + 1; p++) hsa_signal_store_relaxed(u->dl_piece[p], count[p]);
     u->dl_streaming = true; u->dl_timed.store(false); u->dl_t0 = now_ms(); u->dl_stream_bytes = main_bytes; u->dl_est_ms = (double)main_bytes / download_rate().load();
     size_t queued = 0;
-    for (; queued < copies.size(); queued++) { const Copy &c = copies[queued]; if (hsa_amd_memory_async_copy(c.dst, hsa_copy().cpu, c.src, u->dl_agent, c.bytes, 0, nullptr, u->dl_piece[c.piece]) != HSA_STATUS_SUCCESS) break; }
+    for (; queued < copies.size(); queued++) { const Copy &k = copies[queued]; if (hsa_amd_memory_async_copy(k.dst, hsa_copy().cpu, k.src, u->dl_agent, k.bytes, 0, nullptr, u->dl_piece[k.piece]) != HSA_STATUS_SUCCESS) break; }
     if (queued < copies.size()) {      // the engines refused: what was queued still counts down; then the usual way (through HIP from now on)
         for (size_t i = queued; i < copies.size(); i++) hsa_signal_subtract_relaxed(u->dl_piece[copies[i].piece], 1);
         stream_wait_all(u); u->dl_sdma = false; return false;
     }
     wait_signal(u->dl_piece[0]);
     u->stats.n_walk_ids = ni; u->stats.n_special = ns;
-    u->stats.download_bytes = 2 * ni + (ni / 64 + 1) * 12 + nside * 4 + ns * (sizeof(agx_walknode) + sizeof(agx_hop)) + (size_t)u->n_ovf * sizeof(agx_edge_ovf);
+    u->stats.download_bytes = graph_bytes(u, c);
     trace(u, "download (streamed): queued, head in", t0, n_pos);
     return true;
 }
@@ -1535,8 +1555,7 @@ void do_release(agx_unit *u) {
     if (u->uploaded) { (void)hipSetDevice(u->prm.device); (void)hipEventSynchronize(u->ev_uploaded); (void)hipEventSynchronize(u->ev_built); (void)hipEventSynchronize(u->ev_dl); }      // (its commands are done before its memory goes)
     u->huge = false; u->dense = false;
     u->arena.reset();                                  // (empties every d_* view with it)
-    u->h_a_str.release(); u->h_a_meta.release(); u->h_side_xpos.release(); u->h_sp_rank.release(); u->h_sp_bits.release(); u->h_sp_node.release(); u->h_fetch.release(); u->h_a_ovf.release();
-    u->h_sp_hop.release();
+    graph_arrays(u, GraphCounts{}, [](int, auto &h, auto &, size_t, size_t) { h.release(); }); u->h_fetch.release();
     u->pool_cap = u->spill_lo = u->ovf_cap = u->list_cap = u->sp_cap = 0;
     u->uploaded = u->built = u->downloaded = false;
     join_helper(u);
@@ -1928,13 +1947,14 @@ int agx_unit_walk_graph(agx_unit *u, int streamed, agx_walk_graph *g) {
             stream_wait_all(u);           // every window and the bases
         } else do_download(u);
         const GraphView G = view_of(u);
-        const size_t ni = G.n_ids, nw = ni / 64 + 1, ns = G.n_special, nside = ni - G.n_pos;
+        const size_t ni = G.n_ids; size_t nb[GA_N];      // nb: the bytes of each array that were downloaded
+        graph_arrays(u, graph_counts(u), [&](int which, auto &h, auto &, size_t n, size_t) { nb[which] = n * sizeof(*h.p); });
         auto dup = [](const void *p, size_t bytes) { void *q = malloc(bytes + 1); if (!q) throw Error{E_ARG, "out of host memory"}; if (bytes) memcpy(q, p, bytes); return q; };
         g->n_pos = G.n_pos; g->n_ids = G.n_ids; g->n_special = G.n_special; g->n_ovf = (uint32_t)G.n_ovf; g->n_chain_str = u->n_chain_str;
-        g->meta = (uint8_t *)dup(G.meta, ni); g->str = (char *)dup(G.str, ni); g->side_xpos = (uint32_t *)dup(G.side_xpos, nside * 4);
-        g->sp_bits = (uint64_t *)dup(G.sp_bits, nw * 8); g->sp_rank = (uint32_t *)dup(G.sp_rank, nw * 4);
-        g->sp_node = (agx_walk_rec *)dup(G.sp_node, ns * sizeof(agx_walknode)); g->sp_hop = (agx_walk_hop *)dup(G.sp_hop, ns * sizeof(agx_hop));
-        g->ovf = (uint32_t *)dup(G.ovf, G.n_ovf * sizeof(agx_edge_ovf)); g->chain_str = (char *)dup(u->V.chain_str, u->n_chain_str);
+        g->meta = (uint8_t *)dup(G.meta, nb[GA_META]); g->str = (char *)dup(G.str, nb[GA_STR]); g->side_xpos = (uint32_t *)dup(G.side_xpos, nb[GA_XPOS]);
+        g->sp_bits = (uint64_t *)dup(G.sp_bits, nb[GA_BITS]); g->sp_rank = (uint32_t *)dup(G.sp_rank, nb[GA_RANK]);
+        g->sp_node = (agx_walk_rec *)dup(G.sp_node, nb[GA_NODE]); g->sp_hop = (agx_walk_hop *)dup(G.sp_hop, nb[GA_HOP]);
+        g->ovf = (uint32_t *)dup(G.ovf, nb[GA_OVF]); g->chain_str = (char *)dup(u->V.chain_str, u->n_chain_str);
         if (want_all) {                   // every id's record through the fetch path: whole rows of 64 ids a stride apart, then the rest as one row
             g->all_node = (agx_walk_rec *)malloc((ni + 1) * sizeof(agx_walknode));
             if (!g->all_node) throw Error{E_ARG, "out of host memory"};

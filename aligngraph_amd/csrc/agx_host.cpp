@@ -320,18 +320,6 @@ unsigned loader_threads(size_t bytes) {
     const unsigned cores = usable_cpus(), share = std::min(32u, std::max(4u, cores / 4));
     return (unsigned)std::min<size_t>(std::min(share, cores), bytes / (2u << 20) + 1);
 }
-// fn(t) on `threads` threads.  Nothing may leave a worker thread as an exception (it would terminate the process behind a C ABI that promises
-// return codes): whatever a worker throws is carried to the caller and rethrown there; a thread that cannot be started just leaves its
-// share to be done here.
-template <class F> void on_threads(unsigned threads, F fn) {
-    std::vector<std::thread> th; std::vector<std::exception_ptr> ex(threads);
-    auto guarded = [&](unsigned t) { try { fn(t); } catch (...) { ex[t] = std::current_exception(); } };
-    std::vector<unsigned> mine{0u};
-    for (unsigned t = 1; t < threads; t++) { try { th.emplace_back(guarded, t); } catch (const std::system_error &) { mine.push_back(t); } }
-    for (unsigned t : mine) guarded(t);
-    for (auto &x : th) x.join();
-    for (auto &e : ex) if (e) std::rethrow_exception(e);
-}
 
 // One record = a header line and a sequence line; the index holds where every record starts, up to the first empty line (which ends the file for
 // the reference's getline loops), and how many header lines there are (what decides the batch boundaries, AG:361-404).  Two passes at SIMD speed

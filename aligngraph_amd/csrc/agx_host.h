@@ -3,15 +3,31 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <functional>
 #include <memory>
 #include <string>
+#include <system_error>
+#include <thread>
 #include <vector>
 #include "agx_core.h"
 
 namespace agx {
 
 struct Error { int code; std::string msg; };   // thrown inside the library, converted to a return code at the C-ABI
+
+// fn(t) on `threads` threads.  Nothing may leave a worker thread as an exception (it would terminate the process behind a C ABI that promises
+// return codes): whatever a worker throws is carried to the caller and rethrown there; a thread that cannot be started just leaves its
+// share to be done here.
+template <class F> void on_threads(unsigned threads, F fn) {
+    std::vector<std::thread> th; std::vector<std::exception_ptr> ex(threads);
+    auto guarded = [&](unsigned t) { try { fn(t); } catch (...) { ex[t] = std::current_exception(); } };
+    std::vector<unsigned> mine{0u};
+    for (unsigned t = 1; t < threads; t++) { try { th.emplace_back(guarded, t); } catch (const std::system_error &) { mine.push_back(t); } }
+    for (unsigned t : mine) guarded(t);
+    for (auto &x : th) x.join();
+    for (auto &e : ex) if (e) std::rethrow_exception(e);
+}
 
 // error codes (include/agx.h mirrors these)
 enum {
