@@ -24,7 +24,7 @@ EXPORTS = [
     "agx_reads_open", "agx_reads_close", "agx_unit_load_files_shared", "agx_run_unit_shared",
     "agx_unit_stage", "agx_unit_release", "agx_pool_trim", "agx_unit_cache_build", "agx_unit_cache_save", "agx_unit_hbm_needed",
     "agx_unit_trim", "agx_unit_unitigs", "agx_unitigs_free", "agx_unitigs_gfa", "agx_text_free",
-    "agx_unit_walk_graph", "agx_walk_graph_free",
+    "agx_unit_walk_graph", "agx_walk_graph_free", "agx_unit_front", "agx_front_free",
 ]
 
 
@@ -112,6 +112,39 @@ def walk_graph_arrays(g):
             "all_node": arr(g.all_node, ni, WALK_RECORD) if g.all_node else None}
 
 
+class Front(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("n_pos", "n_hits", "n_runs", "n_cm", "n_tiles", "stride", "n_rows", "lookback", "n_entries", "long_count", "n_long",
+                                                "w_err", "w_status", "tiled", "rows_diffed", "ref_packed", "dense_queued", "swept_windows")] + \
+               [(n, ctypes.c_void_p) for n in ("ref", "vcodes", "runs", "cm_start", "cm", "cm_head", "dhit", "perm", "tile_first", "ckey", "tile_cnt", "tile_off",
+                                                "tile_recs", "long_list")]
+
+
+# numpy layouts of the front's records (agx_front, include/agx.h)
+FRONT_DHIT = [("a_t0", "<u4"), ("b_t0", "<u4"), ("a_runs", "<u4"), ("b_runs", "<u4"), ("a_slot", "<u4"), ("len", "<u2"), ("jstar", "<u2"), ("a_nruns", "<u2"), ("b_nruns", "<u2"),
+              ("flags", "<u4"), ("x_lo", "<u4"), ("x_hi", "<u4")]
+FRONT_LREC = [("qoff1", "<u4"), ("boff1", "<u4"), ("qoff2", "<u4"), ("boff2", "<u4"), ("slot", "<u4"), ("lenjs", "<u4"), ("geo", "<u4"), ("hit", "<u4")]
+FRONT_RUN = [("q", "<u4"), ("t", "<u4"), ("n", "<u4")]
+FRONT_CMKEY = [("cid", "<u4"), ("coff", "<u4")]
+FRONT_CMHEAD = [("cid", "<u4"), ("coff", "<u4"), ("n", "<u4"), ("start", "<u4")]
+
+
+def front_arrays(f):
+    """An agx_front-shaped ctypes struct (this library's, or the test executor's) as a dict: the counts and form flags as ints, ref as bytes, the arrays as numpy arrays
+    (records as structured arrays with the fields of FRONT_*; vcodes as [n_rows, stride])."""
+    import numpy as np
+
+    def arr(p, n, dt):
+        return np.frombuffer(ctypes.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy() if p and n else np.zeros(0, dt)
+    out = {n: int(getattr(f, n)) for n, t in Front._fields_ if t is ctypes.c_uint32}
+    nt = f.n_tiles
+    out.update({"ref": ctypes.string_at(f.ref, f.n_pos) if f.ref else b"", "vcodes": arr(f.vcodes, f.n_rows * f.stride, "u1").reshape(f.n_rows, f.stride),
+                "runs": arr(f.runs, f.n_runs, FRONT_RUN), "cm_start": arr(f.cm_start, f.n_pos + 1, "<u4"), "cm": arr(f.cm, f.n_cm, FRONT_CMKEY),
+                "cm_head": arr(f.cm_head, f.n_pos + 1, FRONT_CMHEAD), "dhit": arr(f.dhit, f.n_hits, FRONT_DHIT), "perm": arr(f.perm, f.n_hits, "<u4"),
+                "tile_first": arr(f.tile_first, nt + 1, "<u4"), "ckey": arr(f.ckey, f.n_hits, "<u4"), "tile_cnt": arr(f.tile_cnt, nt + 1, "<u4"),
+                "tile_off": arr(f.tile_off, nt + 1, "<u4"), "tile_recs": arr(f.tile_recs, f.n_entries, FRONT_LREC), "long_list": arr(f.long_list, f.n_long, "<u4")})
+    return out
+
+
 class AgxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("agx error %d: %s" % (code, msg))
@@ -165,6 +198,9 @@ def lib():
         L.agx_unit_walk_graph.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(WalkGraph)]
         L.agx_walk_graph_free.argtypes = [ctypes.POINTER(WalkGraph)]
         L.agx_walk_graph_free.restype = None
+        L.agx_unit_front.argtypes = [ctypes.c_void_p, ctypes.POINTER(Front)]
+        L.agx_front_free.argtypes = [ctypes.POINTER(Front)]
+        L.agx_front_free.restype = None
         L.agx_unit_unitigs.argtypes = [ctypes.c_void_p, ctypes.POINTER(Unitigs)]
         L.agx_unitigs_free.argtypes = [ctypes.POINTER(Unitigs)]
         L.agx_unitigs_free.restype = None
@@ -370,6 +406,16 @@ class Unit:
             return walk_graph_arrays(g)
         finally:
             lib().agx_walk_graph_free(ctypes.byref(g))
+
+    def front(self):
+        """Test and inspection hook (agx_unit_front): what the device holds in front of the node sweep after build() — the expanded inputs, the derived hit records in the
+        device's order, the tile histogram, offsets and lists — as front_arrays() lays it out.  Before download(), trim() and release(); the unit stays usable."""
+        f = Front()
+        self._check(lib().agx_unit_front(self._h, ctypes.byref(f)))
+        try:
+            return front_arrays(f)
+        finally:
+            lib().agx_front_free(ctypes.byref(f))
 
     def unitigs(self):
         """The unit's pruned graph compacted into unitigs on the device (agx_unit_unitigs; needs keep_counts): numpy arrays per segment and link, the

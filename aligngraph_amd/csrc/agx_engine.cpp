@@ -256,6 +256,7 @@ struct agx_unit {
     PBuf<agx_u32> s_chain_end, s_region_off; PBuf<agx_cmseg> s_segs; size_t n_segs = 0;
     // r06, tile-ordered upload (stage_tiled): the wire records and the read rows in the order of the hits' first tiles — what the device is sent instead of s_hits / s_perm / s_codes / s_other
     PBuf<agx_whit> s_hits_t; PBuf<agx_u8> s_codes_t; PBuf<unsigned long long> s_other_t; size_t n_other_t = 0; bool tiled = false; std::vector<agx_u32> slot_row;      // slot_row[i] = staged row of the i-th hit's left mate (the walk's k-mer tails)
+    agx_u32 front_windows = 1;      // windows the last build's node sweep ran in (agx_unit_front)
     agx_u32 n_win = 1, win_tile[9] = {};      // a unit's first build sweeps windows of tiles as their rows land: window w = tiles [win_tile[w], win_tile[w + 1])
     hipEvent_t ev_rows[8] = {}, ev_win[8] = {}, ev_sw0[8] = {}, ev_sw1[8] = {};      // rows of window w in HBM / expanded; around window w's sweep (its time is the sum over the windows)
     PBuf<agx_u32> s_perm, s_tfirst, s_jump_at; agx_u32 lookback = 2;      // the hits in the order of their first tile (stage_order): perm[i] = the i-th hit of that order, tile_first[t] = hits in front of tile t's own; pass J's hits as places in it
@@ -1377,7 +1378,7 @@ void do_build(agx_unit *u) {
 #endif
         break;
     }
-    u->built = true; u->downloaded = false; u->trimmed = false;
+    u->built = true; u->downloaded = false; u->trimmed = false; u->front_windows = swept_windows;
     u->stats.ms_build_span = u->ev.all ? u->ev.span() : 0.0;
     u->stats.ms_prep = u->ev.ms(B_PREP); u->stats.ms_bin = u->ev.ms(B_BIN); u->stats.ms_node_sweep = u->ev.ms(B_NODE);
     if (swept_windows >= 1 && swept_timed) {      // a windowed first build: the sweep's time is the sum over its windows (between them the stream may have waited for rows that were still travelling)
@@ -1972,6 +1973,53 @@ void agx_walk_graph_free(agx_walk_graph *g) {
     if (!g) return;
     free(g->meta); free(g->str); free(g->side_xpos); free(g->sp_bits); free(g->sp_rank); free(g->sp_node); free(g->sp_hop); free(g->ovf); free(g->chain_str); free(g->all_node);
     memset(g, 0, sizeof *g);
+}
+
+// Test and inspection hook: the arrays in front of the node sweep, as the last attempt of the last build left them in HBM.  Every copy goes through the download stream
+// (under its mutex, like a record fetch) into ordinary memory and is waited for there; the unit's own buffers are read, none is taken.
+int agx_unit_front(agx_unit *u, agx_front *f) {
+    if (!u || !f) return AGX_E_ARG;
+    memset(f, 0, sizeof *f);
+    const int rc = guarded(u, [&] {
+        static_assert(sizeof(agx_dhit) == 40 && sizeof(agx_cmkey) == 8 && sizeof(agx_cmhead) == 16 && sizeof(agx_run) == 12, "include/agx.h describes the front's records as words");
+        if (u->prm.flags & AGX_FLAG_ONE_SHOT) throw Error{E_ARG, "front: a one-shot unit gives its arrays away with its only download"};
+        if (!u->built || u->trimmed || u->downloaded) throw Error{E_ARG, "front: the unit is not built (call agx_unit_build; not after agx_unit_download, agx_unit_trim or agx_unit_release)"};
+        HIP_OK(hipSetDevice(u->prm.device));
+        HIP_OK(wait_event(u->ev_built));
+        const size_t n_pos = u->V.n_pos, nh = u->nh, nt = u->n_tiles, vbytes = codes_bytes(u) * 4;
+        const agx_u32 *w = u->h_words.p;
+        f->n_pos = (uint32_t)n_pos; f->n_hits = (uint32_t)nh; f->n_runs = (uint32_t)u->n_runs; f->n_cm = (uint32_t)u->n_cm; f->n_tiles = (uint32_t)nt; f->stride = u->stride;
+        f->n_rows = u->stride ? (uint32_t)(vbytes / u->stride) : 0u; f->lookback = u->lookback;
+        f->long_count = w[W_LONGCOUNT]; f->n_long = std::min<agx_u32>(w[W_LONGCOUNT], AGX_LONG_MAX); f->w_err = w[W_ERR]; f->w_status = w[W_STATUS];
+        f->tiled = u->tiled; f->rows_diffed = u->rows_diffed; f->ref_packed = u->ref_packed; f->dense_queued = u->dense; f->swept_windows = u->front_windows;
+        DeviceTurn &turn = turn_of(u->prm.device);
+        std::lock_guard<std::mutex> l(turn.down_m);
+        auto down = [&](auto *&dst, const void *src, size_t bytes) {
+            dst = (std::remove_reference_t<decltype(dst)>)malloc(bytes + 16);
+            if (!dst) throw Error{E_ARG, "out of host memory"};
+            if (bytes) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, turn.down));
+        };
+        try {
+            down(f->tile_off, u->d_tile_off.p, (nt + 1) * 4);
+            HIP_OK(hipStreamSynchronize(turn.down));
+            f->n_entries = f->tile_off[nt];
+            if (f->n_entries > u->list_cap) throw Error{E_DEVICE, "internal: the tile lists of a converged build do not fit their buffer"};
+            down(f->ref, u->d_ref.p, n_pos); down(f->vcodes, u->d_vcodes.p, (size_t)f->n_rows * u->stride); down(f->runs, u->d_runs.p, u->n_runs * sizeof(agx_run));
+            down(f->cm_start, u->d_cm_start.p, (n_pos + 1) * 4); down(f->cm, u->d_cm.p, u->n_cm * sizeof(agx_cmkey)); down(f->cm_head, u->d_cm_head.p, (n_pos + 1) * sizeof(agx_cmhead));
+            down(f->dhit, u->d_dhit.p, nh * sizeof(agx_dhit)); down(f->perm, u->d_perm.p, nh * 4); down(f->tile_first, u->d_tfirst.p, (nt + 1) * 4); down(f->ckey, u->d_ckey.p, nh * 4);
+            down(f->tile_cnt, u->d_tile_cnt.p, (nt + 1) * 4); down(f->tile_recs, u->d_tile_recs.p, (size_t)f->n_entries * 32); down(f->long_list, u->d_long.p, (size_t)f->n_long * 4);
+            HIP_OK(hipStreamSynchronize(turn.down));
+        } catch (...) { (void)hipStreamSynchronize(turn.down); throw; }      // (no copy outlives the memory it lands in)
+    });
+    if (rc != AGX_OK) agx_front_free(f);
+    return rc;
+}
+
+void agx_front_free(agx_front *f) {
+    if (!f) return;
+    free(f->ref); free(f->vcodes); free(f->runs); free(f->cm_start); free(f->cm); free(f->cm_head); free(f->dhit); free(f->perm); free(f->tile_first); free(f->ckey);
+    free(f->tile_cnt); free(f->tile_off); free(f->tile_recs); free(f->long_list);
+    memset(f, 0, sizeof *f);
 }
 
 // Unitig export: the kernels of agx_unitig.hip on a stream of the export's own, scratch from an arena of its own (given back to the device's

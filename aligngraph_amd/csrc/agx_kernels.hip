@@ -282,7 +282,8 @@ __device__ __forceinline__ void agx_put_rec(uint4 *recs, agx_u32 at, const agx_d
 // order (tile_first), filtered by the last tile each hit reaches (ckey) — coalesced reads of 4-byte keys and hit numbers, no scatter, no atomics — plus the few hits that
 // span more tiles than the window looks back over (long_list).  What is kept is compacted into the wavefront's low lanes, ranked by hit number (= place in the SAM file;
 // unique, so an entry's rank is the number of smaller keys) and the records are written at tile_off[t] + rank.  The count must be the histogram's (hit_prep counted the
-// same hits): err bit 3 otherwise.
+// same hits): err bit 3 otherwise, and — the tile's list is then left unwritten — the status bit that keeps the sweeps and everything behind them from running, so that the
+// host reports the inconsistency instead of the device faulting on records nobody wrote.
 //
 // The kernel's time is the depth of its chain of dependent loads (offsets -> keys -> derived records -> runs -> stores: ~9 us per tile) times the rounds of
 // resident wavefronts (a CU holds 32): 0.51 ms for the 476 k tiles of a 30 Mb unit with a wavefront per tile.  So a wavefront takes TWO tiles and issues each level
@@ -312,7 +313,7 @@ __device__ __forceinline__ void agx_tile_fill_general(const agx_fill_args &A, ag
         const agx_u32 x_lo = in ? A.dhit[i].x_lo : 1u, x_hi = in ? A.dhit[i].x_hi : 0u;
         take(in && x_lo / AGX_TILE <= tile && tile <= x_hi / AGX_TILE, i, in ? A.perm[i] : 0u);
     }
-    if (kept != n) { if (lane == 0) atomicOr(A.err, 8u); return; }
+    if (kept != n) { if (lane == 0) { atomicOr(A.err, 8u); atomicOr(A.status, 16u); } return; }      // (status: the list stays unwritten, so nothing behind this kernel may read the lists — as where they are not made at all)
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // (single wavefront: its LDS / global writes above are visible to its own later reads)
     if (in_lds) {
         for (agx_u32 e = lane; e < n; e += 64) {
@@ -369,7 +370,7 @@ __global__ void __launch_bounds__(256) agx_k_tile_fill(agx_fill_args A) {
     for (agx_u32 t = 0; t < AGX_FILL_TILES; t++) {
         const bool ok = fast[t] && key[t] != AGX_NONE && key[t] >= tile[t];
         const unsigned long long m = __ballot(ok);
-        if (fast[t] && (agx_u32)__popcll(m) != n[t]) { if (lane == 0) atomicOr(A.err, 8u); fast[t] = false; todo[t] = false; }
+        if (fast[t] && (agx_u32)__popcll(m) != n[t]) { if (lane == 0) { atomicOr(A.err, 8u); atomicOr(A.status, 16u); } fast[t] = false; todo[t] = false; }
         if (ok && fast[t]) { const agx_u32 at = (agx_u32)__popcll(m & below); sh[wave][t * 128u + at] = c_lo[t] + lane; sh[wave][t * 128u + 64u + at] = hn[t]; }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // (single wavefront: its LDS writes are visible to its own later reads)

@@ -171,6 +171,33 @@ typedef struct {
     agx_walk_rec *all_node; /* [n_ids] (want_all_node) every id's record, read through the path the walk fetches single records by */
 } agx_walk_graph;
 
+/* The front of a build: what the device holds in front of the node sweep after the last converged attempt of agx_unit_build — the arrays the first build expands
+ * out of their upload forms (whichever forms the unit used: the contents are the same), the derived hit records and the tile lists.  Hits are in the DEVICE's order
+ * (the order of their first tile); perm[i] is the file number of the hit at place i.  malloc'd; free with agx_front_free. */
+typedef struct {
+    uint32_t n_pos, n_hits, n_runs, n_cm, n_tiles, stride, n_rows;   /* n_rows: rows of vcodes (tile-ordered upload: one per hit; else one per staged read row) */
+    uint32_t lookback;         /* tiles a list's window of the tile order looks back over */
+    uint32_t n_entries;        /* = tile_off[n_tiles] */
+    uint32_t long_count, n_long;   /* hits that span lookback tiles or more; n_long = min(long_count, 1024) of them are listed */
+    uint32_t w_err, w_status;  /* the build's error and status words (0, 0: nothing went wrong; status bits that made an earlier attempt repeat are gone) */
+    uint32_t tiled, rows_diffed, ref_packed, dense_queued, swept_windows;   /* the forms the unit used: tile-ordered upload, read rows as differences from the reference, unit sequence as 2 bits
+                                                                               per base, the scatter fallback of the tile lists queued, windows the last attempt's node sweep ran in */
+    char *ref;                 /* [n_pos] */
+    uint8_t *vcodes;           /* [n_rows * stride] vote codes; a row's bytes from the read's length up to the stride are class-0 codes, bytes behind the last row are not copied */
+    agx_run *runs;             /* [n_runs] */
+    uint32_t *cm_start;        /* [n_pos + 1] */
+    uint32_t *cm;              /* [n_cm * 2] cid, coff */
+    uint32_t *cm_head;         /* [(n_pos + 1) * 4] cid, coff, n, start; entry n_pos: "no position" */
+    uint32_t *dhit;            /* [n_hits * 10] the derived records as ten words: a_t0, b_t0, a_runs, b_runs, a_slot, len | jstar << 16, a_nruns | b_nruns << 16, flags, x_lo, x_hi */
+    uint32_t *perm;            /* [n_hits] */
+    uint32_t *tile_first;      /* [n_tiles + 1] places in front of each tile's own hits */
+    uint32_t *ckey;            /* [n_hits] last tile of the hit at place i; 0xFFFFFFFF for skipped and long hits */
+    uint32_t *tile_cnt;        /* [n_tiles + 1] the histogram (entry n_tiles: 0) */
+    uint32_t *tile_off;        /* [n_tiles + 1] its exclusive prefix sum */
+    uint32_t *tile_recs;       /* [n_entries * 8] qoff1, boff1, qoff2, boff2, slot, len | jstar << 16, geo, hit (place in the device's order) */
+    uint32_t *long_list;       /* [n_long] places of the long hits, in the order the atomics gave */
+} agx_front;
+
 /* ---- entry points ------------------------------------------------------------------------------------ */
 
 const char *agx_version(void);
@@ -240,6 +267,11 @@ void agx_graph_free(agx_graph *g);
  * inputs and cannot be made twice. */
 int agx_unit_walk_graph(agx_unit *u, int streamed, agx_walk_graph *g);
 void agx_walk_graph_free(agx_walk_graph *g);
+/* Test and inspection hook: copies the front of the last build out of HBM (agx_front above).  After agx_unit_build, before anything that gives the arrays away: AGX_E_ARG
+ * on a unit that is not built, after agx_unit_download, agx_unit_trim or agx_unit_release, and for AGX_FLAG_ONE_SHOT units.  The copies are queued on the device's download
+ * stream and waited for; nothing is allocated on the device and a build that does not call this pays nothing for it. */
+int agx_unit_front(agx_unit *u, agx_front *f);
+void agx_front_free(agx_front *f);
 /* After agx_unit_build of a unit created with AGX_FLAG_KEEP_COUNTS, before agx_unit_trim / agx_unit_release (AGX_FLAG_ONE_SHOT units: before their download
  * or finish).  Runs on the device over the node table the build left there and changes nothing the walk reads.  AGX_E_ARG otherwise. */
 int agx_unit_unitigs(agx_unit *u, agx_unitigs *t);

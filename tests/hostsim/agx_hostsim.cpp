@@ -43,7 +43,10 @@ struct SimGraph {
 // What a test may ask of the executor besides the graph: the lean record of every list entry (what pass 0 of the device's node sweep reads, made by the
 // same agx_lean_make_v from the same hits), and pass 0 on packed buckets (agx_bucket::packed: the device's layout, counters as 16-bit halves).
 // edges: which path of the edge build made each edge (SimEdges), with the slow list as the device makes it.
-struct SimOptions { bool packed = false, records = false, edges = false; };
+struct SimOptions { bool packed = false, records = false, edges = false, front = false; };
+// front: what lies in front of the node sweep, whole — the expanded vote codes, the conti-mer keys and heads, the derived hit records in file order and the lean record of every
+// list entry with its slot and hit words (SimRecords::recs leaves those two out); the arrays the loaders own (T.ref, P.runs, T.cm_start) are copied by the caller
+struct SimFront { std::vector<agx_u8> vcodes; std::vector<agx_cmkey> cm; std::vector<agx_cmhead> cm_head; std::vector<agx_dhit> dhit; std::vector<agx_u32> tile_off; std::vector<agx_lrec> lrecs; };
 struct SimRecords { std::vector<agx_u32> tile_len, recs; };      // recs: per list entry tile, geo, qoff1, boff1, qoff2, boff2, lenjs
 enum { AGX_SIM_REC_WORDS = 7 };
 // The edge build's paths, counted around the serial loop (tests/edge_units.py names them).  Every counter but the slow ones counts what the executor does; the
@@ -62,7 +65,7 @@ struct SimEdges {
     std::vector<agx_u32> ovf;       // per overflow append, in order: position of the source, of the target, source's variant, 1 if the pair was listed before
 };
 
-void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage, agx_u32 maxv_first, SimGraph &S, int &n_big_tiles, const SimOptions &opt, SimRecords &R, SimEdges &E) {
+void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage, agx_u32 maxv_first, SimGraph &S, int &n_big_tiles, const SimOptions &opt, SimRecords &R, SimEdges &E, SimFront &F) {
     const agx_u32 n_pos = (agx_u32)T.ref.size();
     const agx_u32 n_tiles = (n_pos + AGX_TILE - 1) / AGX_TILE;
     // hit_prep
@@ -95,6 +98,7 @@ void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage,
             // the lean record of the entry (what pass 0 of the device's node sweep reads): wherever it is not kind GENERAL it must give the same arrival on every lane
             const agx_lrec lr = agx_lean_make(dh[h], P.runs.data(), t, k, h);
             lean_kinds[lr.geo >> 30]++;
+            if (opt.front) F.lrecs.push_back(lr);
             if (opt.records) { const agx_u32 w[AGX_SIM_REC_WORDS] = {t, lr.geo, lr.qoff1, lr.boff1, lr.qoff2, lr.boff2, lr.lenjs}; R.recs.insert(R.recs.end(), w, w + AGX_SIM_REC_WORDS); }
             if (lr.slot != dh[h].a_slot || lr.hit != h || lr.lenjs != ((agx_u32)dh[h].len | ((agx_u32)dh[h].jstar << 16)) || (((lr.geo & AGX_LF_AREV) != 0) != ((dh[h].flags & AGX_HF_AREV) != 0)))
                 throw Error{E_ARG, "a lean tile record names another read"};
@@ -170,6 +174,7 @@ void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage,
         if (cm2.size() && memcmp(cm2.data(), cmk.data(), cm2.size() * sizeof(agx_cmkey)) != 0) throw Error{E_ARG, "chunked conti-mer tables: keys differ"};
         if (memcmp(head2.data(), cmh.data(), head2.size() * sizeof(agx_cmhead)) != 0) throw Error{E_ARG, "chunked conti-mer tables: heads differ"};
     }
+    if (opt.front) { F.vcodes = vcodes; F.cm = cmk; F.cm_head = cmh; F.dhit = dh; F.tile_off = tile_off; }
     A.cm_start = T.cm_start.data(); A.cm = cmk.data(); A.cm_head = cmh.data(); A.ref = T.ref.data();
     A.dhit = dh.data(); A.runs = P.runs.data(); A.vcodes = vcodes.data(); A.stride = P.stride;
     A.tile_off = tile_off.data();
@@ -372,9 +377,12 @@ typedef struct {
     // each, the first n_seg0 of rank 0), the device's index of the rank-0 runs and the chain-end positions: what the device's hop search and chain-end marks start from
     agx_walk_graph walk;
     uint32_t n_segs, n_seg0, n_seg_index, n_chain_end; uint32_t *segs, *seg_index, *chain_end;
+    // AGX_SIM_FRONT: the front of the build in the layout of agx_unit_front, hits in FILE order: ref, vcodes (a row per read slot), runs, cm_start, cm, cm_head, dhit, tile_off and
+    // tile_recs (hit = file number, slot = the executor's read slot) are filled; the device's own order (perm, tile_first, ckey), its histogram and its long list are left empty
+    agx_front front;
 } agx_hostsim_result;
 
-enum { AGX_SIM_GRAPH = 1, AGX_SIM_PACKED = 2, AGX_SIM_RECORDS = 4, AGX_SIM_EDGES = 8, AGX_SIM_WALK = 16 };
+enum { AGX_SIM_GRAPH = 1, AGX_SIM_PACKED = 2, AGX_SIM_RECORDS = 4, AGX_SIM_EDGES = 8, AGX_SIM_WALK = 16, AGX_SIM_FRONT = 32 };
 enum { AGX_SIM_SEG_WORDS = 6 };      // pos0, len, rank, hop_str0, hop_len0, hop_end
 
 int agx_hostsim_run_unit(const char *tmp_dir, int unit, int k, int iv, int coverage, long batch, int maxv_first, int options, agx_hostsim_result *out) {
@@ -390,9 +398,9 @@ int agx_hostsim_run_unit(const char *tmp_dir, int unit, int k, int iv, int cover
             reads_index_close(ri);
         } else load_pairs_from_files(d + "/_reads.fa", d + "/_reads_genome." + u + ".bowtie", batch, (agx_u32)k, P);
         const bool want_graph = (options & AGX_SIM_GRAPH) != 0;
-        SimGraph S; int nbig = 0; SimOptions opt; SimRecords R; SimEdges E;
-        opt.packed = (options & AGX_SIM_PACKED) != 0; opt.records = (options & AGX_SIM_RECORDS) != 0; opt.edges = (options & AGX_SIM_EDGES) != 0;
-        simulate(T, P, (agx_u32)k, iv, coverage, maxv_first > 0 ? (agx_u32)maxv_first : AGX_MAXV_LDS, S, nbig, opt, R, E);
+        SimGraph S; int nbig = 0; SimOptions opt; SimRecords R; SimEdges E; SimFront F;
+        opt.packed = (options & AGX_SIM_PACKED) != 0; opt.records = (options & AGX_SIM_RECORDS) != 0; opt.edges = (options & AGX_SIM_EDGES) != 0; opt.front = (options & AGX_SIM_FRONT) != 0;
+        simulate(T, P, (agx_u32)k, iv, coverage, maxv_first > 0 ? (agx_u32)maxv_first : AGX_MAXV_LDS, S, nbig, opt, R, E, F);
         if (opt.edges) {
             memcpy(out->edge_ctr, E.ctr, sizeof E.ctr);
             auto give = [](const std::vector<agx_u32> &v, agx_u32 words, uint32_t &n, uint32_t *&p) { n = (uint32_t)(v.size() / words); p = (uint32_t *)malloc(4 * (v.size() + 1)); if (!v.empty()) memcpy(p, v.data(), 4 * v.size()); };
@@ -402,6 +410,17 @@ int agx_hostsim_run_unit(const char *tmp_dir, int unit, int k, int iv, int cover
         if (opt.records) {
             out->n_tiles = (uint32_t)R.tile_len.size(); out->tile_len = (uint32_t *)malloc(4 * (R.tile_len.size() + 1)); memcpy(out->tile_len, R.tile_len.data(), 4 * R.tile_len.size());
             out->n_recs = R.recs.size() / AGX_SIM_REC_WORDS; out->recs = (uint32_t *)malloc(4 * (R.recs.size() + 1)); memcpy(out->recs, R.recs.data(), 4 * R.recs.size());
+        }
+        if (opt.front) {
+            static_assert(sizeof(agx_dhit) == 40 && sizeof(agx_lrec) == 32 && sizeof(agx_cmkey) == 8 && sizeof(agx_cmhead) == 16, "include/agx.h describes the front's records as words");
+            auto dup = [](const void *p, size_t bytes) { void *q = malloc(bytes + 1); if (bytes) memcpy(q, p, bytes); return q; };
+            agx_front &W = out->front; const size_t n_pos = T.ref.size();
+            W.n_pos = (uint32_t)n_pos; W.n_hits = (uint32_t)F.dhit.size(); W.n_runs = (uint32_t)P.runs.size(); W.n_cm = (uint32_t)F.cm.size(); W.n_tiles = (uint32_t)(F.tile_off.size() - 1);
+            W.stride = P.stride; W.n_rows = P.stride ? (uint32_t)(F.vcodes.size() / P.stride) : 0u; W.n_entries = (uint32_t)F.lrecs.size();
+            W.ref = (char *)dup(T.ref.data(), n_pos); W.vcodes = (uint8_t *)dup(F.vcodes.data(), (size_t)W.n_rows * P.stride); W.runs = (agx_run *)dup(P.runs.data(), P.runs.size() * sizeof(agx_run));
+            W.cm_start = (uint32_t *)dup(T.cm_start.data(), (n_pos + 1) * 4); W.cm = (uint32_t *)dup(F.cm.data(), F.cm.size() * sizeof(agx_cmkey)); W.cm_head = (uint32_t *)dup(F.cm_head.data(), (n_pos + 1) * sizeof(agx_cmhead));
+            W.dhit = (uint32_t *)dup(F.dhit.data(), F.dhit.size() * sizeof(agx_dhit)); W.tile_off = (uint32_t *)dup(F.tile_off.data(), F.tile_off.size() * 4);
+            W.tile_recs = (uint32_t *)dup(F.lrecs.data(), F.lrecs.size() * sizeof(agx_lrec));
         }
         GraphView G; G.n_pos = (agx_u32)T.ref.size(); G.n_ids = S.n_ids;
         G.meta = S.a_meta.data(); G.str = S.a_str.data(); G.side_xpos = S.side_xpos.data();
@@ -537,6 +556,7 @@ void agx_hostsim_free(agx_hostsim_result *r) {
     free(r->node_start); free(r->node_key); free(r->node_cnt); free(r->node_slen); free(r->edge_start); free(r->edge_dst); free(r->tile_len); free(r->recs);
     free(r->slow); free(r->jsteps); free(r->jins); free(r->ovf);
     agx_walk_graph_free_sim(&r->walk); free(r->segs); free(r->seg_index); free(r->chain_end);
+    {   agx_front &W = r->front; free(W.ref); free(W.vcodes); free(W.runs); free(W.cm_start); free(W.cm); free(W.cm_head); free(W.dhit); free(W.tile_off); free(W.tile_recs); }
     memset(r, 0, sizeof *r);
 }
 

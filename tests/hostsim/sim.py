@@ -12,7 +12,7 @@ SRC = [os.path.join(HERE, "agx_hostsim.cpp"), os.path.join(ROOT, "aligngraph_amd
 DEPS = SRC + [os.path.join(ROOT, "aligngraph_amd", "csrc", h) for h in ("agx_core.h", "agx_host.h", "agx_parse.h")] + [os.path.join(ROOT, "include", "agx.h")]
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-import aligngraph_amd as _agx  # noqa: E402  (the ctypes mirror of agx_walk_graph only: the executor never loads libagx.so)
+import aligngraph_amd as _agx  # noqa: E402  (the ctypes mirrors of agx_walk_graph and agx_front only: the executor never loads libagx.so)
 
 
 def build():
@@ -41,6 +41,7 @@ class _Result(ctypes.Structure):
         ("walk", _agx.WalkGraph),
         ("n_segs", ctypes.c_uint32), ("n_seg0", ctypes.c_uint32), ("n_seg_index", ctypes.c_uint32), ("n_chain_end", ctypes.c_uint32),
         ("segs", ctypes.POINTER(ctypes.c_uint32)), ("seg_index", ctypes.POINTER(ctypes.c_uint32)), ("chain_end", ctypes.POINTER(ctypes.c_uint32)),
+        ("front", _agx.Front),
     ]
 
 
@@ -67,14 +68,16 @@ class SimError(RuntimeError):
         self.msg = msg
 
 
-def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, maxv_first=0, graph=False, packed=False, records=False, edges=False, walk=False):
+def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, maxv_first=0, graph=False, packed=False, records=False, edges=False, walk=False, front=False):
     """One unit through the serial executor.  packed: pass 0 of the node sweep on packed buckets (AGX_NFP words per variant, the device's layout; a list of more
     than 65 535 entries goes to the next pass).  records: also returns "records", the lean record of every tile-list entry in list order as a structured
     numpy array with the fields REC_FIELDS, and "tile_len", each tile's list length.  edges: also returns "edges", the counters EDGE_COUNTERS of the edge
     build's paths, "slow" (the slow positions the device lists, ascending; SLOW_FIELDS), "jsteps" (the steps pass J looks at; JSTEP_FIELDS), "jins" (pass J's
     inserts; JINS_FIELDS) and "ovf" (every overflow append in order; OVF_FIELDS); positions, not node ids.  walk: also returns "walk", the walk graph the executor hands to
     the host walk in the layout of aligngraph_amd.Unit.walk_graph(all_node=True), plus "segs" (SEG_FIELDS), "n_seg0", "seg_index" and "chain_end": what the device's
-    hop search and chain-end marks start from."""
+    hop search and chain-end marks start from.  front: also returns "front", what lies in front of the node sweep in the layout of aligngraph_amd.Unit.front() with the
+    hits in FILE order: ref, vcodes (a row per read slot), runs, cm_start, cm, cm_head, dhit, tile_off and tile_recs (whose `hit` is the file number and `slot` the executor's
+    read slot); the arrays of the device's own order (perm, tile_first, ckey, tile_cnt, long_list) are empty."""
     global _lib
     if _lib is None:
         build()
@@ -82,7 +85,7 @@ def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, max
         _lib.agx_hostsim_run_unit.argtypes = [ctypes.c_char_p] + [ctypes.c_int] * 4 + [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_Result)]
         _lib.agx_hostsim_free.argtypes = [ctypes.POINTER(_Result)]
     r = _Result()
-    options = (1 if graph else 0) | (2 if packed else 0) | (4 if records else 0) | (8 if edges else 0) | (16 if walk else 0)
+    options = (1 if graph else 0) | (2 if packed else 0) | (4 if records else 0) | (8 if edges else 0) | (16 if walk else 0) | (32 if front else 0)
     rc = _lib.agx_hostsim_run_unit(tmp_dir.encode(), unit, k, insert_variation, coverage, batch, maxv_first, options, ctypes.byref(r))
     if rc != 0:
         msg = r.error.decode()
@@ -110,6 +113,8 @@ def run(tmp_dir, unit, k=5, insert_variation=50, coverage=20, batch=1000000, max
         w["seg_index"] = np.ctypeslib.as_array(r.seg_index, shape=(r.n_seg_index,)).copy() if r.n_seg_index else np.zeros(0, "uint32")
         w["chain_end"] = np.ctypeslib.as_array(r.chain_end, shape=(r.n_chain_end,)).copy() if r.n_chain_end else np.zeros(0, "uint32")
         out["walk"] = w
+    if front:
+        out["front"] = _agx.front_arrays(r.front)
     if graph:
         def arr(p, n, dt):
             return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)

@@ -27,6 +27,7 @@ def test_exports_match_header(lib):
 
 def test_struct_sizes_match_c_layout(lib):
     assert ctypes.sizeof(lib.Hit) == 32 and ctypes.sizeof(lib.Run) == 12 and ctypes.sizeof(lib.ContiMer) == 20 and ctypes.sizeof(lib.Params) == 24
+    assert ctypes.sizeof(lib.Front) == 18 * 4 + 14 * 8      # agx_front: eighteen words, then fourteen pointers
 
 
 def test_no_gpu_is_a_loud_error_not_a_fallback(lib):
