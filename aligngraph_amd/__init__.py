@@ -23,7 +23,7 @@ EXPORTS = [
     "agx_unit_finish", "agx_result_free", "agx_unit_stats", "agx_unit_graph", "agx_graph_free", "agx_run_unit",
     "agx_reads_open", "agx_reads_close", "agx_unit_load_files_shared", "agx_run_unit_shared",
     "agx_unit_stage", "agx_unit_release", "agx_pool_trim", "agx_unit_cache_build", "agx_unit_cache_save", "agx_unit_hbm_needed",
-    "agx_unit_trim", "agx_unit_unitigs", "agx_unitigs_free", "agx_unitigs_gfa", "agx_text_free",
+    "agx_unit_trim", "agx_unit_unitigs", "agx_unit_unitigs_region", "agx_unitigs_free", "agx_unitigs_gfa", "agx_text_free",
     "agx_unit_walk_graph", "agx_walk_graph_free", "agx_unit_front", "agx_front_free",
 ]
 
@@ -202,6 +202,7 @@ def lib():
         L.agx_front_free.argtypes = [ctypes.POINTER(Front)]
         L.agx_front_free.restype = None
         L.agx_unit_unitigs.argtypes = [ctypes.c_void_p, ctypes.POINTER(Unitigs)]
+        L.agx_unit_unitigs_region.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(Unitigs)]
         L.agx_unitigs_free.argtypes = [ctypes.POINTER(Unitigs)]
         L.agx_unitigs_free.restype = None
         L.agx_unitigs_gfa.argtypes = [ctypes.POINTER(Unitigs), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
@@ -417,20 +418,33 @@ class Unit:
         finally:
             lib().agx_front_free(ctypes.byref(f))
 
-    def unitigs(self):
+    def _export(self, t, region, min_coverage):
+        """agx_unit_unitigs, or agx_unit_unitigs_region when a window or a threshold is given (region alone: the unit's own coverage; min_coverage alone: every position)."""
+        if region is None and min_coverage is None:
+            self._check(lib().agx_unit_unitigs(self._h, ctypes.byref(t)))
+            return
+        lo, hi = region if region is not None else (0, self.stats()["n_pos"])
+        cov = self.params.coverage if min_coverage is None else min_coverage
+        for v in (lo, hi, cov):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise AgxError(AGX_E_ARG, "unitigs: region bounds and min_coverage are unsigned 32-bit numbers")
+        self._check(lib().agx_unit_unitigs_region(self._h, int(lo), int(hi), int(cov), ctypes.byref(t)))
+
+    def unitigs(self, region=None, min_coverage=None):
         """The unit's pruned graph compacted into unitigs on the device (agx_unit_unitigs; needs keep_counts): numpy arrays per segment and link, the
-        bases as bytes."""
+        bases as bytes.  region=(lo, hi) and / or min_coverage: the sub-graph of positions [lo, hi) whose nodes are alive at that coverage
+        (agx_unit_unitigs_region), at a cost that follows the window."""
         t = Unitigs()
-        self._check(lib().agx_unit_unitigs(self._h, ctypes.byref(t)))
+        self._export(t, region, min_coverage)
         try:
             return _unitigs_arrays(t)
         finally:
             lib().agx_unitigs_free(ctypes.byref(t))
 
-    def gfa(self, unit=0):
-        """GFA 1.0 S and L lines of the unit's unitigs, segments named u<unit>_<pos>_<var> (no header line)."""
+    def gfa(self, unit=0, region=None, min_coverage=None):
+        """GFA 1.0 S and L lines of the unit's unitigs, segments named u<unit>_<pos>_<var> (no header line); region and min_coverage as in unitigs()."""
         t = Unitigs()
-        self._check(lib().agx_unit_unitigs(self._h, ctypes.byref(t)))
+        self._export(t, region, min_coverage)
         try:
             return _gfa_text(t, unit)
         finally:

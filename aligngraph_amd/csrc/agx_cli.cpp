@@ -42,6 +42,9 @@ struct Options {
     string read1, read2, contig, genome, ext, rmn, graph;
     int tagRead1 = 0, tagRead2 = 0, tagContig = 0, tagGenome = 0, tagExt = 0, tagRmn = 0, tagK = 0, tagLow = 0, tagHigh = 0, tagIV = 0, tagCov = 0, tagPart = 0;
     int tagGraph = 0;                   // --graphOut: each unit's pruned graph as GFA (not an option of the reference; its usage text stays as it is)
+    // --graphRegion <unit>:<lo>-<hi>, --graphMinCoverage <n> (only with --graphOut): the GFA lines of one unit's positions [lo, hi) and / or with "alive" decided by n
+    // instead of --coverage (agx_unit_unitigs_region)
+    int tagRegion = 0, tagGraphCov = 0, regionUnit = 0, graphCov = 0; uint32_t regionLo = 0, regionHi = 0;
     int fastMap = 0, ratioCheck = 0, uniqueExtension = 0, iterativeMap = 0, misassemblyRemoval = 0, resume = 0;
     int k = 5, distanceLow = 0, distanceHigh = 99999, coverage = 20, insertVariation = 50, part = 1;      // defaults of AG:4701
 };
@@ -97,6 +100,20 @@ void parse_params(const string &file, Options &o) {
     auto infile = [&](int &i, int &tag, string &dst) { dst = value(i, tag); if (!can_read(dst)) { cout << "CANNOT OPEN FILE!" << endl; die_usage(); } };
     auto outfile = [&](int &i, int &tag, string &dst) { dst = value(i, tag); std::ofstream f(dst.c_str()); if (!f.is_open()) { cout << "CANNOT OPEN FILE!" << endl; die_usage(); } };
     auto flag = [&](int &tag) { if (tag == 1) die_usage(); tag = 1; };
+    auto region = [&](int &i) {      // <unit>:<lo>-<hi>, three decimal numbers that round-trip, lo <= hi
+        const string v = value(i, o.tagRegion);
+        const size_t colon = v.find(':'), dash = v.find('-', colon == string::npos ? 0 : colon);
+        if (colon == string::npos || dash == string::npos) die_usage();
+        const string part[3] = {v.substr(0, colon), v.substr(colon + 1, dash - colon - 1), v.substr(dash + 1)};
+        long long n[3];
+        for (int j = 0; j < 3; j++) {
+            if (part[j].empty() || part[j].size() > 10 || part[j].find_first_not_of("0123456789") != string::npos) die_usage();
+            n[j] = atoll(part[j].c_str());
+            if (itoa(n[j]) != part[j] || n[j] > (j == 0 ? 0x7FFFFFFFll : 0xFFFFFFFFll)) die_usage();
+        }
+        if (n[1] > n[2]) die_usage();
+        o.regionUnit = (int)n[0]; o.regionLo = (uint32_t)n[1]; o.regionHi = (uint32_t)n[2];
+    };
     for (int i = 0; i < count; i++) {
         const string &b = t[i];
         if (b == "--read1") infile(i, o.tagRead1, o.read1);
@@ -108,6 +125,8 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--extendedContig") outfile(i, o.tagExt, o.ext);          // opening truncates the file right away, like ofstream::open (AG:4477)
         else if (b == "--remainingContig") outfile(i, o.tagRmn, o.rmn);
         else if (b == "--graphOut") outfile(i, o.tagGraph, o.graph);
+        else if (b == "--graphRegion") region(i);
+        else if (b == "--graphMinCoverage") { integer(i, o.tagGraphCov, o.graphCov); if (o.graphCov < 0) die_usage(); }
         else if (b == "--kMer") integer(i, o.tagK, o.k);
         else if (b == "--insertVariation") integer(i, o.tagIV, o.insertVariation);
         else if (b == "--coverage") integer(i, o.tagCov, o.coverage);
@@ -120,6 +139,15 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--resume") { if (o.resume == 1 || count != 1) die_usage(); o.resume = 1; }
         else die_usage();
     }
+    if ((o.tagRegion || o.tagGraphCov) && !o.tagGraph) die_usage();
+}
+
+// tmp/_graph.<u>.gfa, with the region and the threshold in the name when they are given: a --resume run merges only lines that were made under its own settings
+string graph_part_path(const Options &o, int u) {
+    string s = "tmp/_graph." + itoa(u);
+    if (o.tagRegion) s += "." + itoa(o.regionLo) + "-" + itoa(o.regionHi);
+    if (o.tagGraphCov) s += ".c" + itoa(o.graphCov);
+    return s + ".gfa";
 }
 
 // A text file mapped read-only and read the way the reference's `getline` loops read theirs: lines without their '\n'; past the last byte a
@@ -1151,13 +1179,18 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                 if (rc == AGX_OK) { std::unique_lock<std::mutex> g(mem_mu); waiting[d]++; mem_cv.wait(g, [&] { return used[d] == 0.0 || used[d] + est <= budget[d]; }); waiting[d]--; used[d] += est; admitted = true; }
                 if (rc == AGX_OK) rc = agx_unit_upload(un);
                 if (rc == AGX_OK) rc = agx_unit_build(un);
-                if (rc == AGX_OK && o.tagGraph) {      // --graphOut: the unit's GFA lines, exported before the download (one-shot units) into tmp/_graph.<u>.gfa
+                if (rc == AGX_OK && o.tagGraph && (!o.tagRegion || u == o.regionUnit)) {      // --graphOut: the unit's GFA lines, exported before the download (one-shot units) into tmp/_graph.<u>.gfa
                     agx_unitigs ut; char *text = nullptr; size_t len = 0;
-                    rc = agx_unit_unitigs(un, &ut);
+                    if (!o.tagRegion && !o.tagGraphCov) rc = agx_unit_unitigs(un, &ut);
+                    else {      // --graphRegion / --graphMinCoverage: the window (all positions without a region) at the threshold (--coverage without one)
+                        agx_stats st; memset(&st, 0, sizeof st); memset(&ut, 0, sizeof ut);
+                        rc = agx_unit_stats(un, &st);
+                        if (rc == AGX_OK) rc = agx_unit_unitigs_region(un, o.tagRegion ? o.regionLo : 0u, o.tagRegion ? o.regionHi : (uint32_t)st.n_pos, (uint32_t)(o.tagGraphCov ? o.graphCov : o.coverage), &ut);
+                    }
                     if (rc == AGX_OK) { rc = agx_unitigs_gfa(&ut, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "GFA FORMATTING FAILED"); }
                     agx_unitigs_free(&ut);
                     if (rc == AGX_OK) {
-                        const string path = "tmp/_graph." + itoa(u) + ".gfa";
+                        const string path = graph_part_path(o, u);
                         FILE *f = fopen(path.c_str(), "wb"); bool ok = f != nullptr;
                         if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
                         if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
@@ -1233,6 +1266,7 @@ int main(int argc, char **argv) {
         formalize_reads(o.read1, o.read2); stage("formalize reads");
         formalize_contigs(o.contig, contigIds); stage("formalize contigs");
         units = formalize_genome(o.genome, o.part, genomeIds); stage("formalize genome");
+        if (o.tagRegion && o.regionUnit >= units) die("NO SUCH UNIT FOR --graphRegion!");
         startAlign = time(NULL);
         align_everything(o, units); stage("aligners + distribute + caches");
         endAlign = time(NULL);
@@ -1249,6 +1283,7 @@ int main(int argc, char **argv) {
         wcp.open("tmp/_checkpoint.txt", std::ios::app);
         formalize_contigs(o.contig, contigIds);
         units = formalize_genome(o.genome, o.part, genomeIds);
+        if (o.tagRegion && o.regionUnit >= units) die("NO SUCH UNIT FOR --graphRegion!");
         startAlign = endAlign = time(NULL);
     }
     if (o.ratioCheck == 1) check_ratio(units);
@@ -1259,7 +1294,8 @@ int main(int argc, char **argv) {
         FILE *g = fopen(o.graph.c_str(), "wb");
         bool ok = g != nullptr && fputs("H\tVN:Z:1.0\n", g) >= 0;
         for (int u = 0; ok && u < units; u++) {
-            FILE *f = fopen(("tmp/_graph." + itoa(u) + ".gfa").c_str(), "rb");
+            if (o.tagRegion && u != o.regionUnit) continue;      // (with a region only the named unit has lines)
+            FILE *f = fopen(graph_part_path(o, u).c_str(), "rb");
             if (!f) { ok = false; break; }
             char buf[1 << 16]; size_t n;
             while (ok && (n = fread(buf, 1, sizeof buf, f)) > 0) ok = fwrite(buf, 1, n, g) == n;

@@ -986,6 +986,37 @@ size_t unitig_layout(size_t cap, size_t n_pos, size_t n_ovf, char *base, agx_uni
     return at + 256;
 }
 
+// The scratch of a region export (agx_unit_unitigs_region) carved from the front of the same buffer: `kept` nodes of `n_win` positions.  What must be in place before the
+// kept count is known (the words, the reverse map, the window's counts, the scans' block sums) comes first, at offsets that do not depend on it; the rest is per kept node.
+// 22 words per kept node and one per slot (the reverse map, which is written at the window's slots only) where unitig_layout takes 24 per slot, so from a few hundred
+// slots on it fits the whole export's buffer.  Below that its few more 256-byte-aligned pieces can make it some hundred bytes larger: agx_unit_unitigs_region takes the
+// larger of the two sizes, which then comes out of the regrowth room of the unit's own block (regrow_slack: 6.4 MB at least), never from the device.  Phase 3 reuses what phases 1-2 are done with: the links lie over outs | oout | p_len | p_next, the bases over succ, the scans of segment lengths and
+// link counts and the link cursors over the pointer jumping's arrays.
+size_t unitig_region_layout(size_t cap, size_t n_win, size_t kept, size_t n_ovf, char *base, agx_unitig_region_args *A, agx_u32 **words) {
+    size_t at = 0;
+    auto take = [&](auto *&p, size_t n) { at = (at + 255) & ~(size_t)255; p = base ? (std::remove_reference_t<decltype(*p)> *)(base + at) : nullptr; at += (n ? n : 1) * sizeof(*p); };
+    agx_unitig_region_args T{}; agx_unitig_region_args &R = A ? *A : T; agx_unitig_args &X = R.U; agx_u32 *w = nullptr, *L = nullptr;
+    size_t hash_n = 64; while (hash_n < 2 * n_ovf) hash_n *= 2;
+    const size_t ngrp = (kept + 63) / 64, nmax = std::max(n_win, cap) + 1;
+    take(w, 8); take(R.rmap, cap); take(R.cntw, n_win + 1); take(R.offw, n_win + 1);
+    take(X.scan_tmp, 2 * ((nmax + 4095) / 4096 + 1) + 2 * ((nmax + 4096ull * 4096 - 1) / (4096ull * 4096) + 1) + 8);
+    take(X.ovf_hash, hash_n); take(X.ovf_first, n_ovf);
+    take(R.l_slot, kept); take(X.pos_of, kept); take(L, 4 * kept + n_ovf);
+    take(X.indeg, kept); take(X.succ, kept); take(X.osucc, kept); take(X.nxt, kept); take(X.haspred, kept);
+    take(X.wcnt, ngrp + 1); take(X.woff, ngrp + 1); take(X.hcnt, ngrp + 1); take(X.hoff, ngrp + 1);
+    for (int i = 0; i < 2; i++) { take(X.anc[i], kept + 1); take(X.off[i], kept + 1); }
+    take(X.p_seg, kept);
+    take(X.s_len, kept + 1); take(X.s_links, kept + 1); take(X.s_hpos, kept); take(X.s_hvar, kept); take(X.s_last, kept); take(X.s_cov, kept);
+    if (base) {
+        X.outs = L; X.oout = L + kept; X.p_len = L + 2 * kept; X.p_next = L + 3 * kept;
+        X.l_to = L; X.link_cap = (agx_u32)std::min<size_t>(4 * kept + n_ovf, 0xFFFFFFFFull); X.seq = (char *)X.succ; X.seq_cap = (agx_u32)std::min<size_t>(4 * kept, 0xFFFFFFFFull);
+        X.s_off = X.anc[0]; X.l_off = X.off[0]; X.l_cur = X.anc[1];
+        X.hash_mask = (agx_u32)(hash_n - 1);
+        if (words) *words = w;
+    }
+    return at + 256;
+}
+
 // Capacities of a unit's first build and the HBM they add up to (what do_upload reserves as one block; AlignGraph_amd admits a unit to a device by it:
 // agx_unit_hbm_needed).  From the staged counts: positions, hits, runs, conti-mers, read rows.
 struct Plan { agx_u32 pool_cap, list_cap, ovf_cap, sp_cap; size_t exact, total; };      // exact: what the five groups take; total: with the room to regrow in and the export's scratch
@@ -2086,6 +2117,101 @@ int agx_unit_unitigs(agx_unit *u, agx_unitigs *t) {
         t->seq[nb] = 0;
         const agx_u32 *so = (const agx_u32 *)(pin.p + o_so), *lo = (const agx_u32 *)(pin.p + o_lo);
         for (size_t g = 0; g <= ns; g++) t->seq_off[g] = so[g];      // (a unit's nodes are counted in 32 bits, so are its bases)
+        for (size_t g = 0; g < ns; g++) {
+            if (lo[g] > lo[g + 1] || lo[g + 1] > nl) throw Error{E_DEVICE, "unitigs: link offsets out of range"};
+            for (agx_u32 i = lo[g]; i < lo[g + 1]; i++) t->link_from[i] = (uint32_t)g;
+        }
+    });
+    if (rc != AGX_OK) agx_unitigs_free(t);
+    return rc;
+}
+
+// Region export (DESIGN.md §11 "A region at a chosen coverage"): the unitigs of the sub-graph of positions [pos_lo, pos_hi) whose nodes are alive at min_coverage.  The same
+// scratch buffer, a stream of its own; no launch and no memset below is sized by the unit's positions or node slots, only by the window's positions, its kept nodes and the
+// overflow list (which has no position index).  Four host round trips: the kept nodes, the piece and head counts, the totals, the download.  agx_unit_unitigs above does not
+// come through here: its code path and its timings are what this one is compared with.
+int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t) {
+    if (!u || !t) return AGX_E_ARG;
+    memset(t, 0, sizeof *t);
+    const int rc = guarded(u, [&] {
+        if (!(u->prm.flags & AGX_FLAG_KEEP_COUNTS)) throw Error{E_ARG, "unitigs: the unit was created without AGX_FLAG_KEEP_COUNTS (the segments' coverage needs the counts)"};
+        if (!u->built || u->trimmed) throw Error{E_ARG, "unitigs: the unit is not built (call agx_unit_build; not after agx_unit_trim or agx_unit_release)"};
+        if ((u->prm.flags & AGX_FLAG_ONE_SHOT) && (u->consumed || u->downloaded)) throw Error{E_ARG, "unitigs: a one-shot unit exports before its download or finish"};
+        const agx_u32 n_pos = (agx_u32)u->V.n_pos, cap = u->pool_cap, n_ovf = std::min(u->n_ovf, u->ovf_cap);
+        if (pos_lo > pos_hi || pos_hi > n_pos)
+            throw Error{E_ARG, "unitigs: region [" + std::to_string(pos_lo) + ", " + std::to_string(pos_hi) + ") is not within the unit's positions [0, " + std::to_string(n_pos) + ")"};
+        HIP_OK(hipSetDevice(u->prm.device));
+        HIP_OK(wait_event(u->ev_built));
+        const agx_u32 n_win = pos_hi - pos_lo;
+        if (!n_win || !cap || !u->n_nodes) return;
+        const size_t whole = unitig_layout(cap, n_pos, n_ovf, nullptr, nullptr, nullptr);
+        u->d_ut.alloc(u->arena, std::max(whole, unitig_region_layout(cap, n_win, std::min<size_t>(u->n_nodes, cap), n_ovf, nullptr, nullptr, nullptr)));      // (the buffer of the whole export: the room the upload reserved; a tiny unit: unitig_region_layout)
+        u->stats.device_bytes = u->arena.capacity();
+        struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
+        HIP_OK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+        auto fill = [&](void *p, int v, size_t b) { HIP_OK(hipMemsetAsync(p, v, b ? b : 1, st.s)); };
+        agx_unitig_region_args R{}; agx_u32 *words = nullptr;
+        auto bind = [&](agx_u32 kept) {
+            R = agx_unitig_region_args{};
+            unitig_region_layout(cap, n_win, kept, n_ovf, u->d_ut.p, &R, &words);
+            agx_unitig_args &A = R.U;
+            A.node_start = u->d_node_start.p; A.n_base = u->d_base.p; A.n_next = u->d_next.p; A.n_counts = u->d_counts.p; A.ref = u->d_ref.p; A.ovf = u->d_ovf.p; A.n_ovf = n_ovf;
+            A.pool_cap = kept; A.piece_cap = kept; A.n_pos = (kept + 63u) / 64u; A.err = words;
+            R.nk_cid = u->d_cid.p; R.node_cnt = u->d_node_cnt.p; R.pos_lo = pos_lo; R.n_win = n_win; R.min_cov = min_coverage; R.pool_cap = cap;
+        };
+        bind(0);
+        fill(words, 0, 32);
+        agx_launch_unitig_region_count(&R, st.s);
+        agx_u32 h[4] = {0, 0, 0, 0};
+        HIP_OK(hipMemcpyAsync(h, words, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipMemcpyAsync(h + 1, R.offw + n_win, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
+        if (h[0]) throw Error{E_DEVICE, "unitigs: the node table is inconsistent (error word " + std::to_string(h[0]) + ")"};
+        const agx_u32 kept = h[1];
+        if (kept > u->n_nodes || kept > cap) throw Error{E_DEVICE, "unitigs: more nodes in the region than in the unit"};
+        if (!kept) return;
+        bind(kept);
+        agx_unitig_args &A = R.U;
+        const size_t ngrp = A.n_pos;
+        if (n_ovf) fill(A.ovf_hash, 0xFF, ((size_t)A.hash_mask + 1) * 8);
+        fill(A.wcnt, 0, (ngrp + 1) * 4); fill(A.hcnt, 0, (ngrp + 1) * 4);
+        agx_launch_unitig_region_phase1(&R, st.s);
+        HIP_OK(hipMemcpyAsync(h, words, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipMemcpyAsync(h + 1, A.woff + ngrp, 4, hipMemcpyDeviceToHost, st.s));
+        HIP_OK(hipMemcpyAsync(h + 2, A.hoff + ngrp, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
+        if (h[0] & 1u) throw Error{E_DEVICE, "unitigs: an edge of the node table does not lead to a later position (the graph is not a DAG)"};
+        if (h[0]) throw Error{E_DEVICE, "unitigs: the node table is inconsistent (error word " + std::to_string(h[0]) + ")"};
+        const agx_u32 np = h[1];
+        if (!np || np > kept || h[2] > np) throw Error{E_DEVICE, "unitigs: piece and head counts out of range"};
+        A.piece_cap = np;
+        agx_u32 rounds = 1; while (rounds < 32 && (1ull << (rounds - 1)) < np) rounds++;      // ceil(log2 np) + 1
+        fill(A.p_seg, 0xFF, (size_t)np * 4); fill(A.s_len, 0, ((size_t)np + 1) * 4); fill(A.s_links, 0, ((size_t)np + 1) * 4); fill(A.s_cov, 0, (size_t)np * 8);
+        agx_launch_unitig_region_phase2(&R, rounds, st.s);
+        fill(A.l_cur, 0, ((size_t)np + 1) * 4);          // (over the pointer jumping's second ancestor array: behind the rank kernel)
+        agx_launch_unitig_totals(&A, words + 4, st.s);
+        HIP_OK(hipMemcpyAsync(h, words + 4, 16, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
+        if (h[3]) throw Error{E_DEVICE, "unitigs: the unitig ranks are inconsistent (error word " + std::to_string(h[3]) + ")"};
+        const agx_u32 ns = h[0], nb = h[1], nl = h[2];
+        if (ns > np || nb > kept || nb > A.seq_cap || nl > A.link_cap) throw Error{E_DEVICE, "unitigs: segment totals out of range"};
+        A.seq_cap = nb; A.link_cap = nl;
+        agx_launch_unitig_region_phase3(&R, st.s);
+        // the download and the caller's table: a copy of agx_unit_unitigs' last part, kept apart only because that function's code path is the baseline this one is measured
+        // against — the two must change together (a helper shared by both is the next step once that constraint goes)
+        const size_t o_hp = 0, o_hv = o_hp + 4 * (size_t)ns, o_ln = o_hv + 4 * (size_t)ns, o_lp = o_ln + 4 * (size_t)ns, o_cov = (o_lp + 4 * (size_t)ns + 7) & ~(size_t)7,
+                     o_so = o_cov + 8 * (size_t)ns, o_lo = o_so + 4 * ((size_t)ns + 1), o_lt = o_lo + 4 * ((size_t)ns + 1), o_seq = o_lt + 4 * (size_t)nl, o_end = o_seq + nb;
+        PBuf<char> pin; pin.alloc(o_end + 8);
+        auto down = [&](size_t o, const void *src, size_t b) { if (b) HIP_OK(hipMemcpyAsync(pin.p + o, src, b, hipMemcpyDeviceToHost, st.s)); };
+        down(o_hp, A.s_hpos, 4 * (size_t)ns); down(o_hv, A.s_hvar, 4 * (size_t)ns); down(o_ln, A.s_len, 4 * (size_t)ns); down(o_lp, A.s_last, 4 * (size_t)ns);
+        down(o_cov, A.s_cov, 8 * (size_t)ns); down(o_so, A.s_off, 4 * ((size_t)ns + 1)); down(o_lo, A.l_off, 4 * ((size_t)ns + 1)); down(o_lt, A.l_to, 4 * (size_t)nl); down(o_seq, A.seq, nb);
+        HIP_OK(hipMemcpyAsync(h, words, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
+        if (h[0]) throw Error{E_DEVICE, "unitigs: the segments are inconsistent (error word " + std::to_string(h[0]) + ")"};
+        t->n_segs = ns; t->n_links = nl; t->n_bases = nb;
+        t->head_pos = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->head_var = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->n_nodes = (uint32_t *)malloc(4 * ((size_t)ns + 1));
+        t->last_pos = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->coverage = (uint64_t *)malloc(8 * ((size_t)ns + 1)); t->seq_off = (uint64_t *)malloc(8 * ((size_t)ns + 1));
+        t->seq = (char *)malloc((size_t)nb + 1); t->link_from = (uint32_t *)malloc(4 * ((size_t)nl + 1)); t->link_to = (uint32_t *)malloc(4 * ((size_t)nl + 1));
+        if (!t->head_pos || !t->head_var || !t->n_nodes || !t->last_pos || !t->coverage || !t->seq_off || !t->seq || !t->link_from || !t->link_to) throw Error{E_ARG, "out of host memory"};
+        memcpy(t->head_pos, pin.p + o_hp, 4 * (size_t)ns); memcpy(t->head_var, pin.p + o_hv, 4 * (size_t)ns); memcpy(t->n_nodes, pin.p + o_ln, 4 * (size_t)ns);
+        memcpy(t->last_pos, pin.p + o_lp, 4 * (size_t)ns); memcpy(t->coverage, pin.p + o_cov, 8 * (size_t)ns); memcpy(t->link_to, pin.p + o_lt, 4 * (size_t)nl); memcpy(t->seq, pin.p + o_seq, nb);
+        t->seq[nb] = 0;
+        const agx_u32 *so = (const agx_u32 *)(pin.p + o_so), *lo = (const agx_u32 *)(pin.p + o_lo);
+        for (size_t g = 0; g <= ns; g++) t->seq_off[g] = so[g];
         for (size_t g = 0; g < ns; g++) {
             if (lo[g] > lo[g + 1] || lo[g + 1] > nl) throw Error{E_DEVICE, "unitigs: link offsets out of range"};
             for (agx_u32 i = lo[g]; i < lo[g + 1]; i++) t->link_from[i] = (uint32_t)g;

@@ -78,6 +78,19 @@ struct agx_unitig_args {
     agx_u32 *scan_tmp;                                 // the multi-launch scans' block sums (the export's scans run one after another on its stream)
 };
 
+// Region export (agx_unit_unitigs_region): the same definition on the nodes of positions [pos_lo, pos_lo + n_win) that are alive at the CALLER's coverage.  Those nodes get
+// dense LOCAL ids in (position, variant) order and every later phase runs over local ids, so nothing here is sized by the unit but the reverse map, which is only ever
+// touched at the window's slots.  U is the local view: U.pool_cap = kept nodes, U.n_pos = 64-id groups (hcnt / hoff are per group), U.pos_of[id] = the node's position, the
+// other per-slot arrays of U are per local id and hold local ids; U.node_start, n_base, n_next, n_counts, ref and ovf are the unit's own (U.n_flags is not read: alive is
+// nk_cid and the count against min_cov, never AGX_NF_DEAD).  The piece, totals and link-sort kernels of the whole export run on U unchanged.
+struct agx_unitig_region_args {
+    agx_unitig_args U;
+    const agx_u32 *nk_cid; const agx_u16 *node_cnt; agx_u32 pos_lo, n_win, min_cov, pool_cap;      // pool_cap: the unit's node slots (bounds what the table names)
+    agx_u32 *cntw, *offw;           // [n_win + 1] kept nodes per position, exclusive scan (offw[n_win] = kept nodes)
+    agx_u32 *l_slot;                // [kept] slot of every local id
+    agx_u32 *rmap;                  // [pool_cap] slot -> local id.  Never cleared: slot s is in the export iff rmap[s] < kept and l_slot[rmap[s]] == s, whatever an earlier export left here
+};
+
 #define AGX_SLOW_WAVES 8192u    // wavefronts of the per-hit edge pass if the occupancy query fails (normally: as many as are resident at once)
 
 extern "C" {
@@ -136,5 +149,11 @@ void agx_launch_unitig_phase1(const agx_unitig_args *, hipStream_t);
 void agx_launch_unitig_phase2(const agx_unitig_args *, agx_u32 rounds, hipStream_t);
 void agx_launch_unitig_phase3(const agx_unitig_args *, hipStream_t);      // bases and links, once the scans are in (the host sized seq / links from them)
 void agx_launch_unitig_totals(const agx_unitig_args *, agx_u32 *tot, hipStream_t);      // tot[0..3] = segments, bases, links, error word
+// region export: count (kept nodes per position of the window and their scan; the host reads the total), phase 1 (local ids, degrees, internal edges, pieces, heads per
+// 64-id group; the host reads the piece count), phase 2 and 3 as above; agx_launch_unitig_totals takes &R->U
+void agx_launch_unitig_region_count(const agx_unitig_region_args *, hipStream_t);
+void agx_launch_unitig_region_phase1(const agx_unitig_region_args *, hipStream_t);
+void agx_launch_unitig_region_phase2(const agx_unitig_region_args *, agx_u32 rounds, hipStream_t);
+void agx_launch_unitig_region_phase3(const agx_unitig_region_args *, hipStream_t);
 void agx_launch_node_sweep_huge(const agx_node_kargs *, hipStream_t);
 }

@@ -12,6 +12,9 @@
 // by a scan over positions; segment lengths and link counts scanned for the offsets; then every node writes its base and every tail its links.
 // Every loop is bounded by a count the kernel read, and every store is checked against the capacity of what it writes.  The scans are the multi-launch
 // form (agx_launch_exclusive_scan): nothing here spins, whatever builds run beside an export on the same device.
+//
+// The region export (agx_unit_unitigs_region; the agx_k_utr_* kernels in the second half of the file) applies the same definition to the nodes of a window of positions
+// that are alive at a coverage of the caller's choice, over dense local ids instead of slots: none of its grids is sized by the unit.
 #include <hip/hip_runtime.h>
 #include "agx_kargs.h"
 
@@ -257,9 +260,245 @@ __global__ void __launch_bounds__(256) agx_k_ut_links_sort(agx_unitig_args A) {
     }
 }
 
+// ---- region export (agx_unit_unitigs_region, agx_kargs.h: agx_unitig_region_args) -------------------------------------------------------------------------
+// The same graph definition on a sub-graph: the nodes of the window's positions that are alive at the caller's coverage, and the edges between two of them.  No grid below
+// is sized by the unit: one thread per position of the window (count, compact), per kept node (everything else) or per overflow entry (the list has no position index).
+// Kept nodes are numbered densely in (position, variant) order, so a wavefront takes 64 consecutive local ids, "the internal edge goes to the next id" is the common case
+// as it is for slots in the whole export, and heads are numbered by a scan over the 64-id groups.  R.U is the local view the piece kernels above run on unchanged.
+
+__device__ __forceinline__ bool utr_kept(const agx_unitig_region_args &R, agx_u32 slot) {      // AG:1904-1918 with the caller's threshold
+    return R.nk_cid[slot] != AGX_NONE || (long long)R.U.n_counts[(size_t)slot * 6] >= (long long)R.min_cov;
+}
+// local id of a slot (< R.pool_cap), NONE if the slot is not in the export.  rmap holds whatever the last export of any kind left in it: an entry counts only if the
+// local id it names points back at the slot
+__device__ __forceinline__ agx_u32 utr_local(const agx_unitig_region_args &R, agx_u32 slot) {
+    const agx_u32 r = R.rmap[slot];
+    return r < R.U.pool_cap && R.l_slot[r] == slot ? r : AGX_NONE;
+}
+
+__global__ void __launch_bounds__(256) agx_k_utr_count(agx_unitig_region_args R) {
+    const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i > R.n_win) return;
+    agx_u32 c = 0;
+    if (i < R.n_win) {
+        const agx_u32 X = R.pos_lo + i, s = R.U.node_start[X], n = R.node_cnt[X];
+        for (agx_u32 v = 0; v < n; v++) {
+            if (s + v >= R.pool_cap) { atomicOr(R.U.err, 2u); break; }
+            c += utr_kept(R, s + v) ? 1u : 0u;
+        }
+    }
+    R.cntw[i] = c;                  // (entry n_win: the scan's closing zero)
+}
+// local ids: slot and position of each, the reverse map at its slot, and the zeros the degree kernels add to
+__global__ void __launch_bounds__(256) agx_k_utr_compact(agx_unitig_region_args R) {
+    const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= R.n_win) return;
+    const agx_u32 X = R.pos_lo + i, s = R.U.node_start[X], n = R.node_cnt[X];
+    agx_u32 id = R.offw[i];
+    for (agx_u32 v = 0; v < n && s + v < R.pool_cap; v++) {
+        if (!utr_kept(R, s + v)) continue;
+        if (id >= R.U.pool_cap) { atomicOr(R.U.err, 4u); return; }
+        R.l_slot[id] = s + v; R.U.pos_of[id] = X; R.rmap[s + v] = id;
+        R.U.indeg[id] = 0; R.U.oout[id] = 0; R.U.haspred[id] = 0;
+        id++;
+    }
+}
+__global__ void __launch_bounds__(256) agx_k_utr_degrees(agx_unitig_region_args R) {
+    const agx_u32 id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= R.U.pool_cap) return;
+    const agx_u32 u = R.l_slot[id], X = R.U.pos_of[id];
+    agx_u32 cnt = 0, last = AGX_NONE;
+    if (u < R.pool_cap) {
+        const uint4 nx = *reinterpret_cast<const uint4 *>(R.U.n_next + (size_t)u * AGX_MAXE);
+        const agx_u32 t[AGX_MAXE] = {nx.x, nx.y, nx.z, nx.w};
+        for (agx_u32 e = 0; e < AGX_MAXE; e++) {
+            if (t[e] == AGX_NONE) continue;
+            if (t[e] >= R.pool_cap) { atomicOr(R.U.err, 2u); continue; }
+            const agx_u32 lt = utr_local(R, t[e]);
+            if (lt == AGX_NONE) continue;                                    // pruned at this threshold, or across the window's border
+            if (R.U.pos_of[lt] <= X) { atomicOr(R.U.err, 1u); continue; }
+            cnt++; last = lt;
+            atomicAdd(R.U.indeg + lt, 1u);
+        }
+    } else atomicOr(R.U.err, 2u);
+    R.U.outs[id] = cnt; R.U.succ[id] = last;
+}
+__global__ void __launch_bounds__(256) agx_k_utr_ovf(agx_unitig_region_args R) {
+    const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= R.U.n_ovf) return;
+    R.U.ovf_first[i] = 0;
+    const agx_u32 s = R.U.ovf[i].src, d = R.U.ovf[i].dst;
+    if (s == AGX_NONE || d == AGX_NONE) return;
+    if (s >= R.pool_cap || d >= R.pool_cap) { atomicOr(R.U.err, 2u); return; }
+    const agx_u32 ls = utr_local(R, s), ld = utr_local(R, d);
+    if (ls == AGX_NONE || ld == AGX_NONE) return;
+    if (R.U.pos_of[ld] <= R.U.pos_of[ls]) { atomicOr(R.U.err, 1u); return; }
+    const unsigned long long key = ((unsigned long long)ls << 32) | ld;
+    agx_u32 h = (agx_u32)((key * 0x9E3779B97F4A7C15ull) >> 32) & R.U.hash_mask;
+    for (agx_u32 probe = 0; probe <= R.U.hash_mask; probe++) {          // (the set holds twice the list: a free cell is always found)
+        const unsigned long long old = atomicCAS(R.U.ovf_hash + h, ~0ull, key);
+        if (old == key) return;
+        if (old == ~0ull) {
+            R.U.ovf_first[i] = 1;
+            atomicAdd(R.U.indeg + ld, 1u); atomicAdd(R.U.oout + ls, 1u); R.U.osucc[ls] = ld;
+            return;
+        }
+        h = (h + 1u) & R.U.hash_mask;
+    }
+}
+__global__ void __launch_bounds__(256) agx_k_utr_internal(agx_unitig_region_args R) {
+    const agx_u32 id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= R.U.pool_cap) return;
+    const agx_u32 a = R.U.outs[id], b = R.U.oout[id], d = a + b;
+    const agx_u32 t = d != 1u ? AGX_NONE : a == 1u ? R.U.succ[id] : R.U.osucc[id];
+    agx_u32 nx = AGX_NONE;
+    if (t != AGX_NONE && t < R.U.pool_cap && R.U.indeg[t] == 1u) { nx = t; R.U.haspred[t] = 1; }
+    R.U.outs[id] = d; R.U.nxt[id] = nx; R.U.succ[id] = AGX_NONE;
+}
+
+// 64 consecutive local ids (all of them nodes of the export, up to the last group's tail)
+__device__ __forceinline__ ut_window utr_window_of(const agx_unitig_args &A) {
+    ut_window w;
+    w.u = blockIdx.x * 256u + threadIdx.x; w.lane = threadIdx.x & 63u;
+    w.valid = w.u < A.pool_cap;
+    w.nx = w.valid ? A.nxt[w.u] : AGX_NONE;
+    w.link = w.valid && w.lane < 63u && w.nx == w.u + 1u;
+    w.lm = __ballot(w.link);
+    const bool prev = w.lane > 0 && ((w.lm >> (w.lane - 1u)) & 1ull);
+    w.sm = __ballot(w.valid && !prev);
+    return w;
+}
+// pieces and heads per group (a head starts a piece: a lane behind a link has an internal predecessor)
+__global__ void __launch_bounds__(256) agx_k_utr_group_count(agx_unitig_region_args R) {
+    const ut_window w = utr_window_of(R.U);
+    const unsigned long long hm = __ballot(w.valid && !R.U.haspred[w.valid ? w.u : 0u]);
+    if (w.lane == 0 && w.valid) { R.U.wcnt[w.u / 64u] = (agx_u32)__popcll(w.sm); R.U.hcnt[w.u / 64u] = (agx_u32)__popcll(hm); }
+}
+__global__ void __launch_bounds__(256) agx_k_utr_pieces(agx_unitig_region_args R) {
+    const agx_unitig_args &A = R.U;
+    const ut_window w = utr_window_of(A);
+    const bool start = (w.sm >> w.lane) & 1ull;
+    const agx_u32 end = w.lane + (agx_u32)__builtin_ctzll(~w.lm >> w.lane);      // (bit 63 of ~lm is always set)
+    const agx_u32 nx_end = __shfl(w.nx, (int)end, 64);
+    if (!start) return;
+    const agx_u32 pid = A.woff[w.u / 64u] + (agx_u32)__popcll(w.sm & ((1ull << w.lane) - 1ull));
+    if (pid >= A.piece_cap) { atomicOr(A.err, 4u); return; }
+    A.p_len[pid] = end - w.lane + 1u; A.p_next[pid] = nx_end; A.succ[w.u] = pid;
+}
+__global__ void __launch_bounds__(256) agx_k_utr_head_assign(agx_unitig_region_args R, agx_u32 np) {
+    const agx_unitig_args &A = R.U;
+    const agx_u32 u = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+    const bool valid = u < A.pool_cap, head = valid && !A.haspred[valid ? u : 0u];
+    const unsigned long long hm = __ballot(head);
+    if (!head) return;
+    const agx_u32 seg = A.hoff[u / 64u] + (agx_u32)__popcll(hm & ((1ull << lane) - 1ull)), p = A.succ[u];
+    if (p >= np || seg >= A.piece_cap) { atomicOr(A.err, 4u); return; }
+    const agx_u32 X = A.pos_of[u];
+    A.p_seg[p] = seg; A.s_hpos[seg] = X; A.s_hvar[seg] = R.l_slot[u] - A.node_start[X];      // the variant index among ALL of the position's variants
+}
+__global__ void __launch_bounds__(256) agx_k_utr_rank(agx_unitig_region_args R, agx_u32 np, agx_u32 fin) {
+    const agx_unitig_args &A = R.U;
+    const ut_window w = utr_window_of(A);
+    const unsigned long long below = w.sm & ((2ull << w.lane) - 1ull);
+    const agx_u32 ps = below ? 63u - (agx_u32)__builtin_clzll(below) : 0u;
+    const bool start = (w.sm >> w.lane) & 1ull;
+    const agx_u32 pid_here = start ? A.succ[w.u] : AGX_NONE;
+    const agx_u32 pid = __shfl(pid_here, (int)ps, 64);
+    const agx_u32 slot = w.valid ? R.l_slot[w.u] : AGX_NONE;
+    unsigned long long cov = slot < R.pool_cap ? (unsigned long long)(agx_u32)A.n_counts[(size_t)slot * 6] : 0ull, incl = cov;
+    for (agx_u32 d = 1; d < 64u; d <<= 1) { const unsigned long long o = __shfl_up(incl, d, 64); if (w.lane >= d) incl += o; }
+    const unsigned long long excl_ps = __shfl(incl - cov, (int)ps, 64);
+    if (!w.valid) return;
+    if (pid >= np) { atomicOr(A.err, 4u); return; }
+    const agx_u32 h = A.anc[fin][pid];
+    if (h >= np || A.anc[fin][h] != h) { atomicOr(A.err, 4u); return; }       // (not converged: impossible on a DAG)
+    const agx_u32 seg = A.p_seg[h];
+    if (seg >= A.piece_cap) { atomicOr(A.err, 4u); return; }
+    const agx_u32 rank = A.off[fin][pid] + (w.lane - ps);
+    A.indeg[w.u] = seg; A.osucc[w.u] = rank;
+    if (!w.link) atomicAdd(A.s_cov + seg, incl - excl_ps);            // the piece's last node
+    if (w.nx == AGX_NONE) { A.s_len[seg] = rank + 1u; A.s_last[seg] = A.pos_of[w.u]; A.s_links[seg] = A.outs[w.u]; }
+}
+__global__ void __launch_bounds__(256) agx_k_utr_emit(agx_unitig_region_args R) {
+    const agx_unitig_args &A = R.U;
+    const agx_u32 id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= A.pool_cap) return;
+    const agx_u32 ns = A.hoff[A.n_pos], seg = A.indeg[id], rank = A.osucc[id], u = R.l_slot[id], X = A.pos_of[id];
+    if (seg >= ns || u >= R.pool_cap) { atomicOr(A.err, 4u); return; }
+    const agx_u32 at = A.s_off[seg] + rank;
+    const char c = (char)A.n_base[u];
+    if (at < A.s_off[seg + 1] && at < A.seq_cap) A.seq[at] = c != 'X' ? c : A.ref[X];
+    else atomicOr(A.err, 4u);
+    if (A.nxt[id] != AGX_NONE) return;
+    const agx_u32 lo = A.l_off[seg], hi = A.l_off[seg + 1];
+    const uint4 nx = *reinterpret_cast<const uint4 *>(A.n_next + (size_t)u * AGX_MAXE);
+    const agx_u32 t[AGX_MAXE] = {nx.x, nx.y, nx.z, nx.w};
+    agx_u32 k = 0;
+    for (agx_u32 e = 0; e < AGX_MAXE; e++) {
+        if (t[e] == AGX_NONE || t[e] >= R.pool_cap) continue;
+        const agx_u32 lt = utr_local(R, t[e]);
+        if (lt == AGX_NONE) continue;
+        if (lo + k < hi && lo + k < A.link_cap) A.l_to[lo + k] = A.indeg[lt]; else atomicOr(A.err, 4u);
+        k++;
+    }
+    A.l_cur[seg] = k;
+}
+__global__ void __launch_bounds__(256) agx_k_utr_links_ovf(agx_unitig_region_args R) {
+    const agx_unitig_args &A = R.U;
+    const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= A.n_ovf || !A.ovf_first[i]) return;
+    const agx_u32 s = A.ovf[i].src, d = A.ovf[i].dst;                 // (both in the pool and in the export: agx_k_utr_ovf)
+    if (s >= R.pool_cap || d >= R.pool_cap) { atomicOr(A.err, 4u); return; }
+    const agx_u32 ls = utr_local(R, s), ld = utr_local(R, d);
+    if (ls == AGX_NONE || ld == AGX_NONE) { atomicOr(A.err, 4u); return; }
+    if (A.nxt[ls] == ld) return;
+    const agx_u32 seg = A.indeg[ls], ns = A.hoff[A.n_pos];
+    if (seg >= ns) { atomicOr(A.err, 4u); return; }
+    const agx_u32 at = A.l_off[seg] + atomicAdd(A.l_cur + seg, 1u);
+    if (at < A.l_off[seg + 1] && at < A.link_cap) A.l_to[at] = A.indeg[ld]; else atomicOr(A.err, 4u);
+}
+
 inline dim3 ut_grid(agx_u32 n) { return dim3((n + 255u) / 256u); }
 
 }  // namespace
+
+extern "C" void agx_launch_unitig_region_count(const agx_unitig_region_args *R, hipStream_t st) {
+    hipLaunchKernelGGL(agx_k_utr_count, ut_grid(R->n_win + 1u), dim3(256), 0, st, *R);
+    agx_launch_exclusive_scan(R->cntw, R->offw, R->n_win, R->U.scan_tmp, st);
+}
+
+extern "C" void agx_launch_unitig_region_phase1(const agx_unitig_region_args *R, hipStream_t st) {
+    const agx_u32 n = R->U.pool_cap, ngrp = R->U.n_pos;
+    if (!n) return;
+    hipLaunchKernelGGL(agx_k_utr_compact, ut_grid(R->n_win), dim3(256), 0, st, *R);
+    hipLaunchKernelGGL(agx_k_utr_degrees, ut_grid(n), dim3(256), 0, st, *R);
+    if (R->U.n_ovf) hipLaunchKernelGGL(agx_k_utr_ovf, ut_grid(R->U.n_ovf), dim3(256), 0, st, *R);
+    hipLaunchKernelGGL(agx_k_utr_internal, ut_grid(n), dim3(256), 0, st, *R);
+    hipLaunchKernelGGL(agx_k_utr_group_count, ut_grid(ngrp * 64u), dim3(256), 0, st, *R);
+    agx_launch_exclusive_scan(R->U.wcnt, R->U.woff, ngrp, R->U.scan_tmp, st);
+    agx_launch_exclusive_scan(R->U.hcnt, R->U.hoff, ngrp, R->U.scan_tmp, st);
+    hipLaunchKernelGGL(agx_k_utr_pieces, ut_grid(ngrp * 64u), dim3(256), 0, st, *R);
+}
+
+extern "C" void agx_launch_unitig_region_phase2(const agx_unitig_region_args *R, agx_u32 rounds, hipStream_t st) {
+    const agx_unitig_args *A = &R->U;
+    const agx_u32 np = A->piece_cap, ngrp = A->n_pos;
+    if (!np) return;
+    hipLaunchKernelGGL(agx_k_ut_jump_init, ut_grid(np), dim3(256), 0, st, *A, np);
+    hipLaunchKernelGGL(agx_k_ut_jump_link, ut_grid(np), dim3(256), 0, st, *A, np);
+    for (agx_u32 r = 0; r < rounds; r++) hipLaunchKernelGGL(agx_k_ut_jump, ut_grid(np), dim3(256), 0, st, *A, np, r);
+    hipLaunchKernelGGL(agx_k_utr_head_assign, ut_grid(ngrp * 64u), dim3(256), 0, st, *R, np);
+    hipLaunchKernelGGL(agx_k_utr_rank, ut_grid(ngrp * 64u), dim3(256), 0, st, *R, np, rounds & 1u);
+    agx_launch_exclusive_scan(A->s_len, A->s_off, np, A->scan_tmp, st);          // (s_off and l_off lie over the pointer jumping's arrays, which the rank kernel was the last to read)
+    agx_launch_exclusive_scan(A->s_links, A->l_off, np, A->scan_tmp, st);
+}
+
+extern "C" void agx_launch_unitig_region_phase3(const agx_unitig_region_args *R, hipStream_t st) {
+    if (!R->U.pool_cap) return;
+    hipLaunchKernelGGL(agx_k_utr_emit, ut_grid(R->U.pool_cap), dim3(256), 0, st, *R);
+    if (R->U.n_ovf) hipLaunchKernelGGL(agx_k_utr_links_ovf, ut_grid(R->U.n_ovf), dim3(256), 0, st, *R);
+    if (R->U.piece_cap) hipLaunchKernelGGL(agx_k_ut_links_sort, ut_grid(R->U.piece_cap), dim3(256), 0, st, R->U);
+}
 
 extern "C" void agx_launch_unitig_phase1(const agx_unitig_args *A, hipStream_t st) {
     if (A->n_pos) {

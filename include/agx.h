@@ -275,6 +275,13 @@ void agx_front_free(agx_front *f);
 /* After agx_unit_build of a unit created with AGX_FLAG_KEEP_COUNTS, before agx_unit_trim / agx_unit_release (AGX_FLAG_ONE_SHOT units: before their download
  * or finish).  Runs on the device over the node table the build left there and changes nothing the walk reads.  AGX_E_ARG otherwise. */
 int agx_unit_unitigs(agx_unit *u, agx_unitigs *t);
+/* The same export for a window of the unit at a coverage of the caller's choice, at a cost that follows the window.  A node is in it iff its position lies in
+ * [pos_lo, pos_hi) and (contigID != -1 or coverage >= min_coverage): the build's pruning rule with min_coverage in place of the build's coverage.  An edge is in it iff
+ * both of its ends are (an edge across the window's border is dropped); unitigs, bases, coverage sums, links and their order are DESIGN.md §11's on that sub-graph.
+ * head_pos stays the absolute position and head_var the index among ALL of the position's variants, so a segment keeps its GFA name whatever the window and threshold.
+ * The node table keeps the edges of the nodes the build pruned, so every min_coverage is served, also one below the build's coverage (0: nothing is pruned).
+ * Preconditions and error codes of agx_unit_unitigs; pos_lo > pos_hi or pos_hi > the unit's positions: AGX_E_ARG.  pos_lo == pos_hi gives no segments. */
+int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t);
 void agx_unitigs_free(agx_unitigs *t);
 /* Host only: the S and L lines of GFA 1.0 for unit `unit` (no header line), as DESIGN.md §11 defines them; *text is malloc'd, free it with agx_text_free. */
 int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len);
