@@ -15,6 +15,7 @@ AGX_FLAG_KEEP_COUNTS = 1
 AGX_FLAG_SPARSE_MIN = 2
 AGX_FLAG_TIME_SECTIONS = 4
 AGX_FLAG_ONE_SHOT = 8
+AGX_FLAG_KEEP_PATHS = 16
 
 # every symbol include/agx.h declares (tests check that the built library exports all of them)
 EXPORTS = [
@@ -25,6 +26,7 @@ EXPORTS = [
     "agx_unit_stage", "agx_unit_release", "agx_pool_trim", "agx_unit_cache_build", "agx_unit_cache_save", "agx_unit_hbm_needed",
     "agx_unit_trim", "agx_unit_unitigs", "agx_unit_unitigs_region", "agx_unitigs_free", "agx_unitigs_gfa", "agx_text_free",
     "agx_unit_walk_graph", "agx_walk_graph_free", "agx_unit_front", "agx_front_free",
+    "agx_unit_unitigs_mapped", "agx_idmap_free", "agx_unit_walk_paths", "agx_walk_paths_free", "agx_unitigs_paths_gfa",
 ]
 
 
@@ -84,6 +86,17 @@ class Unitigs(ctypes.Structure):
                 ("head_pos", ctypes.POINTER(ctypes.c_uint32)), ("head_var", ctypes.POINTER(ctypes.c_uint32)), ("n_nodes", ctypes.POINTER(ctypes.c_uint32)),
                 ("last_pos", ctypes.POINTER(ctypes.c_uint32)), ("coverage", ctypes.POINTER(ctypes.c_uint64)), ("seq_off", ctypes.POINTER(ctypes.c_uint64)),
                 ("seq", ctypes.c_void_p), ("link_from", ctypes.POINTER(ctypes.c_uint32)), ("link_to", ctypes.POINTER(ctypes.c_uint32))]
+
+
+class IdMap(ctypes.Structure):
+    _fields_ = [("n_runs", ctypes.c_uint32), ("n_pos", ctypes.c_uint32), ("n_ids", ctypes.c_uint32)] + \
+               [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("id_first", "id_last", "seg", "rank_first")]
+
+
+class WalkPaths(ctypes.Structure):
+    _fields_ = [("n_recs", ctypes.c_uint32), ("n_stretches", ctypes.c_uint64), ("rec_len", ctypes.POINTER(ctypes.c_uint64)), ("st_off", ctypes.POINTER(ctypes.c_uint64)),
+                ("id_first", ctypes.POINTER(ctypes.c_uint32)), ("id_last", ctypes.POINTER(ctypes.c_uint32)), ("base_off", ctypes.POINTER(ctypes.c_uint64)),
+                ("joined", ctypes.POINTER(ctypes.c_uint8))]
 
 
 class WalkGraph(ctypes.Structure):
@@ -203,6 +216,13 @@ def lib():
         L.agx_front_free.restype = None
         L.agx_unit_unitigs.argtypes = [ctypes.c_void_p, ctypes.POINTER(Unitigs)]
         L.agx_unit_unitigs_region.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(Unitigs)]
+        L.agx_unit_unitigs_mapped.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(Unitigs), ctypes.POINTER(IdMap)]
+        L.agx_idmap_free.argtypes = [ctypes.POINTER(IdMap)]
+        L.agx_idmap_free.restype = None
+        L.agx_unit_walk_paths.argtypes = [ctypes.c_void_p, ctypes.POINTER(WalkPaths)]
+        L.agx_walk_paths_free.argtypes = [ctypes.POINTER(WalkPaths)]
+        L.agx_walk_paths_free.restype = None
+        L.agx_unitigs_paths_gfa.argtypes = [ctypes.POINTER(Unitigs), ctypes.POINTER(IdMap), ctypes.POINTER(WalkPaths), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         L.agx_unitigs_free.argtypes = [ctypes.POINTER(Unitigs)]
         L.agx_unitigs_free.restype = None
         L.agx_unitigs_gfa.argtypes = [ctypes.POINTER(Unitigs), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
@@ -303,9 +323,9 @@ class Reads:
 class Unit:
     """One reference unit (chromosome or --part slice): the body of the reference's unit loop, AG:4765-4783."""
 
-    def __init__(self, k=5, insert_variation=50, coverage=20, batch=0, device=0, keep_counts=False, flags=0):
+    def __init__(self, k=5, insert_variation=50, coverage=20, batch=0, device=0, keep_counts=False, flags=0, keep_paths=False):
         self._h = ctypes.c_void_p()
-        self.params = Params(k, insert_variation, coverage, batch, device, (AGX_FLAG_KEEP_COUNTS if keep_counts else 0) | flags)
+        self.params = Params(k, insert_variation, coverage, batch, device, (AGX_FLAG_KEEP_COUNTS if keep_counts else 0) | (AGX_FLAG_KEEP_PATHS if keep_paths else 0) | flags)
         rc = lib().agx_unit_create(ctypes.byref(self.params), ctypes.byref(self._h))
         if rc != AGX_OK:
             self._h = ctypes.c_void_p()
@@ -430,16 +450,48 @@ class Unit:
                 raise AgxError(AGX_E_ARG, "unitigs: region bounds and min_coverage are unsigned 32-bit numbers")
         self._check(lib().agx_unit_unitigs_region(self._h, int(lo), int(hi), int(cov), ctypes.byref(t)))
 
-    def unitigs(self, region=None, min_coverage=None):
+    def unitigs(self, region=None, min_coverage=None, id_map=False):
         """The unit's pruned graph compacted into unitigs on the device (agx_unit_unitigs; needs keep_counts): numpy arrays per segment and link, the
         bases as bytes.  region=(lo, hi) and / or min_coverage: the sub-graph of positions [lo, hi) whose nodes are alive at that coverage
-        (agx_unit_unitigs_region), at a cost that follows the window."""
+        (agx_unit_unitigs_region), at a cost that follows the window.  id_map=True (needs keep_paths; agx_unit_unitigs_mapped): the same table of the window
+        (every position without a region) at the threshold (the unit's coverage without one) with one more entry, "id_map": the runs of walk ids whose nodes
+        are in the export (id_first, id_last, seg, rank_first) and the unit's n_pos and n_ids."""
         t = Unitigs()
-        self._export(t, region, min_coverage)
+        if not id_map:
+            self._export(t, region, min_coverage)
+            try:
+                return _unitigs_arrays(t)
+            finally:
+                lib().agx_unitigs_free(ctypes.byref(t))
+        lo, hi = region if region is not None else (0, self.stats()["n_pos"])
+        cov = self.params.coverage if min_coverage is None else min_coverage
+        for v in (lo, hi, cov):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise AgxError(AGX_E_ARG, "unitigs: region bounds and min_coverage are unsigned 32-bit numbers")
+        m = IdMap()
+        self._check(lib().agx_unit_unitigs_mapped(self._h, int(lo), int(hi), int(cov), ctypes.byref(t), ctypes.byref(m)))
         try:
-            return _unitigs_arrays(t)
+            out = _unitigs_arrays(t)
+            out["id_map"] = _idmap_arrays(m)
+            return out
         finally:
             lib().agx_unitigs_free(ctypes.byref(t))
+            lib().agx_idmap_free(ctypes.byref(m))
+
+    def walk_paths(self):
+        """The graph stretches of the records the last finish() wrote to "pre" (agx_unit_walk_paths; needs keep_paths): rec_len, st_off per record, id_first, id_last,
+        base_off, joined per stretch, as numpy arrays."""
+        import numpy as np
+        w = WalkPaths()
+        self._check(lib().agx_unit_walk_paths(self._h, ctypes.byref(w)))
+        try:
+            def arr(p, n, dt):
+                return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
+            nr, ns = w.n_recs, w.n_stretches
+            return {"rec_len": arr(w.rec_len, nr, "uint64"), "st_off": arr(w.st_off, nr + 1, "uint64"), "id_first": arr(w.id_first, ns, "uint32"),
+                    "id_last": arr(w.id_last, ns, "uint32"), "base_off": arr(w.base_off, ns, "uint64"), "joined": arr(w.joined, ns, "uint8")}
+        finally:
+            lib().agx_walk_paths_free(ctypes.byref(w))
 
     def gfa(self, unit=0, region=None, min_coverage=None):
         """GFA 1.0 S and L lines of the unit's unitigs, segments named u<unit>_<pos>_<var> (no header line); region and min_coverage as in unitigs()."""
@@ -462,6 +514,42 @@ def _unitigs_arrays(t):
             "seq_off": arr(t.seq_off, ns + 1, "uint64") if ns else np.zeros(1, "uint64"),
             "seq": ctypes.string_at(t.seq, t.n_bases) if t.seq and t.n_bases else b"",
             "link_from": arr(t.link_from, nl, "uint32"), "link_to": arr(t.link_to, nl, "uint32")}
+
+
+def _idmap_arrays(m):
+    import numpy as np
+
+    def arr(p, n):
+        return np.ctypeslib.as_array(p, shape=(n,)).astype("uint32", copy=True) if n else np.zeros(0, "uint32")
+    n = m.n_runs
+    return {"n_pos": m.n_pos, "n_ids": m.n_ids, "id_first": arr(m.id_first, n), "id_last": arr(m.id_last, n), "seg": arr(m.seg, n), "rank_first": arr(m.rank_first, n)}
+
+
+def gfa_paths(t, w, unit=0):
+    """GFA P lines (no header) that lay the records of w (the dict Unit.walk_paths() returns) over the segments of t (the dict Unit.unitigs(id_map=True) returns):
+    agx_unitigs_paths_gfa; host only, needs no device."""
+    import numpy as np
+    ts, _keep = _unitigs_struct(t)
+    im = t["id_map"]
+    mk = {k: np.ascontiguousarray(im[k], dtype="uint32") for k in ("id_first", "id_last", "seg", "rank_first")}
+    m = IdMap()
+    m.n_runs, m.n_pos, m.n_ids = len(mk["id_first"]), int(im["n_pos"]), int(im["n_ids"])
+    for k, a in mk.items():
+        setattr(m, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    wk = {k: np.ascontiguousarray(w[k], dtype=dt) for k, dt in (("rec_len", "uint64"), ("st_off", "uint64"), ("id_first", "uint32"), ("id_last", "uint32"),
+                                                                 ("base_off", "uint64"), ("joined", "uint8"))}
+    ws = WalkPaths()
+    ws.n_recs, ws.n_stretches = len(wk["rec_len"]), len(wk["id_first"])
+    for k, a in wk.items():
+        setattr(ws, k, a.ctypes.data_as(ctypes.POINTER({"uint64": ctypes.c_uint64, "uint32": ctypes.c_uint32, "uint8": ctypes.c_uint8}[a.dtype.name])))
+    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
+    rc = lib().agx_unitigs_paths_gfa(ctypes.byref(ts), ctypes.byref(m), ctypes.byref(ws), unit, ctypes.byref(p), ctypes.byref(n))
+    if rc != AGX_OK:
+        raise AgxError(rc, "agx_unitigs_paths_gfa: the unitig table, the id map and the stretches do not agree")
+    try:
+        return ctypes.string_at(p, n.value) if n.value else b""
+    finally:
+        lib().agx_text_free(p)
 
 
 def _gfa_text(t, unit):

@@ -45,6 +45,7 @@ struct Options {
     // --graphRegion <unit>:<lo>-<hi>, --graphMinCoverage <n> (only with --graphOut): the GFA lines of one unit's positions [lo, hi) and / or with "alive" decided by n
     // instead of --coverage (agx_unit_unitigs_region)
     int tagRegion = 0, tagGraphCov = 0, regionUnit = 0, graphCov = 0; uint32_t regionLo = 0, regionHi = 0;
+    int graphPaths = 0;                 // --graphPaths (only with --graphOut): the pre-extended records as P lines over the exported segments (agx_unitigs_paths_gfa)
     int fastMap = 0, ratioCheck = 0, uniqueExtension = 0, iterativeMap = 0, misassemblyRemoval = 0, resume = 0;
     int k = 5, distanceLow = 0, distanceHigh = 99999, coverage = 20, insertVariation = 50, part = 1;      // defaults of AG:4701
 };
@@ -127,6 +128,7 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--graphOut") outfile(i, o.tagGraph, o.graph);
         else if (b == "--graphRegion") region(i);
         else if (b == "--graphMinCoverage") { integer(i, o.tagGraphCov, o.graphCov); if (o.graphCov < 0) die_usage(); }
+        else if (b == "--graphPaths") flag(o.graphPaths);
         else if (b == "--kMer") integer(i, o.tagK, o.k);
         else if (b == "--insertVariation") integer(i, o.tagIV, o.insertVariation);
         else if (b == "--coverage") integer(i, o.tagCov, o.coverage);
@@ -139,14 +141,15 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--resume") { if (o.resume == 1 || count != 1) die_usage(); o.resume = 1; }
         else die_usage();
     }
-    if ((o.tagRegion || o.tagGraphCov) && !o.tagGraph) die_usage();
+    if ((o.tagRegion || o.tagGraphCov || o.graphPaths) && !o.tagGraph) die_usage();
 }
 
-// tmp/_graph.<u>.gfa, with the region and the threshold in the name when they are given: a --resume run merges only lines that were made under its own settings
+// tmp/_graph.<u>.gfa, with the region, the threshold and --graphPaths (.p) in the name when they are given: a --resume run merges only lines that were made under its own settings
 string graph_part_path(const Options &o, int u) {
     string s = "tmp/_graph." + itoa(u);
     if (o.tagRegion) s += "." + itoa(o.regionLo) + "-" + itoa(o.regionHi);
     if (o.tagGraphCov) s += ".c" + itoa(o.graphCov);
+    if (o.graphPaths) s += ".p";
     return s + ".gfa";
 }
 
@@ -1168,7 +1171,7 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                 if (at >= order.size() || failed.load()) return;
                 const int u = order[at];
                 // the five calls of the unit loop (AG:4768-4776) through the split entry points of agx_run_unit, with the admission between load and upload
-                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, AGX_FLAG_ONE_SHOT | (o.tagGraph ? AGX_FLAG_KEEP_COUNTS : 0u)};
+                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, AGX_FLAG_ONE_SHOT | (o.tagGraph ? AGX_FLAG_KEEP_COUNTS : 0u) | (o.graphPaths ? AGX_FLAG_KEEP_PATHS : 0u)};
                 agx_result r; memset(&r, 0, sizeof r); char err[512]; err[0] = 0;
                 agx_unit *un = nullptr;
                 int rc = agx_unit_create(&p, &un);
@@ -1179,16 +1182,23 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                 if (rc == AGX_OK) { std::unique_lock<std::mutex> g(mem_mu); waiting[d]++; mem_cv.wait(g, [&] { return used[d] == 0.0 || used[d] + est <= budget[d]; }); waiting[d]--; used[d] += est; admitted = true; }
                 if (rc == AGX_OK) rc = agx_unit_upload(un);
                 if (rc == AGX_OK) rc = agx_unit_build(un);
-                if (rc == AGX_OK && o.tagGraph && (!o.tagRegion || u == o.regionUnit)) {      // --graphOut: the unit's GFA lines, exported before the download (one-shot units) into tmp/_graph.<u>.gfa
-                    agx_unitigs ut; char *text = nullptr; size_t len = 0;
-                    if (!o.tagRegion && !o.tagGraphCov) rc = agx_unit_unitigs(un, &ut);
+                const bool graph_here = o.tagGraph && (!o.tagRegion || u == o.regionUnit);
+                agx_unitigs ut; agx_idmap im; memset(&ut, 0, sizeof ut); memset(&im, 0, sizeof im);      // (--graphPaths: both outlive the finish, which gives the records)
+                if (rc == AGX_OK && graph_here) {      // --graphOut: the unit's GFA lines, exported before the download (one-shot units) into tmp/_graph.<u>.gfa
+                    char *text = nullptr; size_t len = 0;
+                    if (o.graphPaths) {      // the same window and threshold through the export that also maps the walk's ids
+                        agx_stats st; memset(&st, 0, sizeof st);
+                        rc = agx_unit_stats(un, &st);
+                        if (rc == AGX_OK) rc = agx_unit_unitigs_mapped(un, o.tagRegion ? o.regionLo : 0u, o.tagRegion ? o.regionHi : (uint32_t)st.n_pos, (uint32_t)(o.tagGraphCov ? o.graphCov : o.coverage), &ut, &im);
+                    }
+                    else if (!o.tagRegion && !o.tagGraphCov) rc = agx_unit_unitigs(un, &ut);
                     else {      // --graphRegion / --graphMinCoverage: the window (all positions without a region) at the threshold (--coverage without one)
                         agx_stats st; memset(&st, 0, sizeof st); memset(&ut, 0, sizeof ut);
                         rc = agx_unit_stats(un, &st);
                         if (rc == AGX_OK) rc = agx_unit_unitigs_region(un, o.tagRegion ? o.regionLo : 0u, o.tagRegion ? o.regionHi : (uint32_t)st.n_pos, (uint32_t)(o.tagGraphCov ? o.graphCov : o.coverage), &ut);
                     }
                     if (rc == AGX_OK) { rc = agx_unitigs_gfa(&ut, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "GFA FORMATTING FAILED"); }
-                    agx_unitigs_free(&ut);
+                    if (!o.graphPaths) agx_unitigs_free(&ut);
                     if (rc == AGX_OK) {
                         const string path = graph_part_path(o, u);
                         FILE *f = fopen(path.c_str(), "wb"); bool ok = f != nullptr;
@@ -1204,6 +1214,19 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                     if (rc == AGX_OK && agx_unit_trim(un, &freed) == AGX_OK && freed) { { std::lock_guard<std::mutex> g(mem_mu); const double f = std::min(est, (double)freed); used[d] -= f; est -= f; } mem_cv.notify_all(); }
                 }
                 if (rc == AGX_OK) rc = agx_unit_finish(un, &r);      // (r06: nothing downloaded yet — nobody waits for this unit's HBM — : the download is streamed and the walk begins on what has landed)
+                if (rc == AGX_OK && graph_here && o.graphPaths) {      // the P lines behind the unit's S and L lines
+                    agx_walk_paths wp; char *text = nullptr; size_t len = 0;
+                    rc = agx_unit_walk_paths(un, &wp);
+                    if (rc == AGX_OK) { rc = agx_unitigs_paths_gfa(&ut, &im, &wp, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "GFA FORMATTING FAILED"); }
+                    agx_walk_paths_free(&wp);
+                    if (rc == AGX_OK) {
+                        FILE *f = fopen(graph_part_path(o, u).c_str(), "ab"); bool ok = f != nullptr;
+                        if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
+                        if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
+                    }
+                    agx_text_free(text);
+                }
+                agx_unitigs_free(&ut); agx_idmap_free(&im);
                 if (rc != AGX_OK && un && !err[0]) snprintf(err, sizeof err, "%s", agx_unit_error(un));
                 agx_unit_destroy(un);                                          // (its HBM goes back before the next unit is admitted)
                 if (admitted) { { std::lock_guard<std::mutex> g(mem_mu); used[d] -= est; if (used[d] < 1.0) used[d] = 0.0; } mem_cv.notify_all(); }

@@ -1017,6 +1017,27 @@ size_t unitig_region_layout(size_t cap, size_t n_win, size_t kept, size_t n_ovf,
     return at + 256;
 }
 
+// The scratch of an export's id map (agx_unit_unitigs_mapped, agx_unitig.hip: agx_k_idm_*), behind the export's own in the same buffer: `ids` window ids (the window's main
+// ids and the side ids of its positions), `runs` runs at most (a run holds a kept node at least).  Two words per window id and four per run.
+size_t idmap_layout(size_t ids, size_t runs, char *base, agx_idmap_args *A) {
+    size_t at = 0;
+    auto take = [&](auto *&p, size_t n) { at = (at + 255) & ~(size_t)255; p = base ? (std::remove_reference_t<decltype(*p)> *)(base + at) : nullptr; at += (n ? n : 1) * sizeof(*p); };
+    agx_idmap_args T{}; agx_idmap_args &M = A ? *A : T;
+    take(M.flag, ids + 1); take(M.foff, ids + 1);
+    take(M.scan_tmp, 2 * ((ids + 1 + 1023) / 1024 + 1) + 2 * ((ids + 1 + 1024ull * 1024 - 1) / (1024ull * 1024) + 1) + 16);
+    take(M.r_first, runs); take(M.r_last, runs); take(M.r_seg, runs); take(M.r_rank, runs);
+    return at + 256;
+}
+inline bool keeps_paths(const agx_unit *u) { return (u->prm.flags & (AGX_FLAG_KEEP_PATHS | AGX_FLAG_KEEP_COUNTS)) == (AGX_FLAG_KEEP_PATHS | AGX_FLAG_KEEP_COUNTS); }
+// The export buffer of a unit that keeps paths: every export of such a unit takes the same size — the larger of the two export layouts at their worst, and behind it (at `map_at`)
+// the id map's scratch for a whole-window map — so that exports of any kind in any order never take the buffer twice.
+size_t mapped_scratch(size_t cap, size_t n_pos, size_t n_nodes, size_t n_ids, size_t n_ovf, size_t *map_at) {
+    const size_t kept = std::min(n_nodes, cap), sides = n_ids > n_pos ? n_ids - n_pos : 0;
+    const size_t front = (std::max(unitig_layout(cap, n_pos, n_ovf, nullptr, nullptr, nullptr), unitig_region_layout(cap, n_pos, kept, n_ovf, nullptr, nullptr, nullptr)) + 255) & ~(size_t)255;
+    if (map_at) *map_at = front;
+    return front + idmap_layout(n_pos + sides, std::min(kept, n_pos + sides), nullptr, nullptr);
+}
+
 // Capacities of a unit's first build and the HBM they add up to (what do_upload reserves as one block; AlignGraph_amd admits a unit to a device by it:
 // agx_unit_hbm_needed).  From the staged counts: positions, hits, runs, conti-mers, read rows.
 struct Plan { agx_u32 pool_cap, list_cap, ovf_cap, sp_cap; size_t exact, total; };      // exact: what the five groups take; total: with the room to regrow in and the export's scratch
@@ -1043,6 +1064,7 @@ Plan plan_capacities(const agx_unit *u) {
     Take m; pool_bufs(u, P.pool_cap, m); fixed_bufs(u, m); list_bufs(u, P.list_cap, m); ovf_bufs(u, P.ovf_cap, m); sparse_bufs(u, P.sp_cap, m);
     P.exact = m.bytes;
     P.total = P.exact + regrow_slack(P.exact) + ((u->prm.flags & AGX_FLAG_KEEP_COUNTS) ? unitig_layout(P.pool_cap, n_pos, P.ovf_cap, nullptr, nullptr, nullptr) : 0);      // (counts are kept for the unitig export)
+    if (keeps_paths(u)) P.total += idmap_layout(n_pos + P.pool_cap, P.pool_cap, nullptr, nullptr);      // (a whole-window id map at its worst: every slot a side id and a run)
     return P;
 }
 
@@ -1054,6 +1076,7 @@ void do_upload(agx_unit *u) {
     if (u->consumed) throw Error{E_ARG, "one-shot unit: hand its inputs over again before another upload"};
     if (!u->staged) stage_inputs(u);
     if (u->arena.used()) do_release(u);              // uploaded before: start over (the unit's blocks go through the cache)
+    u->out.paths.clear(); u->out.paths_ready = false;
     const double t0 = now_ms();
     HIP_OK(hipSetDevice(u->prm.device));
     const size_t n_pos = u->V.n_pos, nh = u->nh;
@@ -1592,6 +1615,7 @@ void do_release(agx_unit *u) {
     u->uploaded = u->built = u->downloaded = false;
     join_helper(u);
     u->out.pre_extended.clear(); u->out.extended.clear(); u->out_initial.clear(); u->out_ready = false;
+    u->out.paths.clear(); u->out.paths_ready = false;
 }
 
 // records of non-special walk ids: built on the device from the node table, which stays in HBM (agx_walk_record), then one copy
@@ -1889,7 +1913,9 @@ int agx_unit_finish(agx_unit *u, agx_result *r) {
         } second(u, walkers_now(u->V.n_pos) - 2);      // one thread per further walker: the unit's helper + pool threads
         GraphView G = view_of(u);
         if (streamed) { G.wait_landed = stream_wait_landed; G.wait_str = stream_wait_str; G.land_ctx = u; G.land_ms = std::max(0.01, u->dl_est_ms - (now_ms() - u->dl_t0)); }
+        u->out.keep_paths = (u->prm.flags & AGX_FLAG_KEEP_PATHS) != 0; u->out.paths.clear(); u->out.paths_ready = false;
         walk_join_scaffold(u->V, G, u->out, u->helper.started ? &second : nullptr);
+        u->out.paths_ready = u->out.keep_paths;
         u->stats.ms_walk = now_ms() - t0; u->stats.n_fetched = u->out.n_fetched;
         trace(u, "walk", t0, u->V.n_pos);
         r->initial_len = u->out_initial.n; r->initial_contigs = u->out_initial.release();
@@ -2067,7 +2093,7 @@ int agx_unit_unitigs(agx_unit *u, agx_unitigs *t) {
         const agx_u32 n_pos = (agx_u32)u->V.n_pos, cap = u->pool_cap, n_ovf = std::min(u->n_ovf, u->ovf_cap);
         if (!n_pos || !cap || !u->n_nodes) return;
         const size_t bytes = unitig_layout(cap, n_pos, n_ovf, nullptr, nullptr, nullptr);
-        u->d_ut.alloc(u->arena, bytes);                  // (from the room the upload reserved for it; a unit whose pool or overflow list grew takes the difference)
+        u->d_ut.alloc(u->arena, keeps_paths(u) ? mapped_scratch(cap, n_pos, u->n_nodes, u->n_ids, n_ovf, nullptr) : bytes);      // (from the room the upload reserved for it; a unit whose pool or overflow list grew takes the difference)
         u->stats.device_bytes = u->arena.capacity();
         struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;      // (the export's work is done before the call returns, also on an error)
         HIP_OK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
@@ -2130,22 +2156,25 @@ int agx_unit_unitigs(agx_unit *u, agx_unitigs *t) {
 // scratch buffer, a stream of its own; no launch and no memset below is sized by the unit's positions or node slots, only by the window's positions, its kept nodes and the
 // overflow list (which has no position index).  Four host round trips: the kept nodes, the piece and head counts, the totals, the download.  agx_unit_unitigs above does not
 // come through here: its code path and its timings are what this one is compared with.
-int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t) {
-    if (!u || !t) return AGX_E_ARG;
-    memset(t, 0, sizeof *t);
-    const int rc = guarded(u, [&] {
+// (m: also the id map of the export, agx_unit_unitigs_mapped; nullptr: every command and copy is agx_unit_unitigs_region's)
+static void region_export(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, agx_idmap *m) {
+    {
         if (!(u->prm.flags & AGX_FLAG_KEEP_COUNTS)) throw Error{E_ARG, "unitigs: the unit was created without AGX_FLAG_KEEP_COUNTS (the segments' coverage needs the counts)"};
         if (!u->built || u->trimmed) throw Error{E_ARG, "unitigs: the unit is not built (call agx_unit_build; not after agx_unit_trim or agx_unit_release)"};
         if ((u->prm.flags & AGX_FLAG_ONE_SHOT) && (u->consumed || u->downloaded)) throw Error{E_ARG, "unitigs: a one-shot unit exports before its download or finish"};
+        if (m && !(u->prm.flags & AGX_FLAG_KEEP_PATHS)) throw Error{E_ARG, "unitigs: the unit was created without AGX_FLAG_KEEP_PATHS (the id map's scratch is reserved with the unit's block)"};
         const agx_u32 n_pos = (agx_u32)u->V.n_pos, cap = u->pool_cap, n_ovf = std::min(u->n_ovf, u->ovf_cap);
         if (pos_lo > pos_hi || pos_hi > n_pos)
             throw Error{E_ARG, "unitigs: region [" + std::to_string(pos_lo) + ", " + std::to_string(pos_hi) + ") is not within the unit's positions [0, " + std::to_string(n_pos) + ")"};
         HIP_OK(hipSetDevice(u->prm.device));
         HIP_OK(wait_event(u->ev_built));
         const agx_u32 n_win = pos_hi - pos_lo;
+        if (m) { m->n_pos = n_pos; m->n_ids = u->n_ids; }
         if (!n_win || !cap || !u->n_nodes) return;
         const size_t whole = unitig_layout(cap, n_pos, n_ovf, nullptr, nullptr, nullptr);
-        u->d_ut.alloc(u->arena, std::max(whole, unitig_region_layout(cap, n_win, std::min<size_t>(u->n_nodes, cap), n_ovf, nullptr, nullptr, nullptr)));      // (the buffer of the whole export: the room the upload reserved; a tiny unit: unitig_region_layout)
+        size_t map_at = 0;
+        if (keeps_paths(u)) u->d_ut.alloc(u->arena, mapped_scratch(cap, n_pos, u->n_nodes, u->n_ids, n_ovf, &map_at));
+        else u->d_ut.alloc(u->arena, std::max(whole, unitig_region_layout(cap, n_win, std::min<size_t>(u->n_nodes, cap), n_ovf, nullptr, nullptr, nullptr)));      // (the buffer of the whole export: the room the upload reserved; a tiny unit: unitig_region_layout)
         u->stats.device_bytes = u->arena.capacity();
         struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
         HIP_OK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
@@ -2162,13 +2191,27 @@ int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint3
         bind(0);
         fill(words, 0, 32);
         agx_launch_unitig_region_count(&R, st.s);
-        agx_u32 h[4] = {0, 0, 0, 0};
+        agx_u32 h[4] = {0, 0, 0, 0}, hm[3] = {0, 0, 0};      // hm: the id map's side-id bounds and run count
+        agx_idmap_args M{};
+        if (m) {      // the window's side ids: two bisections on the device, read with the kept nodes
+            M.a_nid = u->d_a_nid.p; M.side_xpos = u->d_side_xpos.p; M.n_pos = n_pos; M.n_ids = u->n_ids; M.n_main = n_win; M.bounds = words + 1;
+            agx_launch_idmap_bounds(&R, &M, st.s);
+            HIP_OK(hipMemcpyAsync(hm, words + 1, 8, hipMemcpyDeviceToHost, st.s));
+        }
         HIP_OK(hipMemcpyAsync(h, words, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipMemcpyAsync(h + 1, R.offw + n_win, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
         if (h[0]) throw Error{E_DEVICE, "unitigs: the node table is inconsistent (error word " + std::to_string(h[0]) + ")"};
         const agx_u32 kept = h[1];
         if (kept > u->n_nodes || kept > cap) throw Error{E_DEVICE, "unitigs: more nodes in the region than in the unit"};
         if (!kept) return;
         bind(kept);
+        agx_u32 n_wids = 0;
+        if (m) {
+            const agx_u32 sides = u->n_ids > n_pos ? u->n_ids - n_pos : 0u;
+            if (hm[0] > hm[1] || hm[1] > sides) throw Error{E_DEVICE, "unitigs: the side ids are not in position order"};
+            M.side_lo = hm[0]; M.n_side = hm[1] - hm[0]; n_wids = n_win + M.n_side;
+            idmap_layout((size_t)n_pos + sides, std::min<size_t>(std::min<size_t>(u->n_nodes, cap), (size_t)n_pos + sides), u->d_ut.p + map_at, &M);      // (the layout the buffer was sized by: this window's ids fit its front)
+            M.run_cap = (agx_u32)std::min<size_t>(kept, n_wids);
+        }
         agx_unitig_args &A = R.U;
         const size_t ngrp = A.n_pos;
         if (n_ovf) fill(A.ovf_hash, 0xFF, ((size_t)A.hash_mask + 1) * 8);
@@ -2186,20 +2229,29 @@ int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint3
         agx_launch_unitig_region_phase2(&R, rounds, st.s);
         fill(A.l_cur, 0, ((size_t)np + 1) * 4);          // (over the pointer jumping's second ancestor array: behind the rank kernel)
         agx_launch_unitig_totals(&A, words + 4, st.s);
+        if (m) {      // run starts and their scan, on the (segment, rank) the rank kernel left per local id; the run count comes with the totals
+            agx_launch_idmap_flags(&R, &M, st.s);
+            HIP_OK(hipMemcpyAsync(hm + 2, M.foff + n_wids, 4, hipMemcpyDeviceToHost, st.s));
+        }
         HIP_OK(hipMemcpyAsync(h, words + 4, 16, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
         if (h[3]) throw Error{E_DEVICE, "unitigs: the unitig ranks are inconsistent (error word " + std::to_string(h[3]) + ")"};
         const agx_u32 ns = h[0], nb = h[1], nl = h[2];
         if (ns > np || nb > kept || nb > A.seq_cap || nl > A.link_cap) throw Error{E_DEVICE, "unitigs: segment totals out of range"};
         A.seq_cap = nb; A.link_cap = nl;
+        const agx_u32 nr = hm[2];
+        if (m && nr > M.run_cap) throw Error{E_DEVICE, "unitigs: more runs in the id map than nodes in the region"};
+        M.run_cap = nr;
         agx_launch_unitig_region_phase3(&R, st.s);
+        if (m) agx_launch_idmap_runs(&R, &M, st.s);
         // the download and the caller's table: a copy of agx_unit_unitigs' last part, kept apart only because that function's code path is the baseline this one is measured
         // against — the two must change together (a helper shared by both is the next step once that constraint goes)
         const size_t o_hp = 0, o_hv = o_hp + 4 * (size_t)ns, o_ln = o_hv + 4 * (size_t)ns, o_lp = o_ln + 4 * (size_t)ns, o_cov = (o_lp + 4 * (size_t)ns + 7) & ~(size_t)7,
-                     o_so = o_cov + 8 * (size_t)ns, o_lo = o_so + 4 * ((size_t)ns + 1), o_lt = o_lo + 4 * ((size_t)ns + 1), o_seq = o_lt + 4 * (size_t)nl, o_end = o_seq + nb;
+                     o_so = o_cov + 8 * (size_t)ns, o_lo = o_so + 4 * ((size_t)ns + 1), o_lt = o_lo + 4 * ((size_t)ns + 1), o_seq = o_lt + 4 * (size_t)nl, o_run = (o_seq + nb + 3) & ~(size_t)3, o_end = o_run + (m ? 16 * (size_t)nr : 0);
         PBuf<char> pin; pin.alloc(o_end + 8);
         auto down = [&](size_t o, const void *src, size_t b) { if (b) HIP_OK(hipMemcpyAsync(pin.p + o, src, b, hipMemcpyDeviceToHost, st.s)); };
         down(o_hp, A.s_hpos, 4 * (size_t)ns); down(o_hv, A.s_hvar, 4 * (size_t)ns); down(o_ln, A.s_len, 4 * (size_t)ns); down(o_lp, A.s_last, 4 * (size_t)ns);
         down(o_cov, A.s_cov, 8 * (size_t)ns); down(o_so, A.s_off, 4 * ((size_t)ns + 1)); down(o_lo, A.l_off, 4 * ((size_t)ns + 1)); down(o_lt, A.l_to, 4 * (size_t)nl); down(o_seq, A.seq, nb);
+        if (m) { down(o_run, M.r_first, 4 * (size_t)nr); down(o_run + 4 * (size_t)nr, M.r_last, 4 * (size_t)nr); down(o_run + 8 * (size_t)nr, M.r_seg, 4 * (size_t)nr); down(o_run + 12 * (size_t)nr, M.r_rank, 4 * (size_t)nr); }
         HIP_OK(hipMemcpyAsync(h, words, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
         if (h[0]) throw Error{E_DEVICE, "unitigs: the segments are inconsistent (error word " + std::to_string(h[0]) + ")"};
         t->n_segs = ns; t->n_links = nl; t->n_bases = nb;
@@ -2216,9 +2268,69 @@ int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint3
             if (lo[g] > lo[g + 1] || lo[g + 1] > nl) throw Error{E_DEVICE, "unitigs: link offsets out of range"};
             for (agx_u32 i = lo[g]; i < lo[g + 1]; i++) t->link_from[i] = (uint32_t)g;
         }
-    });
+        if (m && nr) {
+            m->id_first = (uint32_t *)malloc(4 * (size_t)nr); m->id_last = (uint32_t *)malloc(4 * (size_t)nr); m->seg = (uint32_t *)malloc(4 * (size_t)nr); m->rank_first = (uint32_t *)malloc(4 * (size_t)nr);
+            if (!m->id_first || !m->id_last || !m->seg || !m->rank_first) throw Error{E_ARG, "out of host memory"};
+            memcpy(m->id_first, pin.p + o_run, 4 * (size_t)nr); memcpy(m->id_last, pin.p + o_run + 4 * (size_t)nr, 4 * (size_t)nr);
+            memcpy(m->seg, pin.p + o_run + 8 * (size_t)nr, 4 * (size_t)nr); memcpy(m->rank_first, pin.p + o_run + 12 * (size_t)nr, 4 * (size_t)nr);
+            m->n_runs = nr;
+            // what the kernels wrote must be a map: runs in id order, inside one block of ids, inside their segments
+            for (agx_u32 r = 0; r < nr; r++) {
+                const uint32_t a = m->id_first[r], b = m->id_last[r];
+                if (a > b || b >= u->n_ids || (a < n_pos) != (b < n_pos) || (r && m->id_last[r - 1] >= a) || m->seg[r] >= ns ||
+                    (uint64_t)m->rank_first[r] + (b - a) >= t->n_nodes[m->seg[r]]) throw Error{E_DEVICE, "unitigs: the id map is inconsistent (run " + std::to_string(r) + ")"};
+            }
+        }
+    }
+}
+
+int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t) {
+    if (!u || !t) return AGX_E_ARG;
+    memset(t, 0, sizeof *t);
+    const int rc = guarded(u, [&] { region_export(u, pos_lo, pos_hi, min_coverage, t, nullptr); });
     if (rc != AGX_OK) agx_unitigs_free(t);
     return rc;
+}
+
+int agx_unit_unitigs_mapped(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, agx_idmap *m) {
+    if (!u || !t || !m) return AGX_E_ARG;
+    memset(t, 0, sizeof *t); memset(m, 0, sizeof *m);
+    const int rc = guarded(u, [&] { region_export(u, pos_lo, pos_hi, min_coverage, t, m); });
+    if (rc != AGX_OK) { agx_unitigs_free(t); agx_idmap_free(m); }
+    return rc;
+}
+
+void agx_idmap_free(agx_idmap *m) {
+    if (!m) return;
+    free(m->id_first); free(m->id_last); free(m->seg); free(m->rank_first);
+    memset(m, 0, sizeof *m);
+}
+
+int agx_unit_walk_paths(agx_unit *u, agx_walk_paths *w) {
+    if (!u || !w) return AGX_E_ARG;
+    memset(w, 0, sizeof *w);
+    const int rc = guarded(u, [&] {
+        if (!(u->prm.flags & AGX_FLAG_KEEP_PATHS)) throw Error{E_ARG, "walk paths: the unit was created without AGX_FLAG_KEEP_PATHS"};
+        if (!u->out.paths_ready) throw Error{E_ARG, "walk paths: nothing kept (call agx_unit_finish; not after another upload or agx_unit_release)"};
+        const WalkPaths &P = u->out.paths;
+        const size_t nr = P.rec_len.size(), ns = P.id_first.size();
+        if (nr >= 0xFFFFFFFFull) throw Error{E_OVERFLOW, "walk paths: more than 2^32 records"};
+        w->rec_len = (uint64_t *)malloc(8 * (nr + 1)); w->st_off = (uint64_t *)malloc(8 * (nr + 1)); w->id_first = (uint32_t *)malloc(4 * (ns + 1)); w->id_last = (uint32_t *)malloc(4 * (ns + 1));
+        w->base_off = (uint64_t *)malloc(8 * (ns + 1)); w->joined = (uint8_t *)malloc(ns + 1);
+        if (!w->rec_len || !w->st_off || !w->id_first || !w->id_last || !w->base_off || !w->joined) throw Error{E_ARG, "out of host memory"};
+        w->n_recs = (uint32_t)nr; w->n_stretches = ns;
+        if (nr) memcpy(w->rec_len, P.rec_len.data(), 8 * nr);
+        w->st_off[0] = 0; if (nr) memcpy(w->st_off + 1, P.st_end.data(), 8 * nr);
+        if (ns) { memcpy(w->id_first, P.id_first.data(), 4 * ns); memcpy(w->id_last, P.id_last.data(), 4 * ns); memcpy(w->base_off, P.base_off.data(), 8 * ns); memcpy(w->joined, P.joined.data(), ns); }
+    });
+    if (rc != AGX_OK) agx_walk_paths_free(w);
+    return rc;
+}
+
+void agx_walk_paths_free(agx_walk_paths *w) {
+    if (!w) return;
+    free(w->rec_len); free(w->st_off); free(w->id_first); free(w->id_last); free(w->base_off); free(w->joined);
+    memset(w, 0, sizeof *w);
 }
 
 int agx_run_unit(const agx_params *p, const char *tmp_dir, int unit, int write_files, agx_result *r, char *err, size_t err_len) {

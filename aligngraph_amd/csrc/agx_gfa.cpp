@@ -2,9 +2,11 @@
 //
 //   S	u<unit>_<pos>_<var>	<sequence>	LN:i:<nodes>	KC:i:<coverage>	pe:i:<last position>
 //   L	<from segment>	+	<to segment>	+	0M
+//   P	p<unit>_<record>_<first base>	<segment>+,<segment>+,...	*	ln:i:<nodes>	fs:i:<first rank>	ls:i:<last rank>      (agx_unitigs_paths_gfa)
 //
 // S lines in segment order, then L lines in link order (agx_unit_unitigs leaves both sorted).  A large unit is formatted by several threads, each
 // taking a stretch of segments and a stretch of links; the stretches are joined in order, so the text does not depend on the thread count.
+#include <algorithm>
 #include <charconv>
 #include <cstdlib>
 #include <cstring>
@@ -46,9 +48,107 @@ unsigned gfa_threads(size_t bytes) {
     return (unsigned)std::max<size_t>(1, std::min<size_t>(by_size, usable_cpus()));
 }
 
+// the table must describe itself: offsets non-decreasing and within n_bases, a segment's node count its stretch of bases, links between segments
+bool table_ok(const agx_unitigs *t) {
+    const uint32_t ns = t->n_segs, nl = t->n_links;
+    if (ns && (!t->head_pos || !t->head_var || !t->n_nodes || !t->last_pos || !t->coverage || !t->seq_off)) return false;
+    if (nl && (!t->link_from || !t->link_to || !ns)) return false;
+    if (ns) {
+        for (uint32_t s = 0; s < ns; s++)
+            if (t->seq_off[s + 1] < t->seq_off[s] || t->seq_off[s + 1] - t->seq_off[s] != t->n_nodes[s]) return false;
+        if (t->seq_off[ns] > t->n_bases || (t->seq_off[ns] > t->seq_off[0] && !t->seq)) return false;
+    }
+    for (uint32_t i = 0; i < nl; i++) if (t->link_from[i] >= ns || t->link_to[i] >= ns) return false;
+    return true;
+}
+
+// One record's nodes laid over the segments: the open path, closed into a P line when the next node does not continue it
+struct PathWriter {
+    const agx_unitigs *t; const std::string &seg_prefix, &path_prefix; const std::vector<uint64_t> &links; std::string &o;
+    bool open = false; uint32_t rec = 0, seg = 0, rank = 0, fs = 0; uint64_t first_base = 0, nodes = 0; std::string segs;
+    PathWriter(const agx_unitigs *table, const std::string &sp, const std::string &pp, const std::vector<uint64_t> &l, std::string &out) : t(table), seg_prefix(sp), path_prefix(pp), links(l), o(out) {}
+    void close() {
+        if (!open) return;
+        o += "P\t"; o += path_prefix; put_u64(o, rec); o += '_'; put_u64(o, first_base); o += '\t'; o += segs;
+        o += "\t*\tln:i:"; put_u64(o, nodes); o += "\tfs:i:"; put_u64(o, fs); o += "\tls:i:"; put_u64(o, rank); o += '\n';
+        open = false; segs.clear();
+    }
+    void visit(uint32_t s) { if (!segs.empty()) segs += ','; put_name(segs, seg_prefix, t, s); segs += '+'; }
+    // n nodes of segment s from rank k on, the first one at base `base` of record r; cont: the first one follows the open path's last node (over an edge of the walk).
+    // false: the pair is neither (same segment, rank + 1) nor (a segment's last node -> rank 0 of the next over a link of the table)
+    bool add(uint32_t r, uint64_t base, uint32_t s, uint32_t k, uint32_t n, bool cont) {
+        if (open && cont) {
+            if (s == seg && k == rank + 1u) { rank = k + n - 1u; nodes += n; return true; }
+            if (rank + 1u != t->n_nodes[seg] || k != 0u || !std::binary_search(links.begin(), links.end(), ((uint64_t)seg << 32) | s)) return false;
+            visit(s); seg = s; rank = k + n - 1u; nodes += n;
+            return true;
+        }
+        close();
+        open = true; rec = r; first_base = base; fs = k; nodes = n; seg = s; rank = k + n - 1u; visit(s);
+        return true;
+    }
+};
+
 }  // namespace
 
 extern "C" {
+
+int agx_unitigs_paths_gfa(const agx_unitigs *t, const agx_idmap *m, const agx_walk_paths *w, int unit, char **text, size_t *len) {
+    if (!t || !m || !w || !text || !len || unit < 0) return AGX_E_ARG;
+    *text = nullptr; *len = 0;
+    if (!table_ok(t)) return AGX_E_ARG;
+    const uint32_t ns = t->n_segs, nr = m->n_runs;
+    if (nr && (!m->id_first || !m->id_last || !m->seg || !m->rank_first)) return AGX_E_ARG;
+    if (w->n_recs && (!w->rec_len || !w->st_off)) return AGX_E_ARG;
+    if (w->n_stretches && (!w->id_first || !w->id_last || !w->base_off || !w->joined || !w->n_recs)) return AGX_E_ARG;
+    // the map: runs in id order, main ids or side ids, inside their segments
+    for (uint32_t r = 0; r < nr; r++) {
+        const uint32_t a = m->id_first[r], b = m->id_last[r];
+        if (a > b || b >= m->n_ids || (a < m->n_pos) != (b < m->n_pos) || (r && m->id_last[r - 1] >= a) || m->seg[r] >= ns) return AGX_E_ARG;
+        if ((uint64_t)m->rank_first[r] + (b - a) >= t->n_nodes[m->seg[r]]) return AGX_E_ARG;
+    }
+    try {
+        std::vector<uint64_t> links(t->n_links);
+        for (uint32_t i = 0; i < t->n_links; i++) links[i] = ((uint64_t)t->link_from[i] << 32) | t->link_to[i];
+        std::sort(links.begin(), links.end());
+        const std::string seg_prefix = "u" + std::to_string(unit) + "_", path_prefix = "p" + std::to_string(unit) + "_";
+        std::string o;
+        PathWriter pw(t, seg_prefix, path_prefix, links, o);
+        if (w->n_recs && (w->st_off[0] != 0 || w->st_off[w->n_recs] != w->n_stretches)) return AGX_E_ARG;
+        for (uint32_t r = 0; r < w->n_recs; r++) {
+            if (w->st_off[r] > w->st_off[r + 1]) return AGX_E_ARG;
+            bool prev_end_mapped = false;      // the last id of the stretch in front is in the map
+            for (uint64_t i = w->st_off[r]; i < w->st_off[r + 1]; i++) {
+                const uint32_t a = w->id_first[i], b = w->id_last[i];
+                if (a > b || b >= m->n_ids || (a < m->n_pos) != (b < m->n_pos) || w->base_off[i] + ((uint64_t)b - a + 1) > w->rec_len[r]) return AGX_E_ARG;
+                const bool joined = w->joined[i] != 0;
+                if (i == w->st_off[r] ? joined : (w->base_off[i] < w->base_off[i - 1] + ((uint64_t)w->id_last[i - 1] - w->id_first[i - 1] + 1) ||
+                                                  joined != (w->base_off[i] == w->base_off[i - 1] + ((uint64_t)w->id_last[i - 1] - w->id_first[i - 1] + 1)))) return AGX_E_ARG;
+                // the runs that meet [a, b]: from the first one that ends at or behind a
+                uint32_t q = (uint32_t)(std::lower_bound(m->id_last, m->id_last + nr, a) - m->id_last);
+                uint32_t at = a;               // the next id of the stretch to be placed
+                bool cont = joined && prev_end_mapped;
+                for (; q < nr && m->id_first[q] <= b; q++) {
+                    const uint32_t lo = std::max(a, m->id_first[q]), hi = std::min(b, m->id_last[q]);
+                    if (lo != at) cont = false;               // ids without a node in the export in between
+                    if (!pw.add(r, w->base_off[i] + (lo - a), m->seg[q], m->rank_first[q] + (lo - m->id_first[q]), hi - lo + 1u, cont)) return AGX_E_ARG;
+                    at = hi + 1u; cont = true;
+                    if (hi == b) break;
+                }
+                prev_end_mapped = at == b + 1u && at != a;
+                if (!prev_end_mapped) pw.close();
+            }
+            pw.close();
+        }
+        char *out = (char *)malloc(o.size() + 1);
+        if (!out) return AGX_E_ARG;
+        memcpy(out, o.data(), o.size()); out[o.size()] = 0;
+        *text = out; *len = o.size();
+        return AGX_OK;
+    } catch (...) {
+        return AGX_E_ARG;
+    }
+}
 
 void agx_unitigs_free(agx_unitigs *t) {
     if (!t) return;
@@ -62,15 +162,7 @@ int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len) {
     if (!t || !text || !len || unit < 0) return AGX_E_ARG;
     *text = nullptr; *len = 0;
     const uint32_t ns = t->n_segs, nl = t->n_links;
-    if (ns && (!t->head_pos || !t->head_var || !t->n_nodes || !t->last_pos || !t->coverage || !t->seq_off)) return AGX_E_ARG;
-    if (nl && (!t->link_from || !t->link_to || !ns)) return AGX_E_ARG;
-    // the table must describe itself: offsets non-decreasing and within n_bases, a segment's node count its stretch of bases, links between segments
-    if (ns) {
-        for (uint32_t s = 0; s < ns; s++)
-            if (t->seq_off[s + 1] < t->seq_off[s] || t->seq_off[s + 1] - t->seq_off[s] != t->n_nodes[s]) return AGX_E_ARG;
-        if (t->seq_off[ns] > t->n_bases || (t->seq_off[ns] > t->seq_off[0] && !t->seq)) return AGX_E_ARG;
-    }
-    for (uint32_t i = 0; i < nl; i++) if (t->link_from[i] >= ns || t->link_to[i] >= ns) return AGX_E_ARG;
+    if (!table_ok(t)) return AGX_E_ARG;
     try {
         const std::string prefix = "u" + std::to_string(unit) + "_";
         const size_t bases = ns ? (size_t)(t->seq_off[ns] - t->seq_off[0]) : 0, bytes = bases + (size_t)ns * 64 + (size_t)nl * 56;

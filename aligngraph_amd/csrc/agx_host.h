@@ -152,7 +152,14 @@ struct OutBuf {
     void prefault() { for (size_t i = 0; i < cap; i += 4096) p[i] = 0; }
     void clear() { out_cache_give(p); p = nullptr; n = cap = 0; }
 };
-struct UnitOutput { OutBuf pre_extended, extended; unsigned long long n_fetched = 0; };
+// The graph stretches of the written pre-extended records (agx_unit_walk_paths, include/agx.h: agx_walk_paths): per record its bases and the end of its stretches, per
+// stretch the walk ids, where its bases begin in the record, and whether it continues the stretch in front of it over an edge
+struct WalkPaths {
+    std::vector<uint64_t> rec_len, st_end, base_off; std::vector<agx_u32> id_first, id_last; std::vector<agx_u8> joined;
+    void clear() { rec_len.clear(); st_end.clear(); base_off.clear(); id_first.clear(); id_last.clear(); joined.clear(); }
+};
+struct UnitOutput { OutBuf pre_extended, extended; unsigned long long n_fetched = 0;
+                    bool keep_paths = false, paths_ready = false; WalkPaths paths; };      // keep_paths: the walk fills `paths` (AGX_FLAG_KEEP_PATHS); else it is not touched
 
 // read-only view of a whole file (mmap)
 struct FileView {

@@ -91,6 +91,19 @@ struct agx_unitig_region_args {
     agx_u32 *rmap;                  // [pool_cap] slot -> local id.  Never cleared: slot s is in the export iff rmap[s] < kept and l_slot[rmap[s]] == s, whatever an earlier export left here
 };
 
+// Id map of a region export (agx_unit_unitigs_mapped): the walk ids of the window are WINDOW IDS i in [0, n_main + n_side) — the main ids pos_lo + i, then the side ids
+// n_pos + side_lo + (i - n_main) of the same positions (the side block is position-major, so they are one range; agx_k_idm_bounds finds it by two bisections of side_xpos).
+// Entry of a window id: (segment, rank) of its node through a_nid -> rmap / l_slot -> the (segment, rank) the region's rank kernel left per local id (R.U.indeg, R.U.osucc),
+// or NONE where the id has no node in the export.  A run starts at an id that is present and does not continue its predecessor's segment at rank + 1.
+struct agx_idmap_args {
+    const agx_u32 *a_nid, *side_xpos; agx_u32 n_pos, n_ids;      // the walk preparation's: node slot of every walk id, position of every side id
+    agx_u32 n_main, side_lo, n_side;                             // the window's ids (side_lo, n_side: read back from `bounds`)
+    agx_u32 *bounds;                                             // [2] side ids in front of pos_lo / in front of pos_lo + n_main
+    agx_u32 *flag, *foff;                                        // [n_main + n_side + 1] run-start flags (closing zero) and their exclusive scan
+    agx_u32 *scan_tmp;
+    agx_u32 *r_first, *r_last, *r_seg, *r_rank; agx_u32 run_cap; // [run_cap] the runs
+};
+
 #define AGX_SLOW_WAVES 8192u    // wavefronts of the per-hit edge pass if the occupancy query fails (normally: as many as are resident at once)
 
 extern "C" {
@@ -155,5 +168,10 @@ void agx_launch_unitig_region_count(const agx_unitig_region_args *, hipStream_t)
 void agx_launch_unitig_region_phase1(const agx_unitig_region_args *, hipStream_t);
 void agx_launch_unitig_region_phase2(const agx_unitig_region_args *, agx_u32 rounds, hipStream_t);
 void agx_launch_unitig_region_phase3(const agx_unitig_region_args *, hipStream_t);
+// id map of a region export: bounds (queued beside the region's count: the host reads them with the kept nodes), flags + scan (behind phase 2: the host reads the run count
+// with the totals), runs (beside phase 3)
+void agx_launch_idmap_bounds(const agx_unitig_region_args *, const agx_idmap_args *, hipStream_t);
+void agx_launch_idmap_flags(const agx_unitig_region_args *, const agx_idmap_args *, hipStream_t);
+void agx_launch_idmap_runs(const agx_unitig_region_args *, const agx_idmap_args *, hipStream_t);
 void agx_launch_node_sweep_huge(const agx_node_kargs *, hipStream_t);
 }

@@ -458,6 +458,64 @@ __global__ void __launch_bounds__(256) agx_k_utr_links_ovf(agx_unitig_region_arg
     if (at < A.l_off[seg + 1] && at < A.link_cap) A.l_to[at] = A.indeg[ld]; else atomicOr(A.err, 4u);
 }
 
+// ---- id map of a region export (agx_unit_unitigs_mapped, agx_kargs.h: agx_idmap_args) ------------------------------------------------------------------------
+// One thread per window id; nothing is sized by the unit.  (segment, rank) per local id are the rank kernel's (U.indeg, U.osucc), which phase 3 only reads.
+
+// side ids in front of position x: the first index of side_xpos (sorted) that holds x or more.  32 halvings at most
+__device__ __forceinline__ agx_u32 idm_lower(const agx_u32 *xs, agx_u32 n, agx_u32 x) {
+    agx_u32 lo = 0, hi = n;
+    for (agx_u32 it = 0; it < 32u && lo < hi; it++) { const agx_u32 mid = lo + (hi - lo) / 2u; if (xs[mid] < x) lo = mid + 1u; else hi = mid; }
+    return lo;
+}
+__global__ void agx_k_idm_bounds(agx_unitig_region_args R, agx_idmap_args M) {
+    if (blockIdx.x || threadIdx.x > 1u) return;
+    const agx_u32 n = M.n_ids > M.n_pos ? M.n_ids - M.n_pos : 0u;
+    M.bounds[threadIdx.x] = idm_lower(M.side_xpos, n, threadIdx.x ? R.pos_lo + R.n_win : R.pos_lo);
+}
+struct idm_entry { agx_u32 seg, rank; };
+// the entry of window id i (i < n_main + n_side); seg NONE: not in the export
+__device__ __forceinline__ idm_entry idm_entry_of(const agx_unitig_region_args &R, const agx_idmap_args &M, agx_u32 i) {
+    idm_entry e{AGX_NONE, 0u};
+    const agx_u32 a = i < M.n_main ? R.pos_lo + i : M.n_pos + M.side_lo + (i - M.n_main);
+    if (a >= M.n_ids) return e;
+    const agx_u32 slot = M.a_nid[a];
+    if (slot >= R.pool_cap) return e;                    // NONE: a main id without a node
+    const agx_u32 l = utr_local(R, slot);
+    if (l == AGX_NONE) return e;                         // dead at this coverage
+    const agx_u32 X = R.U.pos_of[l];
+    if (X != (i < M.n_main ? a : M.side_xpos[a - M.n_pos])) { atomicOr(R.U.err, 8u); return e; }      // (the id's position is its node's: main ids are positions)
+    e.seg = R.U.indeg[l]; e.rank = R.U.osucc[l];
+    return e;
+}
+__device__ __forceinline__ bool idm_continues(const idm_entry &p, const idm_entry &e) { return p.seg != AGX_NONE && p.seg == e.seg && p.rank + 1u == e.rank; }
+__global__ void __launch_bounds__(256) agx_k_idm_flags(agx_unitig_region_args R, agx_idmap_args M) {
+    const agx_u32 i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, n = M.n_main + M.n_side;
+    const bool in = i < n;
+    idm_entry e{AGX_NONE, 0u};
+    if (in) e = idm_entry_of(R, M, i);
+    idm_entry p;
+    p.seg = __shfl_up(e.seg, 1, 64); p.rank = __shfl_up(e.rank, 1, 64);
+    if (lane == 0) { p.seg = AGX_NONE; p.rank = 0u; if (in && i > 0) p = idm_entry_of(R, M, i - 1u); }
+    if (i == M.n_main) p.seg = AGX_NONE;                 // a run never holds a main id and a side id
+    if (i <= n) M.flag[i] = in && e.seg != AGX_NONE && !idm_continues(p, e) ? 1u : 0u;      // (entry n: the scan's closing zero)
+}
+__global__ void __launch_bounds__(256) agx_k_idm_runs(agx_unitig_region_args R, agx_idmap_args M) {
+    const agx_u32 i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, n = M.n_main + M.n_side;
+    const bool in = i < n;
+    idm_entry e{AGX_NONE, 0u};
+    if (in) e = idm_entry_of(R, M, i);
+    idm_entry s;
+    s.seg = __shfl_down(e.seg, 1, 64); s.rank = __shfl_down(e.rank, 1, 64);
+    if (lane == 63u) { s.seg = AGX_NONE; s.rank = 0u; if (i + 1u < n) s = idm_entry_of(R, M, i + 1u); }
+    if (!in || e.seg == AGX_NONE) return;
+    if (i + 1u >= n || i + 1u == M.n_main) s.seg = AGX_NONE;
+    const agx_u32 a = i < M.n_main ? R.pos_lo + i : M.n_pos + M.side_lo + (i - M.n_main);
+    const agx_u32 r = M.foff[i + 1u] - 1u;               // starts at or in front of i, less one (an id that is present lies behind a start)
+    if (r >= M.run_cap) { atomicOr(R.U.err, 8u); return; }
+    if (M.flag[i]) { M.r_first[r] = a; M.r_seg[r] = e.seg; M.r_rank[r] = e.rank; }
+    if (!idm_continues(e, s)) M.r_last[r] = a;
+}
+
 inline dim3 ut_grid(agx_u32 n) { return dim3((n + 255u) / 256u); }
 
 }  // namespace
@@ -465,6 +523,19 @@ inline dim3 ut_grid(agx_u32 n) { return dim3((n + 255u) / 256u); }
 extern "C" void agx_launch_unitig_region_count(const agx_unitig_region_args *R, hipStream_t st) {
     hipLaunchKernelGGL(agx_k_utr_count, ut_grid(R->n_win + 1u), dim3(256), 0, st, *R);
     agx_launch_exclusive_scan(R->cntw, R->offw, R->n_win, R->U.scan_tmp, st);
+}
+
+extern "C" void agx_launch_idmap_bounds(const agx_unitig_region_args *R, const agx_idmap_args *M, hipStream_t st) {
+    hipLaunchKernelGGL(agx_k_idm_bounds, dim3(1), dim3(64), 0, st, *R, *M);
+}
+extern "C" void agx_launch_idmap_flags(const agx_unitig_region_args *R, const agx_idmap_args *M, hipStream_t st) {
+    const agx_u32 n = M->n_main + M->n_side;
+    hipLaunchKernelGGL(agx_k_idm_flags, ut_grid(n + 1u), dim3(256), 0, st, *R, *M);
+    agx_launch_exclusive_scan(M->flag, M->foff, n, M->scan_tmp, st);
+}
+extern "C" void agx_launch_idmap_runs(const agx_unitig_region_args *R, const agx_idmap_args *M, hipStream_t st) {
+    const agx_u32 n = M->n_main + M->n_side;
+    if (n && M->run_cap) hipLaunchKernelGGL(agx_k_idm_runs, ut_grid(n), dim3(256), 0, st, *R, *M);
 }
 
 extern "C" void agx_launch_unitig_region_phase1(const agx_unitig_region_args *R, hipStream_t st) {

@@ -106,12 +106,29 @@ inline void format_pre(OutBuf &out, const PreJob &j) {
     char *w = out.grow(hl + j.total + lines); memcpy(w, hdr, hl);
     LineWriter lw(w + hl); for (size_t i = 0; i < j.n_segs; i++) lw.put(j.segs[i].p, j.segs[i].n); lw.end();
 }
+// The graph stretches of a written record (WalkPaths, agx_host.h), from its snapshot: every range that points into the downloaded `str` array is a run of consecutive walk
+// ids.  A stretch directly behind another one was reached over an edge (the walk stepped to the one alive successor, AG:2020-2046); behind a conti-mer chain it was not.
+// The chain's bases and the trailing k-mer lie in other memory and are no stretches.  Only pointers are looked at: the bases of a streamed download may not have landed yet.
+inline void note_paths(const PreJob &j, const GraphView &G, WalkPaths &P) {
+    size_t off = 0; bool prev = false;
+    for (size_t i = 0; i < j.n_segs; i++) {
+        const Seg &g = j.segs[i];
+        const bool in = g.n && g.p >= G.str && g.p < G.str + G.n_ids;
+        if (in) {
+            const agx_u32 a = (agx_u32)(g.p - G.str);
+            P.id_first.push_back(a); P.id_last.push_back(a + (agx_u32)g.n - 1u); P.base_off.push_back(off); P.joined.push_back(prev ? 1 : 0);
+        }
+        prev = in; off += g.n;
+    }
+    P.rec_len.push_back(j.total); P.st_end.push_back(P.id_first.size());
+}
 // The records the walk publishes, formatted in order by the assistant while the walk is still going.  The job array never moves (records
 // beyond its capacity are left to the walk's own thread, after the walk); `published` hands a job over, `finished` ends the assistant's loop.
 struct PreFormat {
     OutBuf &out; Assistant *assistant;
     std::vector<PreJob> jobs, late; size_t cap = 0;
     std::atomic<size_t> published{0}; std::atomic<bool> finished{false}, failed{false};
+    WalkPaths *paths = nullptr; const GraphView *graph = nullptr;      // keep every record's stretches (on the walk's thread, in the order of the records)
     PreFormat(OutBuf &o, Assistant *a, size_t capacity) : out(o), assistant(a), cap(a ? capacity : 0) {
         if (!assistant) return;
         jobs.reserve(cap);
@@ -132,6 +149,7 @@ struct PreFormat {
         });
     }
     void add(const PreJob &j) {
+        if (paths) note_paths(j, *graph, *paths);
         if (!assistant) { format_pre(out, j); return; }
         if (jobs.size() < cap) { jobs.push_back(j); published.store(jobs.size(), std::memory_order_release); }
         else late.push_back(j);
@@ -579,11 +597,12 @@ inline void walk_report(const WalkRun &r) {
 }
 
 // The whole scan by one walker (the written records are formatted by the assistant while it goes on, if there is one).
-void walk(Walker &W, OutBuf &pre_out, std::vector<Rec> &written, Arena *arena, Assistant *assistant) {
+void walk(Walker &W, OutBuf &pre_out, std::vector<Rec> &written, Arena *arena, Assistant *assistant, WalkPaths *paths) {
     if (W.G.wait_landed) W.G.wait_landed(W.G.land_ctx, W.G.n_pos, W.G.n_ids);      // (a streamed download: one walker looks everywhere, and its records are formatted as they come)
     if (W.G.wait_str) W.G.wait_str(W.G.land_ctx);
     pre_out.reserve((size_t)W.G.n_ids + W.G.n_ids / 32 + 4096);
     PreFormat pre(pre_out, assistant, (size_t)W.G.n_pos / 256 + 65536);
+    pre.paths = paths; pre.graph = &W.G;
     WalkRun run(W, arena, written, &pre);
     run.go(W.G.n_pos);
     pre.finish();
@@ -630,7 +649,7 @@ struct SpecWalker {
 };
 
 // false: not split (too small, no assistant): the caller walks the usual way
-bool walk_split(Walker &WA, const UnitView &V, const GraphView &G, OutBuf &pre_out, std::vector<Rec> &written, Arena *arena, Arena *const *more_arenas, Assistant *assistant) {
+bool walk_split(Walker &WA, const UnitView &V, const GraphView &G, OutBuf &pre_out, std::vector<Rec> &written, Arena *arena, Arena *const *more_arenas, Assistant *assistant, WalkPaths *paths) {
     const agx_u32 min_ref = getenv("AGX_WALK_SPLIT_MIN") ? (agx_u32)strtoul(getenv("AGX_WALK_SPLIT_MIN"), nullptr, 10) : 4000000u;
     // The warm-up in front of a walker's stretch must hold every walk that can reach into the stretch: walks are local, and what reaches furthest is a conti-mer chain, which lands
     // where its contig's placement ends.  So: three times the longest reach of a chain in this unit (+ a margin), 100 k to 400 k positions (r03/r04: 400 k whatever the unit; a
@@ -842,6 +861,7 @@ bool walk_split(Walker &WA, const UnitView &V, const GraphView &G, OutBuf &pre_o
     all.insert(all.end(), A.jobs.begin(), A.jobs.begin() + (long)a_first);      // A's in front of the first meeting point, the stretches that stand, A's behind them
     for (int i = 1; i <= stood; i++) all.insert(all.end(), B[(size_t)i - 1].R->jobs.begin(), B[(size_t)i - 1].R->jobs.end());
     all.insert(all.end(), A.jobs.begin() + (long)a_first, A.jobs.end());
+    if (paths) for (const PreJob &j : all) note_paths(j, G, *paths);      // (every walker's view shares the first one's bases: only the visited bytes are a walker's own)
     std::vector<size_t> place(all.size() + 1, 0);
     auto header_len = [](const PreJob &j) { size_t n = 1 + 9 * 2 + 2; for (int i = 0; i < 10; i++) { agx_u32 v = j.f[i]; do { n++; v /= 10u; } while (v); } return n; };
     for (size_t i = 0; i < all.size(); i++) place[i + 1] = place[i] + header_len(all[i]) + all[i].total + (all[i].total + 59) / 60;
@@ -1041,7 +1061,8 @@ void walk_join_scaffold(const UnitView &V, const GraphView &G, UnitOutput &out, 
     for (int i = 0; i < GraphView::MAX_WALKERS - 1; i++) { others.emplace_back(new std::pmr::monotonic_buffer_resource((size_t)1 << 20)); more_arenas[i] = others.back().get(); }
     std::vector<Rec> recs; recs.reserve((size_t)G.n_pos / 1024 + 1024);
     double t0 = now();
-    if (!walk_split(W, V, G, out.pre_extended, recs, &arena, more_arenas, assistant)) walk(W, out.pre_extended, recs, &arena, assistant);
+    WalkPaths *paths = out.keep_paths ? &out.paths : nullptr;
+    if (!walk_split(W, V, G, out.pre_extended, recs, &arena, more_arenas, assistant, paths)) walk(W, out.pre_extended, recs, &arena, assistant, paths);
     double t1 = now();
     join(recs);
     double t2 = now();

@@ -64,6 +64,9 @@ typedef struct {
                                      staged input arrays are dead, and the download lands in that pinned memory instead of mapping and pinning 5 bytes per
                                      position of fresh memory per unit.  Another upload needs the inputs handed over again (agx_unit_load_files / push_pairs) */
 
+#define AGX_FLAG_KEEP_PATHS 16u /* agx_unit_finish keeps the graph stretches of every written pre-extended record for agx_unit_walk_paths, and (with AGX_FLAG_KEEP_COUNTS) the
+                                     unit's block reserves the scratch of agx_unit_unitigs_mapped.  The outputs of a finish are the same bytes with and without it */
+
 /* ---- packed inputs -------------------------------------------------------------------------------- */
 
 /* n read bases from read index q sit on reference offsets t, t+1, ...  (Segment, AG:44-49) */
@@ -150,6 +153,27 @@ typedef struct {
     char *seq;              /* [n_bases] one base per node: the consensus, or the reference base where the node has no votes */
     uint32_t *link_from, *link_to;   /* [n_links] segment indexes */
 } agx_unitigs;
+
+/* The id map of an export (agx_unit_unitigs_mapped): which walk ids have their node in the export, and where.  Runs are sorted by id_first; walk id a lies in run r iff
+ * id_first[r] <= a <= id_last[r], and its node is then node number rank_first[r] + (a - id_first[r]) of segment seg[r].  Runs are maximal (no two neighbours could be merged)
+ * and never hold both a main id (< n_pos) and a side id.  Ids without a node, and ids whose node lies outside the window or is dead at the export's coverage, are in no run.
+ * malloc'd; free with agx_idmap_free. */
+typedef struct {
+    uint32_t n_runs, n_pos, n_ids;      /* n_pos, n_ids: the unit's positions and walk ids */
+    uint32_t *id_first, *id_last, *seg, *rank_first;   /* [n_runs] */
+} agx_idmap;
+
+/* The graph stretches of the records of pre_extended (extdContigs1, AG:1954-2204; the records it writes, AG:2176-2189), kept by a finish of a unit created with
+ * AGX_FLAG_KEEP_PATHS.  Record r is the r-th record of pre_extended (header number seqID = r); its stretches are st_off[r] .. st_off[r + 1).  A stretch is a run of
+ * consecutive walk ids id_first .. id_last (inclusive) whose bases are the record's bases [base_off, base_off + id_last - id_first + 1).  joined = 1 iff the stretch starts
+ * exactly where the previous stretch of the same record ended: the walk then went from the previous id_last to this id_first over an edge; 0 for a record's first
+ * stretch and behind a conti-mer chain.  The bases of chains and the record's trailing k-mer belong to no stretch.  malloc'd; free with agx_walk_paths_free. */
+typedef struct {
+    uint32_t n_recs; uint64_t n_stretches;
+    uint64_t *rec_len;         /* [n_recs] bases of each record */
+    uint64_t *st_off;          /* [n_recs + 1] */
+    uint32_t *id_first, *id_last; uint64_t *base_off; uint8_t *joined;   /* [n_stretches] */
+} agx_walk_paths;
 
 /* The walk graph: what the walk preparation (csrc/agx_core.h "walk preparation") leaves on the device and the download carries to the host walk (GraphView, csrc/agx_host.h).
  * Walk ids [0, n_pos) are the first alive variant of each position, [n_pos, n_ids) the further ones.  malloc'd; free with agx_walk_graph_free. */
@@ -282,9 +306,23 @@ int agx_unit_unitigs(agx_unit *u, agx_unitigs *t);
  * The node table keeps the edges of the nodes the build pruned, so every min_coverage is served, also one below the build's coverage (0: nothing is pruned).
  * Preconditions and error codes of agx_unit_unitigs; pos_lo > pos_hi or pos_hi > the unit's positions: AGX_E_ARG.  pos_lo == pos_hi gives no segments. */
 int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t);
+/* The region export plus the id map of what it exported (agx_idmap above): the join between the walk's ids and the export's segments, made on the device, where the per-node
+ * arrays live.  Preconditions of agx_unit_unitigs_region, and the unit was created with AGX_FLAG_KEEP_PATHS as well (AGX_E_ARG otherwise).  t is what
+ * agx_unit_unitigs_region gives for the same arguments. */
+int agx_unit_unitigs_mapped(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, agx_idmap *m);
+void agx_idmap_free(agx_idmap *m);
+/* The stretches the last agx_unit_finish kept (AGX_FLAG_KEEP_PATHS).  Valid after a finish, also of trimmed and one-shot units, until the next finish, upload or release;
+ * AGX_E_ARG without the flag or before a finish.  The caller gets copies. */
+int agx_unit_walk_paths(agx_unit *u, agx_walk_paths *w);
+void agx_walk_paths_free(agx_walk_paths *w);
 void agx_unitigs_free(agx_unitigs *t);
 /* Host only: the S and L lines of GFA 1.0 for unit `unit` (no header line), as DESIGN.md §11 defines them; *text is malloc'd, free it with agx_text_free. */
 int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len);
+/* Host only: the P lines of GFA 1.0 that lay the records of w over the segments of t (m: the id map of the same export), as DESIGN.md §11 "Paths" defines them:
+ *   P\tp<unit>_<record>_<base_off>\t<seg>+,<seg>+,...\t*\tln:i:<nodes>\tfs:i:<rank of the first node in the first segment>\tls:i:<rank of the last node in the last segment>
+ * one line per maximal piece of a record's node sequence that stays on edges and inside the map, ordered by (record, first base).  AGX_E_ARG where the three tables do not
+ * agree: a consecutive pair of nodes must be (same segment, rank + 1) or (a segment's last node -> rank 0 of the next, with that link in t). */
+int agx_unitigs_paths_gfa(const agx_unitigs *t, const agx_idmap *m, const agx_walk_paths *w, int unit, char **text, size_t *len);
 void agx_text_free(char *text);
 
 /* The five-call seam in one call.  write_files != 0 also writes the three files under tmp_dir like the reference does. */
