@@ -438,17 +438,21 @@ class Unit:
         finally:
             lib().agx_front_free(ctypes.byref(f))
 
-    def _export(self, t, region, min_coverage):
-        """agx_unit_unitigs, or agx_unit_unitigs_region when a window or a threshold is given (region alone: the unit's own coverage; min_coverage alone: every position)."""
-        if region is None and min_coverage is None:
-            self._check(lib().agx_unit_unitigs(self._h, ctypes.byref(t)))
-            return
+    def _window(self, region, min_coverage):
+        """(lo, hi, coverage) of a region export: every position without a region, the unit's own coverage without a threshold."""
         lo, hi = region if region is not None else (0, self.stats()["n_pos"])
         cov = self.params.coverage if min_coverage is None else min_coverage
         for v in (lo, hi, cov):
             if not 0 <= int(v) <= 0xFFFFFFFF:
                 raise AgxError(AGX_E_ARG, "unitigs: region bounds and min_coverage are unsigned 32-bit numbers")
-        self._check(lib().agx_unit_unitigs_region(self._h, int(lo), int(hi), int(cov), ctypes.byref(t)))
+        return int(lo), int(hi), int(cov)
+
+    def _export(self, t, region, min_coverage):
+        """agx_unit_unitigs, or agx_unit_unitigs_region when a window or a threshold is given (region alone: the unit's own coverage; min_coverage alone: every position)."""
+        if region is None and min_coverage is None:
+            self._check(lib().agx_unit_unitigs(self._h, ctypes.byref(t)))
+            return
+        self._check(lib().agx_unit_unitigs_region(self._h, *self._window(region, min_coverage), ctypes.byref(t)))
 
     def unitigs(self, region=None, min_coverage=None, id_map=False):
         """The unit's pruned graph compacted into unitigs on the device (agx_unit_unitigs; needs keep_counts): numpy arrays per segment and link, the
@@ -463,13 +467,8 @@ class Unit:
                 return _unitigs_arrays(t)
             finally:
                 lib().agx_unitigs_free(ctypes.byref(t))
-        lo, hi = region if region is not None else (0, self.stats()["n_pos"])
-        cov = self.params.coverage if min_coverage is None else min_coverage
-        for v in (lo, hi, cov):
-            if not 0 <= int(v) <= 0xFFFFFFFF:
-                raise AgxError(AGX_E_ARG, "unitigs: region bounds and min_coverage are unsigned 32-bit numbers")
         m = IdMap()
-        self._check(lib().agx_unit_unitigs_mapped(self._h, int(lo), int(hi), int(cov), ctypes.byref(t), ctypes.byref(m)))
+        self._check(lib().agx_unit_unitigs_mapped(self._h, *self._window(region, min_coverage), ctypes.byref(t), ctypes.byref(m)))
         try:
             out = _unitigs_arrays(t)
             out["id_map"] = _idmap_arrays(m)

@@ -960,12 +960,20 @@ template <class U> void sparse_bufs(U *u, agx_u32 cap, Take &t) { t.note(u->sp_c
 
 void do_release(agx_unit *u);
 
+// Carves the export layouts below out of one buffer: every array at the next multiple of 256 bytes, an empty one as one element; base == nullptr: only the size
+struct Carve {
+    char *base; size_t at = 0;
+    template <class T> void operator()(T *&p, size_t n) { at = (at + 255) & ~(size_t)255; p = base ? (T *)(base + at) : nullptr; at += (n ? n : 1) * sizeof(T); }
+    size_t bytes() const { return at + 256; }
+};
+// words of block sums that agx_launch_exclusive_scan's two levels take for n entries at `block` entries per workgroup (the callers add their slack)
+inline size_t scan_words(size_t n, size_t block) { return 2 * ((n + block - 1) / block + 1) + 2 * ((n + block * block - 1) / (block * block) + 1); }
+
 // The unitig export's scratch (agx_unit_unitigs, agx_unitig.hip) as one buffer carved in this order; base == nullptr: only the size.  Sized for the worst case — every
 // node slot a piece and a segment — since a unit that keeps counts has it reserved with its block (plan_capacities): an export never asks the device for memory.
 // Phase 3 reuses what phases 1-2 are done with: the links lie over pos_of | outs | oout | p_len | p_next, the bases over succ.
 size_t unitig_layout(size_t cap, size_t n_pos, size_t n_ovf, char *base, agx_unitig_args *A, agx_u32 **words) {
-    size_t at = 0;
-    auto take = [&](auto *&p, size_t n) { at = (at + 255) & ~(size_t)255; p = base ? (std::remove_reference_t<decltype(*p)> *)(base + at) : nullptr; at += (n ? n : 1) * sizeof(*p); };
+    Carve take{base};
     agx_unitig_args T{}; agx_unitig_args &X = A ? *A : T; agx_u32 *w = nullptr, *R = nullptr;
     size_t hash_n = 64; while (hash_n < 2 * n_ovf) hash_n *= 2;
     const size_t nwin = (cap + 63) / 64, nmax = std::max(std::max(cap, n_pos), nwin) + 1;
@@ -976,14 +984,14 @@ size_t unitig_layout(size_t cap, size_t n_pos, size_t n_ovf, char *base, agx_uni
     take(X.p_seg, cap); take(X.hcnt, n_pos + 1); take(X.hoff, n_pos + 1);
     take(X.s_len, cap + 1); take(X.s_links, cap + 1); take(X.s_hpos, cap); take(X.s_hvar, cap); take(X.s_last, cap); take(X.s_cov, cap);
     take(X.s_off, cap + 1); take(X.l_off, cap + 1); take(X.l_cur, cap + 1);
-    take(X.scan_tmp, 2 * ((nmax + 4095) / 4096 + 1) + 2 * ((nmax + 4096ull * 4096 - 1) / (4096ull * 4096) + 1) + 8);
+    take(X.scan_tmp, scan_words(nmax, 4096) + 8);
     if (base) {
         X.pos_of = R; X.outs = R + cap; X.oout = R + 2 * cap; X.p_len = R + 3 * cap; X.p_next = R + 4 * cap;
         X.l_to = R; X.link_cap = (agx_u32)std::min<size_t>(5 * cap + n_ovf, 0xFFFFFFFFull); X.seq = (char *)X.succ; X.seq_cap = (agx_u32)std::min<size_t>(4 * cap, 0xFFFFFFFFull);
         X.hash_mask = (agx_u32)(hash_n - 1);
         if (words) *words = w;
     }
-    return at + 256;
+    return take.bytes();
 }
 
 // The scratch of a region export (agx_unit_unitigs_region) carved from the front of the same buffer: `kept` nodes of `n_win` positions.  What must be in place before the
@@ -993,13 +1001,12 @@ size_t unitig_layout(size_t cap, size_t n_pos, size_t n_ovf, char *base, agx_uni
 // larger of the two sizes, which then comes out of the regrowth room of the unit's own block (regrow_slack: 6.4 MB at least), never from the device.  Phase 3 reuses what phases 1-2 are done with: the links lie over outs | oout | p_len | p_next, the bases over succ, the scans of segment lengths and
 // link counts and the link cursors over the pointer jumping's arrays.
 size_t unitig_region_layout(size_t cap, size_t n_win, size_t kept, size_t n_ovf, char *base, agx_unitig_region_args *A, agx_u32 **words) {
-    size_t at = 0;
-    auto take = [&](auto *&p, size_t n) { at = (at + 255) & ~(size_t)255; p = base ? (std::remove_reference_t<decltype(*p)> *)(base + at) : nullptr; at += (n ? n : 1) * sizeof(*p); };
+    Carve take{base};
     agx_unitig_region_args T{}; agx_unitig_region_args &R = A ? *A : T; agx_unitig_args &X = R.U; agx_u32 *w = nullptr, *L = nullptr;
     size_t hash_n = 64; while (hash_n < 2 * n_ovf) hash_n *= 2;
     const size_t ngrp = (kept + 63) / 64, nmax = std::max(n_win, cap) + 1;
     take(w, 8); take(R.rmap, cap); take(R.cntw, n_win + 1); take(R.offw, n_win + 1);
-    take(X.scan_tmp, 2 * ((nmax + 4095) / 4096 + 1) + 2 * ((nmax + 4096ull * 4096 - 1) / (4096ull * 4096) + 1) + 8);
+    take(X.scan_tmp, scan_words(nmax, 4096) + 8);
     take(X.ovf_hash, hash_n); take(X.ovf_first, n_ovf);
     take(R.l_slot, kept); take(X.pos_of, kept); take(L, 4 * kept + n_ovf);
     take(X.indeg, kept); take(X.succ, kept); take(X.osucc, kept); take(X.nxt, kept); take(X.haspred, kept);
@@ -1014,19 +1021,18 @@ size_t unitig_region_layout(size_t cap, size_t n_win, size_t kept, size_t n_ovf,
         X.hash_mask = (agx_u32)(hash_n - 1);
         if (words) *words = w;
     }
-    return at + 256;
+    return take.bytes();
 }
 
 // The scratch of an export's id map (agx_unit_unitigs_mapped, agx_unitig.hip: agx_k_idm_*), behind the export's own in the same buffer: `ids` window ids (the window's main
 // ids and the side ids of its positions), `runs` runs at most (a run holds a kept node at least).  Two words per window id and four per run.
 size_t idmap_layout(size_t ids, size_t runs, char *base, agx_idmap_args *A) {
-    size_t at = 0;
-    auto take = [&](auto *&p, size_t n) { at = (at + 255) & ~(size_t)255; p = base ? (std::remove_reference_t<decltype(*p)> *)(base + at) : nullptr; at += (n ? n : 1) * sizeof(*p); };
+    Carve take{base};
     agx_idmap_args T{}; agx_idmap_args &M = A ? *A : T;
     take(M.flag, ids + 1); take(M.foff, ids + 1);
-    take(M.scan_tmp, 2 * ((ids + 1 + 1023) / 1024 + 1) + 2 * ((ids + 1 + 1024ull * 1024 - 1) / (1024ull * 1024) + 1) + 16);
+    take(M.scan_tmp, scan_words(ids + 1, 1024) + 16);
     take(M.r_first, runs); take(M.r_last, runs); take(M.r_seg, runs); take(M.r_rank, runs);
-    return at + 256;
+    return take.bytes();
 }
 inline bool keeps_paths(const agx_unit *u) { return (u->prm.flags & (AGX_FLAG_KEEP_PATHS | AGX_FLAG_KEEP_COUNTS)) == (AGX_FLAG_KEEP_PATHS | AGX_FLAG_KEEP_COUNTS); }
 // The export buffer of a unit that keeps paths: every export of such a unit takes the same size — the larger of the two export layouts at their worst, and behind it (at `map_at`)
@@ -2079,74 +2085,136 @@ void agx_front_free(agx_front *f) {
     memset(f, 0, sizeof *f);
 }
 
-// Unitig export: the kernels of agx_unitig.hip on a stream of the export's own, scratch from an arena of its own (given back to the device's
-// caches on return).  Three host round trips: the piece count (the pointer jumping's rounds and arrays), the totals (segments, bases, links), the download.
+// Unitig export: the kernels of agx_unitig.hip on a stream of the export's own, scratch from the buffer the unit's block reserves for it (d_ut).  The whole
+// export (agx_unit_unitigs) and the region export (agx_unit_unitigs_region, agx_unit_unitigs_mapped) each get as far as their piece count in their own way, over slots or
+// over the window's local ids; from there to the table in the caller's memory they are one body, export_body.
+
+// what every export refuses (map: the call also makes an id map)
+static void export_check(const agx_unit *u, bool map) {
+    if (!(u->prm.flags & AGX_FLAG_KEEP_COUNTS)) throw Error{E_ARG, "unitigs: the unit was created without AGX_FLAG_KEEP_COUNTS (the segments' coverage needs the counts)"};
+    if (!u->built || u->trimmed) throw Error{E_ARG, "unitigs: the unit is not built (call agx_unit_build; not after agx_unit_trim or agx_unit_release)"};
+    if ((u->prm.flags & AGX_FLAG_ONE_SHOT) && (u->consumed || u->downloaded)) throw Error{E_ARG, "unitigs: a one-shot unit exports before its download or finish"};
+    if (map && !(u->prm.flags & AGX_FLAG_KEEP_PATHS)) throw Error{E_ARG, "unitigs: the unit was created without AGX_FLAG_KEEP_PATHS (the id map's scratch is reserved with the unit's block)"};
+}
+
+// What an export holds while it runs: the unit's device with its build finished, then (open) the scratch buffer and a stream of the export's own
+struct Export {
+    agx_unit *u; const agx_u32 n_pos, cap, n_ovf; hipStream_t s = nullptr; size_t map_at = 0;      // map_at: where the id map's scratch begins (a unit that keeps paths)
+    explicit Export(agx_unit *unit) : u(unit), n_pos((agx_u32)unit->V.n_pos), cap(unit->pool_cap), n_ovf(std::min(unit->n_ovf, unit->ovf_cap)) {
+        HIP_OK(hipSetDevice(u->prm.device));
+        HIP_OK(wait_event(u->ev_built));
+    }
+    Export(const Export &) = delete;
+    ~Export() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }      // (the export's work is done before the call returns, also on an error)
+    // own: what this export's layout takes — out of the room the upload reserved for it; a unit whose pool or overflow list grew takes the difference.  A unit that keeps
+    // paths takes mapped_scratch whatever the export
+    void open(size_t own) {
+        u->d_ut.alloc(u->arena, keeps_paths(u) ? mapped_scratch(cap, n_pos, u->n_nodes, u->n_ids, n_ovf, &map_at) : own);
+        u->stats.device_bytes = u->arena.capacity();
+        HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    }
+    void fill(void *p, int v, size_t b) const { HIP_OK(hipMemsetAsync(p, v, b ? b : 1, s)); }
+    void read(void *host, const void *dev, size_t b) const { HIP_OK(hipMemcpyAsync(host, dev, b, hipMemcpyDeviceToHost, s)); }
+    void sync() const { HIP_OK(hipStreamSynchronize(s)); }
+};
+
+// the id map of a mapped export: the caller's table, the kernels' arguments and the window's ids
+struct MapJob { agx_idmap *m; agx_idmap_args M{}; agx_u32 n_wids = 0; };
+
+// From "np pieces are cut" to the table in the caller's memory: phase 2 and the totals (a round trip), phase 3 and the download (another).  A is the export's view with its
+// error word at `words`; R: the region export A is the local view of (nullptr: the whole export, whose head counts per position are cleared here); max_nodes bounds the bases;
+// J: also the export's id map — flags read with the totals, runs beside phase 3, four more copies
+static void export_body(const Export &E, agx_unitig_args &A, const agx_unitig_region_args *R, agx_u32 *words, agx_u32 np, agx_u32 max_nodes, agx_unitigs *t, MapJob *J) {
+    A.piece_cap = np;
+    agx_u32 rounds = 1; while (rounds < 32 && (1ull << (rounds - 1)) < np) rounds++;      // ceil(log2 np) + 1
+    E.fill(A.p_seg, 0xFF, (size_t)np * 4);
+    if (!R) E.fill(A.hcnt, 0, ((size_t)A.n_pos + 1) * 4);
+    E.fill(A.s_len, 0, ((size_t)np + 1) * 4); E.fill(A.s_links, 0, ((size_t)np + 1) * 4); E.fill(A.s_cov, 0, (size_t)np * 8);
+    agx_launch_unitig_phase2(&A, R, rounds, E.s);
+    E.fill(A.l_cur, 0, ((size_t)np + 1) * 4);          // (the region's lie over the pointer jumping's second ancestor array: behind the rank kernel)
+    agx_launch_unitig_totals(&A, words + 4, E.s);
+    agx_u32 h[4] = {0, 0, 0, 0}, nr = 0;
+    if (J) {      // run starts and their scan, on the (segment, rank) the rank kernel left per local id; the run count comes with the totals
+        agx_launch_idmap_flags(R, &J->M, E.s);
+        E.read(&nr, J->M.foff + J->n_wids, 4);
+    }
+    E.read(h, words + 4, 16); E.sync();
+    if (h[3]) throw Error{E_DEVICE, "unitigs: the unitig ranks are inconsistent (error word " + std::to_string(h[3]) + ")"};
+    const agx_u32 ns = h[0], nb = h[1], nl = h[2];
+    if (ns > np || nb > max_nodes || nb > A.seq_cap || nl > A.link_cap) throw Error{E_DEVICE, "unitigs: segment totals out of range"};
+    A.seq_cap = nb; A.link_cap = nl;
+    if (J) {
+        if (nr > J->M.run_cap) throw Error{E_DEVICE, "unitigs: more runs in the id map than nodes in the region"};
+        J->M.run_cap = nr;
+    }
+    agx_launch_unitig_phase3(&A, R, E.s);
+    if (J) agx_launch_idmap_runs(R, &J->M, E.s);
+    // the compact arrays (per-node arrays never leave the device) into pinned memory, then into the caller's malloc'd table
+    const size_t o_hp = 0, o_hv = o_hp + 4 * (size_t)ns, o_ln = o_hv + 4 * (size_t)ns, o_lp = o_ln + 4 * (size_t)ns, o_cov = (o_lp + 4 * (size_t)ns + 7) & ~(size_t)7,
+                 o_so = o_cov + 8 * (size_t)ns, o_lo = o_so + 4 * ((size_t)ns + 1), o_lt = o_lo + 4 * ((size_t)ns + 1), o_seq = o_lt + 4 * (size_t)nl,
+                 o_run = (o_seq + nb + 3) & ~(size_t)3, o_end = o_run + 16 * (size_t)nr;      // (runs: only with an id map)
+    PBuf<char> pin; pin.alloc(o_end + 8);
+    auto down = [&](size_t o, const void *src, size_t b) { if (b) E.read(pin.p + o, src, b); };
+    down(o_hp, A.s_hpos, 4 * (size_t)ns); down(o_hv, A.s_hvar, 4 * (size_t)ns); down(o_ln, A.s_len, 4 * (size_t)ns); down(o_lp, A.s_last, 4 * (size_t)ns);
+    down(o_cov, A.s_cov, 8 * (size_t)ns); down(o_so, A.s_off, 4 * ((size_t)ns + 1)); down(o_lo, A.l_off, 4 * ((size_t)ns + 1)); down(o_lt, A.l_to, 4 * (size_t)nl); down(o_seq, A.seq, nb);
+    if (J) { down(o_run, J->M.r_first, 4 * (size_t)nr); down(o_run + 4 * (size_t)nr, J->M.r_last, 4 * (size_t)nr); down(o_run + 8 * (size_t)nr, J->M.r_seg, 4 * (size_t)nr); down(o_run + 12 * (size_t)nr, J->M.r_rank, 4 * (size_t)nr); }
+    E.read(h, words, 4); E.sync();
+    if (h[0]) throw Error{E_DEVICE, "unitigs: the segments are inconsistent (error word " + std::to_string(h[0]) + ")"};
+    t->n_segs = ns; t->n_links = nl; t->n_bases = nb;
+    t->head_pos = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->head_var = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->n_nodes = (uint32_t *)malloc(4 * ((size_t)ns + 1));
+    t->last_pos = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->coverage = (uint64_t *)malloc(8 * ((size_t)ns + 1)); t->seq_off = (uint64_t *)malloc(8 * ((size_t)ns + 1));
+    t->seq = (char *)malloc((size_t)nb + 1); t->link_from = (uint32_t *)malloc(4 * ((size_t)nl + 1)); t->link_to = (uint32_t *)malloc(4 * ((size_t)nl + 1));
+    if (!t->head_pos || !t->head_var || !t->n_nodes || !t->last_pos || !t->coverage || !t->seq_off || !t->seq || !t->link_from || !t->link_to) throw Error{E_ARG, "out of host memory"};
+    memcpy(t->head_pos, pin.p + o_hp, 4 * (size_t)ns); memcpy(t->head_var, pin.p + o_hv, 4 * (size_t)ns); memcpy(t->n_nodes, pin.p + o_ln, 4 * (size_t)ns);
+    memcpy(t->last_pos, pin.p + o_lp, 4 * (size_t)ns); memcpy(t->coverage, pin.p + o_cov, 8 * (size_t)ns); memcpy(t->link_to, pin.p + o_lt, 4 * (size_t)nl); memcpy(t->seq, pin.p + o_seq, nb);
+    t->seq[nb] = 0;
+    const agx_u32 *so = (const agx_u32 *)(pin.p + o_so), *lo = (const agx_u32 *)(pin.p + o_lo);
+    for (size_t g = 0; g <= ns; g++) t->seq_off[g] = so[g];      // (a unit's nodes are counted in 32 bits, so are its bases)
+    for (size_t g = 0; g < ns; g++) {
+        if (lo[g] > lo[g + 1] || lo[g + 1] > nl) throw Error{E_DEVICE, "unitigs: link offsets out of range"};
+        for (agx_u32 i = lo[g]; i < lo[g + 1]; i++) t->link_from[i] = (uint32_t)g;
+    }
+    if (J && nr) {
+        agx_idmap *m = J->m;
+        m->id_first = (uint32_t *)malloc(4 * (size_t)nr); m->id_last = (uint32_t *)malloc(4 * (size_t)nr); m->seg = (uint32_t *)malloc(4 * (size_t)nr); m->rank_first = (uint32_t *)malloc(4 * (size_t)nr);
+        if (!m->id_first || !m->id_last || !m->seg || !m->rank_first) throw Error{E_ARG, "out of host memory"};
+        memcpy(m->id_first, pin.p + o_run, 4 * (size_t)nr); memcpy(m->id_last, pin.p + o_run + 4 * (size_t)nr, 4 * (size_t)nr);
+        memcpy(m->seg, pin.p + o_run + 8 * (size_t)nr, 4 * (size_t)nr); memcpy(m->rank_first, pin.p + o_run + 12 * (size_t)nr, 4 * (size_t)nr);
+        m->n_runs = nr;
+        // what the kernels wrote must be a map: runs in id order, inside one block of ids, inside their segments
+        for (agx_u32 r = 0; r < nr; r++) {
+            const uint32_t a = m->id_first[r], b = m->id_last[r];
+            if (a > b || b >= E.u->n_ids || (a < E.n_pos) != (b < E.n_pos) || (r && m->id_last[r - 1] >= a) || m->seg[r] >= ns ||
+                (uint64_t)m->rank_first[r] + (b - a) >= t->n_nodes[m->seg[r]]) throw Error{E_DEVICE, "unitigs: the id map is inconsistent (run " + std::to_string(r) + ")"};
+        }
+    }
+}
+
+// The whole export.  Three host round trips: the piece count (the pointer jumping's rounds and arrays), the totals (segments, bases, links), the download.
 int agx_unit_unitigs(agx_unit *u, agx_unitigs *t) {
     if (!u || !t) return AGX_E_ARG;
     memset(t, 0, sizeof *t);
     const int rc = guarded(u, [&] {
-        if (!(u->prm.flags & AGX_FLAG_KEEP_COUNTS)) throw Error{E_ARG, "unitigs: the unit was created without AGX_FLAG_KEEP_COUNTS (the segments' coverage needs the counts)"};
-        if (!u->built || u->trimmed) throw Error{E_ARG, "unitigs: the unit is not built (call agx_unit_build; not after agx_unit_trim or agx_unit_release)"};
-        if ((u->prm.flags & AGX_FLAG_ONE_SHOT) && (u->consumed || u->downloaded)) throw Error{E_ARG, "unitigs: a one-shot unit exports before its download or finish"};
-        HIP_OK(hipSetDevice(u->prm.device));
-        HIP_OK(wait_event(u->ev_built));
-        const agx_u32 n_pos = (agx_u32)u->V.n_pos, cap = u->pool_cap, n_ovf = std::min(u->n_ovf, u->ovf_cap);
+        export_check(u, false);
+        Export E(u);
+        const agx_u32 n_pos = E.n_pos, cap = E.cap, n_ovf = E.n_ovf;
         if (!n_pos || !cap || !u->n_nodes) return;
-        const size_t bytes = unitig_layout(cap, n_pos, n_ovf, nullptr, nullptr, nullptr);
-        u->d_ut.alloc(u->arena, keeps_paths(u) ? mapped_scratch(cap, n_pos, u->n_nodes, u->n_ids, n_ovf, nullptr) : bytes);      // (from the room the upload reserved for it; a unit whose pool or overflow list grew takes the difference)
-        u->stats.device_bytes = u->arena.capacity();
-        struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;      // (the export's work is done before the call returns, also on an error)
-        HIP_OK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-        auto fill = [&](void *p, int v, size_t b) { HIP_OK(hipMemsetAsync(p, v, b ? b : 1, st.s)); };
+        E.open(unitig_layout(cap, n_pos, n_ovf, nullptr, nullptr, nullptr));
         agx_unitig_args A{}; agx_u32 *words = nullptr;
         unitig_layout(cap, n_pos, n_ovf, u->d_ut.p, &A, &words);
         A.node_start = u->d_node_start.p; A.node_cnt = u->d_node_cnt.p; A.n_flags = u->d_flags.p; A.n_base = u->d_base.p; A.n_next = u->d_next.p;
         A.n_counts = u->d_counts.p; A.ref = u->d_ref.p; A.ovf = u->d_ovf.p; A.n_ovf = n_ovf; A.n_pos = n_pos; A.pool_cap = cap; A.piece_cap = cap; A.err = words;
         const size_t nwin = ((size_t)cap + 63) / 64;
-        fill(words, 0, 32); fill(A.pos_of, 0xFF, (size_t)cap * 4); fill(A.indeg, 0, (size_t)cap * 4); fill(A.oout, 0, (size_t)cap * 4); fill(A.haspred, 0, cap);
-        fill(A.ovf_hash, 0xFF, ((size_t)A.hash_mask + 1) * 8); fill(A.wcnt, 0, (nwin + 1) * 4);
-        agx_launch_unitig_phase1(&A, st.s);
-        agx_u32 h[4] = {0, 0, 0, 0};
-        HIP_OK(hipMemcpyAsync(h, words, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipMemcpyAsync(h + 1, A.woff + nwin, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
+        E.fill(words, 0, 32); E.fill(A.pos_of, 0xFF, (size_t)cap * 4); E.fill(A.indeg, 0, (size_t)cap * 4); E.fill(A.oout, 0, (size_t)cap * 4); E.fill(A.haspred, 0, cap);
+        E.fill(A.ovf_hash, 0xFF, ((size_t)A.hash_mask + 1) * 8); E.fill(A.wcnt, 0, (nwin + 1) * 4);
+        agx_launch_unitig_phase1(&A, E.s);
+        agx_u32 h[2] = {0, 0};
+        E.read(h, words, 4); E.read(h + 1, A.woff + nwin, 4); E.sync();
         if (h[0] & 1u) throw Error{E_DEVICE, "unitigs: an edge of the node table does not lead to a later position (the graph is not a DAG)"};
         if (h[0]) throw Error{E_DEVICE, "unitigs: the node table is inconsistent (error word " + std::to_string(h[0]) + ")"};
         const agx_u32 np = h[1];
         if (np > cap) throw Error{E_DEVICE, "unitigs: more pieces than node slots"};
-        A.piece_cap = np;
-        agx_u32 rounds = 1; while (rounds < 32 && (1ull << (rounds - 1)) < np) rounds++;      // ceil(log2 np) + 1
-        fill(A.p_seg, 0xFF, (size_t)np * 4); fill(A.hcnt, 0, ((size_t)n_pos + 1) * 4);
-        fill(A.s_len, 0, ((size_t)np + 1) * 4); fill(A.s_links, 0, ((size_t)np + 1) * 4); fill(A.s_cov, 0, (size_t)np * 8); fill(A.l_cur, 0, ((size_t)np + 1) * 4);
-        agx_launch_unitig_phase2(&A, rounds, st.s);
-        agx_launch_unitig_totals(&A, words + 4, st.s);
-        HIP_OK(hipMemcpyAsync(h, words + 4, 16, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
-        if (h[3]) throw Error{E_DEVICE, "unitigs: the unitig ranks are inconsistent (error word " + std::to_string(h[3]) + ")"};
-        const agx_u32 ns = h[0], nb = h[1], nl = h[2];
-        if (ns > np || nb > u->n_nodes || nb > A.seq_cap || nl > A.link_cap) throw Error{E_DEVICE, "unitigs: segment totals out of range"};
-        A.seq_cap = nb; A.link_cap = nl;
-        agx_launch_unitig_phase3(&A, st.s);
-        // the compact arrays (per-node arrays never leave the device) into pinned memory, then into the caller's malloc'd table
-        const size_t o_hp = 0, o_hv = o_hp + 4 * (size_t)ns, o_ln = o_hv + 4 * (size_t)ns, o_lp = o_ln + 4 * (size_t)ns, o_cov = (o_lp + 4 * (size_t)ns + 7) & ~(size_t)7,
-                     o_so = o_cov + 8 * (size_t)ns, o_lo = o_so + 4 * ((size_t)ns + 1), o_lt = o_lo + 4 * ((size_t)ns + 1), o_seq = o_lt + 4 * (size_t)nl, o_end = o_seq + nb;
-        PBuf<char> pin; pin.alloc(o_end + 8);
-        auto down = [&](size_t o, const void *src, size_t b) { if (b) HIP_OK(hipMemcpyAsync(pin.p + o, src, b, hipMemcpyDeviceToHost, st.s)); };
-        down(o_hp, A.s_hpos, 4 * (size_t)ns); down(o_hv, A.s_hvar, 4 * (size_t)ns); down(o_ln, A.s_len, 4 * (size_t)ns); down(o_lp, A.s_last, 4 * (size_t)ns);
-        down(o_cov, A.s_cov, 8 * (size_t)ns); down(o_so, A.s_off, 4 * ((size_t)ns + 1)); down(o_lo, A.l_off, 4 * ((size_t)ns + 1)); down(o_lt, A.l_to, 4 * (size_t)nl); down(o_seq, A.seq, nb);
-        HIP_OK(hipMemcpyAsync(h, words, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
-        if (h[0]) throw Error{E_DEVICE, "unitigs: the segments are inconsistent (error word " + std::to_string(h[0]) + ")"};
-        t->n_segs = ns; t->n_links = nl; t->n_bases = nb;
-        t->head_pos = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->head_var = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->n_nodes = (uint32_t *)malloc(4 * ((size_t)ns + 1));
-        t->last_pos = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->coverage = (uint64_t *)malloc(8 * ((size_t)ns + 1)); t->seq_off = (uint64_t *)malloc(8 * ((size_t)ns + 1));
-        t->seq = (char *)malloc((size_t)nb + 1); t->link_from = (uint32_t *)malloc(4 * ((size_t)nl + 1)); t->link_to = (uint32_t *)malloc(4 * ((size_t)nl + 1));
-        if (!t->head_pos || !t->head_var || !t->n_nodes || !t->last_pos || !t->coverage || !t->seq_off || !t->seq || !t->link_from || !t->link_to) throw Error{E_ARG, "out of host memory"};
-        memcpy(t->head_pos, pin.p + o_hp, 4 * (size_t)ns); memcpy(t->head_var, pin.p + o_hv, 4 * (size_t)ns); memcpy(t->n_nodes, pin.p + o_ln, 4 * (size_t)ns);
-        memcpy(t->last_pos, pin.p + o_lp, 4 * (size_t)ns); memcpy(t->coverage, pin.p + o_cov, 8 * (size_t)ns); memcpy(t->link_to, pin.p + o_lt, 4 * (size_t)nl); memcpy(t->seq, pin.p + o_seq, nb);
-        t->seq[nb] = 0;
-        const agx_u32 *so = (const agx_u32 *)(pin.p + o_so), *lo = (const agx_u32 *)(pin.p + o_lo);
-        for (size_t g = 0; g <= ns; g++) t->seq_off[g] = so[g];      // (a unit's nodes are counted in 32 bits, so are its bases)
-        for (size_t g = 0; g < ns; g++) {
-            if (lo[g] > lo[g + 1] || lo[g + 1] > nl) throw Error{E_DEVICE, "unitigs: link offsets out of range"};
-            for (agx_u32 i = lo[g]; i < lo[g + 1]; i++) t->link_from[i] = (uint32_t)g;
-        }
+        export_body(E, A, nullptr, words, np, u->n_nodes, t, nullptr);
     });
     if (rc != AGX_OK) agx_unitigs_free(t);
     return rc;
@@ -2154,134 +2222,63 @@ int agx_unit_unitigs(agx_unit *u, agx_unitigs *t) {
 
 // Region export (DESIGN.md §11 "A region at a chosen coverage"): the unitigs of the sub-graph of positions [pos_lo, pos_hi) whose nodes are alive at min_coverage.  The same
 // scratch buffer, a stream of its own; no launch and no memset below is sized by the unit's positions or node slots, only by the window's positions, its kept nodes and the
-// overflow list (which has no position index).  Four host round trips: the kept nodes, the piece and head counts, the totals, the download.  agx_unit_unitigs above does not
-// come through here: its code path and its timings are what this one is compared with.
+// overflow list (which has no position index).  Four host round trips: the kept nodes, the piece and head counts, and export_body's two (the totals, the download) — the
+// whole export above comes through the same body with one trip less in front of it.
 // (m: also the id map of the export, agx_unit_unitigs_mapped; nullptr: every command and copy is agx_unit_unitigs_region's)
 static void region_export(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, agx_idmap *m) {
-    {
-        if (!(u->prm.flags & AGX_FLAG_KEEP_COUNTS)) throw Error{E_ARG, "unitigs: the unit was created without AGX_FLAG_KEEP_COUNTS (the segments' coverage needs the counts)"};
-        if (!u->built || u->trimmed) throw Error{E_ARG, "unitigs: the unit is not built (call agx_unit_build; not after agx_unit_trim or agx_unit_release)"};
-        if ((u->prm.flags & AGX_FLAG_ONE_SHOT) && (u->consumed || u->downloaded)) throw Error{E_ARG, "unitigs: a one-shot unit exports before its download or finish"};
-        if (m && !(u->prm.flags & AGX_FLAG_KEEP_PATHS)) throw Error{E_ARG, "unitigs: the unit was created without AGX_FLAG_KEEP_PATHS (the id map's scratch is reserved with the unit's block)"};
-        const agx_u32 n_pos = (agx_u32)u->V.n_pos, cap = u->pool_cap, n_ovf = std::min(u->n_ovf, u->ovf_cap);
-        if (pos_lo > pos_hi || pos_hi > n_pos)
-            throw Error{E_ARG, "unitigs: region [" + std::to_string(pos_lo) + ", " + std::to_string(pos_hi) + ") is not within the unit's positions [0, " + std::to_string(n_pos) + ")"};
-        HIP_OK(hipSetDevice(u->prm.device));
-        HIP_OK(wait_event(u->ev_built));
-        const agx_u32 n_win = pos_hi - pos_lo;
-        if (m) { m->n_pos = n_pos; m->n_ids = u->n_ids; }
-        if (!n_win || !cap || !u->n_nodes) return;
-        const size_t whole = unitig_layout(cap, n_pos, n_ovf, nullptr, nullptr, nullptr);
-        size_t map_at = 0;
-        if (keeps_paths(u)) u->d_ut.alloc(u->arena, mapped_scratch(cap, n_pos, u->n_nodes, u->n_ids, n_ovf, &map_at));
-        else u->d_ut.alloc(u->arena, std::max(whole, unitig_region_layout(cap, n_win, std::min<size_t>(u->n_nodes, cap), n_ovf, nullptr, nullptr, nullptr)));      // (the buffer of the whole export: the room the upload reserved; a tiny unit: unitig_region_layout)
-        u->stats.device_bytes = u->arena.capacity();
-        struct Stream { hipStream_t s = nullptr; ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } st;
-        HIP_OK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-        auto fill = [&](void *p, int v, size_t b) { HIP_OK(hipMemsetAsync(p, v, b ? b : 1, st.s)); };
-        agx_unitig_region_args R{}; agx_u32 *words = nullptr;
-        auto bind = [&](agx_u32 kept) {
-            R = agx_unitig_region_args{};
-            unitig_region_layout(cap, n_win, kept, n_ovf, u->d_ut.p, &R, &words);
-            agx_unitig_args &A = R.U;
-            A.node_start = u->d_node_start.p; A.n_base = u->d_base.p; A.n_next = u->d_next.p; A.n_counts = u->d_counts.p; A.ref = u->d_ref.p; A.ovf = u->d_ovf.p; A.n_ovf = n_ovf;
-            A.pool_cap = kept; A.piece_cap = kept; A.n_pos = (kept + 63u) / 64u; A.err = words;
-            R.nk_cid = u->d_cid.p; R.node_cnt = u->d_node_cnt.p; R.pos_lo = pos_lo; R.n_win = n_win; R.min_cov = min_coverage; R.pool_cap = cap;
-        };
-        bind(0);
-        fill(words, 0, 32);
-        agx_launch_unitig_region_count(&R, st.s);
-        agx_u32 h[4] = {0, 0, 0, 0}, hm[3] = {0, 0, 0};      // hm: the id map's side-id bounds and run count
-        agx_idmap_args M{};
-        if (m) {      // the window's side ids: two bisections on the device, read with the kept nodes
-            M.a_nid = u->d_a_nid.p; M.side_xpos = u->d_side_xpos.p; M.n_pos = n_pos; M.n_ids = u->n_ids; M.n_main = n_win; M.bounds = words + 1;
-            agx_launch_idmap_bounds(&R, &M, st.s);
-            HIP_OK(hipMemcpyAsync(hm, words + 1, 8, hipMemcpyDeviceToHost, st.s));
-        }
-        HIP_OK(hipMemcpyAsync(h, words, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipMemcpyAsync(h + 1, R.offw + n_win, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
-        if (h[0]) throw Error{E_DEVICE, "unitigs: the node table is inconsistent (error word " + std::to_string(h[0]) + ")"};
-        const agx_u32 kept = h[1];
-        if (kept > u->n_nodes || kept > cap) throw Error{E_DEVICE, "unitigs: more nodes in the region than in the unit"};
-        if (!kept) return;
-        bind(kept);
-        agx_u32 n_wids = 0;
-        if (m) {
-            const agx_u32 sides = u->n_ids > n_pos ? u->n_ids - n_pos : 0u;
-            if (hm[0] > hm[1] || hm[1] > sides) throw Error{E_DEVICE, "unitigs: the side ids are not in position order"};
-            M.side_lo = hm[0]; M.n_side = hm[1] - hm[0]; n_wids = n_win + M.n_side;
-            idmap_layout((size_t)n_pos + sides, std::min<size_t>(std::min<size_t>(u->n_nodes, cap), (size_t)n_pos + sides), u->d_ut.p + map_at, &M);      // (the layout the buffer was sized by: this window's ids fit its front)
-            M.run_cap = (agx_u32)std::min<size_t>(kept, n_wids);
-        }
+    export_check(u, m != nullptr);
+    if (pos_lo > pos_hi || pos_hi > (agx_u32)u->V.n_pos)
+        throw Error{E_ARG, "unitigs: region [" + std::to_string(pos_lo) + ", " + std::to_string(pos_hi) + ") is not within the unit's positions [0, " + std::to_string((agx_u32)u->V.n_pos) + ")"};
+    Export E(u);
+    const agx_u32 n_pos = E.n_pos, cap = E.cap, n_ovf = E.n_ovf, n_win = pos_hi - pos_lo;
+    if (m) { m->n_pos = n_pos; m->n_ids = u->n_ids; }
+    if (!n_win || !cap || !u->n_nodes) return;
+    // (the buffer of the whole export: the room the upload reserved; a tiny unit: unitig_region_layout)
+    E.open(std::max(unitig_layout(cap, n_pos, n_ovf, nullptr, nullptr, nullptr), unitig_region_layout(cap, n_win, std::min<size_t>(u->n_nodes, cap), n_ovf, nullptr, nullptr, nullptr)));
+    agx_unitig_region_args R{}; agx_u32 *words = nullptr;
+    auto bind = [&](agx_u32 kept) {
+        R = agx_unitig_region_args{};
+        unitig_region_layout(cap, n_win, kept, n_ovf, u->d_ut.p, &R, &words);
         agx_unitig_args &A = R.U;
-        const size_t ngrp = A.n_pos;
-        if (n_ovf) fill(A.ovf_hash, 0xFF, ((size_t)A.hash_mask + 1) * 8);
-        fill(A.wcnt, 0, (ngrp + 1) * 4); fill(A.hcnt, 0, (ngrp + 1) * 4);
-        agx_launch_unitig_region_phase1(&R, st.s);
-        HIP_OK(hipMemcpyAsync(h, words, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipMemcpyAsync(h + 1, A.woff + ngrp, 4, hipMemcpyDeviceToHost, st.s));
-        HIP_OK(hipMemcpyAsync(h + 2, A.hoff + ngrp, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
-        if (h[0] & 1u) throw Error{E_DEVICE, "unitigs: an edge of the node table does not lead to a later position (the graph is not a DAG)"};
-        if (h[0]) throw Error{E_DEVICE, "unitigs: the node table is inconsistent (error word " + std::to_string(h[0]) + ")"};
-        const agx_u32 np = h[1];
-        if (!np || np > kept || h[2] > np) throw Error{E_DEVICE, "unitigs: piece and head counts out of range"};
-        A.piece_cap = np;
-        agx_u32 rounds = 1; while (rounds < 32 && (1ull << (rounds - 1)) < np) rounds++;      // ceil(log2 np) + 1
-        fill(A.p_seg, 0xFF, (size_t)np * 4); fill(A.s_len, 0, ((size_t)np + 1) * 4); fill(A.s_links, 0, ((size_t)np + 1) * 4); fill(A.s_cov, 0, (size_t)np * 8);
-        agx_launch_unitig_region_phase2(&R, rounds, st.s);
-        fill(A.l_cur, 0, ((size_t)np + 1) * 4);          // (over the pointer jumping's second ancestor array: behind the rank kernel)
-        agx_launch_unitig_totals(&A, words + 4, st.s);
-        if (m) {      // run starts and their scan, on the (segment, rank) the rank kernel left per local id; the run count comes with the totals
-            agx_launch_idmap_flags(&R, &M, st.s);
-            HIP_OK(hipMemcpyAsync(hm + 2, M.foff + n_wids, 4, hipMemcpyDeviceToHost, st.s));
-        }
-        HIP_OK(hipMemcpyAsync(h, words + 4, 16, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
-        if (h[3]) throw Error{E_DEVICE, "unitigs: the unitig ranks are inconsistent (error word " + std::to_string(h[3]) + ")"};
-        const agx_u32 ns = h[0], nb = h[1], nl = h[2];
-        if (ns > np || nb > kept || nb > A.seq_cap || nl > A.link_cap) throw Error{E_DEVICE, "unitigs: segment totals out of range"};
-        A.seq_cap = nb; A.link_cap = nl;
-        const agx_u32 nr = hm[2];
-        if (m && nr > M.run_cap) throw Error{E_DEVICE, "unitigs: more runs in the id map than nodes in the region"};
-        M.run_cap = nr;
-        agx_launch_unitig_region_phase3(&R, st.s);
-        if (m) agx_launch_idmap_runs(&R, &M, st.s);
-        // the download and the caller's table: a copy of agx_unit_unitigs' last part, kept apart only because that function's code path is the baseline this one is measured
-        // against — the two must change together (a helper shared by both is the next step once that constraint goes)
-        const size_t o_hp = 0, o_hv = o_hp + 4 * (size_t)ns, o_ln = o_hv + 4 * (size_t)ns, o_lp = o_ln + 4 * (size_t)ns, o_cov = (o_lp + 4 * (size_t)ns + 7) & ~(size_t)7,
-                     o_so = o_cov + 8 * (size_t)ns, o_lo = o_so + 4 * ((size_t)ns + 1), o_lt = o_lo + 4 * ((size_t)ns + 1), o_seq = o_lt + 4 * (size_t)nl, o_run = (o_seq + nb + 3) & ~(size_t)3, o_end = o_run + (m ? 16 * (size_t)nr : 0);
-        PBuf<char> pin; pin.alloc(o_end + 8);
-        auto down = [&](size_t o, const void *src, size_t b) { if (b) HIP_OK(hipMemcpyAsync(pin.p + o, src, b, hipMemcpyDeviceToHost, st.s)); };
-        down(o_hp, A.s_hpos, 4 * (size_t)ns); down(o_hv, A.s_hvar, 4 * (size_t)ns); down(o_ln, A.s_len, 4 * (size_t)ns); down(o_lp, A.s_last, 4 * (size_t)ns);
-        down(o_cov, A.s_cov, 8 * (size_t)ns); down(o_so, A.s_off, 4 * ((size_t)ns + 1)); down(o_lo, A.l_off, 4 * ((size_t)ns + 1)); down(o_lt, A.l_to, 4 * (size_t)nl); down(o_seq, A.seq, nb);
-        if (m) { down(o_run, M.r_first, 4 * (size_t)nr); down(o_run + 4 * (size_t)nr, M.r_last, 4 * (size_t)nr); down(o_run + 8 * (size_t)nr, M.r_seg, 4 * (size_t)nr); down(o_run + 12 * (size_t)nr, M.r_rank, 4 * (size_t)nr); }
-        HIP_OK(hipMemcpyAsync(h, words, 4, hipMemcpyDeviceToHost, st.s)); HIP_OK(hipStreamSynchronize(st.s));
-        if (h[0]) throw Error{E_DEVICE, "unitigs: the segments are inconsistent (error word " + std::to_string(h[0]) + ")"};
-        t->n_segs = ns; t->n_links = nl; t->n_bases = nb;
-        t->head_pos = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->head_var = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->n_nodes = (uint32_t *)malloc(4 * ((size_t)ns + 1));
-        t->last_pos = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->coverage = (uint64_t *)malloc(8 * ((size_t)ns + 1)); t->seq_off = (uint64_t *)malloc(8 * ((size_t)ns + 1));
-        t->seq = (char *)malloc((size_t)nb + 1); t->link_from = (uint32_t *)malloc(4 * ((size_t)nl + 1)); t->link_to = (uint32_t *)malloc(4 * ((size_t)nl + 1));
-        if (!t->head_pos || !t->head_var || !t->n_nodes || !t->last_pos || !t->coverage || !t->seq_off || !t->seq || !t->link_from || !t->link_to) throw Error{E_ARG, "out of host memory"};
-        memcpy(t->head_pos, pin.p + o_hp, 4 * (size_t)ns); memcpy(t->head_var, pin.p + o_hv, 4 * (size_t)ns); memcpy(t->n_nodes, pin.p + o_ln, 4 * (size_t)ns);
-        memcpy(t->last_pos, pin.p + o_lp, 4 * (size_t)ns); memcpy(t->coverage, pin.p + o_cov, 8 * (size_t)ns); memcpy(t->link_to, pin.p + o_lt, 4 * (size_t)nl); memcpy(t->seq, pin.p + o_seq, nb);
-        t->seq[nb] = 0;
-        const agx_u32 *so = (const agx_u32 *)(pin.p + o_so), *lo = (const agx_u32 *)(pin.p + o_lo);
-        for (size_t g = 0; g <= ns; g++) t->seq_off[g] = so[g];
-        for (size_t g = 0; g < ns; g++) {
-            if (lo[g] > lo[g + 1] || lo[g + 1] > nl) throw Error{E_DEVICE, "unitigs: link offsets out of range"};
-            for (agx_u32 i = lo[g]; i < lo[g + 1]; i++) t->link_from[i] = (uint32_t)g;
-        }
-        if (m && nr) {
-            m->id_first = (uint32_t *)malloc(4 * (size_t)nr); m->id_last = (uint32_t *)malloc(4 * (size_t)nr); m->seg = (uint32_t *)malloc(4 * (size_t)nr); m->rank_first = (uint32_t *)malloc(4 * (size_t)nr);
-            if (!m->id_first || !m->id_last || !m->seg || !m->rank_first) throw Error{E_ARG, "out of host memory"};
-            memcpy(m->id_first, pin.p + o_run, 4 * (size_t)nr); memcpy(m->id_last, pin.p + o_run + 4 * (size_t)nr, 4 * (size_t)nr);
-            memcpy(m->seg, pin.p + o_run + 8 * (size_t)nr, 4 * (size_t)nr); memcpy(m->rank_first, pin.p + o_run + 12 * (size_t)nr, 4 * (size_t)nr);
-            m->n_runs = nr;
-            // what the kernels wrote must be a map: runs in id order, inside one block of ids, inside their segments
-            for (agx_u32 r = 0; r < nr; r++) {
-                const uint32_t a = m->id_first[r], b = m->id_last[r];
-                if (a > b || b >= u->n_ids || (a < n_pos) != (b < n_pos) || (r && m->id_last[r - 1] >= a) || m->seg[r] >= ns ||
-                    (uint64_t)m->rank_first[r] + (b - a) >= t->n_nodes[m->seg[r]]) throw Error{E_DEVICE, "unitigs: the id map is inconsistent (run " + std::to_string(r) + ")"};
-            }
-        }
+        A.node_start = u->d_node_start.p; A.n_base = u->d_base.p; A.n_next = u->d_next.p; A.n_counts = u->d_counts.p; A.ref = u->d_ref.p; A.ovf = u->d_ovf.p; A.n_ovf = n_ovf;
+        A.pool_cap = kept; A.piece_cap = kept; A.n_pos = (kept + 63u) / 64u; A.err = words;
+        R.nk_cid = u->d_cid.p; R.node_cnt = u->d_node_cnt.p; R.pos_lo = pos_lo; R.n_win = n_win; R.min_cov = min_coverage; R.pool_cap = cap;
+    };
+    bind(0);
+    E.fill(words, 0, 32);
+    agx_launch_unitig_region_count(&R, E.s);
+    agx_u32 h[3] = {0, 0, 0}, hm[2] = {0, 0};      // hm: the id map's side-id bounds
+    MapJob J{m};
+    agx_idmap_args &M = J.M;
+    if (m) {      // the window's side ids: two bisections on the device, read with the kept nodes
+        M.a_nid = u->d_a_nid.p; M.side_xpos = u->d_side_xpos.p; M.n_pos = n_pos; M.n_ids = u->n_ids; M.n_main = n_win; M.bounds = words + 1;
+        agx_launch_idmap_bounds(&R, &M, E.s);
+        E.read(hm, words + 1, 8);
     }
+    E.read(h, words, 4); E.read(h + 1, R.offw + n_win, 4); E.sync();
+    if (h[0]) throw Error{E_DEVICE, "unitigs: the node table is inconsistent (error word " + std::to_string(h[0]) + ")"};
+    const agx_u32 kept = h[1];
+    if (kept > u->n_nodes || kept > cap) throw Error{E_DEVICE, "unitigs: more nodes in the region than in the unit"};
+    if (!kept) return;
+    bind(kept);
+    if (m) {
+        const agx_u32 sides = u->n_ids > n_pos ? u->n_ids - n_pos : 0u;
+        if (hm[0] > hm[1] || hm[1] > sides) throw Error{E_DEVICE, "unitigs: the side ids are not in position order"};
+        M.side_lo = hm[0]; M.n_side = hm[1] - hm[0]; J.n_wids = n_win + M.n_side;
+        idmap_layout((size_t)n_pos + sides, std::min<size_t>(std::min<size_t>(u->n_nodes, cap), (size_t)n_pos + sides), u->d_ut.p + E.map_at, &M);      // (the layout the buffer was sized by: this window's ids fit its front)
+        M.run_cap = (agx_u32)std::min<size_t>(kept, J.n_wids);
+    }
+    agx_unitig_args &A = R.U;
+    const size_t ngrp = A.n_pos;
+    if (n_ovf) E.fill(A.ovf_hash, 0xFF, ((size_t)A.hash_mask + 1) * 8);
+    E.fill(A.wcnt, 0, (ngrp + 1) * 4); E.fill(A.hcnt, 0, (ngrp + 1) * 4);
+    agx_launch_unitig_region_phase1(&R, E.s);
+    E.read(h, words, 4); E.read(h + 1, A.woff + ngrp, 4); E.read(h + 2, A.hoff + ngrp, 4); E.sync();
+    if (h[0] & 1u) throw Error{E_DEVICE, "unitigs: an edge of the node table does not lead to a later position (the graph is not a DAG)"};
+    if (h[0]) throw Error{E_DEVICE, "unitigs: the node table is inconsistent (error word " + std::to_string(h[0]) + ")"};
+    const agx_u32 np = h[1];
+    if (!np || np > kept || h[2] > np) throw Error{E_DEVICE, "unitigs: piece and head counts out of range"};
+    export_body(E, A, &R, words, np, kept, t, m ? &J : nullptr);
 }
 
 int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t) {

@@ -82,7 +82,7 @@ struct agx_unitig_args {
 // dense LOCAL ids in (position, variant) order and every later phase runs over local ids, so nothing here is sized by the unit but the reverse map, which is only ever
 // touched at the window's slots.  U is the local view: U.pool_cap = kept nodes, U.n_pos = 64-id groups (hcnt / hoff are per group), U.pos_of[id] = the node's position, the
 // other per-slot arrays of U are per local id and hold local ids; U.node_start, n_base, n_next, n_counts, ref and ovf are the unit's own (U.n_flags is not read: alive is
-// nk_cid and the count against min_cov, never AGX_NF_DEAD).  The piece, totals and link-sort kernels of the whole export run on U unchanged.
+// nk_cid and the count against min_cov, never AGX_NF_DEAD).  The jumping, totals and link-sort kernels of the whole export run on U unchanged; the others share their steps with it (agx_unitig.hip: ut_locals).
 struct agx_unitig_region_args {
     agx_unitig_args U;
     const agx_u32 *nk_cid; const agx_u16 *node_cnt; agx_u32 pos_lo, n_win, min_cov, pool_cap;      // pool_cap: the unit's node slots (bounds what the table names)
@@ -157,17 +157,16 @@ void agx_launch_special(const agx_compact_args *, agx_u32 n_words, agx_u32 *sp_r
 #define AGX_MID_WAVES 3072u     // wavefronts of pass 1 (3 per SIMD fit its LDS buckets); they stride over the list of tiles pass 0 gave up on
 #define AGX_BIG_WAVES 256u      // resident wavefronts of the global-scratch fallback pass
 #define AGX_HUGE_WAVES 32u      // wavefronts of pass 3 (0.85 MB of scratch each)
-// unitig export: phase 1 (degrees, internal edges, pieces), phase 2 (piece ranks, heads, segments, links).  The host reads the piece count between them.
+// unitig export: phase 1 (degrees, internal edges, pieces; the host reads the piece count), phase 2 (piece ranks, heads, segments, link counts; the host reads the totals),
+// phase 3 (bases and links, once the scans are in: the host sized seq / links from them).  The region export has a count in front (kept nodes per position of the window and
+// their scan; the host reads the total) and a phase 1 of its own (local ids, degrees, internal edges, pieces and heads per 64-id group); phases 2 and 3 and the totals are
+// launched on its local view, A = &R->U, with R beside it (R = nullptr: the whole export)
 void agx_launch_unitig_phase1(const agx_unitig_args *, hipStream_t);
-void agx_launch_unitig_phase2(const agx_unitig_args *, agx_u32 rounds, hipStream_t);
-void agx_launch_unitig_phase3(const agx_unitig_args *, hipStream_t);      // bases and links, once the scans are in (the host sized seq / links from them)
-void agx_launch_unitig_totals(const agx_unitig_args *, agx_u32 *tot, hipStream_t);      // tot[0..3] = segments, bases, links, error word
-// region export: count (kept nodes per position of the window and their scan; the host reads the total), phase 1 (local ids, degrees, internal edges, pieces, heads per
-// 64-id group; the host reads the piece count), phase 2 and 3 as above; agx_launch_unitig_totals takes &R->U
 void agx_launch_unitig_region_count(const agx_unitig_region_args *, hipStream_t);
 void agx_launch_unitig_region_phase1(const agx_unitig_region_args *, hipStream_t);
-void agx_launch_unitig_region_phase2(const agx_unitig_region_args *, agx_u32 rounds, hipStream_t);
-void agx_launch_unitig_region_phase3(const agx_unitig_region_args *, hipStream_t);
+void agx_launch_unitig_phase2(const agx_unitig_args *A, const agx_unitig_region_args *R, agx_u32 rounds, hipStream_t);
+void agx_launch_unitig_phase3(const agx_unitig_args *A, const agx_unitig_region_args *R, hipStream_t);
+void agx_launch_unitig_totals(const agx_unitig_args *, agx_u32 *tot, hipStream_t);      // tot[0..3] = segments, bases, links, error word
 // id map of a region export: bounds (queued beside the region's count: the host reads them with the kept nodes), flags + scan (behind phase 2: the host reads the run count
 // with the totals), runs (beside phase 3)
 void agx_launch_idmap_bounds(const agx_unitig_region_args *, const agx_idmap_args *, hipStream_t);

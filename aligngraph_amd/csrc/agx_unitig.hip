@@ -14,13 +14,169 @@
 // form (agx_launch_exclusive_scan): nothing here spins, whatever builds run beside an export on the same device.
 //
 // The region export (agx_unit_unitigs_region; the agx_k_utr_* kernels in the second half of the file) applies the same definition to the nodes of a window of positions
-// that are alive at a coverage of the caller's choice, over dense local ids instead of slots: none of its grids is sized by the unit.
+// that are alive at a coverage of the caller's choice, over dense local ids instead of slots: none of its grids is sized by the unit.  What the two forms do to one node,
+// one window or one overflow entry is written once, over a VIEW (ut_slots, ut_locals) that says how the form names its nodes; the kernels differ in their grids.
 #include <hip/hip_runtime.h>
 #include "agx_kargs.h"
 
 namespace {
 
 __device__ __forceinline__ bool ut_alive(const agx_unitig_args &A, agx_u32 slot) { return !(A.n_flags[slot] & AGX_NF_DEAD); }
+__device__ __forceinline__ bool utr_kept(const agx_unitig_region_args &R, agx_u32 slot) {      // AG:1904-1918 with the caller's threshold
+    return R.nk_cid[slot] != AGX_NONE || (long long)R.U.n_counts[(size_t)slot * 6] >= (long long)R.min_cov;
+}
+
+// A view: how an export names its nodes.  args(): the per-id arrays; slot_cap(): the unit's node slots; in_export(slot): the id of a slot's node, NONE if the slot is
+// outside the pool or its node is not in the export; slot_of(id): the slot of a node of the export; valid(id): whether the id names one.
+// The whole export: a node's id is its slot, and it is in the export unless the build pruned it
+struct ut_slots {
+    const agx_unitig_args &A;
+    __device__ __forceinline__ const agx_unitig_args &args() const { return A; }
+    __device__ __forceinline__ agx_u32 slot_cap() const { return A.pool_cap; }
+    __device__ __forceinline__ agx_u32 in_export(agx_u32 slot) const { return slot < A.pool_cap && ut_alive(A, slot) ? slot : AGX_NONE; }
+    __device__ __forceinline__ agx_u32 slot_of(agx_u32 id) const { return id; }
+    __device__ __forceinline__ bool valid(agx_u32 id) const { return id < A.pool_cap && A.pos_of[id] != AGX_NONE && ut_alive(A, id); }
+};
+// The region export: dense local ids (l_slot: id -> slot; rmap: slot -> id).  rmap holds whatever the last export of any kind left in it: an entry counts only if the
+// local id it names points back at the slot
+struct ut_locals {
+    const agx_unitig_region_args &R;
+    __device__ __forceinline__ const agx_unitig_args &args() const { return R.U; }
+    __device__ __forceinline__ agx_u32 slot_cap() const { return R.pool_cap; }
+    __device__ __forceinline__ agx_u32 in_export(agx_u32 slot) const {
+        if (slot >= R.pool_cap) return AGX_NONE;
+        const agx_u32 r = R.rmap[slot];
+        return r < R.U.pool_cap && R.l_slot[r] == slot ? r : AGX_NONE;
+    }
+    __device__ __forceinline__ agx_u32 slot_of(agx_u32 id) const { return R.l_slot[id]; }
+    __device__ __forceinline__ bool valid(agx_u32 id) const { return id < R.U.pool_cap; }
+};
+
+// ---- the steps both forms take, over a view -------------------------------------------------------------------------------------------------------------------
+
+// entry i of the overflow list: an edge may be listed more than once (two lanes that inserted it at the same time); the first to enter the hash set counts it
+template <class V> __device__ __forceinline__ void ut_ovf_insert(const V &v, agx_u32 i) {
+    const agx_unitig_args &A = v.args();
+    if (i >= A.n_ovf) return;
+    A.ovf_first[i] = 0;
+    const agx_u32 s = A.ovf[i].src, d = A.ovf[i].dst;
+    if (s == AGX_NONE || d == AGX_NONE) return;
+    if (s >= v.slot_cap() || d >= v.slot_cap()) { atomicOr(A.err, 2u); return; }
+    const agx_u32 ls = v.in_export(s), ld = v.in_export(d);
+    if (ls == AGX_NONE || ld == AGX_NONE) return;
+    const agx_u32 sp = A.pos_of[ls], dp = A.pos_of[ld];
+    if (sp == AGX_NONE || dp == AGX_NONE || dp <= sp) { atomicOr(A.err, 1u); return; }
+    const unsigned long long key = ((unsigned long long)ls << 32) | ld;
+    agx_u32 h = (agx_u32)((key * 0x9E3779B97F4A7C15ull) >> 32) & A.hash_mask;
+    for (agx_u32 probe = 0; probe <= A.hash_mask; probe++) {          // (the set holds twice the list: a free cell is always found)
+        const unsigned long long old = atomicCAS(A.ovf_hash + h, ~0ull, key);
+        if (old == key) return;
+        if (old == ~0ull) {
+            A.ovf_first[i] = 1;
+            atomicAdd(A.indeg + ld, 1u); atomicAdd(A.oout + ls, 1u); A.osucc[ls] = ld;      // (osucc is only read where oout == 1)
+            return;
+        }
+        h = (h + 1u) & A.hash_mask;
+    }
+}
+
+// the internal edge of node id (in: it is a node of the export): nxt[id] = the one successor if that has one predecessor; outs[id] becomes the whole out-degree
+__device__ __forceinline__ void ut_internal_of(const agx_unitig_args &A, agx_u32 id, bool in) {
+    agx_u32 nx = AGX_NONE;
+    if (in) {
+        const agx_u32 a = A.outs[id], b = A.oout[id], d = a + b;
+        const agx_u32 t = d != 1u ? AGX_NONE : a == 1u ? A.succ[id] : A.osucc[id];
+        if (t != AGX_NONE && t < A.pool_cap && A.indeg[t] == 1u) { nx = t; A.haspred[t] = 1; }
+        A.outs[id] = d;
+    }
+    A.nxt[id] = nx; A.succ[id] = AGX_NONE;          // (succ becomes the piece id of piece starts)
+}
+
+// 64 consecutive ids, a lane each: which lanes are nodes of the export, which continue into the next id (internal edge u -> u+1), which start a piece
+struct ut_window { agx_u32 u, lane, nx; bool valid, link; unsigned long long lm, sm; };
+template <class V> __device__ __forceinline__ ut_window ut_window_of(const V &v) {
+    const agx_unitig_args &A = v.args();
+    ut_window w;
+    w.u = blockIdx.x * 256u + threadIdx.x; w.lane = threadIdx.x & 63u;
+    w.valid = v.valid(w.u);
+    w.nx = w.valid ? A.nxt[w.u] : AGX_NONE;
+    w.link = w.valid && w.lane < 63u && w.nx == w.u + 1u;
+    w.lm = __ballot(w.link);
+    const bool prev = w.lane > 0 && ((w.lm >> (w.lane - 1u)) & 1ull);
+    w.sm = __ballot(w.valid && !prev);
+    return w;
+}
+
+// the window's pieces: each one's length, the id its last node's internal edge enters, and its piece id at its first node
+// (the ids come from a scan of the windows' counts: one atomic counter per wavefront cost 5.6 ms on a 30 Mb unit, every wavefront waiting for the same address)
+__device__ __forceinline__ void ut_cut(const agx_unitig_args &A, const ut_window &w) {
+    const bool start = (w.sm >> w.lane) & 1ull;
+    const agx_u32 end = w.lane + (agx_u32)__builtin_ctzll(~w.lm >> w.lane);      // (bit 63 of ~lm is always set)
+    const agx_u32 nx_end = __shfl(w.nx, (int)end, 64);
+    if (!start) return;
+    const agx_u32 pid = A.woff[w.u / 64u] + (agx_u32)__popcll(w.sm & ((1ull << w.lane) - 1ull));
+    if (pid >= A.piece_cap) { atomicOr(A.err, 4u); return; }
+    A.p_len[pid] = end - w.lane + 1u; A.p_next[pid] = nx_end; A.succ[w.u] = pid;
+}
+
+// every node: its segment and rank; every tail: its segment's length, last position and link count; coverage summed per piece, one atomic per piece
+template <class V> __device__ __forceinline__ void ut_rank_of(const V &v, agx_u32 np, agx_u32 fin) {
+    const agx_unitig_args &A = v.args();
+    const ut_window w = ut_window_of(v);
+    const unsigned long long below = w.sm & ((2ull << w.lane) - 1ull);
+    const agx_u32 ps = below ? 63u - (agx_u32)__builtin_clzll(below) : 0u;
+    const bool start = (w.sm >> w.lane) & 1ull;
+    const agx_u32 pid_here = start ? A.succ[w.u] : AGX_NONE;
+    const agx_u32 pid = __shfl(pid_here, (int)ps, 64);
+    const agx_u32 slot = w.valid ? v.slot_of(w.u) : AGX_NONE;
+    unsigned long long cov = slot < v.slot_cap() ? (unsigned long long)(agx_u32)A.n_counts[(size_t)slot * 6] : 0ull, incl = cov;
+    for (agx_u32 d = 1; d < 64u; d <<= 1) { const unsigned long long o = __shfl_up(incl, d, 64); if (w.lane >= d) incl += o; }
+    const unsigned long long excl_ps = __shfl(incl - cov, (int)ps, 64);
+    if (!w.valid) return;
+    if (pid >= np) { atomicOr(A.err, 4u); return; }
+    const agx_u32 h = A.anc[fin][pid];
+    if (h >= np || A.anc[fin][h] != h) { atomicOr(A.err, 4u); return; }       // (not converged: impossible on a DAG)
+    const agx_u32 seg = A.p_seg[h];
+    if (seg >= A.piece_cap) { atomicOr(A.err, 4u); return; }
+    const agx_u32 rank = A.off[fin][pid] + (w.lane - ps);
+    A.indeg[w.u] = seg; A.osucc[w.u] = rank;
+    if (!w.link) atomicAdd(A.s_cov + seg, incl - excl_ps);            // the piece's last node
+    if (w.nx == AGX_NONE) { A.s_len[seg] = rank + 1u; A.s_last[seg] = A.pos_of[w.u]; A.s_links[seg] = A.outs[w.u]; }
+}
+
+// node id at position X (ns: the segments): its base at s_off[seg] + rank; a tail's inline links (the overflow list's follow in ut_ovf_link)
+template <class V> __device__ __forceinline__ void ut_emit_node(const V &v, agx_u32 id, agx_u32 X, agx_u32 ns) {
+    const agx_unitig_args &A = v.args();
+    const agx_u32 seg = A.indeg[id], rank = A.osucc[id], u = v.slot_of(id);
+    if (seg >= ns || u >= v.slot_cap()) { atomicOr(A.err, 4u); return; }
+    const agx_u32 at = A.s_off[seg] + rank;
+    const char c = (char)A.n_base[u];
+    if (at < A.s_off[seg + 1] && at < A.seq_cap) A.seq[at] = c != 'X' ? c : A.ref[X];       // consensus, else the reference base (AG:1997-2001)
+    else atomicOr(A.err, 4u);
+    if (A.nxt[id] != AGX_NONE) return;
+    const agx_u32 lo = A.l_off[seg], hi = A.l_off[seg + 1];
+    const uint4 nx = *reinterpret_cast<const uint4 *>(A.n_next + (size_t)u * AGX_MAXE);
+    const agx_u32 t[AGX_MAXE] = {nx.x, nx.y, nx.z, nx.w};
+    agx_u32 k = 0;
+    for (agx_u32 e = 0; e < AGX_MAXE; e++) {
+        const agx_u32 lt = v.in_export(t[e]);          // (NONE is no slot)
+        if (lt == AGX_NONE) continue;
+        if (lo + k < hi && lo + k < A.link_cap) A.l_to[lo + k] = A.indeg[lt]; else atomicOr(A.err, 4u);
+        k++;
+    }
+    A.l_cur[seg] = k;
+}
+
+// the link of an overflow edge s -> d (ids of two nodes of the export) that is the first of its kind on the list
+__device__ __forceinline__ void ut_ovf_link(const agx_unitig_args &A, agx_u32 s, agx_u32 d) {
+    if (A.nxt[s] == d) return;                                          // the internal edge of a node whose only successor is on the list
+    const agx_u32 seg = A.indeg[s], ns = A.hoff[A.n_pos];
+    if (seg >= ns) { atomicOr(A.err, 4u); return; }
+    const agx_u32 at = A.l_off[seg] + atomicAdd(A.l_cur + seg, 1u);
+    if (at < A.l_off[seg + 1] && at < A.link_cap) A.l_to[at] = A.indeg[d]; else atomicOr(A.err, 4u);
+}
+
+// ---- whole export: a thread per position over its variants, or a wavefront per 64 slots -------------------------------------------------------------------------
 
 // pos_of[slot] for every used slot (pos_of was set to NONE before)
 __global__ void __launch_bounds__(256) agx_k_ut_pos(agx_unitig_args A) {
@@ -56,79 +212,19 @@ __global__ void __launch_bounds__(256) agx_k_ut_degrees(agx_unitig_args A) {
         A.outs[u] = cnt; A.succ[u] = last;
     }
 }
-
-// the overflow list: an edge may be listed more than once (two lanes that inserted it at the same time); the first to enter the hash set counts it
-__global__ void __launch_bounds__(256) agx_k_ut_ovf(agx_unitig_args A) {
-    const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= A.n_ovf) return;
-    A.ovf_first[i] = 0;
-    const agx_u32 s = A.ovf[i].src, d = A.ovf[i].dst;
-    if (s == AGX_NONE || d == AGX_NONE) return;
-    if (s >= A.pool_cap || d >= A.pool_cap) { atomicOr(A.err, 2u); return; }
-    if (!ut_alive(A, s) || !ut_alive(A, d)) return;
-    const agx_u32 sp = A.pos_of[s], dp = A.pos_of[d];
-    if (sp == AGX_NONE || dp == AGX_NONE || dp <= sp) { atomicOr(A.err, 1u); return; }
-    const unsigned long long key = ((unsigned long long)s << 32) | d;
-    agx_u32 h = (agx_u32)((key * 0x9E3779B97F4A7C15ull) >> 32) & A.hash_mask;
-    for (agx_u32 probe = 0; probe <= A.hash_mask; probe++) {          // (the set holds twice the list: a free cell is always found)
-        const unsigned long long old = atomicCAS(A.ovf_hash + h, ~0ull, key);
-        if (old == key) return;
-        if (old == ~0ull) {
-            A.ovf_first[i] = 1;
-            atomicAdd(A.indeg + d, 1u); atomicAdd(A.oout + s, 1u); A.osucc[s] = d;      // (osucc is only read where oout == 1)
-            return;
-        }
-        h = (h + 1u) & A.hash_mask;
-    }
-}
-
-// internal edges: nxt[u] = the one alive successor if it has one alive predecessor; outs[u] becomes the whole alive out-degree
+__global__ void __launch_bounds__(256) agx_k_ut_ovf(agx_unitig_args A) { ut_ovf_insert(ut_slots{A}, blockIdx.x * 256u + threadIdx.x); }
 __global__ void __launch_bounds__(256) agx_k_ut_internal(agx_unitig_args A) {
     const agx_u32 X = blockIdx.x * 256u + threadIdx.x;
     if (X >= A.n_pos) return;
     const agx_u32 s = A.node_start[X], n = A.node_cnt[X];
-    for (agx_u32 v = 0; v < n && s + v < A.pool_cap; v++) {
-        const agx_u32 u = s + v;
-        agx_u32 nx = AGX_NONE;
-        if (ut_alive(A, u)) {
-            const agx_u32 a = A.outs[u], b = A.oout[u], d = a + b;
-            const agx_u32 t = d != 1u ? AGX_NONE : a == 1u ? A.succ[u] : A.osucc[u];
-            if (t != AGX_NONE && t < A.pool_cap && A.indeg[t] == 1u) { nx = t; A.haspred[t] = 1; }
-            A.outs[u] = d;
-        }
-        A.nxt[u] = nx; A.succ[u] = AGX_NONE;          // (succ becomes the piece id of piece starts)
-    }
-}
-
-// a 64-slot window: which lanes are alive nodes, which continue into the next slot (internal edge u -> u+1), which start a piece
-struct ut_window { agx_u32 u, lane, nx; bool valid, link; unsigned long long lm, sm; };
-__device__ __forceinline__ ut_window ut_window_of(const agx_unitig_args &A) {
-    ut_window w;
-    w.u = blockIdx.x * 256u + threadIdx.x; w.lane = threadIdx.x & 63u;
-    w.valid = w.u < A.pool_cap && A.pos_of[w.u] != AGX_NONE && ut_alive(A, w.u);
-    w.nx = w.valid ? A.nxt[w.u] : AGX_NONE;
-    w.link = w.valid && w.lane < 63u && w.nx == w.u + 1u;
-    w.lm = __ballot(w.link);
-    const bool prev = w.lane > 0 && ((w.lm >> (w.lane - 1u)) & 1ull);
-    w.sm = __ballot(w.valid && !prev);
-    return w;
+    for (agx_u32 v = 0; v < n && s + v < A.pool_cap; v++) ut_internal_of(A, s + v, ut_alive(A, s + v));
 }
 
 __global__ void __launch_bounds__(256) agx_k_ut_piece_count(agx_unitig_args A) {
-    const ut_window w = ut_window_of(A);
+    const ut_window w = ut_window_of(ut_slots{A});
     if (w.lane == 0 && w.u < A.pool_cap) A.wcnt[w.u / 64u] = (agx_u32)__popcll(w.sm);
 }
-// (the ids come from a scan of the windows' counts: one atomic counter per wavefront cost 5.6 ms on a 30 Mb unit, every wavefront waiting for the same address)
-__global__ void __launch_bounds__(256) agx_k_ut_pieces(agx_unitig_args A) {
-    const ut_window w = ut_window_of(A);
-    const bool start = (w.sm >> w.lane) & 1ull;
-    const agx_u32 end = w.lane + (agx_u32)__builtin_ctzll(~w.lm >> w.lane);      // (bit 63 of ~lm is always set)
-    const agx_u32 nx_end = __shfl(w.nx, (int)end, 64);
-    if (!start) return;
-    const agx_u32 pid = A.woff[w.u / 64u] + (agx_u32)__popcll(w.sm & ((1ull << w.lane) - 1ull));
-    if (pid >= A.piece_cap) { atomicOr(A.err, 4u); return; }
-    A.p_len[pid] = end - w.lane + 1u; A.p_next[pid] = nx_end; A.succ[w.u] = pid;
-}
+__global__ void __launch_bounds__(256) agx_k_ut_pieces(agx_unitig_args A) { ut_cut(A, ut_window_of(ut_slots{A})); }
 
 // pointer jumping over the pieces: anc = predecessor piece (self for a head), off = nodes of the predecessor
 __global__ void __launch_bounds__(256) agx_k_ut_jump_init(agx_unitig_args A, agx_u32 np) {
@@ -178,29 +274,7 @@ __global__ void __launch_bounds__(256) agx_k_ut_head_assign(agx_unitig_args A, a
         seg++;
     }
 }
-
-// every node: its segment and rank; every tail: its segment's length, last position and link count; coverage summed per piece, one atomic per piece
-__global__ void __launch_bounds__(256) agx_k_ut_rank(agx_unitig_args A, agx_u32 np, agx_u32 fin) {
-    const ut_window w = ut_window_of(A);
-    const unsigned long long below = w.sm & ((2ull << w.lane) - 1ull);
-    const agx_u32 ps = below ? 63u - (agx_u32)__builtin_clzll(below) : 0u;
-    const bool start = (w.sm >> w.lane) & 1ull;
-    const agx_u32 pid_here = start ? A.succ[w.u] : AGX_NONE;
-    const agx_u32 pid = __shfl(pid_here, (int)ps, 64);
-    unsigned long long cov = w.valid ? (unsigned long long)(agx_u32)A.n_counts[(size_t)w.u * 6] : 0ull, incl = cov;
-    for (agx_u32 d = 1; d < 64u; d <<= 1) { const unsigned long long o = __shfl_up(incl, d, 64); if (w.lane >= d) incl += o; }
-    const unsigned long long excl_ps = __shfl(incl - cov, (int)ps, 64);
-    if (!w.valid) return;
-    if (pid >= np) { atomicOr(A.err, 4u); return; }
-    const agx_u32 h = A.anc[fin][pid];
-    if (h >= np || A.anc[fin][h] != h) { atomicOr(A.err, 4u); return; }       // (not converged: impossible on a DAG)
-    const agx_u32 seg = A.p_seg[h];
-    if (seg >= A.piece_cap) { atomicOr(A.err, 4u); return; }
-    const agx_u32 rank = A.off[fin][pid] + (w.lane - ps);
-    A.indeg[w.u] = seg; A.osucc[w.u] = rank;
-    if (!w.link) atomicAdd(A.s_cov + seg, incl - excl_ps);            // the piece's last node
-    if (w.nx == AGX_NONE) { A.s_len[seg] = rank + 1u; A.s_last[seg] = A.pos_of[w.u]; A.s_links[seg] = A.outs[w.u]; }
-}
+__global__ void __launch_bounds__(256) agx_k_ut_rank(agx_unitig_args A, agx_u32 np, agx_u32 fin) { ut_rank_of(ut_slots{A}, np, fin); }
 
 __global__ void agx_k_ut_totals(agx_unitig_args A, agx_u32 *tot) {
     if (threadIdx.x || blockIdx.x) return;
@@ -208,43 +282,18 @@ __global__ void agx_k_ut_totals(agx_unitig_args A, agx_u32 *tot) {
     tot[0] = ns; tot[1] = ns <= A.piece_cap ? A.s_off[ns] : 0u; tot[2] = ns <= A.piece_cap ? A.l_off[ns] : 0u; tot[3] = *A.err;
 }
 
-// bases at s_off[seg] + rank; a tail's inline links (the overflow list's follow in agx_k_ut_links_ovf)
 __global__ void __launch_bounds__(256) agx_k_ut_emit(agx_unitig_args A) {
     const agx_u32 X = blockIdx.x * 256u + threadIdx.x;
     if (X >= A.n_pos) return;
     const agx_u32 s = A.node_start[X], n = A.node_cnt[X];
     const agx_u32 ns = A.hoff[A.n_pos];
-    for (agx_u32 v = 0; v < n && s + v < A.pool_cap; v++) {
-        const agx_u32 u = s + v;
-        if (!ut_alive(A, u)) continue;
-        const agx_u32 seg = A.indeg[u], rank = A.osucc[u];
-        if (seg >= ns) { atomicOr(A.err, 4u); continue; }
-        const agx_u32 at = A.s_off[seg] + rank;
-        const char c = (char)A.n_base[u];
-        if (at < A.s_off[seg + 1] && at < A.seq_cap) A.seq[at] = c != 'X' ? c : A.ref[X];       // consensus, else the reference base (AG:1997-2001)
-        else atomicOr(A.err, 4u);
-        if (A.nxt[u] != AGX_NONE) continue;
-        const agx_u32 lo = A.l_off[seg], hi = A.l_off[seg + 1];
-        const uint4 nx = *reinterpret_cast<const uint4 *>(A.n_next + (size_t)u * AGX_MAXE);
-        const agx_u32 t[AGX_MAXE] = {nx.x, nx.y, nx.z, nx.w};
-        agx_u32 k = 0;
-        for (agx_u32 e = 0; e < AGX_MAXE; e++) {
-            if (t[e] == AGX_NONE || t[e] >= A.pool_cap || !ut_alive(A, t[e])) continue;
-            if (lo + k < hi && lo + k < A.link_cap) A.l_to[lo + k] = A.indeg[t[e]]; else atomicOr(A.err, 4u);
-            k++;
-        }
-        A.l_cur[seg] = k;
-    }
+    for (agx_u32 v = 0; v < n && s + v < A.pool_cap; v++)
+        if (ut_alive(A, s + v)) ut_emit_node(ut_slots{A}, s + v, X, ns);
 }
 __global__ void __launch_bounds__(256) agx_k_ut_links_ovf(agx_unitig_args A) {
     const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
     if (i >= A.n_ovf || !A.ovf_first[i]) return;
-    const agx_u32 s = A.ovf[i].src, d = A.ovf[i].dst;                 // (both alive and in the pool: agx_k_ut_ovf)
-    if (A.nxt[s] == d) return;                                          // the internal edge of a node whose only successor is on the list
-    const agx_u32 seg = A.indeg[s], ns = A.hoff[A.n_pos];
-    if (seg >= ns) { atomicOr(A.err, 4u); return; }
-    const agx_u32 at = A.l_off[seg] + atomicAdd(A.l_cur + seg, 1u);
-    if (at < A.l_off[seg + 1] && at < A.link_cap) A.l_to[at] = A.indeg[d]; else atomicOr(A.err, 4u);
+    ut_ovf_link(A, A.ovf[i].src, A.ovf[i].dst);                        // (both alive and in the pool: agx_k_ut_ovf)
 }
 // each segment's links by target segment (link_from is filled on the host from the offsets) (a few per tail; the overflow list's nodes have more), insertion sort in the segment's own range
 __global__ void __launch_bounds__(256) agx_k_ut_links_sort(agx_unitig_args A) {
@@ -264,17 +313,7 @@ __global__ void __launch_bounds__(256) agx_k_ut_links_sort(agx_unitig_args A) {
 // The same graph definition on a sub-graph: the nodes of the window's positions that are alive at the caller's coverage, and the edges between two of them.  No grid below
 // is sized by the unit: one thread per position of the window (count, compact), per kept node (everything else) or per overflow entry (the list has no position index).
 // Kept nodes are numbered densely in (position, variant) order, so a wavefront takes 64 consecutive local ids, "the internal edge goes to the next id" is the common case
-// as it is for slots in the whole export, and heads are numbered by a scan over the 64-id groups.  R.U is the local view the piece kernels above run on unchanged.
-
-__device__ __forceinline__ bool utr_kept(const agx_unitig_region_args &R, agx_u32 slot) {      // AG:1904-1918 with the caller's threshold
-    return R.nk_cid[slot] != AGX_NONE || (long long)R.U.n_counts[(size_t)slot * 6] >= (long long)R.min_cov;
-}
-// local id of a slot (< R.pool_cap), NONE if the slot is not in the export.  rmap holds whatever the last export of any kind left in it: an entry counts only if the
-// local id it names points back at the slot
-__device__ __forceinline__ agx_u32 utr_local(const agx_unitig_region_args &R, agx_u32 slot) {
-    const agx_u32 r = R.rmap[slot];
-    return r < R.U.pool_cap && R.l_slot[r] == slot ? r : AGX_NONE;
-}
+// as it is for slots in the whole export, and heads are numbered by a scan over the 64-id groups.  R.U is the local view the jumping, totals and link-sort kernels run on unchanged.
 
 __global__ void __launch_bounds__(256) agx_k_utr_count(agx_unitig_region_args R) {
     const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
@@ -314,7 +353,7 @@ __global__ void __launch_bounds__(256) agx_k_utr_degrees(agx_unitig_region_args 
         for (agx_u32 e = 0; e < AGX_MAXE; e++) {
             if (t[e] == AGX_NONE) continue;
             if (t[e] >= R.pool_cap) { atomicOr(R.U.err, 2u); continue; }
-            const agx_u32 lt = utr_local(R, t[e]);
+            const agx_u32 lt = ut_locals{R}.in_export(t[e]);
             if (lt == AGX_NONE) continue;                                    // pruned at this threshold, or across the window's border
             if (R.U.pos_of[lt] <= X) { atomicOr(R.U.err, 1u); continue; }
             cnt++; last = lt;
@@ -323,68 +362,19 @@ __global__ void __launch_bounds__(256) agx_k_utr_degrees(agx_unitig_region_args 
     } else atomicOr(R.U.err, 2u);
     R.U.outs[id] = cnt; R.U.succ[id] = last;
 }
-__global__ void __launch_bounds__(256) agx_k_utr_ovf(agx_unitig_region_args R) {
-    const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= R.U.n_ovf) return;
-    R.U.ovf_first[i] = 0;
-    const agx_u32 s = R.U.ovf[i].src, d = R.U.ovf[i].dst;
-    if (s == AGX_NONE || d == AGX_NONE) return;
-    if (s >= R.pool_cap || d >= R.pool_cap) { atomicOr(R.U.err, 2u); return; }
-    const agx_u32 ls = utr_local(R, s), ld = utr_local(R, d);
-    if (ls == AGX_NONE || ld == AGX_NONE) return;
-    if (R.U.pos_of[ld] <= R.U.pos_of[ls]) { atomicOr(R.U.err, 1u); return; }
-    const unsigned long long key = ((unsigned long long)ls << 32) | ld;
-    agx_u32 h = (agx_u32)((key * 0x9E3779B97F4A7C15ull) >> 32) & R.U.hash_mask;
-    for (agx_u32 probe = 0; probe <= R.U.hash_mask; probe++) {          // (the set holds twice the list: a free cell is always found)
-        const unsigned long long old = atomicCAS(R.U.ovf_hash + h, ~0ull, key);
-        if (old == key) return;
-        if (old == ~0ull) {
-            R.U.ovf_first[i] = 1;
-            atomicAdd(R.U.indeg + ld, 1u); atomicAdd(R.U.oout + ls, 1u); R.U.osucc[ls] = ld;
-            return;
-        }
-        h = (h + 1u) & R.U.hash_mask;
-    }
-}
+__global__ void __launch_bounds__(256) agx_k_utr_ovf(agx_unitig_region_args R) { ut_ovf_insert(ut_locals{R}, blockIdx.x * 256u + threadIdx.x); }
 __global__ void __launch_bounds__(256) agx_k_utr_internal(agx_unitig_region_args R) {
     const agx_u32 id = blockIdx.x * 256u + threadIdx.x;
-    if (id >= R.U.pool_cap) return;
-    const agx_u32 a = R.U.outs[id], b = R.U.oout[id], d = a + b;
-    const agx_u32 t = d != 1u ? AGX_NONE : a == 1u ? R.U.succ[id] : R.U.osucc[id];
-    agx_u32 nx = AGX_NONE;
-    if (t != AGX_NONE && t < R.U.pool_cap && R.U.indeg[t] == 1u) { nx = t; R.U.haspred[t] = 1; }
-    R.U.outs[id] = d; R.U.nxt[id] = nx; R.U.succ[id] = AGX_NONE;
+    if (id < R.U.pool_cap) ut_internal_of(R.U, id, true);
 }
 
-// 64 consecutive local ids (all of them nodes of the export, up to the last group's tail)
-__device__ __forceinline__ ut_window utr_window_of(const agx_unitig_args &A) {
-    ut_window w;
-    w.u = blockIdx.x * 256u + threadIdx.x; w.lane = threadIdx.x & 63u;
-    w.valid = w.u < A.pool_cap;
-    w.nx = w.valid ? A.nxt[w.u] : AGX_NONE;
-    w.link = w.valid && w.lane < 63u && w.nx == w.u + 1u;
-    w.lm = __ballot(w.link);
-    const bool prev = w.lane > 0 && ((w.lm >> (w.lane - 1u)) & 1ull);
-    w.sm = __ballot(w.valid && !prev);
-    return w;
-}
 // pieces and heads per group (a head starts a piece: a lane behind a link has an internal predecessor)
 __global__ void __launch_bounds__(256) agx_k_utr_group_count(agx_unitig_region_args R) {
-    const ut_window w = utr_window_of(R.U);
+    const ut_window w = ut_window_of(ut_locals{R});      // (64 consecutive local ids: all of them nodes of the export, up to the last group's tail)
     const unsigned long long hm = __ballot(w.valid && !R.U.haspred[w.valid ? w.u : 0u]);
     if (w.lane == 0 && w.valid) { R.U.wcnt[w.u / 64u] = (agx_u32)__popcll(w.sm); R.U.hcnt[w.u / 64u] = (agx_u32)__popcll(hm); }
 }
-__global__ void __launch_bounds__(256) agx_k_utr_pieces(agx_unitig_region_args R) {
-    const agx_unitig_args &A = R.U;
-    const ut_window w = utr_window_of(A);
-    const bool start = (w.sm >> w.lane) & 1ull;
-    const agx_u32 end = w.lane + (agx_u32)__builtin_ctzll(~w.lm >> w.lane);      // (bit 63 of ~lm is always set)
-    const agx_u32 nx_end = __shfl(w.nx, (int)end, 64);
-    if (!start) return;
-    const agx_u32 pid = A.woff[w.u / 64u] + (agx_u32)__popcll(w.sm & ((1ull << w.lane) - 1ull));
-    if (pid >= A.piece_cap) { atomicOr(A.err, 4u); return; }
-    A.p_len[pid] = end - w.lane + 1u; A.p_next[pid] = nx_end; A.succ[w.u] = pid;
-}
+__global__ void __launch_bounds__(256) agx_k_utr_pieces(agx_unitig_region_args R) { ut_cut(R.U, ut_window_of(ut_locals{R})); }
 __global__ void __launch_bounds__(256) agx_k_utr_head_assign(agx_unitig_region_args R, agx_u32 np) {
     const agx_unitig_args &A = R.U;
     const agx_u32 u = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
@@ -396,66 +386,20 @@ __global__ void __launch_bounds__(256) agx_k_utr_head_assign(agx_unitig_region_a
     const agx_u32 X = A.pos_of[u];
     A.p_seg[p] = seg; A.s_hpos[seg] = X; A.s_hvar[seg] = R.l_slot[u] - A.node_start[X];      // the variant index among ALL of the position's variants
 }
-__global__ void __launch_bounds__(256) agx_k_utr_rank(agx_unitig_region_args R, agx_u32 np, agx_u32 fin) {
-    const agx_unitig_args &A = R.U;
-    const ut_window w = utr_window_of(A);
-    const unsigned long long below = w.sm & ((2ull << w.lane) - 1ull);
-    const agx_u32 ps = below ? 63u - (agx_u32)__builtin_clzll(below) : 0u;
-    const bool start = (w.sm >> w.lane) & 1ull;
-    const agx_u32 pid_here = start ? A.succ[w.u] : AGX_NONE;
-    const agx_u32 pid = __shfl(pid_here, (int)ps, 64);
-    const agx_u32 slot = w.valid ? R.l_slot[w.u] : AGX_NONE;
-    unsigned long long cov = slot < R.pool_cap ? (unsigned long long)(agx_u32)A.n_counts[(size_t)slot * 6] : 0ull, incl = cov;
-    for (agx_u32 d = 1; d < 64u; d <<= 1) { const unsigned long long o = __shfl_up(incl, d, 64); if (w.lane >= d) incl += o; }
-    const unsigned long long excl_ps = __shfl(incl - cov, (int)ps, 64);
-    if (!w.valid) return;
-    if (pid >= np) { atomicOr(A.err, 4u); return; }
-    const agx_u32 h = A.anc[fin][pid];
-    if (h >= np || A.anc[fin][h] != h) { atomicOr(A.err, 4u); return; }       // (not converged: impossible on a DAG)
-    const agx_u32 seg = A.p_seg[h];
-    if (seg >= A.piece_cap) { atomicOr(A.err, 4u); return; }
-    const agx_u32 rank = A.off[fin][pid] + (w.lane - ps);
-    A.indeg[w.u] = seg; A.osucc[w.u] = rank;
-    if (!w.link) atomicAdd(A.s_cov + seg, incl - excl_ps);            // the piece's last node
-    if (w.nx == AGX_NONE) { A.s_len[seg] = rank + 1u; A.s_last[seg] = A.pos_of[w.u]; A.s_links[seg] = A.outs[w.u]; }
-}
+__global__ void __launch_bounds__(256) agx_k_utr_rank(agx_unitig_region_args R, agx_u32 np, agx_u32 fin) { ut_rank_of(ut_locals{R}, np, fin); }
 __global__ void __launch_bounds__(256) agx_k_utr_emit(agx_unitig_region_args R) {
-    const agx_unitig_args &A = R.U;
     const agx_u32 id = blockIdx.x * 256u + threadIdx.x;
-    if (id >= A.pool_cap) return;
-    const agx_u32 ns = A.hoff[A.n_pos], seg = A.indeg[id], rank = A.osucc[id], u = R.l_slot[id], X = A.pos_of[id];
-    if (seg >= ns || u >= R.pool_cap) { atomicOr(A.err, 4u); return; }
-    const agx_u32 at = A.s_off[seg] + rank;
-    const char c = (char)A.n_base[u];
-    if (at < A.s_off[seg + 1] && at < A.seq_cap) A.seq[at] = c != 'X' ? c : A.ref[X];
-    else atomicOr(A.err, 4u);
-    if (A.nxt[id] != AGX_NONE) return;
-    const agx_u32 lo = A.l_off[seg], hi = A.l_off[seg + 1];
-    const uint4 nx = *reinterpret_cast<const uint4 *>(A.n_next + (size_t)u * AGX_MAXE);
-    const agx_u32 t[AGX_MAXE] = {nx.x, nx.y, nx.z, nx.w};
-    agx_u32 k = 0;
-    for (agx_u32 e = 0; e < AGX_MAXE; e++) {
-        if (t[e] == AGX_NONE || t[e] >= R.pool_cap) continue;
-        const agx_u32 lt = utr_local(R, t[e]);
-        if (lt == AGX_NONE) continue;
-        if (lo + k < hi && lo + k < A.link_cap) A.l_to[lo + k] = A.indeg[lt]; else atomicOr(A.err, 4u);
-        k++;
-    }
-    A.l_cur[seg] = k;
+    if (id < R.U.pool_cap) ut_emit_node(ut_locals{R}, id, R.U.pos_of[id], R.U.hoff[R.U.n_pos]);
 }
 __global__ void __launch_bounds__(256) agx_k_utr_links_ovf(agx_unitig_region_args R) {
     const agx_unitig_args &A = R.U;
     const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
     if (i >= A.n_ovf || !A.ovf_first[i]) return;
-    const agx_u32 s = A.ovf[i].src, d = A.ovf[i].dst;                 // (both in the pool and in the export: agx_k_utr_ovf)
+    const agx_u32 s = A.ovf[i].src, d = A.ovf[i].dst;                 // (both in the pool and in the export: agx_k_utr_ovf; looked at again, since the ids have to be looked up anyway)
     if (s >= R.pool_cap || d >= R.pool_cap) { atomicOr(A.err, 4u); return; }
-    const agx_u32 ls = utr_local(R, s), ld = utr_local(R, d);
+    const agx_u32 ls = ut_locals{R}.in_export(s), ld = ut_locals{R}.in_export(d);
     if (ls == AGX_NONE || ld == AGX_NONE) { atomicOr(A.err, 4u); return; }
-    if (A.nxt[ls] == ld) return;
-    const agx_u32 seg = A.indeg[ls], ns = A.hoff[A.n_pos];
-    if (seg >= ns) { atomicOr(A.err, 4u); return; }
-    const agx_u32 at = A.l_off[seg] + atomicAdd(A.l_cur + seg, 1u);
-    if (at < A.l_off[seg + 1] && at < A.link_cap) A.l_to[at] = A.indeg[ld]; else atomicOr(A.err, 4u);
+    ut_ovf_link(A, ls, ld);
 }
 
 // ---- id map of a region export (agx_unit_unitigs_mapped, agx_kargs.h: agx_idmap_args) ------------------------------------------------------------------------
@@ -480,7 +424,7 @@ __device__ __forceinline__ idm_entry idm_entry_of(const agx_unitig_region_args &
     if (a >= M.n_ids) return e;
     const agx_u32 slot = M.a_nid[a];
     if (slot >= R.pool_cap) return e;                    // NONE: a main id without a node
-    const agx_u32 l = utr_local(R, slot);
+    const agx_u32 l = ut_locals{R}.in_export(slot);
     if (l == AGX_NONE) return e;                         // dead at this coverage
     const agx_u32 X = R.U.pos_of[l];
     if (X != (i < M.n_main ? a : M.side_xpos[a - M.n_pos])) { atomicOr(R.U.err, 8u); return e; }      // (the id's position is its node's: main ids are positions)
@@ -551,26 +495,6 @@ extern "C" void agx_launch_unitig_region_phase1(const agx_unitig_region_args *R,
     hipLaunchKernelGGL(agx_k_utr_pieces, ut_grid(ngrp * 64u), dim3(256), 0, st, *R);
 }
 
-extern "C" void agx_launch_unitig_region_phase2(const agx_unitig_region_args *R, agx_u32 rounds, hipStream_t st) {
-    const agx_unitig_args *A = &R->U;
-    const agx_u32 np = A->piece_cap, ngrp = A->n_pos;
-    if (!np) return;
-    hipLaunchKernelGGL(agx_k_ut_jump_init, ut_grid(np), dim3(256), 0, st, *A, np);
-    hipLaunchKernelGGL(agx_k_ut_jump_link, ut_grid(np), dim3(256), 0, st, *A, np);
-    for (agx_u32 r = 0; r < rounds; r++) hipLaunchKernelGGL(agx_k_ut_jump, ut_grid(np), dim3(256), 0, st, *A, np, r);
-    hipLaunchKernelGGL(agx_k_utr_head_assign, ut_grid(ngrp * 64u), dim3(256), 0, st, *R, np);
-    hipLaunchKernelGGL(agx_k_utr_rank, ut_grid(ngrp * 64u), dim3(256), 0, st, *R, np, rounds & 1u);
-    agx_launch_exclusive_scan(A->s_len, A->s_off, np, A->scan_tmp, st);          // (s_off and l_off lie over the pointer jumping's arrays, which the rank kernel was the last to read)
-    agx_launch_exclusive_scan(A->s_links, A->l_off, np, A->scan_tmp, st);
-}
-
-extern "C" void agx_launch_unitig_region_phase3(const agx_unitig_region_args *R, hipStream_t st) {
-    if (!R->U.pool_cap) return;
-    hipLaunchKernelGGL(agx_k_utr_emit, ut_grid(R->U.pool_cap), dim3(256), 0, st, *R);
-    if (R->U.n_ovf) hipLaunchKernelGGL(agx_k_utr_links_ovf, ut_grid(R->U.n_ovf), dim3(256), 0, st, *R);
-    if (R->U.piece_cap) hipLaunchKernelGGL(agx_k_ut_links_sort, ut_grid(R->U.piece_cap), dim3(256), 0, st, R->U);
-}
-
 extern "C" void agx_launch_unitig_phase1(const agx_unitig_args *A, hipStream_t st) {
     if (A->n_pos) {
         hipLaunchKernelGGL(agx_k_ut_pos, ut_grid(A->n_pos), dim3(256), 0, st, *A);
@@ -586,26 +510,36 @@ extern "C" void agx_launch_unitig_phase1(const agx_unitig_args *A, hipStream_t s
     }
 }
 
-extern "C" void agx_launch_unitig_phase2(const agx_unitig_args *A, agx_u32 rounds, hipStream_t st) {
+// phases 2 and 3 of either form.  R: the region export whose local view A is (A == &R->U, with its pieces: the host has refused a window without any); nullptr: the whole export
+extern "C" void agx_launch_unitig_phase2(const agx_unitig_args *A, const agx_unitig_region_args *R, agx_u32 rounds, hipStream_t st) {
     const agx_u32 np = A->piece_cap;
     if (np) {
         hipLaunchKernelGGL(agx_k_ut_jump_init, ut_grid(np), dim3(256), 0, st, *A, np);
         hipLaunchKernelGGL(agx_k_ut_jump_link, ut_grid(np), dim3(256), 0, st, *A, np);
         for (agx_u32 r = 0; r < rounds; r++) hipLaunchKernelGGL(agx_k_ut_jump, ut_grid(np), dim3(256), 0, st, *A, np, r);
     }
-    if (A->n_pos) {
+    if (R) {          // (heads were counted per 64-id group with the pieces; A->n_pos is the groups)
+        if (np) hipLaunchKernelGGL(agx_k_utr_head_assign, ut_grid(A->n_pos * 64u), dim3(256), 0, st, *R, np);
+    } else if (A->n_pos) {
         hipLaunchKernelGGL(agx_k_ut_head_count, ut_grid(A->n_pos), dim3(256), 0, st, *A);
         agx_launch_exclusive_scan(A->hcnt, A->hoff, A->n_pos, A->scan_tmp, st);
         hipLaunchKernelGGL(agx_k_ut_head_assign, ut_grid(A->n_pos), dim3(256), 0, st, *A, np);
     }
-    if (np) hipLaunchKernelGGL(agx_k_ut_rank, ut_grid((A->pool_cap + 63u) / 64u * 64u), dim3(256), 0, st, *A, np, rounds & 1u);
-    agx_launch_exclusive_scan(A->s_len, A->s_off, np, A->scan_tmp, st);
+    if (np) {
+        if (R) hipLaunchKernelGGL(agx_k_utr_rank, ut_grid(A->n_pos * 64u), dim3(256), 0, st, *R, np, rounds & 1u);
+        else hipLaunchKernelGGL(agx_k_ut_rank, ut_grid((A->pool_cap + 63u) / 64u * 64u), dim3(256), 0, st, *A, np, rounds & 1u);
+    }
+    agx_launch_exclusive_scan(A->s_len, A->s_off, np, A->scan_tmp, st);          // (the region's s_off and l_off lie over the pointer jumping's arrays, which the rank kernel was the last to read)
     agx_launch_exclusive_scan(A->s_links, A->l_off, np, A->scan_tmp, st);
 }
 
-extern "C" void agx_launch_unitig_phase3(const agx_unitig_args *A, hipStream_t st) {
-    if (A->n_pos) hipLaunchKernelGGL(agx_k_ut_emit, ut_grid(A->n_pos), dim3(256), 0, st, *A);
-    if (A->n_ovf) hipLaunchKernelGGL(agx_k_ut_links_ovf, ut_grid(A->n_ovf), dim3(256), 0, st, *A);
+extern "C" void agx_launch_unitig_phase3(const agx_unitig_args *A, const agx_unitig_region_args *R, hipStream_t st) {
+    if (R) { if (A->pool_cap) hipLaunchKernelGGL(agx_k_utr_emit, ut_grid(A->pool_cap), dim3(256), 0, st, *R); }
+    else if (A->n_pos) hipLaunchKernelGGL(agx_k_ut_emit, ut_grid(A->n_pos), dim3(256), 0, st, *A);
+    if (A->n_ovf) {
+        if (R) hipLaunchKernelGGL(agx_k_utr_links_ovf, ut_grid(A->n_ovf), dim3(256), 0, st, *R);
+        else hipLaunchKernelGGL(agx_k_ut_links_ovf, ut_grid(A->n_ovf), dim3(256), 0, st, *A);
+    }
     if (A->piece_cap) hipLaunchKernelGGL(agx_k_ut_links_sort, ut_grid(A->piece_cap), dim3(256), 0, st, *A);
 }
 
