@@ -26,7 +26,7 @@ EXPORTS = [
     "agx_unit_stage", "agx_unit_release", "agx_pool_trim", "agx_unit_cache_build", "agx_unit_cache_save", "agx_unit_hbm_needed",
     "agx_unit_trim", "agx_unit_unitigs", "agx_unit_unitigs_region", "agx_unitigs_free", "agx_unitigs_gfa", "agx_text_free",
     "agx_unit_walk_graph", "agx_walk_graph_free", "agx_unit_front", "agx_front_free",
-    "agx_unit_unitigs_mapped", "agx_idmap_free", "agx_unit_walk_paths", "agx_walk_paths_free", "agx_unitigs_paths_gfa",
+    "agx_unit_unitigs_mapped", "agx_idmap_free", "agx_unit_walk_paths", "agx_walk_paths_free", "agx_unitigs_paths_gfa", "agx_unit_reprune",
 ]
 
 
@@ -71,7 +71,7 @@ class Stats(ctypes.Structure):
                [(n, ctypes.c_double) for n in ("ms_stage", "ms_upload_dev")] + \
                [(n, ctypes.c_uint64) for n in ("upload_bytes", "device_bytes", "pinned_bytes_cached", "device_bytes_cached", "n_spilled")] + \
                [("build_attempts", ctypes.c_uint32), ("from_cache", ctypes.c_uint32), ("dense_lists", ctypes.c_uint32), ("rows_by_reference", ctypes.c_uint32)] + \
-               [("n_edge_slow", ctypes.c_uint64)]
+               [("n_edge_slow", ctypes.c_uint64), ("reprune_attempts", ctypes.c_uint32), ("ms_reprune", ctypes.c_double)]
 
 
 class Graph(ctypes.Structure):
@@ -201,6 +201,7 @@ def lib():
         L.agx_pool_trim.restype = None
         for f in ("agx_unit_upload", "agx_unit_build", "agx_unit_download", "agx_unit_stage", "agx_unit_release"):
             getattr(L, f).argtypes = [ctypes.c_void_p]
+        L.agx_unit_reprune.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
         L.agx_unit_finish.argtypes = [ctypes.c_void_p, ctypes.POINTER(Result)]
         L.agx_result_free.argtypes = [ctypes.POINTER(Result)]
         L.agx_result_free.restype = None
@@ -384,6 +385,14 @@ class Unit:
 
     def build(self):
         self._check(lib().agx_unit_build(self._h))
+
+    def reprune(self, coverage):
+        """Re-prunes the built unit at another coverage without building it again (agx_unit_reprune; needs keep_counts): afterwards the unit is what build() leaves on a
+        unit created with that coverage, and params.coverage follows, so gfa(region=...) without a threshold keeps meaning "the unit's own coverage"."""
+        if not 0 <= int(coverage) <= 0xFFFFFFFF:
+            raise AgxError(AGX_E_ARG, "reprune: coverage is an unsigned 32-bit number")
+        self._check(lib().agx_unit_reprune(self._h, int(coverage)))
+        self.params.coverage = int(coverage)
 
     def download(self):
         self._check(lib().agx_unit_download(self._h))

@@ -1025,6 +1025,36 @@ AGX_HD agx_u32 agx_node_write_lane(const agx_sweep_args &A, agx_u32 X, const agx
 static_assert(63u * (AGX_MAXV_HUGE - 1u) < 65536u && AGX_MAXV_HUGE <= 65535u, "side ids of a tile's first 63 positions must fit 16 bits");
 AGX_HD agx_u32 agx_side_pack(agx_u32 before_in_tile, agx_u32 here) { return before_in_tile | (here << 16); }
 
+// ---- reprune: the prune of a built node table at another coverage (agx_unit_reprune) -------------------------------------
+// Coverage decides one bit per node (AGX_NF_DEAD above) and the side-id counts that follow from it; keys, votes, bases and edges do not look at it, and the
+// table keeps the pruned nodes with their counts (n_counts: units created with AGX_FLAG_KEEP_COUNTS).  So the walk graph at another coverage is this pass over
+// the positions plus a second run of the walk preparation below.
+struct agx_reprune_args {
+    const agx_u32 *node_start; const agx_u16 *node_cnt;      // [n_pos]
+    const agx_u32 *nk_cid; const int *n_counts;              // per node slot: contigID, and coverage at n_counts[slot * 6]
+    agx_u8 *n_flags;                                         // per node slot: only AGX_NF_DEAD is rewritten
+    agx_u32 *side_pk, *tile_side;                            // [n_pos], [n_tiles]: what the node sweep's write-out leaves (agx_side_pack)
+    agx_u32 n_pos, pool_cap; int coverage;                   // pool_cap: the node slots the arrays hold
+    const agx_u32 *abort;                                    // device only: the build's status word (non-zero: the node table is incomplete, the kernel does nothing)
+};
+// position X: the DEAD bit of each of its variants by agx_node_write_lane's rule (signed comparison), every other bit of the byte kept.
+// Returns the position's side ids, as agx_node_write_lane does.
+AGX_HD agx_u32 agx_reprune_lane(const agx_reprune_args &A, agx_u32 X) {
+    if (X >= A.n_pos) return 0;
+    const agx_u32 s = A.node_start[X]; agx_u32 n = A.node_cnt[X];
+    if (n > AGX_MAXV_HUGE) n = AGX_MAXV_HUGE;             // (no position holds more, no variant lies behind the pool: the bounds do not rest on the table being intact)
+    if (s >= A.pool_cap) n = 0; else if (n > A.pool_cap - s) n = A.pool_cap - s;
+    agx_u32 alive = 0;
+    for (agx_u32 v = 0; v < n; v++) {
+        const agx_u32 id = s + v;
+        const bool dead = A.nk_cid[id] == AGX_NONE && A.n_counts[(size_t)id * 6] < A.coverage;
+        const agx_u8 fl = A.n_flags[id], want = (agx_u8)(dead ? (fl | AGX_NF_DEAD) : (fl & ~AGX_NF_DEAD));
+        if (want != fl) A.n_flags[id] = want;
+        alive += dead ? 0u : 1u;
+    }
+    return alive ? alive - 1 : 0;
+}
+
 // ---- edge sweep (AG:1589-1623) ---------------------------------------------------------------------------------
 
 struct agx_edge_ovf { agx_u32 src, dst; };

@@ -1209,6 +1209,37 @@ void start_helper(agx_unit *u) {
     u->helper.submit(UnitHelper::OUT, [u] { const double th0 = now_ms(); prepare_outputs(u); trace(u, "helper: output buffers", th0, u->V.n_pos); });      // (no helper: finish prepares the outputs itself)
 }
 
+// The back of a build behind its edge passes, and all of a reprune behind its kernel: the walk preparation over the side counts in side_pk / tile_side (side counts ->
+// scan -> walk ids, node records, rewritten edges, forced-run flags -> special ids with the stream cuts), then the counters to the host by a kernel at the end of the chain
+// and the event their reader waits for.  before_counters: what the caller records between the two (a build: its section mark and the device's build_done event).
+// Assumes zeroed: a_mark (agx_k_assign_aid and agx_k_emit_alive only ever store 1), sp_bits and sp_cnt (agx_k_special_bits writes the words of the live ids only),
+// tile_side[n_tiles] (the scan's closing entry) and the descriptors of the two scans.  Every other array it writes it writes for every live id, node or special record.
+template <class F> void queue_walk_prep(agx_unit *u, hipStream_t st, F before_counters) {
+    const agx_u32 n_pos = (agx_u32)u->V.n_pos;
+    agx_compact_args C; memset(&C, 0, sizeof C);
+    C.node_start = u->d_node_start.p; C.node_cnt = u->d_node_cnt.p; C.n_flags = u->d_flags.p; C.n_base = u->d_base.p;
+    C.nk_off0 = u->d_off0.p; C.n_sref = u->d_sref.p; C.n_next = u->d_next.p; C.ref = u->d_ref.p; C.n_pos = n_pos;
+    C.side_pk = u->d_side_pk.p; C.tile_side_start = u->d_tile_side_start.p; C.aid_of = u->d_aid_of.p;
+    C.a_str = u->d_a_str.p; C.a_meta = u->d_a_meta.p; C.a_nid = u->d_a_nid.p; C.ovf = u->d_ovf.p; C.n_ovf = 0; C.a_ovf = u->d_a_ovf.p;
+    C.abort = u->d_words.p + W_STATUS;
+    C.a_mark = u->d_a_mark.p; C.side_xpos = u->d_side_xpos.p; C.sparse_min = (u->prm.flags & AGX_FLAG_SPARSE_MIN) ? 1u : 0u;
+    C.sp_bits = u->d_sp_bits.p; C.sp_cnt = u->d_sp_cnt.p; C.sp_rank = u->d_sp_rank.p; C.sp_node = u->d_sp_node.p; C.sp_cap = u->sp_cap;
+    C.segs = u->d_segs.p; C.n_seg0 = u->n_seg0; C.cm_start = u->d_cm_start.p; C.sp_hop = u->d_sp_hop.p; C.seg_index = u->d_segindex.p;
+    if (g_scan1) agx_launch_exclusive_scan1(u->d_tile_side.p, u->d_tile_side_start.p, u->n_tiles, u->d_scan_desc.p + u->scan_desc_n, st);
+    else agx_launch_exclusive_scan(u->d_tile_side.p, u->d_tile_side_start.p, u->n_tiles, u->d_scan_tmp.p, st);      // per tile: the sweep has scanned inside the tiles
+    agx_launch_compact(&C, u->d_chain_end.p, u->n_chain_end, u->d_words.p + W_OVFCOUNT, u->ovf_cap, st);
+    AGX_CHECKPOINT("compact");
+    u->cuts = stream_cuts(n_pos); u->cuts.cut_out = u->d_words.p + W_CUT;
+    agx_launch_special(&C, u->n_words, u->d_sp_rank.p, u->d_scan_tmp.p, g_scan1 ? u->d_scan_desc.p + 2 * u->scan_desc_n : nullptr,
+                       u->d_words.p + W_N, u->d_tile_off.p + u->n_tiles, u->d_tile_side_start.p + u->n_tiles, u->d_pool_cnt.p, u->n_regions, u->d_words.p + W_POOL, u->cuts.n ? &u->cuts : nullptr, st);
+    u->walk_args = C;
+    AGX_CHECKPOINT("special");
+    before_counters();
+    {   void *dst = u->h_words.dev(); const void *src = u->d_words.p; const size_t bytes = W_TOTAL * 4;      // the counters, by a kernel at the end of the chain (a copy
+        agx_launch_copy_out(&dst, &src, &bytes, 1, st); }                                                              // command would queue behind the uploads on the copy engines)
+    HIP_OK(hipEventRecord(u->ev_built, st));
+}
+
 // All kernels of one build are queued back to back with the current buffer capacities; the counters they produce (tile-list
 // entries, nodes, overflowed tiles, edge overflow, side variants) are read after ONE synchronisation.  A capacity that proved too
 // small is grown and the build repeats — the first guesses (do_upload) are made so that this is rare.
@@ -1360,33 +1391,13 @@ void do_build(agx_unit *u) {
         AGX_CHECKPOINT("edge_slow");
         u->ev.mark(B_SLOW, st);
         if (side_j) HIP_OK(hipStreamWaitEvent(st, u->ev_passJ, 0));
-        // ---- walk preparation: side counts -> scan -> walk ids, node records, rewritten edges, forced-run flags ----
-        agx_compact_args C; memset(&C, 0, sizeof C);
-        C.node_start = u->d_node_start.p; C.node_cnt = u->d_node_cnt.p; C.n_flags = u->d_flags.p; C.n_base = u->d_base.p;
-        C.nk_off0 = u->d_off0.p; C.n_sref = u->d_sref.p; C.n_next = u->d_next.p; C.ref = u->d_ref.p; C.n_pos = n_pos;
-        C.side_pk = u->d_side_pk.p; C.tile_side_start = u->d_tile_side_start.p; C.aid_of = u->d_aid_of.p;
-        C.a_str = u->d_a_str.p; C.a_meta = u->d_a_meta.p; C.a_nid = u->d_a_nid.p; C.ovf = u->d_ovf.p; C.n_ovf = 0; C.a_ovf = u->d_a_ovf.p;
-        C.abort = u->d_words.p + W_STATUS;
-        C.a_mark = u->d_a_mark.p; C.side_xpos = u->d_side_xpos.p; C.sparse_min = (u->prm.flags & AGX_FLAG_SPARSE_MIN) ? 1u : 0u;
-        C.sp_bits = u->d_sp_bits.p; C.sp_cnt = u->d_sp_cnt.p; C.sp_rank = u->d_sp_rank.p; C.sp_node = u->d_sp_node.p; C.sp_cap = u->sp_cap;
-        C.segs = u->d_segs.p; C.n_seg0 = u->n_seg0; C.cm_start = u->d_cm_start.p; C.sp_hop = u->d_sp_hop.p; C.seg_index = u->d_segindex.p;
-        if (g_scan1) agx_launch_exclusive_scan1(u->d_tile_side.p, u->d_tile_side_start.p, u->n_tiles, u->d_scan_desc.p + u->scan_desc_n, st);
-        else agx_launch_exclusive_scan(u->d_tile_side.p, u->d_tile_side_start.p, u->n_tiles, u->d_scan_tmp.p, st);      // per tile: the sweep has scanned inside the tiles
-        agx_launch_compact(&C, u->d_chain_end.p, u->n_chain_end, u->d_words.p + W_OVFCOUNT, u->ovf_cap, st);
-        AGX_CHECKPOINT("compact");
-        u->cuts = stream_cuts(n_pos); u->cuts.cut_out = u->d_words.p + W_CUT;
-        agx_launch_special(&C, u->n_words, u->d_sp_rank.p, u->d_scan_tmp.p, g_scan1 ? u->d_scan_desc.p + 2 * u->scan_desc_n : nullptr,
-                           u->d_words.p + W_N, u->d_tile_off.p + u->n_tiles, u->d_tile_side_start.p + u->n_tiles, u->d_pool_cnt.p, u->n_regions, u->d_words.p + W_POOL, u->cuts.n ? &u->cuts : nullptr, st);
-        u->walk_args = C;
-        AGX_CHECKPOINT("special");
-        u->ev.mark(B_COMPACT, st);
-        // ---- the one synchronisation ----
-        u->stats.edge_sweep_launches++;
-        if (u->ev.all) HIP_OK(hipEventRecord(u->ev.last, st));
-        HIP_OK(hipEventRecord(turn.build_done[turn.n & 1], st));               // (a stream wait binds to the record that precedes it: the handle may be recorded again later)
-        {   void *dst = u->h_words.dev(); const void *src = u->d_words.p; const size_t bytes = W_TOTAL * 4;      // the counters, by a kernel at the end of the chain (a copy
-            agx_launch_copy_out(&dst, &src, &bytes, 1, st); }                                                              // command would queue behind the uploads on the copy engines)
-        HIP_OK(hipEventRecord(u->ev_built, st));
+        // ---- walk preparation, then the one synchronisation ----
+        queue_walk_prep(u, st, [&] {
+            u->ev.mark(B_COMPACT, st);
+            u->stats.edge_sweep_launches++;
+            if (u->ev.all) HIP_OK(hipEventRecord(u->ev.last, st));
+            HIP_OK(hipEventRecord(turn.build_done[turn.n & 1], st));               // (a stream wait binds to the record that precedes it: the handle may be recorded again later)
+        });
         turn.n++; turn.prev_exclusive = u->ev.all;
         my_turn.unlock();
         trace(u, "build: queue kernels", tb1, n_pos);
@@ -1447,6 +1458,62 @@ void do_build(agx_unit *u) {
     }
     u->stats.ms_node_big = u->ev.ms(B_BIG); u->stats.ms_edge_fast = u->ev.ms(B_EDGE); u->stats.ms_edge_slow = u->ev.ms(B_SLOW); u->stats.ms_edge_sweep = u->stats.ms_edge_fast + u->stats.ms_edge_slow; u->stats.ms_compact = u->ev.ms(B_COMPACT);
     if (u->up_timed) { float f = 0; if (hipEventElapsedTime(&f, u->ev_up0, u->ev_uploaded) == hipSuccess) u->stats.ms_upload_dev = f; else (void)hipGetLastError(); }
+}
+
+void stream_wait_all(agx_unit *u);
+
+// The prune of a built unit at another coverage (agx_unit_reprune).  Coverage decides AGX_NF_DEAD and what follows from it — the side counts and the walk
+// preparation —, nothing else of a build: one kernel rewrites the bit and the side counts from the per-node coverage the unit kept (agx_k_reprune), then the build's own
+// tail runs again (queue_walk_prep).  It takes the device's turn and the main build stream like a build, and waits for its own counters.  Cleared first: only what the walk
+// preparation counts into or marks (a build's agx_launch_zero clears that among everything else); W_POOL, W_OVFCOUNT, the region counters and W_STATUS are the
+// converged build's and are read again.  Lowering the threshold makes more special ids: the sparse record table grows as in the build's retry loop.
+void do_reprune(agx_unit *u, uint32_t coverage) {
+    const double t0 = now_ms();
+    if (!(u->prm.flags & AGX_FLAG_KEEP_COUNTS)) throw Error{E_ARG, "reprune: the unit was created without AGX_FLAG_KEEP_COUNTS (the per-node coverage stays on the device only with it)"};
+    if (coverage > 0x7FFFFFFFu) throw Error{E_ARG, "reprune: coverage above 2^31 - 1 (the prune compares signed numbers)"};
+    if (!u->built || u->trimmed) throw Error{E_ARG, "reprune: the unit is not built (call agx_unit_build; not after agx_unit_trim or agx_unit_release)"};
+    if ((u->prm.flags & AGX_FLAG_ONE_SHOT) && (u->consumed || u->downloaded)) throw Error{E_ARG, "reprune: a one-shot unit is re-pruned before its download or finish (its landing memory is used once)"};
+    HIP_OK(hipSetDevice(u->prm.device));
+    stream_wait_all(u);                              // (no download of the old walk graph is on its way)
+    join_helper(u);
+    u->out.paths.clear(); u->out.paths_ready = false;      // the kept stretches name the old walk ids
+    const agx_u32 n_pos = (agx_u32)u->V.n_pos;
+    DeviceTurn &turn = turn_of(u->prm.device);
+    struct Failed { agx_unit *u; bool armed; ~Failed() { if (armed) u->built = false; } } failed{u, true};      // (an error behind the first launch leaves flags nobody has counted: the next build makes them again)
+    for (int attempt = 0;; attempt++) {
+        if (attempt > 2) throw Error{E_DEVICE, "reprune did not converge"};
+        const size_t ids_cap = (size_t)n_pos + u->pool_cap;
+        {
+            std::unique_lock<std::mutex> my_turn(turn.m);
+            hipStream_t st = turn.main;
+            agx_zero_args Z; memset(&Z, 0, sizeof Z);
+            auto seg = [&](int i, agx_u32 *ptr, size_t words) { Z.p[i] = ptr; Z.n[i] = (agx_u32)words; };
+            seg(0, u->d_words.p + W_N, W_TOTAL - W_N); seg(1, u->d_tile_side.p + u->n_tiles, 1); seg(2, u->d_sp_cnt.p, (size_t)u->n_words + 1);
+            seg(3, reinterpret_cast<agx_u32 *>(u->d_scan_desc.p + u->scan_desc_n), 4 * u->scan_desc_n); seg(4, reinterpret_cast<agx_u32 *>(u->d_sp_bits.p), 2 * ((size_t)u->n_words + 1));
+            agx_launch_zero(&Z, st);
+            HIP_OK(hipMemsetAsync(u->d_a_mark.p, 0, ids_cap + 2, st));
+            agx_reprune_args R; memset(&R, 0, sizeof R);
+            R.node_start = u->d_node_start.p; R.node_cnt = u->d_node_cnt.p; R.nk_cid = u->d_cid.p; R.n_counts = u->d_counts.p; R.n_flags = u->d_flags.p;
+            R.side_pk = u->d_side_pk.p; R.tile_side = u->d_tile_side.p; R.n_pos = n_pos; R.pool_cap = u->pool_cap; R.coverage = (int)coverage; R.abort = u->d_words.p + W_STATUS;
+            agx_launch_reprune(&R, u->n_tiles, st);
+            AGX_CHECKPOINT("reprune");
+            queue_walk_prep(u, st, [] {});
+        }
+        HIP_OK(wait_event(u->ev_built));
+        HIP_OK(hipGetLastError());
+        const agx_u32 *w = u->h_words.p;
+        if (w[W_STATUS]) throw Error{E_DEVICE, "internal: reprune of a unit whose build left a status word"};      // (the kernels have returned at once)
+        u->stats.reprune_attempts = (uint32_t)attempt + 1;
+        if (w[W_N + 2] > u->sp_cap) { Take grow{&u->arena}; sparse_bufs(u, w[W_N + 2] + w[W_N + 2] / 8 + 1024, grow); u->stats.device_bytes = u->arena.capacity(); continue; }
+        const unsigned long long ids = (unsigned long long)n_pos + w[W_N + 1];
+        if (ids >= 0xFFFFFF00ull) throw Error{E_OVERFLOW, "walk graph exceeds 2^32 ids"};
+        u->n_ids = (agx_u32)ids; u->n_special = w[W_N + 2];
+        break;
+    }
+    failed.armed = false;
+    u->prm.coverage = coverage; u->downloaded = false;
+    u->stats.ms_reprune = now_ms() - t0;
+    trace(u, "reprune", t0, n_pos);
 }
 
 // the pinned buffers a download lands in (a one-shot unit: cut from its dead staged inputs)
@@ -1879,6 +1946,7 @@ int agx_unit_release(agx_unit *u) { if (!u) return AGX_E_ARG; return guarded(u, 
 int agx_unit_trim(agx_unit *u, uint64_t *freed) { if (!u) return AGX_E_ARG; if (freed) *freed = 0; return guarded(u, [&] { const size_t f = do_trim(u); u->trimmed = true; if (freed) *freed = f; }); }
 void agx_pool_trim(int device) { if (device >= 0) dev_trim(device); else if (device == -1) { host_trim(); scratch_trim(); out_cache_trim(); } else host_retire(); }      // (-1 also unmaps the loaders' cached scratch memory: up to 16 GB of touched pages per process otherwise stay until exit)
 int agx_unit_build(agx_unit *u) { if (!u) return AGX_E_ARG; return guarded(u, [&] { do_build(u); }); }
+int agx_unit_reprune(agx_unit *u, uint32_t coverage) { if (!u) return AGX_E_ARG; return guarded(u, [&] { do_reprune(u, coverage); }); }
 int agx_unit_download(agx_unit *u) { if (!u) return AGX_E_ARG; return guarded(u, [&] { do_download(u); }); }
 
 int agx_unit_finish(agx_unit *u, agx_result *r) {

@@ -143,6 +143,8 @@ void agx_launch_edge_slow(const agx_edge_kargs *, hipStream_t);           // pas
 void agx_launch_copy_out(void *const *dst, const void *const *src, const size_t *bytes, int n, hipStream_t);      // HBM -> registered host memory, by a kernel
 void agx_launch_fetch_records(const agx_compact_args *, agx_u32 first, agx_u32 stride, agx_u32 rows, agx_u32 width, agx_walknode *out, hipStream_t);
 void agx_launch_compact(const agx_compact_args *, const agx_u32 *chain_end, agx_u32 n_chain_end, const agx_u32 *n_ovf_dev, agx_u32 ovf_cap, hipStream_t);
+// reprune (agx_core.h): DEAD bits, side_pk and tile_side[0 .. n_tiles) of a built node table at A->coverage; the caller zeroes tile_side[n_tiles] and queues the walk preparation behind it
+void agx_launch_reprune(const agx_reprune_args *, agx_u32 n_tiles, hipStream_t);
 // special ids: bitmap, rank scan (desc: the one-launch scan; null: the three-launch one with scan_tmp), records; block 0 of the last kernel also leaves the
 // totals the host reads: out[0..2] = *a, *b, sp_rank[n_words]; *sum = nodes handed out = the sum of the region counters
 // r06: where a streamed download cuts the walk graph (agx_engine.cpp: begin_streamed_download): piece w holds main ids [64 * word[w], 64 * word[w + 1]) (the last one: up to n_pos)

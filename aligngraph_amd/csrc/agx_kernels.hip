@@ -947,6 +947,20 @@ __global__ void __launch_bounds__(256) agx_k_emit_alive(agx_compact_args A, cons
         if (!cont) for (agx_u32 e = 0; e < k; e++) A.a_mark[next[e]] = 1;      // racing stores of the same value
     }
 }
+// ---- reprune (agx_core.h): the DEAD bits and the side counts of a built node table at another coverage --------------------------
+// The node sweep's write-out shape: a wavefront per tile, lane = position, the in-tile prefix by the same DPP scan.  What follows it is the walk preparation
+// as a build queues it (agx_engine.cpp: queue_walk_prep).
+__global__ void __launch_bounds__(256) agx_k_reprune(agx_reprune_args A, agx_u32 n_tiles) {
+    AGX_RETURN_IF_ABORTED(A.abort);
+    const agx_u32 lane = threadIdx.x & 63u;
+    const agx_u32 tile = (agx_u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+    if (tile >= n_tiles) return;                                              // wave-uniform: every lane of a tile reaches the scan
+    const agx_u32 X = tile * AGX_TILE + lane;
+    const agx_u32 side = agx_reprune_lane(A, X);                              // (0 for the lanes past n_pos of the last tile)
+    const agx_u32 side_incl = agx_wave_incl_scan(side, lane);
+    if (X < A.n_pos) A.side_pk[X] = agx_side_pack(side_incl - side, side);
+    if (lane == 63u) A.tile_side[tile] = side_incl;
+}
 // the special-id bitmap and its popcounts (input of the rank scan).  A wavefront takes four 64-id words — every lane one id of each, so that their loads
 // are in flight together — and writes nothing for words past the live ids: sp_bits / sp_cnt are zeroed at the start of the build (the grid covers the id
 // CAPACITY, 2.4 x the live ids of a first build: r02 spent 0.42 ms here on a 30 Mb unit, most of it rounds of threads that only found out they were idle)
@@ -1192,6 +1206,9 @@ void agx_launch_copy_out(void *const *dst, const void *const *src, const size_t 
 void agx_launch_fetch_records(const agx_compact_args *A, agx_u32 first, agx_u32 stride, agx_u32 rows, agx_u32 width, agx_walknode *out, hipStream_t st) {
     const agx_u32 n = rows * width;
     if (n) hipLaunchKernelGGL(agx_k_fetch_records, dim3((n + 255) / 256), dim3(256), 0, st, *A, first, stride, rows, width, out);
+}
+void agx_launch_reprune(const agx_reprune_args *A, agx_u32 n_tiles, hipStream_t st) {
+    if (n_tiles) hipLaunchKernelGGL(agx_k_reprune, dim3((n_tiles + 3u) / 4u), dim3(256), 0, st, *A, n_tiles);
 }
 void agx_launch_compact(const agx_compact_args *A, const agx_u32 *chain_end, agx_u32 n_chain_end, const agx_u32 *n_ovf_dev, agx_u32 ovf_cap, hipStream_t st) {
     const agx_u32 n1 = A->n_pos > n_chain_end ? A->n_pos : n_chain_end, n2 = A->n_pos > ovf_cap ? A->n_pos : ovf_cap;

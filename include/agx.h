@@ -125,6 +125,8 @@ typedef struct {
                                                                     alignment (AGX_ROW_DIFF, engine: stage_rows; 0: all rows crossed as 2-bit classes) */
     uint64_t n_edge_slow;                                        /* positions the edge build's pass B resolved hit by hit: multi-variant positions with a step elsewhere, listed by the
                                                                     node sweep, and the positions pass A found with several variants there or at x+1 */
+    uint32_t reprune_attempts;                                   /* of the last agx_unit_reprune: 1 unless the sparse record table had to grow and the reprune was repeated */
+    double ms_reprune;                                           /* host wall time of the last agx_unit_reprune, from entry to its counters being back */
 } agx_stats;
 
 /* Node/edge tables in canonical numbering (position-major, variant order), for parity tests. malloc'd; free with agx_graph_free. */
@@ -264,6 +266,17 @@ int agx_unit_hbm_needed(agx_unit *u, uint64_t *bytes);   /* the HBM block agx_un
                                                     device between units of very different sizes admits them by (AlignGraph_amd); a build that has to grow a capacity takes more */
 int agx_unit_upload(agx_unit *u);                /* staged arrays -> HBM: one device block, asynchronous copies behind those of the device's earlier uploads; returns without waiting */
 int agx_unit_build(agx_unit *u);                 /* kernels: updateGenomeWithRead/updateKMer (AG:1635-1870, 1353-1624) + filterLowCoverage (AG:1904-1918) */
+/* Re-prunes a built unit at another coverage without building it again.  After the call the unit is, in everything a caller can observe, what agx_unit_build leaves on a unit
+ * created with `coverage` in agx_params and given the same inputs: the walk graph (agx_unit_walk_graph, both forms), the three outputs of agx_unit_finish byte for byte,
+ * agx_stats n_walk_ids / n_special / download_bytes, agx_unit_unitigs, the id map of agx_unit_unitigs_mapped and the stretches of the next finish.  agx_unit_graph and the
+ * exports at an explicit threshold (agx_unit_unitigs_region) do not change: they never looked at the prune.  The unit's coverage is the new one from then on: a later
+ * agx_unit_build, or agx_unit_upload + build, uses it.  Costs one kernel over the positions and a second run of the walk preparation; agx_stats
+ * reprune_attempts and ms_reprune describe the last call.
+ * AGX_E_ARG, with the reason in agx_unit_error, unless: the unit is built; it was created with AGX_FLAG_KEEP_COUNTS (the per-node coverage stays on the device only then); it is
+ * not trimmed and not released; coverage <= 0x7FFFFFFF (the prune compares signed numbers, as the build does).  A unit that has been downloaded or finished may be re-pruned:
+ * it is "not downloaded" again, and the next finish downloads the new walk graph.  AGX_FLAG_ONE_SHOT units only before their download or finish (their landing memory is
+ * used once).  The stretches kept by AGX_FLAG_KEEP_PATHS are dropped.  A refused call leaves the unit as it was. */
+int agx_unit_reprune(agx_unit *u, uint32_t coverage);
 int agx_unit_download(agx_unit *u);              /* HBM -> pinned host memory (the whole walk graph; returns when it is there).  Only needed by a caller that wants the unit's HBM back
                                                     before the walk (agx_unit_trim): agx_unit_finish downloads what has not been downloaded, and does it better */
 int agx_unit_finish(agx_unit *u, agx_result *r); /* extdContigs1/2 + scaffoldContigs (AG:1954-2464) on the host.  On a unit that has not been downloaded (r06) the download is STREAMED: the
@@ -311,7 +324,7 @@ int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint3
  * agx_unit_unitigs_region gives for the same arguments. */
 int agx_unit_unitigs_mapped(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, agx_idmap *m);
 void agx_idmap_free(agx_idmap *m);
-/* The stretches the last agx_unit_finish kept (AGX_FLAG_KEEP_PATHS).  Valid after a finish, also of trimmed and one-shot units, until the next finish, upload or release;
+/* The stretches the last agx_unit_finish kept (AGX_FLAG_KEEP_PATHS).  Valid after a finish, also of trimmed and one-shot units, until the next finish, upload, reprune or release;
  * AGX_E_ARG without the flag or before a finish.  The caller gets copies. */
 int agx_unit_walk_paths(agx_unit *u, agx_walk_paths *w);
 void agx_walk_paths_free(agx_walk_paths *w);
