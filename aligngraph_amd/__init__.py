@@ -16,6 +16,7 @@ AGX_FLAG_SPARSE_MIN = 2
 AGX_FLAG_TIME_SECTIONS = 4
 AGX_FLAG_ONE_SHOT = 8
 AGX_FLAG_KEEP_PATHS = 16
+AGX_FLAG_EDGE_SUPPORT = 32
 
 # every symbol include/agx.h declares (tests check that the built library exports all of them)
 EXPORTS = [
@@ -27,6 +28,7 @@ EXPORTS = [
     "agx_unit_trim", "agx_unit_unitigs", "agx_unit_unitigs_region", "agx_unitigs_free", "agx_unitigs_gfa", "agx_text_free",
     "agx_unit_walk_graph", "agx_walk_graph_free", "agx_unit_front", "agx_front_free",
     "agx_unit_unitigs_mapped", "agx_idmap_free", "agx_unit_walk_paths", "agx_walk_paths_free", "agx_unitigs_paths_gfa", "agx_unit_reprune",
+    "agx_unit_edge_support", "agx_edge_support_free", "agx_unit_unitigs_support", "agx_link_support_free", "agx_unitigs_gfa_support",
 ]
 
 
@@ -71,7 +73,8 @@ class Stats(ctypes.Structure):
                [(n, ctypes.c_double) for n in ("ms_stage", "ms_upload_dev")] + \
                [(n, ctypes.c_uint64) for n in ("upload_bytes", "device_bytes", "pinned_bytes_cached", "device_bytes_cached", "n_spilled")] + \
                [("build_attempts", ctypes.c_uint32), ("from_cache", ctypes.c_uint32), ("dense_lists", ctypes.c_uint32), ("rows_by_reference", ctypes.c_uint32)] + \
-               [("n_edge_slow", ctypes.c_uint64), ("reprune_attempts", ctypes.c_uint32), ("ms_reprune", ctypes.c_double)]
+               [("n_edge_slow", ctypes.c_uint64), ("reprune_attempts", ctypes.c_uint32), ("ms_reprune", ctypes.c_double)] + \
+               [("ms_edge_support", ctypes.c_double), ("n_support_events", ctypes.c_uint64)]
 
 
 class Graph(ctypes.Structure):
@@ -86,6 +89,11 @@ class Unitigs(ctypes.Structure):
                 ("head_pos", ctypes.POINTER(ctypes.c_uint32)), ("head_var", ctypes.POINTER(ctypes.c_uint32)), ("n_nodes", ctypes.POINTER(ctypes.c_uint32)),
                 ("last_pos", ctypes.POINTER(ctypes.c_uint32)), ("coverage", ctypes.POINTER(ctypes.c_uint64)), ("seq_off", ctypes.POINTER(ctypes.c_uint64)),
                 ("seq", ctypes.c_void_p), ("link_from", ctypes.POINTER(ctypes.c_uint32)), ("link_to", ctypes.POINTER(ctypes.c_uint32))]
+
+
+class EdgeSupport(ctypes.Structure):
+    _fields_ = [("n_nodes", ctypes.c_uint32), ("n_edges", ctypes.c_uint32), ("n_events", ctypes.c_uint64), ("n_contributions", ctypes.c_uint64)] + \
+               [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("edge_start", "edge_dst", "edge_cnt")]
 
 
 class IdMap(ctypes.Structure):
@@ -227,6 +235,14 @@ def lib():
         L.agx_unitigs_free.argtypes = [ctypes.POINTER(Unitigs)]
         L.agx_unitigs_free.restype = None
         L.agx_unitigs_gfa.argtypes = [ctypes.POINTER(Unitigs), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+        L.agx_unit_edge_support.argtypes = [ctypes.c_void_p, ctypes.POINTER(EdgeSupport)]
+        L.agx_edge_support_free.argtypes = [ctypes.POINTER(EdgeSupport)]
+        L.agx_edge_support_free.restype = None
+        L.agx_unit_unitigs_support.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(Unitigs),
+                                               ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)), ctypes.POINTER(IdMap)]
+        L.agx_link_support_free.argtypes = [ctypes.POINTER(ctypes.c_uint32)]
+        L.agx_link_support_free.restype = None
+        L.agx_unitigs_gfa_support.argtypes = [ctypes.POINTER(Unitigs), ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         L.agx_text_free.argtypes = [ctypes.c_void_p]
         L.agx_text_free.restype = None
         L.agx_run_unit.argtypes = [ctypes.POINTER(Params), ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Result), ctypes.c_char_p, ctypes.c_size_t]
@@ -324,9 +340,10 @@ class Reads:
 class Unit:
     """One reference unit (chromosome or --part slice): the body of the reference's unit loop, AG:4765-4783."""
 
-    def __init__(self, k=5, insert_variation=50, coverage=20, batch=0, device=0, keep_counts=False, flags=0, keep_paths=False):
+    def __init__(self, k=5, insert_variation=50, coverage=20, batch=0, device=0, keep_counts=False, flags=0, keep_paths=False, edge_support=False):
         self._h = ctypes.c_void_p()
-        self.params = Params(k, insert_variation, coverage, batch, device, (AGX_FLAG_KEEP_COUNTS if keep_counts else 0) | (AGX_FLAG_KEEP_PATHS if keep_paths else 0) | flags)
+        self.params = Params(k, insert_variation, coverage, batch, device, (AGX_FLAG_KEEP_COUNTS if keep_counts else 0) | (AGX_FLAG_KEEP_PATHS if keep_paths else 0) |
+                             (AGX_FLAG_EDGE_SUPPORT if edge_support else 0) | flags)
         rc = lib().agx_unit_create(ctypes.byref(self.params), ctypes.byref(self._h))
         if rc != AGX_OK:
             self._h = ctypes.c_void_p()
@@ -463,12 +480,35 @@ class Unit:
             return
         self._check(lib().agx_unit_unitigs_region(self._h, *self._window(region, min_coverage), ctypes.byref(t)))
 
-    def unitigs(self, region=None, min_coverage=None, id_map=False):
+    def edge_support(self):
+        """How many events name each edge of the built graph (agx_unit_edge_support; the unit was created with edge_support=True): edge_start and edge_dst are graph()'s,
+        edge_cnt[e] the support of edge e, n_events the events counted and n_contributions the sum of edge_cnt.  The first call after a build counts on the device; later
+        calls reuse the counters."""
+        import numpy as np
+        s = EdgeSupport()
+        self._check(lib().agx_unit_edge_support(self._h, ctypes.byref(s)))
+        try:
+            def arr(p, n):
+                return np.ctypeslib.as_array(p, shape=(n,)).astype("uint32", copy=True) if n else np.zeros(0, "uint32")
+            return {"n_nodes": s.n_nodes, "n_edges": s.n_edges, "n_events": s.n_events, "n_contributions": s.n_contributions,
+                    "edge_start": arr(s.edge_start, s.n_nodes + 1), "edge_dst": arr(s.edge_dst, s.n_edges), "edge_cnt": arr(s.edge_cnt, s.n_edges)}
+        finally:
+            lib().agx_edge_support_free(ctypes.byref(s))
+
+    def _export_support(self, t, region, min_coverage, m=None):
+        """agx_unit_unitigs_support over the window and threshold of _window(); returns the links' support as a ctypes array the caller frees (agx_link_support_free)."""
+        sup = ctypes.POINTER(ctypes.c_uint32)()
+        self._check(lib().agx_unit_unitigs_support(self._h, *self._window(region, min_coverage), ctypes.byref(t), ctypes.byref(sup), ctypes.byref(m) if m is not None else None))
+        return sup
+
+    def unitigs(self, region=None, min_coverage=None, id_map=False, edge_support=False):
         """The unit's pruned graph compacted into unitigs on the device (agx_unit_unitigs; needs keep_counts): numpy arrays per segment and link, the
         bases as bytes.  region=(lo, hi) and / or min_coverage: the sub-graph of positions [lo, hi) whose nodes are alive at that coverage
         (agx_unit_unitigs_region), at a cost that follows the window.  id_map=True (needs keep_paths; agx_unit_unitigs_mapped): the same table of the window
         (every position without a region) at the threshold (the unit's coverage without one) with one more entry, "id_map": the runs of walk ids whose nodes
         are in the export (id_first, id_last, seg, rank_first) and the unit's n_pos and n_ids."""
+        if edge_support:
+            return self._unitigs_support(region, min_coverage, id_map)
         t = Unitigs()
         if not id_map:
             self._export(t, region, min_coverage)
@@ -486,6 +526,24 @@ class Unit:
             lib().agx_unitigs_free(ctypes.byref(t))
             lib().agx_idmap_free(ctypes.byref(m))
 
+    def _unitigs_support(self, region, min_coverage, id_map):
+        """unitigs(edge_support=True): the region export's table (every position without a region, the unit's coverage without a threshold) plus "link_support", the
+        support of each link's edge (agx_unit_unitigs_support; the unit was created with edge_support=True)."""
+        import numpy as np
+        t, m = Unitigs(), IdMap() if id_map else None
+        sup = self._export_support(t, region, min_coverage, m)
+        try:
+            out = _unitigs_arrays(t)
+            out["link_support"] = np.ctypeslib.as_array(sup, shape=(t.n_links,)).astype("uint32", copy=True) if t.n_links else np.zeros(0, "uint32")
+            if id_map:
+                out["id_map"] = _idmap_arrays(m)
+            return out
+        finally:
+            lib().agx_unitigs_free(ctypes.byref(t))
+            lib().agx_link_support_free(sup)
+            if id_map:
+                lib().agx_idmap_free(ctypes.byref(m))
+
     def walk_paths(self):
         """The graph stretches of the records the last finish() wrote to "pre" (agx_unit_walk_paths; needs keep_paths): rec_len, st_off per record, id_first, id_last,
         base_off, joined per stretch, as numpy arrays."""
@@ -501,9 +559,17 @@ class Unit:
         finally:
             lib().agx_walk_paths_free(ctypes.byref(w))
 
-    def gfa(self, unit=0, region=None, min_coverage=None):
-        """GFA 1.0 S and L lines of the unit's unitigs, segments named u<unit>_<pos>_<var> (no header line); region and min_coverage as in unitigs()."""
+    def gfa(self, unit=0, region=None, min_coverage=None, edge_support=False):
+        """GFA 1.0 S and L lines of the unit's unitigs, segments named u<unit>_<pos>_<var> (no header line); region and min_coverage as in unitigs().
+        edge_support=True: every L line also carries RC:i:<events that name the link's edge> (agx_unitigs_gfa_support)."""
         t = Unitigs()
+        if edge_support:
+            sup = self._export_support(t, region, min_coverage)
+            try:
+                return _gfa_text(t, unit, sup)
+            finally:
+                lib().agx_unitigs_free(ctypes.byref(t))
+                lib().agx_link_support_free(sup)
         self._export(t, region, min_coverage)
         try:
             return _gfa_text(t, unit)
@@ -560,9 +626,13 @@ def gfa_paths(t, w, unit=0):
         lib().agx_text_free(p)
 
 
-def _gfa_text(t, unit):
+def _gfa_text(t, unit, link_support=None):
+    """link_support: a ctypes uint32 pointer for the RC tags (agx_unitigs_gfa_support), or None"""
     p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
-    rc = lib().agx_unitigs_gfa(ctypes.byref(t), unit, ctypes.byref(p), ctypes.byref(n))
+    if link_support is None:
+        rc = lib().agx_unitigs_gfa(ctypes.byref(t), unit, ctypes.byref(p), ctypes.byref(n))
+    else:
+        rc = lib().agx_unitigs_gfa_support(ctypes.byref(t), link_support, unit, ctypes.byref(p), ctypes.byref(n))
     if rc != AGX_OK:
         raise AgxError(rc, "agx_unitigs_gfa: the unitig table is inconsistent")
     try:
@@ -585,10 +655,17 @@ def _unitigs_struct(u):
     return t, (keep, seq)
 
 
-def unitigs_gfa(u, unit=0):
-    """GFA S/L lines (no header) of a unitig table given as the dict Unit.unitigs() returns (agx_unitigs_gfa; host only, needs no device)."""
+def unitigs_gfa(u, unit=0, edge_support=False):
+    """GFA S/L lines (no header) of a unitig table given as the dict Unit.unitigs() returns (agx_unitigs_gfa; host only, needs no device).  edge_support=True: with the RC
+    tags of u["link_support"] (agx_unitigs_gfa_support)."""
+    import numpy as np
     t, _keep = _unitigs_struct(u)
-    return _gfa_text(t, unit)
+    if not edge_support:
+        return _gfa_text(t, unit)
+    sup = np.ascontiguousarray(u["link_support"], dtype="uint32")
+    if len(sup) != t.n_links:
+        raise AgxError(AGX_E_ARG, "agx_unitigs_gfa_support: one number per link")
+    return _gfa_text(t, unit, sup.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
 
 
 def cache_build(tmp_dir, unit, batch=0, device=0, reads=None, k=5):

@@ -46,6 +46,7 @@ struct Options {
     // instead of --coverage (agx_unit_unitigs_region)
     int tagRegion = 0, tagGraphCov = 0, regionUnit = 0, graphCov = 0; uint32_t regionLo = 0, regionHi = 0;
     int graphPaths = 0;                 // --graphPaths (only with --graphOut): the pre-extended records as P lines over the exported segments (agx_unitigs_paths_gfa)
+    int graphSupport = 0;               // --graphEdgeSupport (only with --graphOut): RC:i:<events that name the link's edge> on every L line (agx_unit_unitigs_support)
     int fastMap = 0, ratioCheck = 0, uniqueExtension = 0, iterativeMap = 0, misassemblyRemoval = 0, resume = 0;
     int k = 5, distanceLow = 0, distanceHigh = 99999, coverage = 20, insertVariation = 50, part = 1;      // defaults of AG:4701
 };
@@ -129,6 +130,7 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--graphRegion") region(i);
         else if (b == "--graphMinCoverage") { integer(i, o.tagGraphCov, o.graphCov); if (o.graphCov < 0) die_usage(); }
         else if (b == "--graphPaths") flag(o.graphPaths);
+        else if (b == "--graphEdgeSupport") flag(o.graphSupport);
         else if (b == "--kMer") integer(i, o.tagK, o.k);
         else if (b == "--insertVariation") integer(i, o.tagIV, o.insertVariation);
         else if (b == "--coverage") integer(i, o.tagCov, o.coverage);
@@ -141,15 +143,16 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--resume") { if (o.resume == 1 || count != 1) die_usage(); o.resume = 1; }
         else die_usage();
     }
-    if ((o.tagRegion || o.tagGraphCov || o.graphPaths) && !o.tagGraph) die_usage();
+    if ((o.tagRegion || o.tagGraphCov || o.graphPaths || o.graphSupport) && !o.tagGraph) die_usage();
 }
 
-// tmp/_graph.<u>.gfa, with the region, the threshold and --graphPaths (.p) in the name when they are given: a --resume run merges only lines that were made under its own settings
+// tmp/_graph.<u>.gfa, with the region, the threshold, --graphPaths (.p) and --graphEdgeSupport (.s) in the name when they are given: a --resume run merges only lines that were made under its own settings
 string graph_part_path(const Options &o, int u) {
     string s = "tmp/_graph." + itoa(u);
     if (o.tagRegion) s += "." + itoa(o.regionLo) + "-" + itoa(o.regionHi);
     if (o.tagGraphCov) s += ".c" + itoa(o.graphCov);
     if (o.graphPaths) s += ".p";
+    if (o.graphSupport) s += ".s";
     return s + ".gfa";
 }
 
@@ -1171,7 +1174,8 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                 if (at >= order.size() || failed.load()) return;
                 const int u = order[at];
                 // the five calls of the unit loop (AG:4768-4776) through the split entry points of agx_run_unit, with the admission between load and upload
-                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, AGX_FLAG_ONE_SHOT | (o.tagGraph ? AGX_FLAG_KEEP_COUNTS : 0u) | (o.graphPaths ? AGX_FLAG_KEEP_PATHS : 0u)};
+                // (--graphEdgeSupport: the counting reads the front of the build, which a one-shot unit does not promise to keep — such a run's units are ordinary ones, with the edge counters)
+                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, (o.graphSupport ? AGX_FLAG_EDGE_SUPPORT : AGX_FLAG_ONE_SHOT) | (o.tagGraph ? AGX_FLAG_KEEP_COUNTS : 0u) | (o.graphPaths ? AGX_FLAG_KEEP_PATHS : 0u)};
                 agx_result r; memset(&r, 0, sizeof r); char err[512]; err[0] = 0;
                 agx_unit *un = nullptr;
                 int rc = agx_unit_create(&p, &un);
@@ -1185,8 +1189,13 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                 const bool graph_here = o.tagGraph && (!o.tagRegion || u == o.regionUnit);
                 agx_unitigs ut; agx_idmap im; memset(&ut, 0, sizeof ut); memset(&im, 0, sizeof im);      // (--graphPaths: both outlive the finish, which gives the records)
                 if (rc == AGX_OK && graph_here) {      // --graphOut: the unit's GFA lines, exported before the download (one-shot units) into tmp/_graph.<u>.gfa
-                    char *text = nullptr; size_t len = 0;
-                    if (o.graphPaths) {      // the same window and threshold through the export that also maps the walk's ids
+                    char *text = nullptr; size_t len = 0; uint32_t *sup = nullptr;
+                    if (o.graphSupport) {    // the same window and threshold through the export that also counts the events behind every link (and maps the walk's ids for --graphPaths)
+                        agx_stats st; memset(&st, 0, sizeof st);
+                        rc = agx_unit_stats(un, &st);
+                        if (rc == AGX_OK) rc = agx_unit_unitigs_support(un, o.tagRegion ? o.regionLo : 0u, o.tagRegion ? o.regionHi : (uint32_t)st.n_pos, (uint32_t)(o.tagGraphCov ? o.graphCov : o.coverage), &ut, &sup, o.graphPaths ? &im : nullptr);
+                    }
+                    else if (o.graphPaths) {      // the same window and threshold through the export that also maps the walk's ids
                         agx_stats st; memset(&st, 0, sizeof st);
                         rc = agx_unit_stats(un, &st);
                         if (rc == AGX_OK) rc = agx_unit_unitigs_mapped(un, o.tagRegion ? o.regionLo : 0u, o.tagRegion ? o.regionHi : (uint32_t)st.n_pos, (uint32_t)(o.tagGraphCov ? o.graphCov : o.coverage), &ut, &im);
@@ -1197,7 +1206,8 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                         rc = agx_unit_stats(un, &st);
                         if (rc == AGX_OK) rc = agx_unit_unitigs_region(un, o.tagRegion ? o.regionLo : 0u, o.tagRegion ? o.regionHi : (uint32_t)st.n_pos, (uint32_t)(o.tagGraphCov ? o.graphCov : o.coverage), &ut);
                     }
-                    if (rc == AGX_OK) { rc = agx_unitigs_gfa(&ut, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "GFA FORMATTING FAILED"); }
+                    if (rc == AGX_OK) { rc = o.graphSupport ? agx_unitigs_gfa_support(&ut, sup, u, &text, &len) : agx_unitigs_gfa(&ut, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "GFA FORMATTING FAILED"); }
+                    agx_link_support_free(sup);
                     if (!o.graphPaths) agx_unitigs_free(&ut);
                     if (rc == AGX_OK) {
                         const string path = graph_part_path(o, u);

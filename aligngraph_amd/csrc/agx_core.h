@@ -1224,6 +1224,84 @@ AGX_HD agx_u32 agx_edge_slow_pair(const agx_sweep_args &A, const agx_slow_ctx &c
     return (hit && (c.allowed & bit)) ? bit : 0u;
 }
 
+// ---- edge support: the events behind each edge (agx_unit_edge_support) -------------------------------------------------
+// The edge passes above insert into sets.  The support of an edge is the number of EVENTS that name it: an event is one (hit, X) whose arrival has a successor inside the
+// unit, and it names every allowed (s, d) of S x D once — S, D: the variants its candidate keys resolve to in the FINAL buckets of X and of the successor's position
+// (agx_edge_slow_hit's rule at every position, as a multiset).  Counting is one more pass over the tile lists, on request, over the node table a build left behind.
+
+// The distinct variants the candidate keys of (x, p0) resolve to, each once, in the order of the first candidate that resolved to it: f(id).  A candidate is the first of
+// its variant iff no candidate in front of it resolves there, which is asked by resolving those again — no list of seen variants (a position holds up to AGX_MAXV_HUGE), and
+// nearly every arrival has one candidate.  Every loop runs to a count it read.  false: x, p0 or x's bucket lies outside the tables (nothing was read there, f was not called).
+template <class F>
+AGX_HD bool agx_for_variants(const agx_sweep_args &A, agx_u32 x, agx_u32 p0, F f) {
+    if (x >= A.n_pos || (p0 != AGX_NONE && p0 >= A.n_pos)) return false;
+    const agx_u32 s = A.node_start[x], n = A.node_cnt[x];
+    if (n > AGX_MAXV_HUGE || s >= A.pool_cap || n > A.pool_cap - s) return false;      // (agx_reprune_lane's bounds: they do not rest on the table being intact)
+    const agx_u32 cx_s = A.cm_start[x], cx_n = A.cm_start[x + 1] - cx_s;
+    agx_u32 ci = 0;
+    agx_for_candidates(A, cx_s, cx_n, p0, [&](const agx_key &key) {
+        const agx_u32 id = agx_resolve(A, x, key);
+        bool first = id != AGX_NONE;
+        if (first && ci) {
+            agx_u32 cj = 0;
+            agx_for_candidates(A, cx_s, cx_n, p0, [&](const agx_key &earlier) {
+                if (cj >= ci) return false;
+                cj++;
+                if (agx_resolve(A, x, earlier) == id) { first = false; return false; }
+                return true;
+            });
+        }
+        ci++;
+        if (first) f(id);
+        return true;
+    });
+    return true;
+}
+
+// The contributions of one event: source position X, arrival a (a.has && a.has_succ && a.xs < n_pos: the caller has looked).  add(src, dst) once per named edge.
+// single_ok: where X and a.xs hold one variant each, every candidate key resolves to it (pass A's argument), so the pair is that of the two buckets and only the
+// contig-consistency predicate is asked; without it the same positions go through the candidates like all others (tests run both forms against each other).
+// false: an index outside the tables — the event contributed nothing.
+template <class ADD>
+AGX_HD bool agx_support_event(const agx_sweep_args &A, agx_u32 X, const agx_arrival &a, bool single_ok, ADD add) {
+    if (X >= A.n_pos || a.xs >= A.n_pos) return false;
+    if (single_ok && A.node_cnt[X] == 1 && A.node_cnt[a.xs] == 1) {
+        const agx_u32 src = A.node_start[X], dst = A.node_start[a.xs];
+        if (src >= A.pool_cap || dst >= A.pool_cap) return false;
+        if (agx_edge_allowed(A, src, dst)) add(src, dst);
+        return true;
+    }
+    bool ok = true;
+    const bool ok_src = agx_for_variants(A, X, a.p0, [&](agx_u32 src) {
+        ok = agx_for_variants(A, a.xs, a.p0s, [&](agx_u32 dst) { if (agx_edge_allowed(A, src, dst)) add(src, dst); }) && ok;
+    });
+    return ok && ok_src;
+}
+
+// One (hit record, X): 1 if it is an event (its contributions went through add), else 0.  *bad is set where an event met an index outside the tables.
+template <class ADD>
+AGX_HD agx_u32 agx_support_lane(const agx_sweep_args &A, agx_u32 X, const agx_dhit &d, bool single_ok, bool *bad, ADD add) {
+    if (X >= A.n_pos) return 0;
+    const agx_arrival a = agx_decode_arrival(d, A.runs, X, A.k);
+    if (!a.has || !a.has_succ || a.xs >= A.n_pos) return 0;
+    if (!agx_support_event(A, X, a, single_ok, add)) *bad = true;
+    return 1;
+}
+
+// Where the counter of edge src -> dst is: the inline slot of n_next[src] that holds dst (AGX_MAXE: none does), else the first entry of the overflow list that names the pair
+// (n_ovf: none does).  The list may hold a pair twice; consumers sum over duplicates, so the first one takes every count.  A walk of the whole list by the asking lane: only
+// sources with AGX_NF_EOVF pay it (more than AGX_MAXE successors).
+AGX_HD agx_u32 agx_support_slot(const agx_u32 *n_next, agx_u32 src, agx_u32 dst) {
+    const agx_u32 *slots = n_next + (size_t)src * AGX_MAXE;
+    agx_u32 e = AGX_MAXE;
+    for (agx_u32 i = AGX_MAXE; i-- > 0;) e = slots[i] == dst ? i : e;
+    return e;
+}
+AGX_HD agx_u32 agx_support_ovf_entry(const agx_edge_ovf *ovf, agx_u32 n_ovf, agx_u32 src, agx_u32 dst) {
+    for (agx_u32 i = 0; i < n_ovf; i++) if (ovf[i].src == src && ovf[i].dst == dst) return i;
+    return n_ovf;
+}
+
 // ---- walk preparation: alive-node renumbering and forced-run flags -------------------------------------------------------
 // The path walk (AG:1954-2204) only ever stands on nodes that survived the coverage prune.  After the edge sweep the
 // surviving ("alive") nodes get walk ids ("aid") laid out so that the main strand of the graph is contiguous:

@@ -285,6 +285,8 @@ struct agx_unit {
     DBuf<agx_u32> d_pool_cnt, d_region_off; agx_u32 n_regions = 0;      // the node pool's slices (AGX_REGION_TILES tiles each) and their counters
     DBuf<agx_u32> d_node_start, d_slow_list, d_perm, d_tfirst, d_ckey, d_long; DBuf<agx_u16> d_node_cnt; DBuf<agx_u8> d_pos_succ;
     DBuf<agx_u32> d_cid, d_coff, d_cid0, d_coff0, d_off0, d_next; DBuf<agx_u8> d_base, d_flags; DBuf<agx_sref> d_sref; DBuf<int> d_counts;
+    DBuf<agx_u32> d_e_cnt, d_ovf_cnt, d_sup_tot, d_lsup;      // AGX_FLAG_EDGE_SUPPORT: counters parallel to d_next / d_ovf, per-tile totals (events, contributions, then the unmatched word); d_lsup: the links' numbers of the last export with support (taken when first needed)
+    bool support_valid = false; uint64_t sup_events = 0, sup_adds = 0;      // the counters hold the last build's counts (ensure_support)
     DBuf<char> d_ut;                   // the unitig export's scratch (unitig_layout): reserved with the unit's block when it keeps counts, reused by every export
     DBuf<agx_edge_ovf> d_ovf; DBuf<agx_u32> d_mid_list, d_big_list, d_scratch, d_huge_list, d_scratch_huge; bool huge = false, dense = false;      // dense: the scatter fallback of the tile lists is queued (a build met more than AGX_LONG_MAX long hits); huge: pass 3 of the node sweep is queued (a build met a position beyond AGX_MAXV_BIG variants)
     // walk graph (agx_core.h "walk preparation")
@@ -928,6 +930,7 @@ template <class U> void pool_bufs(U *u, agx_u32 cap, Take &t) {
     t.note(u->keep_end, t.arena ? t.arena->first_block_at() : 0);      // (do_trim; ~0: this pool is a regrown one in a later block)
     t(u->d_cid, kcap); t(u->d_coff, kcap); t(u->d_cid0, kcap); t(u->d_coff0, kcap); t(u->d_base, cap); t(u->d_flags, cap);
     if (u->prm.flags & AGX_FLAG_KEEP_COUNTS) t(u->d_counts, (size_t)cap * 6);
+    if (u->prm.flags & AGX_FLAG_EDGE_SUPPORT) t(u->d_e_cnt, (size_t)cap * AGX_MAXE);
     t(u->d_a_str, ids_cap + 1); t(u->d_a_meta, ids_cap + 16); t(u->d_a_mark, ids_cap + 2); t(u->d_side_xpos, (size_t)cap + 1);
     t(u->d_sp_bits, n_words + 1); t(u->d_sp_cnt, n_words + 1); t(u->d_sp_rank, n_words + 2);
     const size_t nb = (std::max<size_t>(n_pos, n_words) + 1 + 1023) / 1024;
@@ -953,9 +956,10 @@ template <class U> void fixed_bufs(U *u, Take &t) {
     t(u->d_big_list, n_tiles + 1); t(u->d_mid_list, n_tiles + 1);
     t(u->d_scratch, (size_t)AGX_BIG_WAVES * AGX_NF * AGX_MAXV_BIG * 64);
     t(u->d_region_off, n_regions + 1); t(u->d_pool_cnt, n_regions * AGX_REGION_PAD);
+    if (u->prm.flags & AGX_FLAG_EDGE_SUPPORT) t(u->d_sup_tot, 2 * n_tiles + 2);
 }
 template <class U> void list_bufs(U *u, agx_u32 cap, Take &t) { t.note(u->list_cap, cap); t(u->d_unsorted, (size_t)cap + 1); t(u->d_tile_recs, ((size_t)cap + 4) * 8); }      // the tile lists
-template <class U> void ovf_bufs(U *u, agx_u32 cap, Take &t) { t.note(u->ovf_cap, cap); t(u->d_ovf, cap); t(u->d_a_ovf, (size_t)cap + 1); }                                  // the edge overflow list
+template <class U> void ovf_bufs(U *u, agx_u32 cap, Take &t) { t.note(u->ovf_cap, cap); t(u->d_ovf, cap); t(u->d_a_ovf, (size_t)cap + 1); if (u->prm.flags & AGX_FLAG_EDGE_SUPPORT) t(u->d_ovf_cnt, cap); }                                  // the edge overflow list
 template <class U> void sparse_bufs(U *u, agx_u32 cap, Take &t) { t.note(u->sp_cap, cap); t(u->d_sp_node, (size_t)cap + 1); t(u->d_sp_hop, (size_t)cap + 2); }               // the sparse record table
 
 void do_release(agx_unit *u);
@@ -1069,8 +1073,14 @@ Plan plan_capacities(const agx_unit *u) {
     P.sp_cap = u->sp_cap ? u->sp_cap : (agx_u32)std::min<size_t>(g_tiny ? 32 : ids_cap / 4 + 4096, 0xFFFFFF00ull);      // special ids: 8 % on the bench unit
     Take m; pool_bufs(u, P.pool_cap, m); fixed_bufs(u, m); list_bufs(u, P.list_cap, m); ovf_bufs(u, P.ovf_cap, m); sparse_bufs(u, P.sp_cap, m);
     P.exact = m.bytes;
-    P.total = P.exact + regrow_slack(P.exact) + ((u->prm.flags & AGX_FLAG_KEEP_COUNTS) ? unitig_layout(P.pool_cap, n_pos, P.ovf_cap, nullptr, nullptr, nullptr) : 0);      // (counts are kept for the unitig export)
+    // What AGX_FLAG_EDGE_SUPPORT adds to the groups (d_e_cnt, d_ovf_cnt, d_sup_tot, in Take's alignment) is reserved ON TOP of the block the unit would take without the flag,
+    // rounded as a block is: a unit with the flag never plans less than the same unit without it plus its counters, whatever the rounding of blocks does to either sum.
+    auto aligned = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t counters = (u->prm.flags & AGX_FLAG_EDGE_SUPPORT) ? aligned((size_t)P.pool_cap * AGX_MAXE * 4) + aligned((size_t)P.ovf_cap * 4) + aligned((2 * (size_t)tiles_of(u) + 2) * 4) : 0;
+    const size_t plain = P.exact - counters;
+    P.total = plain + regrow_slack(plain) + ((u->prm.flags & AGX_FLAG_KEEP_COUNTS) ? unitig_layout(P.pool_cap, n_pos, P.ovf_cap, nullptr, nullptr, nullptr) : 0);      // (counts are kept for the unitig export)
     if (keeps_paths(u)) P.total += idmap_layout(n_pos + P.pool_cap, P.pool_cap, nullptr, nullptr);      // (a whole-window id map at its worst: every slot a side id and a run)
+    if (counters) P.total = round_block(P.total) + counters;
     return P;
 }
 
@@ -1172,7 +1182,7 @@ void do_upload(agx_unit *u) {
     if (!(u->prm.flags & AGX_FLAG_ONE_SHOT)) u->helper.submit(UnitHelper::DL, dl_buffers);      // (a one-shot unit's download borrows the staged inputs' memory: nothing to pin)
     start_helper(u);                                     // then the output buffers
 
-    u->uploaded = true; u->built = false; u->downloaded = false;
+    u->uploaded = true; u->built = false; u->downloaded = false; u->support_valid = false;
     if (!u->pending_walk) { u->pending_walk = true; g_walks_pending.fetch_add(1); }
     u->stats.ms_upload = now_ms() - t0;
     u->stats.device_bytes = u->arena.capacity();
@@ -1249,6 +1259,7 @@ void do_build(agx_unit *u) {
     const agx_u32 n_pos = (agx_u32)u->V.n_pos, nh = (agx_u32)u->nh;
     hipStream_t st = nullptr;              // the device's build stream, taken with the turn
     u->stats.node_sweep_launches = u->stats.edge_sweep_launches = 0;
+    u->support_valid = false; u->stats.n_support_events = 0;      // (the edge counters are the last build's: counted again on the next request)
     agx_u32 swept_windows = 1; bool swept_timed = false;      // of the last attempt
     for (int attempt = 0;; attempt++) {
         if (attempt > 8) throw Error{E_DEVICE, "build did not converge"};
@@ -1685,7 +1696,7 @@ void do_release(agx_unit *u) {
     u->arena.reset();                                  // (empties every d_* view with it)
     graph_arrays(u, GraphCounts{}, [](int, auto &h, auto &, size_t, size_t) { h.release(); }); u->h_fetch.release();
     u->pool_cap = u->spill_lo = u->ovf_cap = u->list_cap = u->sp_cap = 0;
-    u->uploaded = u->built = u->downloaded = false;
+    u->uploaded = u->built = u->downloaded = false; u->support_valid = false;
     join_helper(u);
     u->out.pre_extended.clear(); u->out.extended.clear(); u->out_initial.clear(); u->out_ready = false;
     u->out.paths.clear(); u->out.paths_ready = false;
@@ -2010,6 +2021,21 @@ int agx_unit_stats(const agx_unit *u, agx_stats *s) {
     return AGX_OK;
 }
 
+// canonical numbering (position-major, variant order) of the used slots of a node table that came down whole: canon[slot] = id (NONE: unused), slot_of[id] = slot
+static void number_nodes(const std::vector<agx_u32> &node_start, const std::vector<agx_u16> &node_cnt, agx_u32 cap, agx_u32 nn, std::vector<agx_u32> &canon, std::vector<agx_u32> &slot_of, uint32_t *start_out) {
+    canon.assign(cap, AGX_NONE); slot_of.assign(nn, 0); agx_u32 id = 0;
+    const agx_u32 n_pos = (agx_u32)node_start.size();
+    for (agx_u32 x = 0; x < n_pos; x++) {
+        if (start_out) start_out[x] = id;
+        for (agx_u32 v = 0; v < node_cnt[x]; v++) {
+            if ((size_t)node_start[x] + v >= cap || id >= nn) throw Error{E_DEVICE, "node table is inconsistent (count mismatch)"};
+            slot_of[id] = node_start[x] + v; canon[node_start[x] + v] = id++;
+        }
+    }
+    if (start_out) start_out[n_pos] = id;
+    if (id != nn) throw Error{E_DEVICE, "node table is inconsistent (count mismatch)"};
+}
+
 int agx_unit_graph(agx_unit *u, agx_graph *g) {
     if (!u || !g) return AGX_E_ARG;
     memset(g, 0, sizeof *g);
@@ -2033,16 +2059,8 @@ int agx_unit_graph(agx_unit *u, agx_graph *g) {
         g->n_pos = n_pos; g->n_nodes = nn;
         g->node_start = (uint32_t *)malloc(4 * ((size_t)n_pos + 1)); g->node_key = (uint32_t *)malloc(24 * ((size_t)nn + 1)); g->node_cnt = (int32_t *)malloc(24 * ((size_t)nn + 1));
         g->node_slen = (uint32_t *)malloc(4 * ((size_t)nn + 1)); g->edge_start = (uint32_t *)malloc(4 * ((size_t)nn + 1));
-        std::vector<agx_u32> canon(cap, AGX_NONE), slot_of(nn); agx_u32 id = 0;
-        for (agx_u32 x = 0; x < n_pos; x++) {
-            g->node_start[x] = id;
-            for (agx_u32 v = 0; v < node_cnt[x]; v++) {
-                if ((size_t)node_start[x] + v >= cap || id >= nn) throw Error{E_DEVICE, "node table is inconsistent (count mismatch)"};
-                slot_of[id] = node_start[x] + v; canon[node_start[x] + v] = id++;
-            }
-        }
-        g->node_start[n_pos] = id;
-        if (id != nn) throw Error{E_DEVICE, "node table is inconsistent (count mismatch)"};
+        std::vector<agx_u32> canon, slot_of;
+        number_nodes(node_start, node_cnt, cap, nn, canon, slot_of, g->node_start);
         std::vector<std::vector<agx_u32> > adj(nn);
         for (agx_u32 c = 0; c < nn; c++) for (agx_u32 e = 0; e < AGX_MAXE; e++) { const agx_u32 d = next[(size_t)slot_of[c] * AGX_MAXE + e]; if (d != AGX_NONE) adj[c].push_back(canon[d]); }
         for (agx_u32 i = 0; i < u->n_ovf; i++) adj[canon[ovf[i].src]].push_back(canon[ovf[i].dst]);
@@ -2179,8 +2197,9 @@ struct Export {
     void open(size_t own) {
         u->d_ut.alloc(u->arena, keeps_paths(u) ? mapped_scratch(cap, n_pos, u->n_nodes, u->n_ids, n_ovf, &map_at) : own);
         u->stats.device_bytes = u->arena.capacity();
-        HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        open_stream();
     }
+    void open_stream() { HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }      // (alone: a call that needs none of the export's scratch)
     void fill(void *p, int v, size_t b) const { HIP_OK(hipMemsetAsync(p, v, b ? b : 1, s)); }
     void read(void *host, const void *dev, size_t b) const { HIP_OK(hipMemcpyAsync(host, dev, b, hipMemcpyDeviceToHost, s)); }
     void sync() const { HIP_OK(hipStreamSynchronize(s)); }
@@ -2188,11 +2207,46 @@ struct Export {
 
 // the id map of a mapped export: the caller's table, the kernels' arguments and the window's ids
 struct MapJob { agx_idmap *m; agx_idmap_args M{}; agx_u32 n_wids = 0; };
+// the links' support of an export with support: where the caller wants the array
+struct SupportJob { uint32_t **out; };
+
+// what the edge-support calls refuse: agx_unit_front's preconditions and the flag
+static void support_check(const agx_unit *u) {
+    if (!(u->prm.flags & AGX_FLAG_EDGE_SUPPORT)) throw Error{E_ARG, "edge support: the unit was created without AGX_FLAG_EDGE_SUPPORT (the counters are reserved with the unit's block)"};
+    if (u->prm.flags & AGX_FLAG_ONE_SHOT) throw Error{E_ARG, "edge support: a one-shot unit gives the arrays the counting reads away with its only download"};
+    if (!u->built || u->trimmed || u->downloaded) throw Error{E_ARG, "edge support: the unit is not built (call agx_unit_build; not after agx_unit_download, agx_unit_trim or agx_unit_release)"};
+}
+
+// The edge counters of the last build, made on the first request after it: cleared — e_cnt, ovf_cnt, the unmatched word; the per-tile totals are written for
+// every tile —, counted by agx_k_edge_support on the export's stream, the totals read back and summed.  They stay valid until the next build, upload or release.
+static void ensure_support(const Export &E) {
+    agx_unit *u = E.u;
+    const double t0 = now_ms();
+    if (!u->support_valid) {
+        const size_t nt = u->n_tiles;
+        agx_support_kargs K; fill_sweep_args(u, K.S);
+        K.ovf = u->d_ovf.p; K.n_ovf = E.n_ovf; K.n_hits = (agx_u32)u->nh; K.list_cap = u->list_cap;
+        K.e_cnt = u->d_e_cnt.p; K.ovf_cnt = u->d_ovf_cnt.p; K.tile_events = u->d_sup_tot.p; K.tile_adds = u->d_sup_tot.p + nt; K.unmatched = u->d_sup_tot.p + 2 * nt;
+        K.abort = u->d_words.p + W_STATUS;
+        E.fill(K.e_cnt, 0, (size_t)u->pool_cap * AGX_MAXE * 4); E.fill(K.ovf_cnt, 0, (size_t)u->ovf_cap * 4); E.fill(u->d_sup_tot.p, 0, (2 * nt + 2) * 4);
+        agx_launch_edge_support(&K, E.s);
+        std::vector<agx_u32> tot(2 * nt + 1);
+        E.read(tot.data(), u->d_sup_tot.p, tot.size() * 4); E.sync();
+        HIP_OK(hipGetLastError());
+        if (tot[2 * nt]) throw Error{E_DEVICE, "internal: edge support: " + std::to_string(tot[2 * nt]) + " contributions found no edge of the built graph"};
+        uint64_t ev = 0, ad = 0;
+        for (size_t t = 0; t < nt; t++) { ev += tot[t]; ad += tot[nt + t]; }
+        u->sup_events = ev; u->sup_adds = ad; u->support_valid = true;
+        u->stats.n_support_events = ev;
+    }
+    u->stats.ms_edge_support = now_ms() - t0;
+}
 
 // From "np pieces are cut" to the table in the caller's memory: phase 2 and the totals (a round trip), phase 3 and the download (another).  A is the export's view with its
 // error word at `words`; R: the region export A is the local view of (nullptr: the whole export, whose head counts per position are cleared here); max_nodes bounds the bases;
 // J: also the export's id map — flags read with the totals, runs beside phase 3, four more copies
-static void export_body(const Export &E, agx_unitig_args &A, const agx_unitig_region_args *R, agx_u32 *words, agx_u32 np, agx_u32 max_nodes, agx_unitigs *t, MapJob *J) {
+// S (region exports only): also the support of every link — one kernel behind phase 3 and one more copy; without it the body queues what it queued before
+static void export_body(const Export &E, agx_unitig_args &A, const agx_unitig_region_args *R, agx_u32 *words, agx_u32 np, agx_u32 max_nodes, agx_unitigs *t, MapJob *J, SupportJob *S = nullptr) {
     A.piece_cap = np;
     agx_u32 rounds = 1; while (rounds < 32 && (1ull << (rounds - 1)) < np) rounds++;      // ceil(log2 np) + 1
     E.fill(A.p_seg, 0xFF, (size_t)np * 4);
@@ -2217,17 +2271,27 @@ static void export_body(const Export &E, agx_unitig_args &A, const agx_unitig_re
     }
     agx_launch_unitig_phase3(&A, R, E.s);
     if (J) agx_launch_idmap_runs(R, &J->M, E.s);
+    if (S && nl) {      // (the array grows by half when it must: what a regrow leaves behind stays in the arena until the unit is released)
+        E.u->d_lsup.alloc(E.u->arena, (size_t)nl + nl / 2 + 64); E.u->stats.device_bytes = E.u->arena.capacity();
+        agx_launch_unitig_link_support(R, E.u->d_flags.p, E.u->d_e_cnt.p, E.u->d_ovf_cnt.p, E.u->d_lsup.p, E.s);
+    }
     // the compact arrays (per-node arrays never leave the device) into pinned memory, then into the caller's malloc'd table
     const size_t o_hp = 0, o_hv = o_hp + 4 * (size_t)ns, o_ln = o_hv + 4 * (size_t)ns, o_lp = o_ln + 4 * (size_t)ns, o_cov = (o_lp + 4 * (size_t)ns + 7) & ~(size_t)7,
                  o_so = o_cov + 8 * (size_t)ns, o_lo = o_so + 4 * ((size_t)ns + 1), o_lt = o_lo + 4 * ((size_t)ns + 1), o_seq = o_lt + 4 * (size_t)nl,
-                 o_run = (o_seq + nb + 3) & ~(size_t)3, o_end = o_run + 16 * (size_t)nr;      // (runs: only with an id map)
+                 o_run = (o_seq + nb + 3) & ~(size_t)3, o_sup = o_run + 16 * (size_t)nr, o_end = o_sup + (S ? 4 * (size_t)nl : 0);      // (runs: only with an id map; support: only on request)
     PBuf<char> pin; pin.alloc(o_end + 8);
     auto down = [&](size_t o, const void *src, size_t b) { if (b) E.read(pin.p + o, src, b); };
     down(o_hp, A.s_hpos, 4 * (size_t)ns); down(o_hv, A.s_hvar, 4 * (size_t)ns); down(o_ln, A.s_len, 4 * (size_t)ns); down(o_lp, A.s_last, 4 * (size_t)ns);
     down(o_cov, A.s_cov, 8 * (size_t)ns); down(o_so, A.s_off, 4 * ((size_t)ns + 1)); down(o_lo, A.l_off, 4 * ((size_t)ns + 1)); down(o_lt, A.l_to, 4 * (size_t)nl); down(o_seq, A.seq, nb);
     if (J) { down(o_run, J->M.r_first, 4 * (size_t)nr); down(o_run + 4 * (size_t)nr, J->M.r_last, 4 * (size_t)nr); down(o_run + 8 * (size_t)nr, J->M.r_seg, 4 * (size_t)nr); down(o_run + 12 * (size_t)nr, J->M.r_rank, 4 * (size_t)nr); }
+    if (S && nl) down(o_sup, E.u->d_lsup.p, 4 * (size_t)nl);
     E.read(h, words, 4); E.sync();
     if (h[0]) throw Error{E_DEVICE, "unitigs: the segments are inconsistent (error word " + std::to_string(h[0]) + ")"};
+    if (S && nl) {
+        *S->out = (uint32_t *)malloc(4 * (size_t)nl);
+        if (!*S->out) throw Error{E_ARG, "out of host memory"};
+        memcpy(*S->out, pin.p + o_sup, 4 * (size_t)nl);
+    }
     t->n_segs = ns; t->n_links = nl; t->n_bases = nb;
     t->head_pos = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->head_var = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->n_nodes = (uint32_t *)malloc(4 * ((size_t)ns + 1));
     t->last_pos = (uint32_t *)malloc(4 * ((size_t)ns + 1)); t->coverage = (uint64_t *)malloc(8 * ((size_t)ns + 1)); t->seq_off = (uint64_t *)malloc(8 * ((size_t)ns + 1));
@@ -2292,8 +2356,10 @@ int agx_unit_unitigs(agx_unit *u, agx_unitigs *t) {
 // scratch buffer, a stream of its own; no launch and no memset below is sized by the unit's positions or node slots, only by the window's positions, its kept nodes and the
 // overflow list (which has no position index).  Four host round trips: the kept nodes, the piece and head counts, and export_body's two (the totals, the download) — the
 // whole export above comes through the same body with one trip less in front of it.
-// (m: also the id map of the export, agx_unit_unitigs_mapped; nullptr: every command and copy is agx_unit_unitigs_region's)
-static void region_export(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, agx_idmap *m) {
+// (m: also the id map of the export, agx_unit_unitigs_mapped; nullptr: every command and copy is agx_unit_unitigs_region's; link_support: also the links' support,
+// agx_unit_unitigs_support — the counters are made first if this is the first request since the build)
+static void region_export(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, agx_idmap *m, uint32_t **link_support = nullptr) {
+    if (link_support) support_check(u);
     export_check(u, m != nullptr);
     if (pos_lo > pos_hi || pos_hi > (agx_u32)u->V.n_pos)
         throw Error{E_ARG, "unitigs: region [" + std::to_string(pos_lo) + ", " + std::to_string(pos_hi) + ") is not within the unit's positions [0, " + std::to_string((agx_u32)u->V.n_pos) + ")"};
@@ -2303,6 +2369,8 @@ static void region_export(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_
     if (!n_win || !cap || !u->n_nodes) return;
     // (the buffer of the whole export: the room the upload reserved; a tiny unit: unitig_region_layout)
     E.open(std::max(unitig_layout(cap, n_pos, n_ovf, nullptr, nullptr, nullptr), unitig_region_layout(cap, n_win, std::min<size_t>(u->n_nodes, cap), n_ovf, nullptr, nullptr, nullptr)));
+    if (link_support) ensure_support(E);
+    SupportJob SJ{link_support};
     agx_unitig_region_args R{}; agx_u32 *words = nullptr;
     auto bind = [&](agx_u32 kept) {
         R = agx_unitig_region_args{};
@@ -2346,7 +2414,7 @@ static void region_export(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_
     if (h[0]) throw Error{E_DEVICE, "unitigs: the node table is inconsistent (error word " + std::to_string(h[0]) + ")"};
     const agx_u32 np = h[1];
     if (!np || np > kept || h[2] > np) throw Error{E_DEVICE, "unitigs: piece and head counts out of range"};
-    export_body(E, A, &R, words, np, kept, t, m ? &J : nullptr);
+    export_body(E, A, &R, words, np, kept, t, m ? &J : nullptr, link_support ? &SJ : nullptr);
 }
 
 int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t) {
@@ -2369,6 +2437,71 @@ void agx_idmap_free(agx_idmap *m) {
     if (!m) return;
     free(m->id_first); free(m->id_last); free(m->seg); free(m->rank_first);
     memset(m, 0, sizeof *m);
+}
+
+int agx_unit_unitigs_support(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, uint32_t **link_support, agx_idmap *m) {
+    if (!u || !t || !link_support) return AGX_E_ARG;
+    memset(t, 0, sizeof *t); *link_support = nullptr; if (m) memset(m, 0, sizeof *m);
+    const int rc = guarded(u, [&] {
+        region_export(u, pos_lo, pos_hi, min_coverage, t, m, link_support);
+        if (!*link_support && !(*link_support = (uint32_t *)malloc(4))) throw Error{E_ARG, "out of host memory"};      // (no links: still an array, agx_unitigs_gfa_support refuses NULL)
+    });
+    if (rc != AGX_OK) { agx_unitigs_free(t); agx_link_support_free(*link_support); *link_support = nullptr; if (m) agx_idmap_free(m); }
+    return rc;
+}
+
+void agx_link_support_free(uint32_t *link_support) { free(link_support); }
+
+// The counters in agx_unit_graph's numbering.  The node table's edge arrays come down whole, as in that call, and are renumbered on the host; the overflow list's duplicates
+// merge with their counts summed.
+int agx_unit_edge_support(agx_unit *u, agx_edge_support *s) {
+    if (!u || !s) return AGX_E_ARG;
+    memset(s, 0, sizeof *s);
+    const int rc = guarded(u, [&] {
+        support_check(u);
+        Export E(u);
+        E.open_stream();
+        ensure_support(E);
+        const agx_u32 n_pos = E.n_pos, nn = u->n_nodes, cap = E.cap, n_ovf = E.n_ovf;
+        std::vector<agx_u32> node_start(n_pos), next((size_t)cap * AGX_MAXE), e_cnt((size_t)cap * AGX_MAXE), ovf_cnt(n_ovf); std::vector<agx_u16> node_cnt(n_pos); std::vector<agx_edge_ovf> ovf(n_ovf);
+        if (n_pos) { E.read(node_start.data(), u->d_node_start.p, (size_t)n_pos * 4); E.read(node_cnt.data(), u->d_node_cnt.p, (size_t)n_pos * 2); }
+        if (cap) { E.read(next.data(), u->d_next.p, next.size() * 4); E.read(e_cnt.data(), u->d_e_cnt.p, e_cnt.size() * 4); }
+        if (n_ovf) { E.read(ovf.data(), u->d_ovf.p, (size_t)n_ovf * sizeof(agx_edge_ovf)); E.read(ovf_cnt.data(), u->d_ovf_cnt.p, (size_t)n_ovf * 4); }
+        E.sync();
+        std::vector<agx_u32> canon, slot_of;
+        number_nodes(node_start, node_cnt, cap, nn, canon, slot_of, nullptr);
+        std::vector<std::vector<std::pair<agx_u32, agx_u32> > > adj(nn);      // (target, count)
+        for (agx_u32 c = 0; c < nn; c++) for (agx_u32 e = 0; e < AGX_MAXE; e++) {
+            const size_t at = (size_t)slot_of[c] * AGX_MAXE + e;
+            if (next[at] == AGX_NONE) continue;
+            if (next[at] >= cap) throw Error{E_DEVICE, "node table is inconsistent (an edge outside the pool)"};
+            adj[c].emplace_back(canon[next[at]], e_cnt[at]);
+        }
+        for (agx_u32 i = 0; i < n_ovf; i++) {
+            if (ovf[i].src >= cap || ovf[i].dst >= cap || canon[ovf[i].src] == AGX_NONE) throw Error{E_DEVICE, "node table is inconsistent (an overflow edge outside the pool)"};
+            adj[canon[ovf[i].src]].emplace_back(canon[ovf[i].dst], ovf_cnt[i]);
+        }
+        size_t ne = 0;
+        for (auto &a : adj) {
+            std::sort(a.begin(), a.end());
+            size_t k = 0;
+            for (size_t i = 0; i < a.size(); i++) { if (k && a[k - 1].first == a[i].first) a[k - 1].second += a[i].second; else a[k++] = a[i]; }
+            a.resize(k); ne += k;
+        }
+        s->n_nodes = nn; s->n_edges = (uint32_t)ne; s->n_events = u->sup_events; s->n_contributions = u->sup_adds;
+        s->edge_start = (uint32_t *)malloc(4 * ((size_t)nn + 1)); s->edge_dst = (uint32_t *)malloc(4 * (ne + 1)); s->edge_cnt = (uint32_t *)malloc(4 * (ne + 1));
+        if (!s->edge_start || !s->edge_dst || !s->edge_cnt) throw Error{E_ARG, "out of host memory"};
+        size_t eo = 0;
+        for (agx_u32 c = 0; c < nn; c++) { s->edge_start[c] = (uint32_t)eo; for (const auto &d : adj[c]) { s->edge_dst[eo] = d.first; s->edge_cnt[eo++] = d.second; } }
+        s->edge_start[nn] = (uint32_t)eo;
+    });
+    if (rc != AGX_OK) agx_edge_support_free(s);
+    return rc;
+}
+
+void agx_edge_support_free(agx_edge_support *s) {
+    if (!s) return;
+    free(s->edge_start); free(s->edge_dst); free(s->edge_cnt); memset(s, 0, sizeof *s);
 }
 
 int agx_unit_walk_paths(agx_unit *u, agx_walk_paths *w) {

@@ -1,7 +1,7 @@
 // agx_gfa.cpp — GFA 1.0 text of a unit's unitigs (agx_unitigs_gfa).  Host only: needs no device.
 //
 //   S	u<unit>_<pos>_<var>	<sequence>	LN:i:<nodes>	KC:i:<coverage>	pe:i:<last position>
-//   L	<from segment>	+	<to segment>	+	0M
+//   L	<from segment>	+	<to segment>	+	0M      (agx_unitigs_gfa_support: + RC:i:<events that name the link's edge>)
 //   P	p<unit>_<record>_<first base>	<segment>+,<segment>+,...	*	ln:i:<nodes>	fs:i:<first rank>	ls:i:<last rank>      (agx_unitigs_paths_gfa)
 //
 // S lines in segment order, then L lines in link order (agx_unit_unitigs leaves both sorted).  A large unit is formatted by several threads, each
@@ -34,10 +34,13 @@ void format_segments(const agx_unitigs *t, const std::string &prefix, uint32_t l
     }
 }
 
-void format_links(const agx_unitigs *t, const std::string &prefix, uint32_t lo, uint32_t hi, std::string &o) {
-    o.reserve((size_t)(hi - lo) * 56);
+// sup: the links' support for the RC tag, or nullptr for the line without it
+void format_links(const agx_unitigs *t, const uint32_t *sup, const std::string &prefix, uint32_t lo, uint32_t hi, std::string &o) {
+    o.reserve((size_t)(hi - lo) * (sup ? 72 : 56));
     for (uint32_t i = lo; i < hi; i++) {
-        o += "L\t"; put_name(o, prefix, t, t->link_from[i]); o += "\t+\t"; put_name(o, prefix, t, t->link_to[i]); o += "\t+\t0M\n";
+        o += "L\t"; put_name(o, prefix, t, t->link_from[i]); o += "\t+\t"; put_name(o, prefix, t, t->link_to[i]); o += "\t+\t0M";
+        if (sup) { o += "\tRC:i:"; put_u64(o, sup[i]); }
+        o += '\n';
     }
 }
 
@@ -158,7 +161,8 @@ void agx_unitigs_free(agx_unitigs *t) {
 
 void agx_text_free(char *text) { free(text); }
 
-int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len) {
+// the S and L lines of either form (sup: see format_links)
+static int gfa_text(const agx_unitigs *t, const uint32_t *sup, int unit, char **text, size_t *len) {
     if (!t || !text || !len || unit < 0) return AGX_E_ARG;
     *text = nullptr; *len = 0;
     const uint32_t ns = t->n_segs, nl = t->n_links;
@@ -178,7 +182,7 @@ int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len) {
             }
         }
         std::vector<std::string> so(nt), lo(nt);
-        auto work = [&](unsigned k) { format_segments(t, prefix, sb[k], sb[k + 1], so[k]); format_links(t, prefix, lb[k], lb[k + 1], lo[k]); };
+        auto work = [&](unsigned k) { format_segments(t, prefix, sb[k], sb[k + 1], so[k]); format_links(t, sup, prefix, lb[k], lb[k + 1], lo[k]); };
         if (nt == 1) work(0);
         else {
             std::vector<std::thread> th;
@@ -199,6 +203,15 @@ int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len) {
     } catch (...) {
         return AGX_E_ARG;
     }
+}
+
+int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len) { return gfa_text(t, nullptr, unit, text, len); }
+
+int agx_unitigs_gfa_support(const agx_unitigs *t, const uint32_t *link_support, int unit, char **text, size_t *len) {
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (!link_support) return AGX_E_ARG;
+    return gfa_text(t, link_support, unit, text, len);
 }
 
 }  // extern "C"

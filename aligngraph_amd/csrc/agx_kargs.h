@@ -47,6 +47,16 @@ struct agx_edge_kargs {
     const agx_u32 *abort;                      // the node sweeps' status word: non-zero = the node table is incomplete, do nothing
     const agx_u32 *big_list; const agx_u32 *big_n;   // tiles the fallback pass wrote (their edges are all pass A/B's)
 };
+// Edge support (agx_k_edge_support): one more pass over the tile lists of a converged build.  It reads the front of the build and the final node table and writes
+// only the counters: e_cnt parallel to n_next, ovf_cnt parallel to the overflow list (n_ovf: its live entries), and per tile the events it saw and the contributions it made
+// (summed on the host: one counter for all wavefronts would be one contended address).  unmatched: contributions that found no edge, and events that met an index outside the tables.
+struct agx_support_kargs {
+    agx_sweep_args S; const agx_edge_ovf *ovf; agx_u32 n_ovf, n_hits, list_cap;
+    agx_u32 *e_cnt, *ovf_cnt;          // [pool_cap * AGX_MAXE], [ovf_cap]: zeroed by the caller
+    agx_u32 *tile_events, *tile_adds;  // [n_tiles] each: written for every tile
+    agx_u32 *unmatched;                // zeroed by the caller
+    const agx_u32 *abort;              // the build's status word
+};
 // Unitig export (agx_unitig.hip): reads the node table a build left in HBM, writes only its own scratch.  Slot arrays are [pool_cap], piece arrays
 // [piece_cap], segment arrays [piece_cap + 1] (every unitig head is a piece start, so there are never more segments than pieces).
 struct agx_unitig_args {
@@ -175,4 +185,8 @@ void agx_launch_idmap_bounds(const agx_unitig_region_args *, const agx_idmap_arg
 void agx_launch_idmap_flags(const agx_unitig_region_args *, const agx_idmap_args *, hipStream_t);
 void agx_launch_idmap_runs(const agx_unitig_region_args *, const agx_idmap_args *, hipStream_t);
 void agx_launch_node_sweep_huge(const agx_node_kargs *, hipStream_t);
+void agx_launch_edge_support(const agx_support_kargs *, hipStream_t);
+// behind phase 3 of a region export: l_sup[i] = support of link i's edge, the last node of its source segment -> the head node of its target segment, overflow duplicates summed
+// (n_flags: the unit's, for AGX_NF_EOVF — only such tails walk the overflow list, once per link)
+void agx_launch_unitig_link_support(const agx_unitig_region_args *, const agx_u8 *n_flags, const agx_u32 *e_cnt, const agx_u32 *ovf_cnt, agx_u32 *l_sup, hipStream_t);
 }

@@ -961,6 +961,70 @@ __global__ void __launch_bounds__(256) agx_k_reprune(agx_reprune_args A, agx_u32
     if (X < A.n_pos) A.side_pk[X] = agx_side_pack(side_incl - side, side);
     if (lane == 63u) A.tile_side[tile] = side_incl;
 }
+// ---- edge support (agx_core.h): how many events name each edge -----------------------------------------------------------------------------
+// The node sweep's shape once more: a wavefront per tile, lane = position, the tile's list read in order with wave-uniform (scalar) record loads (a lean record names
+// its hit, tile_recs[2 * i + 1].w, for the lanes that need the hit's own record).  Every (hit, X) is in the list
+// of X's tile only, so every event is seen once, by one lane.  Nearly every position holds one variant and so does its neighbour: such a lane counts its x -> x+1 events in a
+// register and stores the sum once — no other lane and no atomic of its own reaches that counter, since only events with source X name edges out of X's node and all of this
+// lane's with successor X+1 take the register.  Everything else (several variants on either side, steps that skip positions) resolves through agx_support_event and adds
+// atomically to the counter of the slot that holds the target; integer adds, so the counts do not depend on the order.  A target in no inline slot is an overflow edge: the lane
+// walks the overflow list for its entry (sources with AGX_NF_EOVF only).  A contribution without an edge goes to `unmatched`, never to memory it does not own: every index
+// is checked against the capacity of what it names (agx_for_variants, agx_support_event, below).
+__device__ __forceinline__ void agx_support_count(const agx_support_kargs &K, agx_u32 src, agx_u32 dst, agx_u32 n) {      // src < pool_cap
+    const agx_u32 e = agx_support_slot(K.S.n_next, src, dst);
+    if (e < AGX_MAXE) { atomicAdd(K.e_cnt + (size_t)src * AGX_MAXE + e, n); return; }
+    const agx_u32 i = (K.S.n_flags[src] & AGX_NF_EOVF) ? agx_support_ovf_entry(K.ovf, K.n_ovf, src, dst) : K.n_ovf;
+    if (i < K.n_ovf) atomicAdd(K.ovf_cnt + i, n); else atomicAdd(K.unmatched, n);
+}
+__global__ void __launch_bounds__(256) agx_k_edge_support(agx_support_kargs K) {
+    AGX_RETURN_IF_ABORTED(K.abort);
+    const agx_u32 lane = threadIdx.x & 63u;
+    const agx_u32 tile = (agx_u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * AGX_WAVES_PER_BLOCK + (threadIdx.x >> 6)));
+    if (tile >= K.S.n_tiles) return;                                          // wave-uniform: every lane of a tile reaches the scans
+    const agx_u32 X = tile * AGX_TILE + lane;
+    const bool live = X < K.S.n_pos, has1 = live && X + 1 < K.S.n_pos;
+    agx_u32 hi = K.S.tile_off[tile + 1], lo = K.S.tile_off[tile];
+    hi = hi < K.list_cap ? hi : K.list_cap; lo = lo < hi ? lo : hi;
+    const agx_u32 own_n = live ? K.S.node_cnt[X] : 0u, own_s = live ? K.S.node_start[X] : 0u, nb_n = has1 ? K.S.node_cnt[X + 1] : 0u, nb_s = has1 ? K.S.node_start[X + 1] : 0u;
+    const bool single = own_n == 1u && nb_n == 1u && own_s < K.S.pool_cap && nb_s < K.S.pool_cap;
+    const bool ok1 = single && agx_edge_allowed(K.S, own_s, nb_s);
+    agx_u32 c_fast = 0, events = 0, adds = 0, bad = 0;
+    const agx_tile_recs recs{K.S.tile_recs, K.S.dhit};
+    auto add = [&](agx_u32 src, agx_u32 dst) { adds++; agx_support_count(K, src, dst, 1u); };
+    for (agx_u32 i = lo; i < hi; i++) {                                       // wave-uniform trip count
+        // The entry's lean record says, for every kind but GENERAL, what agx_decode_arrival says on every lane of the tile (agx_lean_make's contract): an arrival that is not
+        // the hit's last one is an event, and its successor is X + 1 unless the record marks a jump.  That is all the register path needs — one scalar load and a handful
+        // of vector instructions per entry, as in pass 0 of the node sweep.  The hit's own derived record is fetched only when some lane needs more: a GENERAL record, a
+        // jump, an event at a position that is not single -> single.  (Measured and dropped: resolving such an event from the lean record alone where its successor lies
+        // in the same tile — the next lane's mate position is the successor's — took 4.45 ms on the 30.4 Mb unit against 2.74: DESIGN.md §13.)
+        const agx_lrec r = recs.lean(i);
+        const agx_larr la = agx_lean_decode(r, lane);
+        const bool lean_event = live && la.has && !la.last;                   // (kind GENERAL: no lane has an arrival)
+        const bool reg = lean_event && !la.jump && single;                    // (single: X + 1 lies inside the unit)
+        const bool need = (r.geo >> 30) == (agx_u32)AGX_LK_GENERAL ? live : (lean_event && !reg);
+        events += reg ? 1u : 0u;
+        c_fast += (reg && ok1) ? 1u : 0u;
+        if (__ballot(need) == 0ull) continue;                                 // wave-uniform
+        if (r.hit >= K.n_hits) { bad += lane == 0u ? 1u : 0u; continue; }
+        const agx_dhit d = recs.of_hit(r.hit);
+        if (need) {
+            const agx_arrival a = agx_decode_arrival(d, K.S.runs, X, K.S.k);
+            if (a.has && a.has_succ && a.xs < K.S.n_pos) {
+                events++;
+                if (single && a.xs == X + 1) c_fast += ok1 ? 1u : 0u;         // (a GENERAL record's step at a single -> single position: the register owns that counter)
+                else bad += agx_support_event(K.S, X, a, true, add) ? 0u : 1u;
+            }
+        }
+    }
+    if (c_fast) {
+        const agx_u32 e = agx_support_slot(K.S.n_next, own_s, nb_s);
+        if (e < AGX_MAXE) K.e_cnt[(size_t)own_s * AGX_MAXE + e] = c_fast; else agx_support_count(K, own_s, nb_s, c_fast);
+        adds += c_fast;
+    }
+    if (bad) atomicAdd(K.unmatched, bad);
+    const agx_u32 ev_incl = agx_wave_incl_scan(events, lane), add_incl = agx_wave_incl_scan(adds, lane);
+    if (lane == 63u) { K.tile_events[tile] = ev_incl; K.tile_adds[tile] = add_incl; }
+}
 // the special-id bitmap and its popcounts (input of the rank scan).  A wavefront takes four 64-id words — every lane one id of each, so that their loads
 // are in flight together — and writes nothing for words past the live ids: sp_bits / sp_cnt are zeroed at the start of the build (the grid covers the id
 // CAPACITY, 2.4 x the live ids of a first build: r02 spent 0.42 ms here on a 30 Mb unit, most of it rounds of threads that only found out they were idle)
@@ -1206,6 +1270,9 @@ void agx_launch_copy_out(void *const *dst, const void *const *src, const size_t 
 void agx_launch_fetch_records(const agx_compact_args *A, agx_u32 first, agx_u32 stride, agx_u32 rows, agx_u32 width, agx_walknode *out, hipStream_t st) {
     const agx_u32 n = rows * width;
     if (n) hipLaunchKernelGGL(agx_k_fetch_records, dim3((n + 255) / 256), dim3(256), 0, st, *A, first, stride, rows, width, out);
+}
+void agx_launch_edge_support(const agx_support_kargs *K, hipStream_t st) {
+    if (K->S.n_tiles) hipLaunchKernelGGL(agx_k_edge_support, dim3((K->S.n_tiles + AGX_WAVES_PER_BLOCK - 1) / AGX_WAVES_PER_BLOCK), dim3(64 * AGX_WAVES_PER_BLOCK), 0, st, *K);
 }
 void agx_launch_reprune(const agx_reprune_args *A, agx_u32 n_tiles, hipStream_t st) {
     if (n_tiles) hipLaunchKernelGGL(agx_k_reprune, dim3((n_tiles + 3u) / 4u), dim3(256), 0, st, *A, n_tiles);

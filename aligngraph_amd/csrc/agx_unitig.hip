@@ -402,6 +402,30 @@ __global__ void __launch_bounds__(256) agx_k_utr_links_ovf(agx_unitig_region_arg
     ut_ovf_link(A, ls, ld);
 }
 
+// the support of every link of a region export (agx_unit_unitigs_support), behind phase 3: a thread per kept node, the tails work.  Link i of the tail's segment enters
+// segment l_to[i] at its head node (a node a link enters has no internal predecessor); the edge tail -> head sits in an inline slot of the tail, or — tails with
+// AGX_NF_EOVF only — on the overflow list, whose duplicates are summed.  Every link is written by its one tail.
+__global__ void __launch_bounds__(256) agx_k_utr_link_support(agx_unitig_region_args R, const agx_u8 *n_flags, const agx_u32 *e_cnt, const agx_u32 *ovf_cnt, agx_u32 *l_sup) {
+    const agx_unitig_args &A = R.U;
+    const agx_u32 id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= A.pool_cap || A.nxt[id] != AGX_NONE) return;
+    const agx_u32 seg = A.indeg[id], ns = A.hoff[A.n_pos], u = R.l_slot[id];
+    if (seg >= ns || u >= R.pool_cap) { atomicOr(A.err, 4u); return; }
+    const agx_u32 lo = A.l_off[seg], hi = A.l_off[seg + 1] < A.link_cap ? A.l_off[seg + 1] : A.link_cap;
+    const uint4 nx = *reinterpret_cast<const uint4 *>(A.n_next + (size_t)u * AGX_MAXE);
+    const agx_u32 t[AGX_MAXE] = {nx.x, nx.y, nx.z, nx.w};
+    const bool eovf = (n_flags[u] & AGX_NF_EOVF) != 0;
+    for (agx_u32 i = lo; i < hi; i++) {
+        const agx_u32 g = A.l_to[i];
+        if (g >= ns) { atomicOr(A.err, 4u); continue; }
+        const agx_u32 h = A.node_start[A.s_hpos[g]] + A.s_hvar[g];      // (s_hpos: a position of the window, written from pos_of)
+        agx_u32 sum = 0;
+        for (agx_u32 e = 0; e < AGX_MAXE; e++) sum += t[e] == h ? e_cnt[(size_t)u * AGX_MAXE + e] : 0u;
+        if (eovf) for (agx_u32 j = 0; j < A.n_ovf; j++) sum += (A.ovf[j].src == u && A.ovf[j].dst == h) ? ovf_cnt[j] : 0u;
+        l_sup[i] = sum;
+    }
+}
+
 // ---- id map of a region export (agx_unit_unitigs_mapped, agx_kargs.h: agx_idmap_args) ------------------------------------------------------------------------
 // One thread per window id; nothing is sized by the unit.  (segment, rank) per local id are the rank kernel's (U.indeg, U.osucc), which phase 3 only reads.
 
@@ -541,6 +565,10 @@ extern "C" void agx_launch_unitig_phase3(const agx_unitig_args *A, const agx_uni
         else hipLaunchKernelGGL(agx_k_ut_links_ovf, ut_grid(A->n_ovf), dim3(256), 0, st, *A);
     }
     if (A->piece_cap) hipLaunchKernelGGL(agx_k_ut_links_sort, ut_grid(A->piece_cap), dim3(256), 0, st, *A);
+}
+
+extern "C" void agx_launch_unitig_link_support(const agx_unitig_region_args *R, const agx_u8 *n_flags, const agx_u32 *e_cnt, const agx_u32 *ovf_cnt, agx_u32 *l_sup, hipStream_t st) {
+    if (R->U.pool_cap && R->U.link_cap) hipLaunchKernelGGL(agx_k_utr_link_support, ut_grid(R->U.pool_cap), dim3(256), 0, st, *R, n_flags, e_cnt, ovf_cnt, l_sup);
 }
 
 extern "C" void agx_launch_unitig_totals(const agx_unitig_args *A, agx_u32 *tot, hipStream_t st) {

@@ -67,6 +67,9 @@ typedef struct {
 #define AGX_FLAG_KEEP_PATHS 16u /* agx_unit_finish keeps the graph stretches of every written pre-extended record for agx_unit_walk_paths, and (with AGX_FLAG_KEEP_COUNTS) the
                                      unit's block reserves the scratch of agx_unit_unitigs_mapped.  The outputs of a finish are the same bytes with and without it */
 
+#define AGX_FLAG_EDGE_SUPPORT 32u /* the unit's block also holds one counter per edge (four bytes per inline edge slot and per overflow entry) for agx_unit_edge_support and
+                                     agx_unit_unitigs_support.  A build queues nothing for it: the counting runs on the first request after a build */
+
 /* ---- packed inputs -------------------------------------------------------------------------------- */
 
 /* n read bases from read index q sit on reference offsets t, t+1, ...  (Segment, AG:44-49) */
@@ -127,6 +130,9 @@ typedef struct {
                                                                     node sweep, and the positions pass A found with several variants there or at x+1 */
     uint32_t reprune_attempts;                                   /* of the last agx_unit_reprune: 1 unless the sparse record table had to grow and the reprune was repeated */
     double ms_reprune;                                           /* host wall time of the last agx_unit_reprune, from entry to its counters being back */
+    double ms_edge_support;                                      /* host wall time the last agx_unit_edge_support / agx_unit_unitigs_support spent making sure the edge counters are there: zeroing,
+                                                                    the counting kernel and the wait for its totals on the first call after a build, next to nothing on later ones */
+    uint64_t n_support_events;                                   /* events the counting saw (agx_edge_support::n_events); 0 before the first counting call after a build */
 } agx_stats;
 
 /* Node/edge tables in canonical numbering (position-major, variant order), for parity tests. malloc'd; free with agx_graph_free. */
@@ -155,6 +161,14 @@ typedef struct {
     char *seq;              /* [n_bases] one base per node: the consensus, or the reference base where the node has no votes */
     uint32_t *link_from, *link_to;   /* [n_links] segment indexes */
 } agx_unitigs;
+
+/* Edge support: for every edge of agx_unit_graph, in its numbering (edge_start / edge_dst are that call's arrays), the number of EVENTS that name it.  An event
+ * is one step of one kept hit from an aligned position P to the next one N inside the unit — one call of the reference's updateKMer (AG:1353-1624) with a k2 half.  It names
+ * every pair (s, d) of a variant s that one of its candidate keys at P resolves to and a variant d that one of its candidate keys at N resolves to, if the pair passes the
+ * contig-consistency test of AG:1602-1615; each pair once per event.  Every edge has support >= 1, no event names a pair that is not an edge, and the numbers do not depend on
+ * the coverage threshold.  n_events: the events; n_contributions: the sum of edge_cnt.  malloc'd; free with agx_edge_support_free. */
+typedef struct { uint32_t n_nodes, n_edges; uint64_t n_events, n_contributions;
+                 uint32_t *edge_start, *edge_dst, *edge_cnt; } agx_edge_support;
 
 /* The id map of an export (agx_unit_unitigs_mapped): which walk ids have their node in the export, and where.  Runs are sorted by id_first; walk id a lies in run r iff
  * id_first[r] <= a <= id_last[r], and its node is then node number rank_first[r] + (a - id_first[r]) of segment seg[r].  Runs are maximal (no two neighbours could be merged)
@@ -324,6 +338,18 @@ int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint3
  * agx_unit_unitigs_region gives for the same arguments. */
 int agx_unit_unitigs_mapped(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, agx_idmap *m);
 void agx_idmap_free(agx_idmap *m);
+/* Edge support of a built unit created with AGX_FLAG_EDGE_SUPPORT.  Preconditions of agx_unit_front (built; not downloaded, trimmed or released; not AGX_FLAG_ONE_SHOT) plus the
+ * flag: AGX_E_ARG with the reason otherwise, and a refused call leaves the unit as it was.  The first call after a build zeroes the counters and runs one kernel over the tile
+ * lists (agx_k_edge_support); the counters then stay valid until the next build, upload or release (agx_unit_reprune does not touch them), and later calls only convert.
+ * A contribution that finds no edge is AGX_E_DEVICE ("internal:").  The conversion to agx_unit_graph's numbering is done on the host and costs what that call's does. */
+int agx_unit_edge_support(agx_unit *u, agx_edge_support *s);
+void agx_edge_support_free(agx_edge_support *s);
+/* agx_unit_unitigs_region (m == NULL) or agx_unit_unitigs_mapped (m != NULL) plus, for every link of t, the support of its edge: from the LAST node of segment link_from[i] to the
+ * head node of segment link_to[i].  The number is the edge's own: it does not depend on the window or the threshold.  t and m are what the calls without support give for the
+ * same arguments.  Preconditions of agx_unit_edge_support and of the export (AGX_FLAG_KEEP_COUNTS; AGX_FLAG_KEEP_PATHS when m != NULL).  *link_support: [t->n_links], malloc'd,
+ * free it with agx_link_support_free (never NULL after AGX_OK, also without links). */
+int agx_unit_unitigs_support(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, uint32_t **link_support, agx_idmap *m);
+void agx_link_support_free(uint32_t *link_support);
 /* The stretches the last agx_unit_finish kept (AGX_FLAG_KEEP_PATHS).  Valid after a finish, also of trimmed and one-shot units, until the next finish, upload, reprune or release;
  * AGX_E_ARG without the flag or before a finish.  The caller gets copies. */
 int agx_unit_walk_paths(agx_unit *u, agx_walk_paths *w);
@@ -331,6 +357,8 @@ void agx_walk_paths_free(agx_walk_paths *w);
 void agx_unitigs_free(agx_unitigs *t);
 /* Host only: the S and L lines of GFA 1.0 for unit `unit` (no header line), as DESIGN.md §11 defines them; *text is malloc'd, free it with agx_text_free. */
 int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len);
+/* Host only: the bytes of agx_unitigs_gfa with "\tRC:i:<link_support[i]>" appended to the L line of link i (GFA 1.0's read-count tag).  AGX_E_ARG also for link_support == NULL. */
+int agx_unitigs_gfa_support(const agx_unitigs *t, const uint32_t *link_support, int unit, char **text, size_t *len);
 /* Host only: the P lines of GFA 1.0 that lay the records of w over the segments of t (m: the id map of the same export), as DESIGN.md §11 "Paths" defines them:
  *   P\tp<unit>_<record>_<base_off>\t<seg>+,<seg>+,...\t*\tln:i:<nodes>\tfs:i:<rank of the first node in the first segment>\tls:i:<rank of the last node in the last segment>
  * one line per maximal piece of a record's node sequence that stays on edges and inside the map, ordered by (record, first base).  AGX_E_ARG where the three tables do not
