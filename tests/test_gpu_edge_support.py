@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import edge_support_model as ESM
+from gpu_checks import check_counts
 from test_edge_support_cases import EDGE_UNITS, SEED_UNITS, UNITS, modelled  # noqa: F401  (modelled: the module fixture)
 
 pytestmark = pytest.mark.gpu
@@ -73,15 +74,6 @@ def engine_of(agx, modelled):
             made[name] = run_engine(agx, u, tmp, reprune_to=u.coverage + 2)
         return made[name]
     return get
-
-
-def check_counts(got, graph, model):
-    assert np.array_equal(got["edge_start"], graph["edge_start"]) and np.array_equal(got["edge_dst"], graph["edge_dst"])
-    assert np.array_equal(got["edge_start"], model["edge_start"]) and np.array_equal(got["edge_dst"], model["edge_dst"])
-    assert got["n_nodes"] == graph["n_nodes"] and got["n_edges"] == graph["n_edges"]
-    assert np.array_equal(got["edge_cnt"], model["edge_cnt"])
-    assert got["n_events"] == model["n_events"] and got["n_contributions"] == model["n_contributions"]
-    assert (got["edge_cnt"] >= 1).all()
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -18,8 +18,8 @@ import pytest
 import edge_units as EU
 import harness as H
 import lean_units as LU
-import walk_model as WM
 import walk_units as WU
+from gpu_checks import check_walk as check
 from hostsim import sim
 
 pytestmark = pytest.mark.gpu
@@ -68,18 +68,6 @@ def run_engine(agx, tmp, k, iv, cov, forms, flags=0, unit=0):
         out = u.finish()
         out["stats"] = u.stats()
     return dumps, out
-
-
-def check(o, dumps, out, cov, executor=None, sparse_min=False):
-    m = WM.build(o["graph"], cov, sparse_min=sparse_min)
-    for w in dumps:
-        assert WM.mismatch(m, w) is None
-        if executor is not None:
-            assert WM.same_bits(executor, w) is None
-    for key in ("initial", "pre", "extended"):
-        assert out[key] == o[key], key
-    assert out["stats"]["n_walk_ids"] == m["n_ids"] and out["stats"]["n_special"] == m["n_special"]
-    return m
 
 
 def streams(o):
