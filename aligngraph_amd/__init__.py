@@ -29,6 +29,7 @@ EXPORTS = [
     "agx_unit_walk_graph", "agx_walk_graph_free", "agx_unit_front", "agx_front_free",
     "agx_unit_unitigs_mapped", "agx_idmap_free", "agx_unit_walk_paths", "agx_walk_paths_free", "agx_unitigs_paths_gfa", "agx_unit_reprune",
     "agx_unit_edge_support", "agx_edge_support_free", "agx_unit_unitigs_support", "agx_link_support_free", "agx_unitigs_gfa_support",
+    "agx_unit_walk_evidence", "agx_walk_evidence_free", "agx_walk_evidence_bed",
 ]
 
 
@@ -74,7 +75,7 @@ class Stats(ctypes.Structure):
                [(n, ctypes.c_uint64) for n in ("upload_bytes", "device_bytes", "pinned_bytes_cached", "device_bytes_cached", "n_spilled")] + \
                [("build_attempts", ctypes.c_uint32), ("from_cache", ctypes.c_uint32), ("dense_lists", ctypes.c_uint32), ("rows_by_reference", ctypes.c_uint32)] + \
                [("n_edge_slow", ctypes.c_uint64), ("reprune_attempts", ctypes.c_uint32), ("ms_reprune", ctypes.c_double)] + \
-               [("ms_edge_support", ctypes.c_double), ("n_support_events", ctypes.c_uint64)]
+               [("ms_edge_support", ctypes.c_double), ("n_support_events", ctypes.c_uint64), ("ms_walk_evidence", ctypes.c_double)]
 
 
 class Graph(ctypes.Structure):
@@ -105,6 +106,19 @@ class WalkPaths(ctypes.Structure):
     _fields_ = [("n_recs", ctypes.c_uint32), ("n_stretches", ctypes.c_uint64), ("rec_len", ctypes.POINTER(ctypes.c_uint64)), ("st_off", ctypes.POINTER(ctypes.c_uint64)),
                 ("id_first", ctypes.POINTER(ctypes.c_uint32)), ("id_last", ctypes.POINTER(ctypes.c_uint32)), ("base_off", ctypes.POINTER(ctypes.c_uint64)),
                 ("joined", ctypes.POINTER(ctypes.c_uint8))]
+
+
+class WalkEvidence(ctypes.Structure):
+    _fields_ = [("n_recs", ctypes.c_uint32), ("n_intervals", ctypes.c_uint32), ("n_graph_bases", ctypes.c_uint64), ("n_steps", ctypes.c_uint64), ("n_steps_without_edge", ctypes.c_uint64)] + \
+               [(n, ctypes.POINTER(ctypes.c_uint64)) for n in ("rec_graph_bases", "rec_steps", "rec_depth_sum")] + \
+               [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("rec_depth_min", "rec_depth_min_at", "rec_step_min", "rec_step_min_at",
+                                                               "iv_rec", "iv_first", "iv_last", "iv_depth_min", "iv_step_min")] + \
+               [("rec_lo", ctypes.c_uint32), ("rec_hi", ctypes.c_uint32), ("n_track", ctypes.c_uint64), ("track_off", ctypes.POINTER(ctypes.c_uint64))] + \
+               [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("depth", "votes", "step")]
+
+
+REC_EVIDENCE = ("rec_graph_bases", "rec_steps", "rec_depth_sum", "rec_depth_min", "rec_depth_min_at", "rec_step_min", "rec_step_min_at")
+IV_EVIDENCE = ("iv_rec", "iv_first", "iv_last", "iv_depth_min", "iv_step_min")
 
 
 class WalkGraph(ctypes.Structure):
@@ -244,6 +258,10 @@ def lib():
         L.agx_link_support_free.restype = None
         L.agx_unitigs_gfa_support.argtypes = [ctypes.POINTER(Unitigs), ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         L.agx_text_free.argtypes = [ctypes.c_void_p]
+        L.agx_unit_walk_evidence.argtypes = [ctypes.c_void_p, ctypes.POINTER(WalkPaths)] + [ctypes.c_uint32] * 5 + [ctypes.POINTER(WalkEvidence)]
+        L.agx_walk_evidence_free.argtypes = [ctypes.POINTER(WalkEvidence)]
+        L.agx_walk_evidence_free.restype = None
+        L.agx_walk_evidence_bed.argtypes = [ctypes.POINTER(WalkEvidence), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         L.agx_text_free.restype = None
         L.agx_run_unit.argtypes = [ctypes.POINTER(Params), ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Result), ctypes.c_char_p, ctypes.c_size_t]
         _lib = L
@@ -559,6 +577,39 @@ class Unit:
         finally:
             lib().agx_walk_paths_free(ctypes.byref(w))
 
+    def walk_evidence(self, w=None, min_depth=0, min_support=0, tracks=False, records=None):
+        """The evidence under the records of a stretch table (agx_unit_walk_evidence; needs keep_counts, and edge_support for the steps): w is a dict like walk_paths()
+        returns (None: walk_paths() itself).  Per record rec_graph_bases, rec_steps, rec_depth_sum, rec_depth_min / _at, rec_step_min / _at; the weak intervals at the
+        thresholds iv_rec, iv_first, iv_last, iv_depth_min, iv_step_min; the totals n_graph_bases, n_steps, n_steps_without_edge.  0xFFFFFFFF: no number.  tracks=True:
+        also depth, votes and step per graph base of the records `records` = (lo, hi) (None: all) with track_off per stretch of those records, and rec_lo, rec_hi."""
+        import numpy as np
+        if w is None:
+            w = self.walk_paths()
+        ws, _keep = _walk_paths_struct(w)
+        lo, hi = (0, ws.n_recs) if records is None else records
+        for v in (min_depth, min_support, lo, hi):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise AgxError(AGX_E_ARG, "walk evidence: thresholds and record bounds are unsigned 32-bit numbers")
+        e = WalkEvidence()
+        self._check(lib().agx_unit_walk_evidence(self._h, ctypes.byref(ws), int(min_depth), int(min_support), 1 if tracks else 0, int(lo), int(hi), ctypes.byref(e)))
+        try:
+            def arr(p, n, dt):
+                return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
+            out = {"n_graph_bases": e.n_graph_bases, "n_steps": e.n_steps, "n_steps_without_edge": e.n_steps_without_edge}
+            for k in REC_EVIDENCE:
+                out[k] = arr(getattr(e, k), e.n_recs, "uint64" if k in REC_EVIDENCE[:3] else "uint32")
+            for k in IV_EVIDENCE:
+                out[k] = arr(getattr(e, k), e.n_intervals, "uint32")
+            if tracks:
+                st = np.asarray(w["st_off"]).astype(np.int64)
+                n_st = int(st[hi] - st[lo]) if len(st) else 0
+                out.update(rec_lo=e.rec_lo, rec_hi=e.rec_hi, track_off=arr(e.track_off, n_st + 1, "uint64"))
+                for k in ("depth", "votes", "step"):
+                    out[k] = arr(getattr(e, k), e.n_track, "uint32")
+            return out
+        finally:
+            lib().agx_walk_evidence_free(ctypes.byref(e))
+
     def gfa(self, unit=0, region=None, min_coverage=None, edge_support=False):
         """GFA 1.0 S and L lines of the unit's unitigs, segments named u<unit>_<pos>_<var> (no header line); region and min_coverage as in unitigs().
         edge_support=True: every L line also carries RC:i:<events that name the link's edge> (agx_unitigs_gfa_support)."""
@@ -620,6 +671,36 @@ def gfa_paths(t, w, unit=0):
     rc = lib().agx_unitigs_paths_gfa(ctypes.byref(ts), ctypes.byref(m), ctypes.byref(ws), unit, ctypes.byref(p), ctypes.byref(n))
     if rc != AGX_OK:
         raise AgxError(rc, "agx_unitigs_paths_gfa: the unitig table, the id map and the stretches do not agree")
+    try:
+        return ctypes.string_at(p, n.value) if n.value else b""
+    finally:
+        lib().agx_text_free(p)
+
+
+def _walk_paths_struct(w):
+    """An agx_walk_paths over the arrays of a dict like Unit.walk_paths() returns; returns (struct, the buffers it points into)."""
+    import numpy as np
+    wk = {k: np.ascontiguousarray(w[k], dtype=dt) for k, dt in (("rec_len", "uint64"), ("st_off", "uint64"), ("id_first", "uint32"), ("id_last", "uint32"),
+                                                                 ("base_off", "uint64"), ("joined", "uint8"))}
+    ws = WalkPaths()
+    ws.n_recs, ws.n_stretches = len(wk["rec_len"]), len(wk["id_first"])
+    for k, a in wk.items():
+        setattr(ws, k, a.ctypes.data_as(ctypes.POINTER({"uint64": ctypes.c_uint64, "uint32": ctypes.c_uint32, "uint8": ctypes.c_uint8}[a.dtype.name])))
+    return ws, wk
+
+
+def evidence_bed(e, unit=0):
+    """BED text of the weak intervals of a dict like Unit.walk_evidence() returns (agx_walk_evidence_bed; host only, needs no device)."""
+    import numpy as np
+    keep = {k: np.ascontiguousarray(e[k], dtype="uint32") for k in IV_EVIDENCE}
+    s = WalkEvidence()
+    s.n_recs, s.n_intervals = len(e["rec_graph_bases"]), len(keep["iv_rec"])
+    for k, a in keep.items():
+        setattr(s, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
+    rc = lib().agx_walk_evidence_bed(ctypes.byref(s), unit, ctypes.byref(p), ctypes.byref(n))
+    if rc != AGX_OK:
+        raise AgxError(rc, "agx_walk_evidence_bed: the interval table is inconsistent")
     try:
         return ctypes.string_at(p, n.value) if n.value else b""
     finally:

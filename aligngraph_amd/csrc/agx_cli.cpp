@@ -46,6 +46,9 @@ struct Options {
     // instead of --coverage (agx_unit_unitigs_region)
     int tagRegion = 0, tagGraphCov = 0, regionUnit = 0, graphCov = 0; uint32_t regionLo = 0, regionHi = 0;
     int graphPaths = 0;                 // --graphPaths (only with --graphOut): the pre-extended records as P lines over the exported segments (agx_unitigs_paths_gfa)
+    // --evidenceOut <file> [--evidenceMinDepth n] [--evidenceMinSupport n]: the weak intervals of every unit's pre-extended records as BED (agx_unit_walk_evidence);
+    // the thresholds default to --coverage and 2
+    int tagEvidence = 0; string evidence; int tagEvDepth = 0, evDepth = 0, tagEvSupport = 0, evSupport = 2;
     int graphSupport = 0;               // --graphEdgeSupport (only with --graphOut): RC:i:<events that name the link's edge> on every L line (agx_unit_unitigs_support)
     int fastMap = 0, ratioCheck = 0, uniqueExtension = 0, iterativeMap = 0, misassemblyRemoval = 0, resume = 0;
     int k = 5, distanceLow = 0, distanceHigh = 99999, coverage = 20, insertVariation = 50, part = 1;      // defaults of AG:4701
@@ -131,6 +134,9 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--graphMinCoverage") { integer(i, o.tagGraphCov, o.graphCov); if (o.graphCov < 0) die_usage(); }
         else if (b == "--graphPaths") flag(o.graphPaths);
         else if (b == "--graphEdgeSupport") flag(o.graphSupport);
+        else if (b == "--evidenceOut") outfile(i, o.tagEvidence, o.evidence);
+        else if (b == "--evidenceMinDepth") { integer(i, o.tagEvDepth, o.evDepth); if (o.evDepth < 0) die_usage(); }
+        else if (b == "--evidenceMinSupport") { integer(i, o.tagEvSupport, o.evSupport); if (o.evSupport < 0) die_usage(); }
         else if (b == "--kMer") integer(i, o.tagK, o.k);
         else if (b == "--insertVariation") integer(i, o.tagIV, o.insertVariation);
         else if (b == "--coverage") integer(i, o.tagCov, o.coverage);
@@ -144,7 +150,12 @@ void parse_params(const string &file, Options &o) {
         else die_usage();
     }
     if ((o.tagRegion || o.tagGraphCov || o.graphPaths || o.graphSupport) && !o.tagGraph) die_usage();
+    if ((o.tagEvDepth || o.tagEvSupport) && !o.tagEvidence) die_usage();
 }
+
+// tmp/_evidence.<u>.d<depth>.s<support>.bed, the thresholds in the name: a --resume run merges only intervals that were made under its own settings
+uint32_t evidence_depth(const Options &o) { return (uint32_t)(o.tagEvDepth ? o.evDepth : std::max(o.coverage, 0)); }
+string evidence_part_path(const Options &o, int u) { return "tmp/_evidence." + itoa(u) + ".d" + itoa((long long)evidence_depth(o)) + ".s" + itoa(o.evSupport) + ".bed"; }
 
 // tmp/_graph.<u>.gfa, with the region, the threshold, --graphPaths (.p) and --graphEdgeSupport (.s) in the name when they are given: a --resume run merges only lines that were made under its own settings
 string graph_part_path(const Options &o, int u) {
@@ -1175,7 +1186,9 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                 const int u = order[at];
                 // the five calls of the unit loop (AG:4768-4776) through the split entry points of agx_run_unit, with the admission between load and upload
                 // (--graphEdgeSupport: the counting reads the front of the build, which a one-shot unit does not promise to keep — such a run's units are ordinary ones, with the edge counters)
-                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, (o.graphSupport ? AGX_FLAG_EDGE_SUPPORT : AGX_FLAG_ONE_SHOT) | (o.tagGraph ? AGX_FLAG_KEEP_COUNTS : 0u) | (o.graphPaths ? AGX_FLAG_KEEP_PATHS : 0u)};
+                // (--evidenceOut: ordinary units too, with the counts, the stretches and the edge counters: the evidence is asked for after the finish)
+                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, (o.graphSupport || o.tagEvidence ? AGX_FLAG_EDGE_SUPPORT : AGX_FLAG_ONE_SHOT) |
+                                (o.tagGraph || o.tagEvidence ? AGX_FLAG_KEEP_COUNTS : 0u) | (o.graphPaths || o.tagEvidence ? AGX_FLAG_KEEP_PATHS : 0u)};
                 agx_result r; memset(&r, 0, sizeof r); char err[512]; err[0] = 0;
                 agx_unit *un = nullptr;
                 int rc = agx_unit_create(&p, &un);
@@ -1217,7 +1230,7 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                     }
                     agx_text_free(text);
                 }
-                bool wanted = false; if (rc == AGX_OK) { std::lock_guard<std::mutex> g(mem_mu); wanted = waiting[d] > 0; }
+                bool wanted = false; if (rc == AGX_OK) { std::lock_guard<std::mutex> g(mem_mu); wanted = waiting[d] > 0 && !o.tagEvidence; }      // (--evidenceOut: never trimmed before the finish, the evidence reads the node table behind it)
                 if (rc == AGX_OK && wanted) {      // r05: somebody waits for room on this device — the whole download first, then what the walk cannot ask the device for goes back: the next unit is admitted while this one is walked on the host
                     rc = agx_unit_download(un);
                     uint64_t freed = 0;
@@ -1231,6 +1244,20 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                     agx_walk_paths_free(&wp);
                     if (rc == AGX_OK) {
                         FILE *f = fopen(graph_part_path(o, u).c_str(), "ab"); bool ok = f != nullptr;
+                        if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
+                        if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
+                    }
+                    agx_text_free(text);
+                }
+                if (rc == AGX_OK && o.tagEvidence) {      // --evidenceOut: the weak intervals of the records just written, into tmp/_evidence.<u>.d<depth>.s<support>.bed
+                    agx_walk_paths wp; agx_walk_evidence ev; char *text = nullptr; size_t len = 0;
+                    memset(&ev, 0, sizeof ev);
+                    rc = agx_unit_walk_paths(un, &wp);
+                    if (rc == AGX_OK) rc = agx_unit_walk_evidence(un, &wp, evidence_depth(o), (uint32_t)o.evSupport, 0, 0, 0, &ev);
+                    if (rc == AGX_OK) { rc = agx_walk_evidence_bed(&ev, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "BED FORMATTING FAILED"); }
+                    agx_walk_paths_free(&wp); agx_walk_evidence_free(&ev);
+                    if (rc == AGX_OK) {
+                        FILE *f = fopen(evidence_part_path(o, u).c_str(), "wb"); bool ok = f != nullptr;
                         if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
                         if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
                     }
@@ -1337,6 +1364,20 @@ int main(int argc, char **argv) {
         if (g) ok = (fclose(g) == 0) && ok;
         if (!ok) die("CANNOT OPEN FILE!");
         stage("graph output");
+    }
+    if (o.tagEvidence) {                                                      // --evidenceOut: every unit's intervals, in unit order (a --resume run finds the earlier units' files in tmp/)
+        FILE *g = fopen(o.evidence.c_str(), "wb");
+        bool ok = g != nullptr;
+        for (int u = 0; ok && u < units; u++) {
+            FILE *f = fopen(evidence_part_path(o, u).c_str(), "rb");
+            if (!f) { ok = false; break; }
+            char buf[1 << 16]; size_t n;
+            while (ok && (n = fread(buf, 1, sizeof buf, f)) > 0) ok = fwrite(buf, 1, n, g) == n;
+            fclose(f);
+        }
+        if (g) ok = (fclose(g) == 0) && ok;
+        if (!ok) die("CANNOT OPEN FILE!");
+        stage("evidence output");
     }
     refinement(o, units, genomeIds, contigIds);
     stage("refinement");

@@ -1302,6 +1302,66 @@ AGX_HD agx_u32 agx_support_ovf_entry(const agx_edge_ovf *ovf, agx_u32 n_ovf, agx
     return n_ovf;
 }
 
+// ---- evidence under the walk's records ---------------------------------------------------------------------
+// The stretch table of agx_walk_paths in the form the device reads (one entry per stretch, in the table's order; the host has checked it): first walk id, first base offset,
+// record, the flat index of the first base (st_pre: the exclusive prefix of the stretch lengths, entry n_st = n_flat = all graph bases) and the joined flag (entry n_st: 0);
+// and the arrays of the built unit that the gather reads.  e_cnt == nullptr: the unit has no edge counters, every step is without a number.
+struct agx_evidence_tab {
+    const agx_u32 *st_first, *st_base, *st_rec, *st_pre; const agx_u8 *st_join; agx_u32 n_st, n_flat;
+    const agx_u32 *a_nid; agx_u32 n_ids, pool_cap; const int *n_counts; const agx_u32 *n_next; const agx_u8 *n_flags;
+    const agx_edge_ovf *ovf; agx_u32 n_ovf; const agx_u32 *e_cnt, *ovf_cnt;
+};
+// One graph base.  st == NONE: the flat index names no base.  depth, votes: NONE without a node.  has_step: a step leaves the base, toward walk id next_id;
+// inner: that step stays inside the stretch (its target is the next flat base's id either way: a joined stretch follows its predecessor in the table).
+struct agx_evidence_base { agx_u32 st, rec, off, id, slot, depth, votes, next_id; bool has_step, inner; };
+
+// the node slot of a walk id; NONE: the id has no node (beyond the ids, a_nid says none, or the slot lies outside the pool)
+AGX_HD agx_u32 agx_evidence_slot(const agx_evidence_tab &T, agx_u32 id) {
+    if (id >= T.n_ids) return AGX_NONE;
+    const agx_u32 s = T.a_nid[id];
+    return s < T.pool_cap ? s : AGX_NONE;
+}
+
+// Flat base i: its stretch by bisecting st_pre (the last stretch that begins at or in front of i; stretches hold a base at least, so the prefix rises strictly;
+// 32 halvings at most), then record, offset, id, slot, the node's coverage and the largest of its five vote counters, and the step that leaves it
+AGX_HD agx_evidence_base agx_evidence_lane(const agx_evidence_tab &T, agx_u32 i) {
+    agx_evidence_base b{AGX_NONE, AGX_NONE, 0u, AGX_NONE, AGX_NONE, AGX_NONE, AGX_NONE, AGX_NONE, false, false};
+    if (i >= T.n_flat || !T.n_st) return b;
+    agx_u32 lo = 0, hi = T.n_st;      // the answer lies in [lo, hi)
+    for (agx_u32 it = 0; it < 32u && hi - lo > 1u; it++) { const agx_u32 mid = lo + (hi - lo) / 2u; if (T.st_pre[mid] <= i) lo = mid; else hi = mid; }
+    const agx_u32 first = T.st_pre[lo], end = T.st_pre[lo + 1];
+    if (i < first || i >= end) return b;      // (a prefix that does not rise: nothing is read through it)
+    b.st = lo; b.rec = T.st_rec[lo]; b.off = T.st_base[lo] + (i - first); b.id = T.st_first[lo] + (i - first);
+    b.slot = agx_evidence_slot(T, b.id);
+    if (b.slot != AGX_NONE) {
+        const int *c = T.n_counts + (size_t)b.slot * 6;
+        b.depth = (agx_u32)c[0];
+        agx_u32 v = 0;
+        for (int j = 1; j < 6; j++) v = (agx_u32)c[j] > v ? (agx_u32)c[j] : v;
+        b.votes = v;
+    }
+    if (i + 1u < end) { b.has_step = true; b.inner = true; b.next_id = b.id + 1u; }
+    else if (lo + 1u < T.n_st && T.st_join[lo + 1u] && T.st_rec[lo + 1u] == b.rec) { b.has_step = true; b.next_id = T.st_first[lo + 1u]; }
+    return b;
+}
+
+// The support of edge src -> dst (slots inside the pool) as agx_k_utr_link_support reads it: the inline slots of n_next[src] that hold dst with e_cnt, and — sources with
+// AGX_NF_EOVF — every entry of the overflow list that names the pair with ovf_cnt, duplicates summed.  NONE with *no_edge set: the node table holds no such edge.
+AGX_HD agx_u32 agx_evidence_step(const agx_evidence_tab &T, agx_u32 src, agx_u32 dst, bool *no_edge) {
+    if (src >= T.pool_cap || dst >= T.pool_cap || !T.e_cnt) return AGX_NONE;
+    agx_u32 sum = 0; bool found = false;
+    for (agx_u32 e = 0; e < AGX_MAXE; e++) if (T.n_next[(size_t)src * AGX_MAXE + e] == dst) { sum += T.e_cnt[(size_t)src * AGX_MAXE + e]; found = true; }
+    if (T.n_flags[src] & AGX_NF_EOVF)
+        for (agx_u32 j = 0; j < T.n_ovf; j++) if (T.ovf[j].src == src && T.ovf[j].dst == dst) { sum += T.ovf_cnt[j]; found = true; }
+    if (!found) { *no_edge = true; return AGX_NONE; }
+    return sum;
+}
+
+// weak: no node, depth below min_depth, or a numbered step below min_support (charged to the base the step leaves)
+AGX_HD bool agx_evidence_weak(agx_u32 depth, agx_u32 step, agx_u32 min_depth, agx_u32 min_support) {
+    return depth == AGX_NONE || depth < min_depth || (step != AGX_NONE && step < min_support);
+}
+
 // ---- walk preparation: alive-node renumbering and forced-run flags -------------------------------------------------------
 // The path walk (AG:1954-2204) only ever stands on nodes that survived the coverage prune.  After the edge sweep the
 // surviving ("alive") nodes get walk ids ("aid") laid out so that the main strand of the graph is contiguous:

@@ -1038,6 +1038,22 @@ size_t idmap_layout(size_t ids, size_t runs, char *base, agx_idmap_args *A) {
     take(M.r_first, runs); take(M.r_last, runs); take(M.r_seg, runs); take(M.r_rank, runs);
     return take.bytes();
 }
+// The scratch of the evidence under the walk's records (agx_unit_walk_evidence, agx_evidence.hip), from the front of the same buffer: the uploaded stretch table with its
+// prefix and the per-record table (the whole call's), then what one CHUNK of flat graph bases takes — depth and step per base (and votes when the tracks are wanted), the
+// interval-start flags with their scan, and the chunk's intervals at their worst (every base one).  40 bytes per base of the chunk, 44 with tracks.
+size_t evidence_layout(size_t n_st, size_t n_recs, size_t chunk, bool tracks, char *base, agx_evidence_args *A, agx_u32 **words) {
+    Carve take{base};
+    agx_evidence_args T{}; agx_evidence_args &E = A ? *A : T; agx_u32 *w = nullptr;
+    take(w, 8);
+    take(E.T.st_first, n_st); take(E.T.st_base, n_st); take(E.T.st_rec, n_st); take(E.T.st_pre, n_st + 1); take(E.T.st_join, n_st + 1);
+    take(E.r_steps, n_recs); take(E.r_dsum, n_recs); take(E.r_dmin, n_recs); take(E.r_smin, n_recs);
+    take(E.c_depth, chunk); take(E.c_step, chunk);
+    if (tracks) take(E.c_votes, chunk);
+    take(E.flag, chunk + 1); take(E.foff, chunk + 1); take(E.scan_tmp, scan_words(chunk + 1, 1024) + 16);
+    take(E.iv_rec, chunk); take(E.iv_first, chunk); take(E.iv_last, chunk); take(E.iv_dmin, chunk); take(E.iv_smin, chunk);
+    if (base) { E.noedge = w + 1; E.err = w; if (words) *words = w; }
+    return take.bytes();
+}
 inline bool keeps_paths(const agx_unit *u) { return (u->prm.flags & (AGX_FLAG_KEEP_PATHS | AGX_FLAG_KEEP_COUNTS)) == (AGX_FLAG_KEEP_PATHS | AGX_FLAG_KEEP_COUNTS); }
 // The export buffer of a unit that keeps paths: every export of such a unit takes the same size — the larger of the two export layouts at their worst, and behind it (at `map_at`)
 // the id map's scratch for a whole-window map — so that exports of any kind in any order never take the buffer twice.
@@ -2529,6 +2545,151 @@ void agx_walk_paths_free(agx_walk_paths *w) {
     if (!w) return;
     free(w->rec_len); free(w->st_off); free(w->id_first); free(w->id_last); free(w->base_off); free(w->joined);
     memset(w, 0, sizeof *w);
+}
+
+// Evidence under the walk's records: the stretch table is checked and flattened on the host, uploaded into the export's scratch, and gathered over in chunks
+// of flat graph bases on the export's own stream (agx_evidence.hip).  Two host round trips per chunk: the interval count, then the intervals (and the tracks' piece).
+static void walk_evidence(agx_unit *u, const agx_walk_paths &w, uint32_t min_depth, uint32_t min_support, bool tracks, uint32_t rec_lo, uint32_t rec_hi, agx_walk_evidence *e) {
+    const double t0 = now_ms();
+    if (!(u->prm.flags & AGX_FLAG_KEEP_COUNTS)) throw Error{E_ARG, "walk evidence: the unit was created without AGX_FLAG_KEEP_COUNTS (the depth is the kept per-node coverage)"};
+    if (!u->built || u->trimmed) throw Error{E_ARG, "walk evidence: the unit is not built (call agx_unit_build; not after agx_unit_trim or agx_unit_release)"};
+    if ((u->prm.flags & AGX_FLAG_ONE_SHOT) && (u->consumed || u->downloaded)) throw Error{E_ARG, "walk evidence: a one-shot unit is asked before its download or finish"};
+    const bool counted = (u->prm.flags & AGX_FLAG_EDGE_SUPPORT) != 0;
+    if (min_support && !counted) throw Error{E_ARG, "walk evidence: min_support needs the edge counters (the unit was created without AGX_FLAG_EDGE_SUPPORT)"};
+    // the table, before anything is uploaded
+    const size_t nr = w.n_recs; const uint64_t ns64 = w.n_stretches;
+    auto bad = [](const std::string &why) { return Error{E_ARG, "walk evidence: " + why}; };
+    if (nr && (!w.rec_len || !w.st_off)) throw bad("the stretch table has records but no rec_len / st_off");
+    if (ns64 && (!w.id_first || !w.id_last || !w.base_off || !w.joined || !nr)) throw bad("the stretch table has stretches but no arrays or no records");
+    if (nr && (w.st_off[0] != 0 || w.st_off[nr] != ns64)) throw bad("st_off does not run from 0 to n_stretches");
+    if (tracks && (rec_lo > rec_hi || rec_hi > nr)) throw bad("track records [" + std::to_string(rec_lo) + ", " + std::to_string(rec_hi) + ") are not within the table's " + std::to_string(nr));
+    if (ns64 >= 0xFFFFFFFFull) throw Error{E_UNSUPPORTED, "walk evidence: 2^32 stretches or more"};
+    const size_t ns = (size_t)ns64;
+    std::vector<agx_u32> st_first(ns), st_base(ns), st_rec(ns), st_pre(ns + 1); std::vector<agx_u8> st_join(ns + 1, 0);
+    std::vector<uint64_t> rec_bases(nr, 0);
+    uint64_t total = 0;
+    for (size_t r = 0; r < nr; r++) if (w.st_off[r] > w.st_off[r + 1] || w.st_off[r + 1] > ns64) throw bad("st_off is not monotone at record " + std::to_string(r));
+    for (size_t r = 0; r < nr; r++) {
+        if (w.st_off[r] < w.st_off[r + 1] && w.rec_len[r] > 0xFFFFFFFFull) throw Error{E_UNSUPPORTED, "walk evidence: record " + std::to_string(r) + " has 2^32 bases or more"};
+        uint64_t end = 0;
+        for (size_t i = (size_t)w.st_off[r]; i < (size_t)w.st_off[r + 1]; i++) {
+            const std::string at = "stretch " + std::to_string(i) + " of record " + std::to_string(r);
+            if (w.id_last[i] < w.id_first[i]) throw bad(at + ": id_last < id_first");
+            if (w.id_last[i] >= u->n_ids) throw bad(at + ": id_last is not a walk id of the unit (" + std::to_string(u->n_ids) + " ids)");
+            const uint64_t len = (uint64_t)w.id_last[i] - w.id_first[i] + 1;
+            if (w.base_off[i] > w.rec_len[r] || len > w.rec_len[r] - w.base_off[i]) throw bad(at + " does not lie inside its record");
+            const bool first = i == (size_t)w.st_off[r];
+            if (!first && w.base_off[i] < end) throw bad(at + " overlaps or lies in front of the stretch before it");
+            if (w.joined[i] > 1) throw bad(at + ": joined is neither 0 nor 1");
+            if (w.joined[i] && (first || w.base_off[i] != end)) throw bad(at + ": joined, but not directly behind the previous stretch of the record");
+            st_first[i] = w.id_first[i]; st_base[i] = (agx_u32)w.base_off[i]; st_rec[i] = (agx_u32)r; st_pre[i] = (agx_u32)total; st_join[i] = w.joined[i];
+            end = w.base_off[i] + len; total += len; rec_bases[r] += len;
+            if (total >= 0xFFFFFFFFull) throw Error{E_UNSUPPORTED, "walk evidence: 2^32 graph bases or more"};
+        }
+    }
+    st_pre[ns] = (agx_u32)total;
+    if (counted) support_check(u);
+    // the caller's tables (the per-record ones are always produced)
+    auto mk = [](auto *&p, size_t n) { using T = std::remove_reference_t<decltype(*p)>; p = (T *)calloc(n + 1, sizeof(T)); if (!p) throw Error{E_ARG, "out of host memory"}; };
+    e->n_recs = (uint32_t)nr; e->n_graph_bases = total;
+    mk(e->rec_graph_bases, nr); mk(e->rec_steps, nr); mk(e->rec_depth_sum, nr); mk(e->rec_depth_min, nr); mk(e->rec_depth_min_at, nr); mk(e->rec_step_min, nr); mk(e->rec_step_min_at, nr);
+    for (size_t r = 0; r < nr; r++) { e->rec_graph_bases[r] = rec_bases[r]; e->rec_depth_min[r] = e->rec_step_min[r] = AGX_NONE; }
+    size_t s_lo = 0, s_hi = 0; uint64_t t_lo = 0, t_hi = 0;      // the tracks' stretches and flat bases
+    if (tracks) {
+        s_lo = nr ? (size_t)w.st_off[rec_lo] : 0; s_hi = nr ? (size_t)w.st_off[rec_hi] : 0; t_lo = st_pre[s_lo]; t_hi = st_pre[s_hi];
+        e->rec_lo = rec_lo; e->rec_hi = rec_hi; e->n_track = t_hi - t_lo;
+        mk(e->track_off, s_hi - s_lo + 1); mk(e->depth, (size_t)e->n_track); mk(e->votes, (size_t)e->n_track); mk(e->step, (size_t)e->n_track);
+        for (size_t i = s_lo; i <= s_hi; i++) e->track_off[i - s_lo] = st_pre[i] - t_lo;
+    }
+    Export E(u);
+    const agx_u32 n_pos = E.n_pos, cap = E.cap, n_ovf = E.n_ovf;
+    E.open(unitig_layout(cap, n_pos, n_ovf, nullptr, nullptr, nullptr));      // (the buffer every export of the unit takes: the room the upload reserved)
+    if (counted) ensure_support(E);
+    std::vector<agx_u32> iv[5];      // rec, first, last, depth_min, step_min
+    if (total) {
+        const size_t avail = u->d_ut.n;
+        size_t chunk = std::min<size_t>(((size_t)total + 63) & ~(size_t)63, (size_t)1 << 30);
+        if (const char *env = getenv("AGX_EVIDENCE_CHUNK")) { const long long v = atoll(env); if (v > 0) chunk = std::min<size_t>(((size_t)v + 63) & ~(size_t)63, (size_t)1 << 30); }
+        while (chunk > 64 && evidence_layout(ns, nr, chunk, tracks, nullptr, nullptr, nullptr) > avail) chunk = ((chunk / 2) + 63) & ~(size_t)63;
+        if (evidence_layout(ns, nr, chunk, tracks, nullptr, nullptr, nullptr) > avail)
+            throw Error{E_UNSUPPORTED, "walk evidence: the stretch table (" + std::to_string(ns) + " stretches, " + std::to_string(nr) + " records) does not fit the export's scratch of " + std::to_string(avail) + " bytes"};
+        agx_evidence_args A{}; agx_u32 *words = nullptr;
+        evidence_layout(ns, nr, chunk, tracks, u->d_ut.p, &A, &words);
+        agx_evidence_tab &T = A.T;
+        T.n_st = (agx_u32)ns; T.n_flat = (agx_u32)total;
+        T.a_nid = u->d_a_nid.p; T.n_ids = u->n_ids; T.pool_cap = cap; T.n_counts = u->d_counts.p; T.n_next = u->d_next.p; T.n_flags = u->d_flags.p; T.ovf = u->d_ovf.p; T.n_ovf = n_ovf;
+        T.e_cnt = counted ? u->d_e_cnt.p : nullptr; T.ovf_cnt = counted ? u->d_ovf_cnt.p : nullptr;
+        A.min_depth = min_depth; A.min_support = min_support; A.n_recs = (agx_u32)nr;
+        auto up = [&](const void *dst, const void *src, size_t b) { if (b) HIP_OK(hipMemcpyAsync(const_cast<void *>(dst), src, b, hipMemcpyHostToDevice, E.s)); };
+        up(T.st_first, st_first.data(), ns * 4); up(T.st_base, st_base.data(), ns * 4); up(T.st_rec, st_rec.data(), ns * 4); up(T.st_pre, st_pre.data(), (ns + 1) * 4); up(T.st_join, st_join.data(), ns + 1);
+        E.fill(words, 0, 32); E.fill(A.r_steps, 0, nr * 8); E.fill(A.r_dsum, 0, nr * 8); E.fill(A.r_dmin, 0xFF, nr * 8); E.fill(A.r_smin, 0xFF, nr * 8);
+        std::vector<agx_u32> got[5];
+        for (uint64_t lo = 0; lo < total; lo += chunk) {
+            const agx_u32 n = (agx_u32)std::min<uint64_t>(chunk, total - lo);
+            A.lo = (agx_u32)lo; A.n = n; A.iv_cap = 0;
+            agx_launch_evidence_gather(&A, E.s);
+            agx_u32 cnt = 0;
+            E.read(&cnt, A.foff + n, 4); E.sync();
+            if (cnt > n) throw Error{E_DEVICE, "walk evidence: more intervals than bases"};
+            if (cnt) {
+                A.iv_cap = cnt;
+                E.fill(A.iv_dmin, 0xFF, (size_t)cnt * 4); E.fill(A.iv_smin, 0xFF, (size_t)cnt * 4);
+                agx_launch_evidence_runs(&A, E.s);
+                agx_u32 *src[5] = {A.iv_rec, A.iv_first, A.iv_last, A.iv_dmin, A.iv_smin};
+                for (int k = 0; k < 5; k++) { got[k].resize(cnt); E.read(got[k].data(), src[k], (size_t)cnt * 4); }
+            }
+            if (tracks) {      // the piece of the tracks that lies in this chunk
+                const uint64_t a = std::max<uint64_t>(lo, t_lo), b = std::min<uint64_t>(lo + n, t_hi);
+                if (a < b) {
+                    E.read(e->depth + (a - t_lo), A.c_depth + (a - lo), (size_t)(b - a) * 4); E.read(e->votes + (a - t_lo), A.c_votes + (a - lo), (size_t)(b - a) * 4);
+                    E.read(e->step + (a - t_lo), A.c_step + (a - lo), (size_t)(b - a) * 4);
+                }
+            }
+            E.sync();
+            for (agx_u32 i = 0; i < cnt; i++) {
+                if (got[0][i] >= nr || got[1][i] > got[2][i]) throw Error{E_DEVICE, "walk evidence: the intervals are inconsistent (chunk at base " + std::to_string(lo) + ", interval " + std::to_string(i) + ")"};
+                // an interval cut by the chunk's border: the same record, the next base offset
+                if (i == 0 && !iv[0].empty() && iv[0].back() == got[0][0] && (uint64_t)iv[2].back() + 1 == got[1][0]) {
+                    iv[2].back() = got[2][0]; iv[3].back() = std::min(iv[3].back(), got[3][0]); iv[4].back() = std::min(iv[4].back(), got[4][0]);
+                    continue;
+                }
+                for (int k = 0; k < 5; k++) iv[k].push_back(got[k][i]);
+            }
+        }
+        std::vector<unsigned long long> rs(nr), rd(nr), rmin(nr), smin(nr); agx_u32 wd[2] = {0, 0};
+        if (nr) { E.read(rs.data(), A.r_steps, nr * 8); E.read(rd.data(), A.r_dsum, nr * 8); E.read(rmin.data(), A.r_dmin, nr * 8); E.read(smin.data(), A.r_smin, nr * 8); }
+        E.read(wd, words, 8); E.sync();
+        HIP_OK(hipGetLastError());
+        if (wd[0]) throw Error{E_DEVICE, "walk evidence: the interval numbers are inconsistent (error word " + std::to_string(wd[0]) + ")"};
+        e->n_steps_without_edge = wd[1];
+        for (size_t r = 0; r < nr; r++) {
+            e->rec_steps[r] = rs[r]; e->rec_depth_sum[r] = rd[r]; e->n_steps += rs[r];
+            if (rmin[r] != ~0ull) { e->rec_depth_min[r] = (uint32_t)(rmin[r] >> 32); e->rec_depth_min_at[r] = (uint32_t)rmin[r]; }
+            if (smin[r] != ~0ull) { e->rec_step_min[r] = (uint32_t)(smin[r] >> 32); e->rec_step_min_at[r] = (uint32_t)smin[r]; }
+        }
+    }
+    const size_t ni = iv[0].size();
+    e->n_intervals = (uint32_t)ni;
+    mk(e->iv_rec, ni); mk(e->iv_first, ni); mk(e->iv_last, ni); mk(e->iv_depth_min, ni); mk(e->iv_step_min, ni);
+    uint32_t *dst[5] = {e->iv_rec, e->iv_first, e->iv_last, e->iv_depth_min, e->iv_step_min};
+    for (int k = 0; k < 5; k++) if (ni) memcpy(dst[k], iv[k].data(), ni * 4);
+    u->stats.ms_walk_evidence = now_ms() - t0;
+}
+
+int agx_unit_walk_evidence(agx_unit *u, const agx_walk_paths *w, uint32_t min_depth, uint32_t min_support, uint32_t want_tracks, uint32_t rec_lo, uint32_t rec_hi, agx_walk_evidence *e) {
+    if (!u || !w || !e) return AGX_E_ARG;
+    memset(e, 0, sizeof *e);
+    const int rc = guarded(u, [&] { walk_evidence(u, *w, min_depth, min_support, want_tracks != 0, rec_lo, rec_hi, e); });
+    if (rc != AGX_OK) agx_walk_evidence_free(e);
+    return rc;
+}
+
+void agx_walk_evidence_free(agx_walk_evidence *e) {
+    if (!e) return;
+    free(e->rec_graph_bases); free(e->rec_steps); free(e->rec_depth_sum); free(e->rec_depth_min); free(e->rec_depth_min_at); free(e->rec_step_min); free(e->rec_step_min_at);
+    free(e->iv_rec); free(e->iv_first); free(e->iv_last); free(e->iv_depth_min); free(e->iv_step_min);
+    free(e->track_off); free(e->depth); free(e->votes); free(e->step);
+    memset(e, 0, sizeof *e);
 }
 
 int agx_run_unit(const agx_params *p, const char *tmp_dir, int unit, int write_files, agx_result *r, char *err, size_t err_len) {

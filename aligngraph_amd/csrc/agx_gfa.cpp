@@ -214,4 +214,31 @@ int agx_unitigs_gfa_support(const agx_unitigs *t, const uint32_t *link_support, 
     return gfa_text(t, link_support, unit, text, len);
 }
 
+// The weak intervals of agx_unit_walk_evidence as BED, one line per interval in the table's order:
+//   p<unit>_<rec>	<base_first>	<base_last + 1>	weak	0	+	dm:i:<depth_min>	sm:i:<step_min>      ("." for a number that is 0xFFFFFFFF)
+int agx_walk_evidence_bed(const agx_walk_evidence *e, int unit, char **text, size_t *len) {
+    if (!e || !text || !len || unit < 0) return AGX_E_ARG;
+    *text = nullptr; *len = 0;
+    const uint32_t n = e->n_intervals;
+    if (n && (!e->iv_rec || !e->iv_first || !e->iv_last || !e->iv_depth_min || !e->iv_step_min)) return AGX_E_ARG;
+    for (uint32_t i = 0; i < n; i++) if (e->iv_last[i] < e->iv_first[i] || e->iv_rec[i] >= e->n_recs) return AGX_E_ARG;
+    try {
+        const std::string prefix = "p" + std::to_string(unit) + "_";
+        std::string o;
+        o.reserve((size_t)n * 64);
+        auto put_or_dot = [&](uint32_t v) { if (v == 0xFFFFFFFFu) o += '.'; else put_u64(o, v); };
+        for (uint32_t i = 0; i < n; i++) {
+            o += prefix; put_u64(o, e->iv_rec[i]); o += '\t'; put_u64(o, e->iv_first[i]); o += '\t'; put_u64(o, (uint64_t)e->iv_last[i] + 1);
+            o += "\tweak\t0\t+\tdm:i:"; put_or_dot(e->iv_depth_min[i]); o += "\tsm:i:"; put_or_dot(e->iv_step_min[i]); o += '\n';
+        }
+        char *out = (char *)malloc(o.size() + 1);
+        if (!out) return AGX_E_ARG;
+        memcpy(out, o.data(), o.size()); out[o.size()] = 0;
+        *text = out; *len = o.size();
+        return AGX_OK;
+    } catch (...) {
+        return AGX_E_ARG;
+    }
+}
+
 }  // extern "C"

@@ -114,7 +114,23 @@ struct agx_idmap_args {
     agx_u32 *r_first, *r_last, *r_seg, *r_rank; agx_u32 run_cap; // [run_cap] the runs
 };
 
-#define AGX_SLOW_WAVES 8192u    // wavefronts of the per-hit edge pass if the occupancy query fails (normally: as many as are resident at once)
+// Evidence under the walk's records (agx_evidence.hip, agx_unit_walk_evidence): one launch set per CHUNK of flat graph bases [lo, lo + n) (lo a multiple of 64).
+// The record arrays are the whole table's and accumulate over the chunks; everything named c_ / flag / foff / iv_ is the chunk's, indexed by flat base - lo or by the
+// chunk's interval number.
+struct agx_evidence_args {
+    agx_evidence_tab T;
+    agx_u32 lo, n, min_depth, min_support, n_recs;
+    unsigned long long *r_steps, *r_dsum;      // [n_recs] numbered steps, depth summed over the bases with a node
+    unsigned long long *r_dmin, *r_smin;       // [n_recs] value << 32 | base offset of the smallest depth / step (all ones: none yet), one 64-bit atomicMin each
+    agx_u32 *noedge;                           // steps between two nodes that the node table holds no edge for
+    agx_u32 *c_depth, *c_step, *c_votes;       // [n] per base (c_votes: only when the tracks are wanted, else nullptr)
+    agx_u32 *flag, *foff, *scan_tmp;           // [n + 1] interval-start flags (closing zero) and their exclusive scan
+    agx_u32 iv_cap;                            // the chunk's intervals (read back from foff[n] before the runs kernel)
+    agx_u32 *iv_rec, *iv_first, *iv_last, *iv_dmin, *iv_smin;      // [iv_cap]; the minima start as all ones
+    agx_u32 *err;                              // bit 0: an interval number beyond iv_cap
+};
+
+#define AGX_SLOW_WAVES 8192u   // wavefronts of the per-hit edge pass if the occupancy query fails (normally: as many as are resident at once)
 
 extern "C" {
 // one kernel that zeroes up to eight u32 ranges
@@ -189,4 +205,8 @@ void agx_launch_edge_support(const agx_support_kargs *, hipStream_t);
 // behind phase 3 of a region export: l_sup[i] = support of link i's edge, the last node of its source segment -> the head node of its target segment, overflow duplicates summed
 // (n_flags: the unit's, for AGX_NF_EOVF — only such tails walk the overflow list, once per link)
 void agx_launch_unitig_link_support(const agx_unitig_region_args *, const agx_u8 *n_flags, const agx_u32 *e_cnt, const agx_u32 *ovf_cnt, agx_u32 *l_sup, hipStream_t);
+// evidence of one chunk: the gather with the record summaries, the per-base numbers, the interval-start flags and their scan (the host reads foff[n]); then, with iv_cap set
+// and the interval minima filled with ones, the intervals
+void agx_launch_evidence_gather(const agx_evidence_args *, hipStream_t);
+void agx_launch_evidence_runs(const agx_evidence_args *, hipStream_t);
 }

@@ -133,6 +133,7 @@ typedef struct {
     double ms_edge_support;                                      /* host wall time the last agx_unit_edge_support / agx_unit_unitigs_support spent making sure the edge counters are there: zeroing,
                                                                     the counting kernel and the wait for its totals on the first call after a build, next to nothing on later ones */
     uint64_t n_support_events;                                   /* events the counting saw (agx_edge_support::n_events); 0 before the first counting call after a build */
+    double ms_walk_evidence;                                     /* host wall time of the last agx_unit_walk_evidence, from entry to its tables being in the caller's memory */
 } agx_stats;
 
 /* Node/edge tables in canonical numbering (position-major, variant order), for parity tests. malloc'd; free with agx_graph_free. */
@@ -190,6 +191,22 @@ typedef struct {
     uint64_t *st_off;          /* [n_recs + 1] */
     uint32_t *id_first, *id_last; uint64_t *base_off; uint8_t *joined;   /* [n_stretches] */
 } agx_walk_paths;
+
+/* Evidence under the walk's records: the per-node coverage and votes and the per-edge support (§13) joined, on the device, to the bases of the records
+ * of a stretch table w.  A GRAPH BASE is a base that lies in a stretch; base b of stretch s is walk id id_first[s] + (b - base_off[s]).  A STEP leaves a graph base toward
+ * the next base of its stretch, or — from a stretch's last base — toward the first base of the next stretch of the record if that has joined = 1.  0xFFFFFFFF stands
+ * for "no number" everywhere: a depth of an id without a node, a step that does not exist, has an end without a node, or names a pair the node table holds no edge for
+ * (those are counted in n_steps_without_edge), and every step of a unit without AGX_FLAG_EDGE_SUPPORT.
+ * Per record: graph bases, numbered steps, the depth summed over the bases with a node, the smallest depth and the smallest numbered step, each with the smallest base
+ * offset that has it (value 0xFFFFFFFF, offset 0: none).  Weak intervals: maximal runs of weak bases of one record at consecutive base offsets, by (rec, first); a base
+ * is weak iff it has no node, its depth is below min_depth, or its step has a number below min_support; iv_depth_min / iv_step_min: the smallest depth of a node / the
+ * smallest numbered step in the interval.  Tracks (want_tracks): depth, votes (the largest of the node's five vote counters) and step per graph base of the records
+ * [rec_lo, rec_hi) in stretch order; track_off has one entry per stretch of those records and a closing one: the stretch st_off[rec_lo] + i begins at entry track_off[i].
+ * malloc'd; free with agx_walk_evidence_free. */
+typedef struct { uint32_t n_recs, n_intervals; uint64_t n_graph_bases, n_steps, n_steps_without_edge;
+                 /* [n_recs] */ uint64_t *rec_graph_bases, *rec_steps, *rec_depth_sum; uint32_t *rec_depth_min, *rec_depth_min_at, *rec_step_min, *rec_step_min_at;
+                 /* [n_intervals] */ uint32_t *iv_rec, *iv_first, *iv_last, *iv_depth_min, *iv_step_min;
+                 /* tracks, want_tracks only */ uint32_t rec_lo, rec_hi; uint64_t n_track; uint64_t *track_off; uint32_t *depth, *votes, *step; } agx_walk_evidence;
 
 /* The walk graph: what the walk preparation (csrc/agx_core.h "walk preparation") leaves on the device and the download carries to the host walk (GraphView, csrc/agx_host.h).
  * Walk ids [0, n_pos) are the first alive variant of each position, [n_pos, n_ids) the further ones.  malloc'd; free with agx_walk_graph_free. */
@@ -354,6 +371,20 @@ void agx_link_support_free(uint32_t *link_support);
  * AGX_E_ARG without the flag or before a finish.  The caller gets copies. */
 int agx_unit_walk_paths(agx_unit *u, agx_walk_paths *w);
 void agx_walk_paths_free(agx_walk_paths *w);
+/* The evidence under the records of w (agx_walk_evidence above): normally the table agx_unit_walk_paths returned after the last finish, but any table that passes the checks
+ * is served — st_off rises from 0 to n_stretches; id_first <= id_last < the unit's walk ids; every stretch inside its record; a record's stretches in base order without
+ * overlap; joined = 1 only directly behind the previous stretch of the same record (AGX_E_ARG with the reason otherwise; AGX_E_UNSUPPORTED for 2^32 graph bases or more, or a
+ * record of 2^32 bases or more: offsets are 32-bit).  Preconditions of agx_unit_unitigs_region (AGX_FLAG_KEEP_COUNTS; built and not trimmed; one-shot units before their
+ * download); allowed after agx_unit_finish; AGX_FLAG_KEEP_PATHS is not needed.  With AGX_FLAG_EDGE_SUPPORT the counters are made first if need be, under
+ * agx_unit_edge_support's preconditions; without it every step is 0xFFFFFFFF, n_steps and n_steps_without_edge are 0 and a non-zero min_support is AGX_E_ARG.  want_tracks
+ * != 0 needs rec_lo <= rec_hi <= n_recs.  Runs on the device out of the export's scratch (no allocation; a table too large for it goes through in chunks of bases,
+ * AGX_EVIDENCE_CHUNK=<bases> forces a chunk size) and writes nothing the walk or an export reads.  A refused call leaves the unit as it was. */
+int agx_unit_walk_evidence(agx_unit *u, const agx_walk_paths *w, uint32_t min_depth, uint32_t min_support,
+                           uint32_t want_tracks, uint32_t rec_lo, uint32_t rec_hi, agx_walk_evidence *e);
+void agx_walk_evidence_free(agx_walk_evidence *e);
+/* Host only: the weak intervals as BED, one line per interval: p<unit>_<rec> <tab> base_first <tab> base_last + 1 <tab> weak <tab> 0 <tab> + <tab> dm:i:<depth_min> <tab>
+ * sm:i:<step_min>, "." in place of a number that is 0xFFFFFFFF; *text is malloc'd, free it with agx_text_free. */
+int agx_walk_evidence_bed(const agx_walk_evidence *e, int unit, char **text, size_t *len);
 void agx_unitigs_free(agx_unitigs *t);
 /* Host only: the S and L lines of GFA 1.0 for unit `unit` (no header line), as DESIGN.md §11 defines them; *text is malloc'd, free it with agx_text_free. */
 int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len);
