@@ -30,6 +30,7 @@ EXPORTS = [
     "agx_unit_unitigs_mapped", "agx_idmap_free", "agx_unit_walk_paths", "agx_walk_paths_free", "agx_unitigs_paths_gfa", "agx_unit_reprune",
     "agx_unit_edge_support", "agx_edge_support_free", "agx_unit_unitigs_support", "agx_link_support_free", "agx_unitigs_gfa_support",
     "agx_unit_walk_evidence", "agx_walk_evidence_free", "agx_walk_evidence_bed",
+    "agx_test_scan", "agx_test_zero", "agx_test_copy_out",
 ]
 
 
@@ -210,6 +211,10 @@ def lib():
         L.agx_unit_push_pairs.argtypes = [ctypes.c_void_p, ctypes.POINTER(PairBatch)]
         L.agx_device_memory.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.agx_selftest_scan.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]
+        L.agx_test_scan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+                                    ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+        L.agx_test_zero.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+        L.agx_test_copy_out.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)]
         L.agx_unit_load_files.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
         L.agx_reads_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p, ctypes.c_size_t]
         L.agx_reads_close.argtypes = [ctypes.c_void_p]

@@ -1025,6 +1025,22 @@ AGX_HD agx_u32 agx_node_write_lane(const agx_sweep_args &A, agx_u32 X, const agx
 static_assert(63u * (AGX_MAXV_HUGE - 1u) < 65536u && AGX_MAXV_HUGE <= 65535u, "side ids of a tile's first 63 positions must fit 16 bits");
 AGX_HD agx_u32 agx_side_pack(agx_u32 before_in_tile, agx_u32 here) { return before_in_tile | (here << 16); }
 
+// ---- the one-launch scan's look-back (agx_k_scan_lookback, agx_kernels.hip) ------------------------------------------------------
+// A block's descriptor: two flag bits on top (0: nothing published yet), the block's 32-bit value below — AGG: the sum of its own 4096 elements, PFX: the inclusive
+// prefix up to and with the block.  A lane in front of block 0 holds AGX_SCAN_FRONT: a prefix of 0.
+#define AGX_SCAN_AGG (1ull << 62)
+#define AGX_SCAN_PFX (2ull << 62)
+#define AGX_SCAN_FRONT AGX_SCAN_PFX
+AGX_HD bool agx_scan_is_prefix(unsigned long long d) { return (d >> 62) == 2; }
+// What a lane takes from one window of 64 predecessors (lane 0: the nearest), every lane's descriptor published.  pfx: the lanes that hold a prefix (the ballot of
+// agx_scan_is_prefix).  The walk stops BEHIND the nearest prefix: that lane and every nearer one give their value, the lanes beyond it nothing, and a window without a
+// prefix gives all 64 aggregates and sends the walk on.  The sum of what the lanes return (mod 2^32) is the window's share of the block's exclusive prefix.
+AGX_HD agx_u32 agx_scan_window_take(unsigned long long pfx, unsigned long long d, agx_u32 lane, bool &last) {
+    const agx_u32 stop = pfx ? (agx_u32)__builtin_ctzll(pfx) : 63u;   // nearest predecessor that holds an inclusive prefix
+    last = pfx != 0;
+    return lane <= stop ? (agx_u32)d : 0u;
+}
+
 // ---- reprune: the prune of a built node table at another coverage (agx_unit_reprune) -------------------------------------
 // Coverage decides one bit per node (AGX_NF_DEAD above) and the side-id counts that follow from it; keys, votes, bases and edges do not look at it, and the
 // table keeps the pruned nodes with their counts (n_counts: units created with AGX_FLAG_KEEP_COUNTS).  So the walk graph at another coverage is this pass over

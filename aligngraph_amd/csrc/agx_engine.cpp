@@ -1787,6 +1787,102 @@ int agx_selftest_scan(int device, uint32_t n, uint32_t seed) {
     } catch (const Error &) { return AGX_E_DEVICE; }
 }
 
+// ---- test hooks of the primitives under every build and export (tests/test_gpu_primitives.py): the caller's arrays through the product's launchers, every device array
+// followed (agx_test_zero: also preceded) by AGX_TEST_GUARD words of 0xA5 bytes that come back with it.  They need no unit, and a build that does not call them runs none of this.
+int agx_test_scan(int device, int form, const uint32_t *in, uint32_t n, uint32_t *out, uint32_t grid_cap, int seeded, int streams, uint64_t *desc, uint32_t *tmp, uint32_t *grid_limit) {
+    if (!in || !out || (form != 0 && form != 1) || n == 0xFFFFFFFFu || streams < 1 || streams > 2 || (streams == 2 && grid_cap)) return AGX_E_ARG;
+    if (form == 0 ? (!tmp || grid_cap || seeded) : !desc) return AGX_E_ARG;
+    hipStream_t st[2] = {nullptr, nullptr};
+    int rc = AGX_OK;
+    try {
+        HIP_OK(hipSetDevice(device));
+        const size_t m = (size_t)n + 1, G = AGX_TEST_GUARD, nb = (m + 4095) / 4096, nb2 = (nb + 4095) / 4096, tw = 2 * (nb + 1) + 2 * (nb2 + 1);
+        DBuf<agx_u32> d_in, d_out[2], d_tmp[2]; DBuf<unsigned long long> d_desc[2];
+        DevArena arena; arena.device = device;
+        std::vector<unsigned long long> d0(nb + G, 0xA5A5A5A5A5A5A5A5ull);      // the descriptors as the launch finds them: zero, or (seeded) every block's own aggregate already there
+        for (size_t b = 0; b < nb; b++) {
+            agx_u32 t = 0;
+            if (seeded) for (size_t i = b * 4096; i < m && i < (b + 1) * 4096; i++) t += in[i];
+            d0[b] = seeded ? AGX_SCAN_AGG | t : 0ull;
+        }
+        d_in.alloc(arena, m);
+        HIP_OK(hipMemcpy(d_in.p, in, m * 4, hipMemcpyHostToDevice));
+        for (int s = 0; s < streams; s++) {
+            d_out[s].alloc(arena, m + G); HIP_OK(hipMemset(d_out[s].p, 0xA5, (m + G) * 4));
+            if (form == 1) { d_desc[s].alloc(arena, nb + G); HIP_OK(hipMemcpy(d_desc[s].p, d0.data(), (nb + G) * 8, hipMemcpyHostToDevice)); }
+            else { d_tmp[s].alloc(arena, tw + G); HIP_OK(hipMemset(d_tmp[s].p, 0xA5, (tw + G) * 4)); }
+        }
+        if (streams == 2) for (int s = 0; s < 2; s++) HIP_OK(hipStreamCreateWithFlags(&st[s], hipStreamNonBlocking));      // (a build's front and main stream)
+        HIP_OK(hipDeviceSynchronize());
+        if (grid_limit) *grid_limit = agx_scan_grid_limit(grid_cap);
+        for (int s = 0; s < streams; s++) {
+            if (form == 1) agx_launch_exclusive_scan1_capped(d_in.p, d_out[s].p, n, d_desc[s].p, grid_cap, st[s]);
+            else agx_launch_exclusive_scan(d_in.p, d_out[s].p, n, d_tmp[s].p, st[s]);
+        }
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipDeviceSynchronize());
+        for (int s = 0; s < streams; s++) {
+            HIP_OK(hipMemcpy(out + (size_t)s * (m + G), d_out[s].p, (m + G) * 4, hipMemcpyDeviceToHost));
+            if (form == 1) HIP_OK(hipMemcpy(desc + (size_t)s * (nb + G), d_desc[s].p, (nb + G) * 8, hipMemcpyDeviceToHost));
+            else HIP_OK(hipMemcpy(tmp + (size_t)s * (tw + G), d_tmp[s].p, (tw + G) * 4, hipMemcpyDeviceToHost));
+        }
+    } catch (const Error &) { rc = AGX_E_DEVICE; }
+      catch (const std::bad_alloc &) { rc = AGX_E_ARG; }
+    for (hipStream_t s : st) if (s) (void)hipStreamDestroy(s);
+    return rc;
+}
+
+int agx_test_zero(int device, const uint32_t *len, uint32_t *words) {
+    if (!len || !words) return AGX_E_ARG;
+    try {
+        HIP_OK(hipSetDevice(device));
+        const size_t G = AGX_TEST_GUARD;
+        DBuf<agx_u32> d[8];
+        DevArena arena; arena.device = device;
+        agx_zero_args Z; memset(&Z, 0, sizeof Z);
+        for (int s = 0; s < 8; s++) {
+            d[s].alloc(arena, (size_t)len[s] + 2 * G); HIP_OK(hipMemset(d[s].p, 0xA5, ((size_t)len[s] + 2 * G) * 4));
+            Z.p[s] = d[s].p + G; Z.n[s] = len[s];
+        }
+        HIP_OK(hipDeviceSynchronize());
+        agx_launch_zero(&Z, nullptr);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipDeviceSynchronize());
+        size_t at = 0;
+        for (int s = 0; s < 8; s++) { HIP_OK(hipMemcpy(words + at, d[s].p, ((size_t)len[s] + 2 * G) * 4, hipMemcpyDeviceToHost)); at += (size_t)len[s] + 2 * G; }
+        return AGX_OK;
+    } catch (const Error &) { return AGX_E_DEVICE; }
+      catch (const std::bad_alloc &) { return AGX_E_ARG; }
+}
+
+int agx_test_copy_out(int device, int n_seg, const uint64_t *bytes, const uint8_t *src, uint8_t *dst) {
+    if (n_seg < 1 || n_seg > 16 || !bytes || !src || !dst) return AGX_E_ARG;
+    try {
+        HIP_OK(hipSetDevice(device));
+        const size_t G = AGX_TEST_GUARD * 4;
+        DBuf<agx_u8> d_src[16]; PBuf<agx_u8> h_dst;
+        DevArena arena; arena.device = device;
+        size_t total = 0, at = 0, from = 0;
+        for (int s = 0; s < n_seg; s++) total += ((size_t)bytes[s] + 15) / 16 * 16 + G;
+        h_dst.alloc(total); memset(h_dst.p, 0xA5, total);
+        void *dp[16]; const void *sp[16]; size_t nbytes[16];
+        for (int s = 0; s < n_seg; s++) {
+            const size_t r = ((size_t)bytes[s] + 15) / 16 * 16;
+            d_src[s].alloc(arena, r);
+            if (r) HIP_OK(hipMemcpy(d_src[s].p, src + from, r, hipMemcpyHostToDevice));
+            dp[s] = (char *)h_dst.dev() + at; sp[s] = d_src[s].p; nbytes[s] = (size_t)bytes[s];
+            at += r + G; from += r;
+        }
+        HIP_OK(hipDeviceSynchronize());
+        agx_launch_copy_out(dp, sp, nbytes, n_seg, nullptr);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipDeviceSynchronize());
+        memcpy(dst, h_dst.p, total);
+        return AGX_OK;
+    } catch (const Error &) { return AGX_E_DEVICE; }
+      catch (const std::bad_alloc &) { return AGX_E_ARG; }
+}
+
 int agx_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes) {
     size_t f = 0, t = 0;
     if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(&f, &t) != hipSuccess) return AGX_E_DEVICE;

@@ -148,9 +148,11 @@ void agx_launch_patch_codes(const unsigned long long *other, size_t n_other, voi
 void agx_launch_expand_runs(const void *wruns, agx_run *runs, agx_u32 n_runs, hipStream_t);      // wire formats (agx_core.h) -> working arrays
 void agx_launch_expand_ref(const void *packed, void *ref, size_t n_pos16, const void *refx, agx_u32 n_refx, hipStream_t);      // 2-bit reference bases + the stretches of other bytes -> letters; n_pos16 a multiple of 16
 void agx_launch_hit_prep(const agx_prep_args *, hipStream_t);
-// exclusive scan of in[0..n] (n+1 entries, in[n] must be 0) into out[0..n]; out[n] = total
+// exclusive scan of in[0..n] (n+1 entries; in[n] is read, its value reaches no output) into out[0..n]; out[n] = total.  tmp: 2*(nb+1) + 2*(nb2+1) words, nb = ceil((n+1)/4096), nb2 = ceil(nb/4096)
 void agx_launch_exclusive_scan(const agx_u32 *in, agx_u32 *out, agx_u32 n, agx_u32 *tmp, hipStream_t);
 void agx_launch_exclusive_scan1(const agx_u32 *in, agx_u32 *out, agx_u32 n, unsigned long long *desc, hipStream_t);      // one launch; desc: ceil((n+1)/4096) zeroed words
+void agx_launch_exclusive_scan1_capped(const agx_u32 *in, agx_u32 *out, agx_u32 n, unsigned long long *desc, agx_u32 grid_cap, hipStream_t);      // the same with at most grid_cap workgroups (0: the launcher's own grid; the test hooks)
+agx_u32 agx_scan_grid_limit(agx_u32 grid_cap);      // the workgroups such a launch takes at most on the current device: min(grid_cap, what the device holds at once)
 void agx_launch_bin_fill(const agx_bin_args *, hipStream_t);
 // the tile lists as the sweeps read them (32-byte records in SAM order): agx_k_tile_fill from the window of the tile order, or — the fallback — agx_k_tile_sort from bin_fill's dense lists
 struct agx_fill_args { const agx_u32 *tile_off, *tile_first, *perm, *ckey; const agx_dhit *dhit; const agx_run *runs; void *recs; agx_u32 *scratch /* = bin_fill's `unsorted` */;

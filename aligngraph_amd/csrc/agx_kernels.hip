@@ -220,8 +220,7 @@ __global__ void __launch_bounds__(256) agx_k_scan_add(agx_u32 *out, const agx_u3
 // not promise dispatch in blockIdx order.  The grid is therefore capped at what the device holds at once (agx_scan_grid: from the occupancy
 // query, halved because two build streams may scan at the same time) and workgroup g takes the 4096-element blocks g, g + grid, g + 2 grid, .. in that order: whatever a block waits
 // for belongs to a workgroup that is running or has only earlier blocks to finish first.
-#define AGX_SCAN_AGG (1ull << 62)
-#define AGX_SCAN_PFX (2ull << 62)
+// (The descriptor's two forms and what a lane takes from a window of them: agx_core.h, AGX_SCAN_AGG / AGX_SCAN_PFX and agx_scan_window_take, shared with tests/scan_shim.cpp.)
 #define AGX_SCAN_GRID 1024u      // upper bound; the launcher takes what the device at hand holds at once (agx_scan_grid)
 __global__ void __launch_bounds__(256) agx_k_scan_lookback(const agx_u32 *in, agx_u32 *out, agx_u32 n, unsigned long long *desc, agx_u32 n_blocks) {
     __shared__ agx_u32 sh[256];
@@ -246,14 +245,13 @@ __global__ void __launch_bounds__(256) agx_k_scan_lookback(const agx_u32 *in, ag
             agx_u32 excl = 0;
             for (long long hi = (long long)b - 1; hi >= 0;) {                     // window of predecessors hi, hi-1, .., hi-63
                 const long long j = hi - lane;
-                unsigned long long d = AGX_SCAN_PFX;                              // lanes before block 0: a prefix of 0
+                unsigned long long d = AGX_SCAN_FRONT;                            // lanes before block 0: a prefix of 0
                 if (j >= 0) do { d = __hip_atomic_load(&desc[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((d >> 62) == 0);
-                const unsigned long long pfx = __ballot((d >> 62) == 2);
-                const agx_u32 stop = pfx ? (agx_u32)__builtin_ctzll(pfx) : 63u;   // nearest predecessor that holds an inclusive prefix
-                agx_u32 part = lane <= stop ? (agx_u32)d : 0u;
+                bool last;
+                agx_u32 part = agx_scan_window_take(__ballot(agx_scan_is_prefix(d)), d, lane, last);
                 for (agx_u32 o = 32; o; o >>= 1) part += __shfl_down(part, o, 64);
                 excl += __shfl(part, 0, 64);
-                if (pfx) break;
+                if (last) break;
                 hi -= 64;
             }
             if (lane == 0) {
@@ -1172,9 +1170,11 @@ void agx_launch_hit_prep(const agx_prep_args *A, hipStream_t st) {
     if (A->n_hits) hipLaunchKernelGGL(agx_k_hit_prep, dim3((A->n_hits + 255) / 256), dim3(256), 0, st, *A);
 }
 
-// exclusive scan of in[0..n) into out[0..n]; out[n] = total.  tmp must hold 2*(ceil(n/4096)+1) + 2*(ceil(n/4096^2)+1) + 8 words (the engine sizes it for blocks of 1024).
+// exclusive scan of in[0..n) into out[0..n]; out[n] = total.  With nb = ceil((n+1)/4096) and nb2 = ceil(nb/4096), tmp must hold 2*(nb+1) + 2*(nb2+1) words and needs
+// no initial value (nb == 1: it is not touched); nothing is written behind them (tests/test_gpu_primitives.py runs it with guard words there).  The engine's scan_words()
+// is this figure for the largest n a buffer serves, and d_scan_tmp is sized for blocks of 1024; the callers' further slack is not needed.
 void agx_launch_exclusive_scan(const agx_u32 *in, agx_u32 *out, agx_u32 n, agx_u32 *tmp, hipStream_t st) {
-    // scan n+1 elements (a trailing zero-extended element gives the total in out[n]); callers allocate in with n+1 entries, in[n]=0
+    // scan n+1 elements (the closing element gives the total in out[n]); callers allocate in with n+1 entries: in[n] is read, its value reaches no output
     const agx_u32 m = n + 1;
     const agx_u32 nb = (m + AGX_SCAN_BLOCK - 1) / AGX_SCAN_BLOCK;
     if (nb == 1) { hipLaunchKernelGGL(agx_k_scan_blocks, dim3(1), dim3(256), 0, st, in, out, (agx_u32 *)nullptr, m); return; }
@@ -1208,11 +1208,14 @@ static agx_u32 agx_scan_grid() {
     }
     return g;
 }
-void agx_launch_exclusive_scan1(const agx_u32 *in, agx_u32 *out, agx_u32 n, unsigned long long *desc, hipStream_t st) {
-    const agx_u32 m = n + 1;                              // callers allocate in with n+1 entries, in[n] = 0: out[n] = total
-    const agx_u32 nb = (m + AGX_SCAN_BLOCK - 1) / AGX_SCAN_BLOCK, grid = agx_scan_grid();
+// the most workgroups a one-launch scan takes on the current device; grid_cap: 0, or a smaller limit (the test hooks': never more than agx_scan_grid allows)
+agx_u32 agx_scan_grid_limit(agx_u32 grid_cap) { const agx_u32 g = agx_scan_grid(); return grid_cap && grid_cap < g ? grid_cap : g; }
+void agx_launch_exclusive_scan1_capped(const agx_u32 *in, agx_u32 *out, agx_u32 n, unsigned long long *desc, agx_u32 grid_cap, hipStream_t st) {
+    const agx_u32 m = n + 1;                              // callers allocate in with n+1 entries (in[n] is read, its value reaches no output): out[n] = total
+    const agx_u32 nb = (m + AGX_SCAN_BLOCK - 1) / AGX_SCAN_BLOCK, grid = agx_scan_grid_limit(grid_cap);
     hipLaunchKernelGGL(agx_k_scan_lookback, dim3(nb < grid ? nb : grid), dim3(256), 0, st, in, out, m, desc, nb);
 }
+void agx_launch_exclusive_scan1(const agx_u32 *in, agx_u32 *out, agx_u32 n, unsigned long long *desc, hipStream_t st) { agx_launch_exclusive_scan1_capped(in, out, n, desc, 0u, st); }
 
 void agx_launch_bin_fill(const agx_bin_args *A, hipStream_t st) {
     if (A->n_hits) hipLaunchKernelGGL(agx_k_bin_fill, dim3((A->n_hits + 255) / 256), dim3(256), 0, st, *A);

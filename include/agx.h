@@ -262,6 +262,22 @@ int agx_device_count(void);                                   /* HIP devices vis
 int agx_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes);   /* HBM of one device (hipMemGetInfo) */
 int agx_selftest_scan(int device, uint32_t n, uint32_t seed);   /* test hook: the build's one-launch prefix scan over n pseudo-random counts against a host scan; AGX_OK or AGX_E_DEVICE */
 
+/* Test hooks of the primitives under every build and export: the caller's arrays through the library's own launchers.  Every device array is followed
+   (agx_test_zero: also preceded) by AGX_TEST_GUARD words of 0xA5 bytes that come back with it.  AGX_OK, AGX_E_ARG or AGX_E_DEVICE.
+   agx_test_scan: the exclusive scan of in[0 .. n] (n + 1 words; in[n] is read, no output may depend on it) into out[0 .. n].
+     form 0: the multi-launch scan; tmp[2 (nb + 1) + 2 (nb2 + 1) + guard] comes back, nb = ceil((n + 1) / 4096), nb2 = ceil(nb / 4096); grid_cap = seeded = 0.
+     form 1: the one-launch scan; desc[nb + guard] comes back (zeroed before the launch).  grid_cap: 0, or the most workgroups the launch may take (never more than the
+             launcher's own grid); *grid_limit = the limit that held.  seeded: every desc[b] holds the aggregate flag and block b's own sum before the launch.
+     streams: 1, or 2 (grid_cap = 0): the scan twice at once on two streams; out, desc and tmp then hold the second run behind the first. */
+#define AGX_TEST_GUARD 64
+int agx_test_scan(int device, int form, const uint32_t *in, uint32_t n, uint32_t *out /* [streams][n + 1 + guard] */, uint32_t grid_cap, int seeded, int streams,
+                  uint64_t *desc, uint32_t *tmp, uint32_t *grid_limit);
+/* agx_k_zero over eight arrays of len[0 .. 7] words; words: the eight arrays one after the other, each as guard | len[s] | guard */
+int agx_test_zero(int device, const uint32_t *len, uint32_t *words);
+/* agx_launch_copy_out of n_seg (1 .. 16) segments from device memory to registered host memory.  src: the segments one after the other, each padded to a multiple of
+   16 bytes; dst: what the host buffer holds afterwards, each segment as (padded bytes | guard) */
+int agx_test_copy_out(int device, int n_seg, const uint64_t *bytes, const uint8_t *src, uint8_t *dst);
+
 int agx_unit_create(const agx_params *p, agx_unit **out);
 void agx_unit_destroy(agx_unit *u);
 const char *agx_unit_error(const agx_unit *u);
