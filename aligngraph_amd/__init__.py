@@ -30,6 +30,7 @@ EXPORTS = [
     "agx_unit_unitigs_mapped", "agx_idmap_free", "agx_unit_walk_paths", "agx_walk_paths_free", "agx_unitigs_paths_gfa", "agx_unit_reprune",
     "agx_unit_edge_support", "agx_edge_support_free", "agx_unit_unitigs_support", "agx_link_support_free", "agx_unitigs_gfa_support",
     "agx_unit_walk_evidence", "agx_walk_evidence_free", "agx_walk_evidence_bed",
+    "agx_unit_edge_reads", "agx_edge_reads_free", "agx_edge_reads_tsv",
     "agx_test_scan", "agx_test_zero", "agx_test_copy_out",
 ]
 
@@ -76,7 +77,7 @@ class Stats(ctypes.Structure):
                [(n, ctypes.c_uint64) for n in ("upload_bytes", "device_bytes", "pinned_bytes_cached", "device_bytes_cached", "n_spilled")] + \
                [("build_attempts", ctypes.c_uint32), ("from_cache", ctypes.c_uint32), ("dense_lists", ctypes.c_uint32), ("rows_by_reference", ctypes.c_uint32)] + \
                [("n_edge_slow", ctypes.c_uint64), ("reprune_attempts", ctypes.c_uint32), ("ms_reprune", ctypes.c_double)] + \
-               [("ms_edge_support", ctypes.c_double), ("n_support_events", ctypes.c_uint64), ("ms_walk_evidence", ctypes.c_double)]
+               [("ms_edge_support", ctypes.c_double), ("n_support_events", ctypes.c_uint64), ("ms_walk_evidence", ctypes.c_double), ("ms_edge_reads", ctypes.c_double)]
 
 
 class Graph(ctypes.Structure):
@@ -93,9 +94,17 @@ class Unitigs(ctypes.Structure):
                 ("seq", ctypes.c_void_p), ("link_from", ctypes.POINTER(ctypes.c_uint32)), ("link_to", ctypes.POINTER(ctypes.c_uint32))]
 
 
+EDGE_READS_EDGE = ("src_pos", "src_var", "dst_pos", "dst_var", "support")
+
+
 class EdgeSupport(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_uint32), ("n_edges", ctypes.c_uint32), ("n_events", ctypes.c_uint64), ("n_contributions", ctypes.c_uint64)] + \
                [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("edge_start", "edge_dst", "edge_cnt")]
+
+
+class EdgeReads(ctypes.Structure):
+    _fields_ = [("n_edges", ctypes.c_uint32), ("n_hits", ctypes.c_uint64)] + \
+               [(n, ctypes.POINTER(ctypes.c_uint32)) for n in EDGE_READS_EDGE] + [("hit_off", ctypes.POINTER(ctypes.c_uint64)), ("hit", ctypes.POINTER(ctypes.c_uint32))]
 
 
 class IdMap(ctypes.Structure):
@@ -268,6 +277,10 @@ def lib():
         L.agx_walk_evidence_free.restype = None
         L.agx_walk_evidence_bed.argtypes = [ctypes.POINTER(WalkEvidence), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         L.agx_text_free.restype = None
+        L.agx_unit_edge_reads.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EdgeReads)]
+        L.agx_edge_reads_free.argtypes = [ctypes.POINTER(EdgeReads)]
+        L.agx_edge_reads_free.restype = None
+        L.agx_edge_reads_tsv.argtypes = [ctypes.POINTER(EdgeReads), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         L.agx_run_unit.argtypes = [ctypes.POINTER(Params), ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Result), ctypes.c_char_p, ctypes.c_size_t]
         _lib = L
     return _lib
@@ -518,6 +531,28 @@ class Unit:
         finally:
             lib().agx_edge_support_free(ctypes.byref(s))
 
+    def edge_reads(self, region=None, max_support=None):
+        """The hits behind the edges of a window (agx_unit_edge_reads; the unit was created with keep_counts=True and edge_support=True): every edge whose source position
+        lies in region = (lo, hi) (None: every position) and whose support is <= max_support (None: every edge), as src_pos, src_var, dst_pos, dst_var, support per edge in
+        the order (src_pos, src_var, dst_pos, dst_var), and the hit numbers of the events that name edge e, ascending, in hit[hit_off[e]:hit_off[e + 1]].  A hit number is
+        the hit's place in file order: the index into front()["dhit"] after undoing perm, the i-th hit handed to push_pairs."""
+        import numpy as np
+        lo, hi = region if region is not None else (0, self.stats()["n_pos"])
+        top = 0xFFFFFFFF if max_support is None else max_support
+        for v in (lo, hi, top):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise AgxError(AGX_E_ARG, "edge reads: region bounds and max_support are unsigned 32-bit numbers")
+        r = EdgeReads()
+        self._check(lib().agx_unit_edge_reads(self._h, int(lo), int(hi), int(top), ctypes.byref(r)))
+        try:
+            def arr(p, n, dt):
+                return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
+            out = {k: arr(getattr(r, k), r.n_edges, "uint32") for k in EDGE_READS_EDGE}
+            out.update(hit_off=arr(r.hit_off, r.n_edges + 1, "uint64"), hit=arr(r.hit, r.n_hits, "uint32"))
+            return out
+        finally:
+            lib().agx_edge_reads_free(ctypes.byref(r))
+
     def _export_support(self, t, region, min_coverage, m=None):
         """agx_unit_unitigs_support over the window and threshold of _window(); returns the links' support as a ctypes array the caller frees (agx_link_support_free)."""
         sup = ctypes.POINTER(ctypes.c_uint32)()
@@ -706,6 +741,28 @@ def evidence_bed(e, unit=0):
     rc = lib().agx_walk_evidence_bed(ctypes.byref(s), unit, ctypes.byref(p), ctypes.byref(n))
     if rc != AGX_OK:
         raise AgxError(rc, "agx_walk_evidence_bed: the interval table is inconsistent")
+    try:
+        return ctypes.string_at(p, n.value) if n.value else b""
+    finally:
+        lib().agx_text_free(p)
+
+
+def edge_reads_tsv(r, unit=0):
+    """TSV text of a dict like Unit.edge_reads() returns, one line per edge: unit, src_pos, src_var, dst_pos, dst_var, support, the hit numbers joined by commas
+    (agx_edge_reads_tsv; host only, needs no device)."""
+    import numpy as np
+    keep = {k: np.ascontiguousarray(r[k], dtype="uint32") for k in EDGE_READS_EDGE + ("hit",)}
+    keep["hit_off"] = np.ascontiguousarray(r["hit_off"], dtype="uint64")
+    s = EdgeReads()
+    s.n_edges, s.n_hits = len(keep["src_pos"]), len(keep["hit"])
+    if len(keep["hit_off"]) != s.n_edges + 1 or any(len(keep[k]) != s.n_edges for k in EDGE_READS_EDGE):
+        raise AgxError(AGX_E_ARG, "agx_edge_reads_tsv: one entry per edge, and one offset more")
+    for k, a in keep.items():
+        setattr(s, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64 if k == "hit_off" else ctypes.c_uint32)))
+    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
+    rc = lib().agx_edge_reads_tsv(ctypes.byref(s), unit, ctypes.byref(p), ctypes.byref(n))
+    if rc != AGX_OK:
+        raise AgxError(rc, "agx_edge_reads_tsv: the table is inconsistent")
     try:
         return ctypes.string_at(p, n.value) if n.value else b""
     finally:

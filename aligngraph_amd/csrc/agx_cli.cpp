@@ -49,6 +49,9 @@ struct Options {
     // --evidenceOut <file> [--evidenceMinDepth n] [--evidenceMinSupport n]: the weak intervals of every unit's pre-extended records as BED (agx_unit_walk_evidence);
     // the thresholds default to --coverage and 2
     int tagEvidence = 0; string evidence; int tagEvDepth = 0, evDepth = 0, tagEvSupport = 0, evSupport = 2;
+    // --graphEdgeReads <file> [--graphEdgeReadsMax n]: the edges of support <= n (default 2) of every unit — with --graphRegion: of that unit's positions [lo, hi) — with the
+    // numbers of the hits behind them, as TSV (agx_unit_edge_reads)
+    int tagEdgeReads = 0; string edgeReads; int tagEdgeReadsMax = 0, edgeReadsMax = 2;
     int graphSupport = 0;               // --graphEdgeSupport (only with --graphOut): RC:i:<events that name the link's edge> on every L line (agx_unit_unitigs_support)
     int fastMap = 0, ratioCheck = 0, uniqueExtension = 0, iterativeMap = 0, misassemblyRemoval = 0, resume = 0;
     int k = 5, distanceLow = 0, distanceHigh = 99999, coverage = 20, insertVariation = 50, part = 1;      // defaults of AG:4701
@@ -134,6 +137,8 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--graphMinCoverage") { integer(i, o.tagGraphCov, o.graphCov); if (o.graphCov < 0) die_usage(); }
         else if (b == "--graphPaths") flag(o.graphPaths);
         else if (b == "--graphEdgeSupport") flag(o.graphSupport);
+        else if (b == "--graphEdgeReads") outfile(i, o.tagEdgeReads, o.edgeReads);
+        else if (b == "--graphEdgeReadsMax") { integer(i, o.tagEdgeReadsMax, o.edgeReadsMax); if (o.edgeReadsMax < 0) die_usage(); }
         else if (b == "--evidenceOut") outfile(i, o.tagEvidence, o.evidence);
         else if (b == "--evidenceMinDepth") { integer(i, o.tagEvDepth, o.evDepth); if (o.evDepth < 0) die_usage(); }
         else if (b == "--evidenceMinSupport") { integer(i, o.tagEvSupport, o.evSupport); if (o.evSupport < 0) die_usage(); }
@@ -149,13 +154,22 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--resume") { if (o.resume == 1 || count != 1) die_usage(); o.resume = 1; }
         else die_usage();
     }
-    if ((o.tagRegion || o.tagGraphCov || o.graphPaths || o.graphSupport) && !o.tagGraph) die_usage();
+    if ((o.tagGraphCov || o.graphPaths || o.graphSupport) && !o.tagGraph) die_usage();
+    if (o.tagRegion && !o.tagGraph && !o.tagEdgeReads) die_usage();
+    if (o.tagEdgeReadsMax && !o.tagEdgeReads) die_usage();
     if ((o.tagEvDepth || o.tagEvSupport) && !o.tagEvidence) die_usage();
 }
 
 // tmp/_evidence.<u>.d<depth>.s<support>.bed, the thresholds in the name: a --resume run merges only intervals that were made under its own settings
 uint32_t evidence_depth(const Options &o) { return (uint32_t)(o.tagEvDepth ? o.evDepth : std::max(o.coverage, 0)); }
 string evidence_part_path(const Options &o, int u) { return "tmp/_evidence." + itoa(u) + ".d" + itoa((long long)evidence_depth(o)) + ".s" + itoa(o.evSupport) + ".bed"; }
+
+// tmp/_edge_reads.<u>.m<max>.tsv, with the region in the name when one is given: a --resume run merges only lines that were made under its own settings
+string edge_reads_part_path(const Options &o, int u) {
+    string s = "tmp/_edge_reads." + itoa(u);
+    if (o.tagRegion) s += "." + itoa(o.regionLo) + "-" + itoa(o.regionHi);
+    return s + ".m" + itoa(o.edgeReadsMax) + ".tsv";
+}
 
 // tmp/_graph.<u>.gfa, with the region, the threshold, --graphPaths (.p) and --graphEdgeSupport (.s) in the name when they are given: a --resume run merges only lines that were made under its own settings
 string graph_part_path(const Options &o, int u) {
@@ -1187,8 +1201,9 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                 // the five calls of the unit loop (AG:4768-4776) through the split entry points of agx_run_unit, with the admission between load and upload
                 // (--graphEdgeSupport: the counting reads the front of the build, which a one-shot unit does not promise to keep — such a run's units are ordinary ones, with the edge counters)
                 // (--evidenceOut: ordinary units too, with the counts, the stretches and the edge counters: the evidence is asked for after the finish)
-                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, (o.graphSupport || o.tagEvidence ? AGX_FLAG_EDGE_SUPPORT : AGX_FLAG_ONE_SHOT) |
-                                (o.tagGraph || o.tagEvidence ? AGX_FLAG_KEEP_COUNTS : 0u) | (o.graphPaths || o.tagEvidence ? AGX_FLAG_KEEP_PATHS : 0u)};
+                // (--graphEdgeReads: as for --graphEdgeSupport, with the counts as well: the listing's scratch is the export's buffer)
+                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, (o.graphSupport || o.tagEvidence || o.tagEdgeReads ? AGX_FLAG_EDGE_SUPPORT : AGX_FLAG_ONE_SHOT) |
+                                (o.tagGraph || o.tagEvidence || o.tagEdgeReads ? AGX_FLAG_KEEP_COUNTS : 0u) | (o.graphPaths || o.tagEvidence ? AGX_FLAG_KEEP_PATHS : 0u)};
                 agx_result r; memset(&r, 0, sizeof r); char err[512]; err[0] = 0;
                 agx_unit *un = nullptr;
                 int rc = agx_unit_create(&p, &un);
@@ -1225,6 +1240,20 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                     if (rc == AGX_OK) {
                         const string path = graph_part_path(o, u);
                         FILE *f = fopen(path.c_str(), "wb"); bool ok = f != nullptr;
+                        if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
+                        if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
+                    }
+                    agx_text_free(text);
+                }
+                if (rc == AGX_OK && o.tagEdgeReads && (!o.tagRegion || u == o.regionUnit)) {      // --graphEdgeReads: the hits behind the weak edges, before the download, into tmp/_edge_reads.<u>...tsv
+                    agx_edge_reads er; char *text = nullptr; size_t len = 0; agx_stats st;
+                    memset(&er, 0, sizeof er); memset(&st, 0, sizeof st);
+                    rc = agx_unit_stats(un, &st);
+                    if (rc == AGX_OK) rc = agx_unit_edge_reads(un, o.tagRegion ? o.regionLo : 0u, o.tagRegion ? o.regionHi : (uint32_t)st.n_pos, (uint32_t)o.edgeReadsMax, &er);
+                    if (rc == AGX_OK) { rc = agx_edge_reads_tsv(&er, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "TSV FORMATTING FAILED"); }
+                    agx_edge_reads_free(&er);
+                    if (rc == AGX_OK) {
+                        FILE *f = fopen(edge_reads_part_path(o, u).c_str(), "wb"); bool ok = f != nullptr;
                         if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
                         if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
                     }
@@ -1364,6 +1393,21 @@ int main(int argc, char **argv) {
         if (g) ok = (fclose(g) == 0) && ok;
         if (!ok) die("CANNOT OPEN FILE!");
         stage("graph output");
+    }
+    if (o.tagEdgeReads) {                                                     // --graphEdgeReads: every unit's lines, in unit order (a --resume run finds the earlier units' files in tmp/)
+        FILE *g = fopen(o.edgeReads.c_str(), "wb");
+        bool ok = g != nullptr;
+        for (int u = 0; ok && u < units; u++) {
+            if (o.tagRegion && u != o.regionUnit) continue;      // (with a region only the named unit has lines)
+            FILE *f = fopen(edge_reads_part_path(o, u).c_str(), "rb");
+            if (!f) { ok = false; break; }
+            char buf[1 << 16]; size_t n;
+            while (ok && (n = fread(buf, 1, sizeof buf, f)) > 0) ok = fwrite(buf, 1, n, g) == n;
+            fclose(f);
+        }
+        if (g) ok = (fclose(g) == 0) && ok;
+        if (!ok) die("CANNOT OPEN FILE!");
+        stage("edge reads output");
     }
     if (o.tagEvidence) {                                                      // --evidenceOut: every unit's intervals, in unit order (a --resume run finds the earlier units' files in tmp/)
         FILE *g = fopen(o.evidence.c_str(), "wb");

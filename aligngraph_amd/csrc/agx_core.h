@@ -1318,6 +1318,50 @@ AGX_HD agx_u32 agx_support_ovf_entry(const agx_edge_ovf *ovf, agx_u32 n_ovf, agx
     return n_ovf;
 }
 
+// ---- edge reads: the hits behind the edges of a window (agx_unit_edge_reads) ---------------------------------------------
+// The counting pass once more with a store in place of an add: the events, the pairs they name and the place of a pair's counter are the functions above, unchanged.
+// The only arithmetic of its own is whether a contribution's edge is SELECTED — its counter, the one the counting pass filled, against max_support — and whether the
+// event's source position lies in the window [pos_lo, pos_hi).  The target's position is not asked: an event belongs to its source.
+struct agx_reads_tab {
+    const agx_u32 *n_next; const agx_u8 *n_flags; const agx_edge_ovf *ovf; agx_u32 n_ovf; const agx_u32 *e_cnt, *ovf_cnt;
+    agx_u32 pos_lo, pos_hi, max_support;
+};
+// The support of edge src -> dst (src < pool_cap) as the counters hold it: the inline slot's, else the FIRST overflow entry's of the pair (it took every count).
+// *found = false: the node table holds no such edge (the number is 0 then).
+AGX_HD agx_u32 agx_reads_counter(const agx_reads_tab &T, agx_u32 src, agx_u32 dst, bool *found) {
+    const agx_u32 e = agx_support_slot(T.n_next, src, dst);
+    if (e < AGX_MAXE) { *found = true; return T.e_cnt[(size_t)src * AGX_MAXE + e]; }
+    const agx_u32 i = (T.n_flags[src] & AGX_NF_EOVF) ? agx_support_ovf_entry(T.ovf, T.n_ovf, src, dst) : T.n_ovf;
+    *found = i < T.n_ovf;
+    return *found ? T.ovf_cnt[i] : 0u;
+}
+AGX_HD bool agx_reads_selected(const agx_reads_tab &T, agx_u32 support) { return support <= T.max_support; }
+// the window test: a position lists its events iff it lies in [pos_lo, pos_hi) (the kernel's lanes and agx_reads_lane both ask here)
+AGX_HD bool agx_reads_in_window(const agx_reads_tab &T, agx_u32 X) { return X >= T.pos_lo && X < T.pos_hi; }
+// The record words of a contribution: the variants' indexes at their positions (a position holds AGX_MAXV_HUGE variants at most)
+AGX_HD agx_u32 agx_reads_vars(const agx_sweep_args &A, agx_u32 X, agx_u32 xs, agx_u32 src, agx_u32 dst) { return ((src - A.node_start[X]) & 0xFFFFu) | ((dst - A.node_start[xs]) << 16); }
+// The selected contributions of one event (agx_support_event's arguments): put(src_pos, dst_pos, src_var | dst_var << 16) once per selected edge the event names.
+// false: an index outside the tables, or a contribution whose edge the node table does not hold or whose counter is 0.
+template <class PUT>
+AGX_HD bool agx_reads_event(const agx_sweep_args &A, const agx_reads_tab &T, agx_u32 X, const agx_arrival &a, bool single_ok, PUT put) {
+    bool ok = true;
+    const bool ran = agx_support_event(A, X, a, single_ok, [&](agx_u32 src, agx_u32 dst) {
+        bool found; const agx_u32 c = agx_reads_counter(T, src, dst, &found);
+        if (!found || !c) { ok = false; return; }
+        if (agx_reads_selected(T, c)) put(X, a.xs, agx_reads_vars(A, X, a.xs, src, dst));
+    });
+    return ran && ok;
+}
+// One (hit record, X), as agx_support_lane: 1 if it is an event of the window, else 0.
+template <class PUT>
+AGX_HD agx_u32 agx_reads_lane(const agx_sweep_args &A, const agx_reads_tab &T, agx_u32 X, const agx_dhit &d, bool single_ok, bool *bad, PUT put) {
+    if (X >= A.n_pos || !agx_reads_in_window(T, X)) return 0;
+    const agx_arrival a = agx_decode_arrival(d, A.runs, X, A.k);
+    if (!a.has || !a.has_succ || a.xs >= A.n_pos) return 0;
+    if (!agx_reads_event(A, T, X, a, single_ok, put)) *bad = true;
+    return 1;
+}
+
 // ---- evidence under the walk's records ---------------------------------------------------------------------
 // The stretch table of agx_walk_paths in the form the device reads (one entry per stretch, in the table's order; the host has checked it): first walk id, first base offset,
 // record, the flat index of the first base (st_pre: the exclusive prefix of the stretch lengths, entry n_st = n_flat = all graph bases) and the joined flag (entry n_st: 0);

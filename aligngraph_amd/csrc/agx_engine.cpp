@@ -1054,6 +1054,17 @@ size_t evidence_layout(size_t n_st, size_t n_recs, size_t chunk, bool tracks, ch
     if (base) { E.noedge = w + 1; E.err = w; if (words) *words = w; }
     return take.bytes();
 }
+// The scratch of the edge reads (agx_unit_edge_reads, agx_k_edge_reads), from the front of the same buffer: what one CHUNK of `tiles` tiles takes — the count per position
+// with its scan (a closing entry each) and the scan's block sums — and behind it `recs` records of 16 bytes.  recs = 0: what must fit before any record does.
+size_t edge_reads_layout(size_t tiles, size_t recs, char *base, agx_reads_kargs *K, agx_u32 **words) {
+    Carve take{base};
+    agx_reads_kargs T{}; agx_reads_kargs &R = K ? *K : T; agx_u32 *w = nullptr;
+    const size_t n = tiles * AGX_TILE;
+    take(w, 8); take(R.cnt, n + 1); take(R.off, n + 1); take(R.scan_tmp, scan_words(n + 1, 1024) + 16);
+    take(R.recs, 4 * recs);
+    if (base) { R.err = w; if (words) *words = w; }
+    return take.bytes();
+}
 inline bool keeps_paths(const agx_unit *u) { return (u->prm.flags & (AGX_FLAG_KEEP_PATHS | AGX_FLAG_KEEP_COUNTS)) == (AGX_FLAG_KEEP_PATHS | AGX_FLAG_KEEP_COUNTS); }
 // The export buffer of a unit that keeps paths: every export of such a unit takes the same size — the larger of the two export layouts at their worst, and behind it (at `map_at`)
 // the id map's scratch for a whole-window map — so that exports of any kind in any order never take the buffer twice.
@@ -2614,6 +2625,139 @@ int agx_unit_edge_support(agx_unit *u, agx_edge_support *s) {
 void agx_edge_support_free(agx_edge_support *s) {
     if (!s) return;
     free(s->edge_start); free(s->edge_dst); free(s->edge_cnt); memset(s, 0, sizeof *s);
+}
+
+// Edge reads: the hits behind the selected edges of a window.  Per chunk of the window's tiles two host round trips — the count pass and its scan (the total
+// comes back), the emit pass (the records come back) —, then one more for the whole call: the counters of the listed edges (agx_k_edge_reads_support), which are the table's
+// `support` and must equal the number of hits each edge lists.  The scratch is the export's buffer; what does not fit goes through in smaller chunks.
+static void edge_reads(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t max_support, agx_edge_reads *r) {
+    const double t0 = now_ms();
+    support_check(u);
+    if (!(u->prm.flags & AGX_FLAG_KEEP_COUNTS)) throw Error{E_ARG, "edge reads: the unit was created without AGX_FLAG_KEEP_COUNTS (the scratch is the export's buffer, which only such units reserve)"};
+    if (pos_lo > pos_hi || pos_hi > (agx_u32)u->V.n_pos)
+        throw Error{E_ARG, "edge reads: window [" + std::to_string(pos_lo) + ", " + std::to_string(pos_hi) + ") is not within the unit's positions [0, " + std::to_string((agx_u32)u->V.n_pos) + ")"};
+    struct Rec { agx_u32 sp, dp, vars, hit; };
+    static_assert(sizeof(Rec) == 16, "a record is four words");
+    std::vector<Rec> recs;
+    std::vector<agx_u32> sup;
+    unsigned n_chunks = 0;
+    Export E(u);
+    const agx_u32 n_pos = E.n_pos, cap = E.cap, n_ovf = E.n_ovf;
+    if (pos_lo < pos_hi && cap && u->n_nodes && u->n_tiles) {
+        E.open(unitig_layout(cap, n_pos, n_ovf, nullptr, nullptr, nullptr));      // (the buffer every export of the unit takes: the room the upload reserved)
+        ensure_support(E);
+        const size_t avail = u->d_ut.n;
+        const agx_u32 t_lo = pos_lo / AGX_TILE, t_hi = std::min<agx_u32>((pos_hi + AGX_TILE - 1) / AGX_TILE, u->n_tiles);
+        auto fixed = [](size_t tiles) { return edge_reads_layout(tiles, 0, nullptr, nullptr, nullptr) + 16; };
+        size_t chunk = t_hi - t_lo;
+        if (const char *env = getenv("AGX_EDGE_READS_CHUNK")) { const long long v = atoll(env); if (v > 0) chunk = std::min<size_t>((size_t)v, chunk); }
+        chunk = std::min<size_t>(chunk, (0xFFFFFF00u / AGX_TILE));
+        while (chunk > 1 && fixed(chunk) > avail) chunk = (chunk + 1) / 2;
+        if (fixed(chunk) > avail) throw Error{E_UNSUPPORTED, "edge reads: the export's scratch of " + std::to_string(avail) + " bytes does not hold the counts of one tile"};
+        // A chunk's total is a 32-bit scan.  A selection is a part of all contributions, so it cannot wrap while those number less than 2^32; a unit with more has its
+        // chunks cut where the per-tile totals of the counting pass (still in d_sup_tot) say a chunk could reach 2^32.
+        std::vector<agx_u32> tile_adds;
+        if (u->sup_adds >= 0xFFFFFFFFull) { tile_adds.resize(u->n_tiles); E.read(tile_adds.data(), u->d_sup_tot.p + u->n_tiles, (size_t)u->n_tiles * 4); E.sync(); }
+        agx_reads_kargs K{}; fill_sweep_args(u, K.S);
+        agx_reads_tab &T = K.T;
+        T.n_next = u->d_next.p; T.n_flags = u->d_flags.p; T.ovf = u->d_ovf.p; T.n_ovf = n_ovf; T.e_cnt = u->d_e_cnt.p; T.ovf_cnt = u->d_ovf_cnt.p;
+        T.pos_lo = pos_lo; T.pos_hi = pos_hi; T.max_support = max_support;
+        K.perm = u->d_perm.p; K.n_hits = (agx_u32)u->nh; K.list_cap = u->list_cap; K.abort = u->d_words.p + W_STATUS;
+        auto failed = [](agx_u32 w) {
+            return Error{E_DEVICE, std::string("internal: edge reads: ") + ((w & 1u) ? "a contribution found no edge of the built graph" : "the emit pass disagrees with its count") + " (error word " + std::to_string(w) + ")"};
+        };
+        for (agx_u32 t = t_lo; t < t_hi;) {
+            size_t nt = std::min<size_t>(chunk, t_hi - t);
+            if (!tile_adds.empty()) {
+                uint64_t s = 0; size_t fit = 0;
+                while (fit < nt && s + tile_adds[t + fit] < 0xFFFFFFFFull) s += tile_adds[t + fit++];
+                nt = std::max<size_t>(fit, 1);
+            }
+            agx_u32 total = 0, w = 0; agx_u32 *words = nullptr; size_t n = 0;
+            for (;;) {      // the count pass, again over half the tiles while the records do not fit behind the counts
+                n = nt * AGX_TILE;
+                edge_reads_layout(nt, 0, u->d_ut.p, &K, &words);
+                K.tile_lo = t; K.n_tiles = (agx_u32)nt; K.emit = 0; K.rec_cap = 0;
+                E.fill(words, 0, 32); E.fill(K.cnt + n, 0, 4);
+                agx_launch_edge_reads(&K, E.s);
+                agx_launch_exclusive_scan(K.cnt, K.off, (agx_u32)n, K.scan_tmp, E.s);
+                E.read(&total, K.off + n, 4); E.read(&w, words, 4); E.sync();
+                HIP_OK(hipGetLastError());
+                if (w) throw failed(w);
+                if ((size_t)total <= (avail - fixed(nt)) / 16) break;
+                if (nt == 1) throw Error{E_UNSUPPORTED, "edge reads: the " + std::to_string(total) + " records of tile " + std::to_string(t) + " do not fit the export's scratch of " + std::to_string(avail) + " bytes"};
+                nt = (nt + 1) / 2; chunk = nt;
+            }
+            n_chunks++;
+            if (total) {
+                if ((uint64_t)recs.size() + total >= 0xFFFFFFFFull) throw Error{E_UNSUPPORTED, "edge reads: 2^32 listed hits or more"};
+                K.emit = 1; K.rec_cap = total;
+                agx_launch_edge_reads(&K, E.s);
+                const size_t at = recs.size();
+                recs.resize(at + total);
+                E.read(recs.data() + at, K.recs, (size_t)total * 16); E.read(&w, words, 4); E.sync();
+                HIP_OK(hipGetLastError());
+                if (w) throw failed(w);
+            }
+            t += (agx_u32)nt;
+        }
+        // canonical order: edges by (src_pos, src_var, dst_pos, dst_var).  The host only groups, stably: that an edge's hits ascend is the device's doing (a lane walks its
+        // list in order, the list is ranked by hit number) and is checked below, not made here
+        auto key = [](const Rec &a) { return std::make_tuple(a.sp, a.vars & 0xFFFFu, a.dp, a.vars >> 16); };
+        if (!std::is_sorted(recs.begin(), recs.end(), [&](const Rec &a, const Rec &b) { return key(a) < key(b); }))
+            std::stable_sort(recs.begin(), recs.end(), [&](const Rec &a, const Rec &b) { return key(a) < key(b); });
+        // the counters of the listed edges, in pieces the scratch holds: three words in and one out per edge
+        std::vector<agx_u32> e_sp, e_dp, e_vars;
+        for (size_t i = 0; i < recs.size(); i++)
+            if (!i || recs[i].sp != recs[i - 1].sp || recs[i].dp != recs[i - 1].dp || recs[i].vars != recs[i - 1].vars) { e_sp.push_back(recs[i].sp); e_dp.push_back(recs[i].dp); e_vars.push_back(recs[i].vars); }
+        const size_t ne = e_sp.size(), piece = std::max<size_t>((avail - 2048) / 16, 1);
+        sup.resize(ne);
+        for (size_t at = 0; at < ne; at += piece) {
+            const size_t m = std::min(piece, ne - at);
+            Carve take{u->d_ut.p};
+            agx_reads_sup_args S{}; S.T = T; S.node_start = u->d_node_start.p; S.node_cnt = u->d_node_cnt.p; S.n_pos = n_pos; S.pool_cap = cap; S.n = (agx_u32)m;
+            take(S.sp, m); take(S.dp, m); take(S.vars, m); take(S.sup, m);
+            HIP_OK(hipMemcpyAsync(S.sp, e_sp.data() + at, m * 4, hipMemcpyHostToDevice, E.s)); HIP_OK(hipMemcpyAsync(S.dp, e_dp.data() + at, m * 4, hipMemcpyHostToDevice, E.s));
+            HIP_OK(hipMemcpyAsync(S.vars, e_vars.data() + at, m * 4, hipMemcpyHostToDevice, E.s));
+            agx_launch_edge_reads_support(&S, E.s);
+            E.read(sup.data() + at, S.sup, m * 4); E.sync();
+            HIP_OK(hipGetLastError());
+        }
+    }
+    // the caller's table
+    const size_t nh = recs.size(), ne = sup.size();
+    auto mk = [](auto *&p, size_t n) { using T = std::remove_reference_t<decltype(*p)>; p = (T *)calloc(n + 1, sizeof(T)); if (!p) throw Error{E_ARG, "out of host memory"}; };
+    mk(r->src_pos, ne); mk(r->src_var, ne); mk(r->dst_pos, ne); mk(r->dst_var, ne); mk(r->support, ne); mk(r->hit_off, ne + 1); mk(r->hit, nh);
+    size_t e = 0;
+    for (size_t i = 0; i < nh; i++) {
+        const bool first = !i || recs[i].sp != recs[i - 1].sp || recs[i].dp != recs[i - 1].dp || recs[i].vars != recs[i - 1].vars;
+        if (first) { r->src_pos[e] = recs[i].sp; r->src_var[e] = recs[i].vars & 0xFFFFu; r->dst_pos[e] = recs[i].dp; r->dst_var[e] = recs[i].vars >> 16; r->support[e] = sup[e]; r->hit_off[e] = i; e++; }
+        else if (recs[i].hit <= recs[i - 1].hit)
+            throw Error{E_DEVICE, "internal: edge reads: the hits behind an edge do not ascend (hit " + std::to_string(recs[i].hit) + " behind hit " + std::to_string(recs[i - 1].hit) + ": listed twice, or emitted out of order)"};
+        r->hit[i] = recs[i].hit;
+    }
+    r->hit_off[ne] = nh; r->n_edges = (uint32_t)ne; r->n_hits = nh;
+    for (size_t i = 0; i < ne; i++)
+        if (r->hit_off[i + 1] - r->hit_off[i] != r->support[i])
+            throw Error{E_DEVICE, "internal: edge reads: the edge (" + std::to_string(r->src_pos[i]) + ", " + std::to_string(r->src_var[i]) + ") -> (" + std::to_string(r->dst_pos[i]) + ", " + std::to_string(r->dst_var[i]) +
+                                  ") lists " + std::to_string(r->hit_off[i + 1] - r->hit_off[i]) + " hits, its counter holds " + std::to_string(r->support[i])};
+    u->stats.ms_edge_reads = now_ms() - t0;
+    if (g_trace) fprintf(stderr, "[agx trace] unit %p edge reads [%u, %u) <= %u: %u chunks, %zu records of 16 bytes, %zu edges\n", (void *)u, pos_lo, pos_hi, max_support, n_chunks, nh, ne);
+    trace(u, "edge_reads", t0, u->V.n_pos);
+}
+
+int agx_unit_edge_reads(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t max_support, agx_edge_reads *r) {
+    if (!u || !r) return AGX_E_ARG;
+    memset(r, 0, sizeof *r);
+    const int rc = guarded(u, [&] { edge_reads(u, pos_lo, pos_hi, max_support, r); });
+    if (rc != AGX_OK) agx_edge_reads_free(r);
+    return rc;
+}
+
+void agx_edge_reads_free(agx_edge_reads *r) {
+    if (!r) return;
+    free(r->src_pos); free(r->src_var); free(r->dst_pos); free(r->dst_var); free(r->support); free(r->hit_off); free(r->hit);
+    memset(r, 0, sizeof *r);
 }
 
 int agx_unit_walk_paths(agx_unit *u, agx_walk_paths *w) {

@@ -241,4 +241,33 @@ int agx_walk_evidence_bed(const agx_walk_evidence *e, int unit, char **text, siz
     }
 }
 
+// The edges of agx_unit_edge_reads with the hits behind them, one line per edge in the table's order:
+//   <unit>	<src_pos>	<src_var>	<dst_pos>	<dst_var>	<support>	<hit>,<hit>,...
+int agx_edge_reads_tsv(const agx_edge_reads *r, int unit, char **text, size_t *len) {
+    if (!r || !text || !len || unit < 0) return AGX_E_ARG;
+    *text = nullptr; *len = 0;
+    const uint32_t n = r->n_edges;
+    if (n && (!r->src_pos || !r->src_var || !r->dst_pos || !r->dst_var || !r->support || !r->hit_off)) return AGX_E_ARG;
+    if (r->n_hits && !r->hit) return AGX_E_ARG;
+    if (n && (r->hit_off[0] != 0 || r->hit_off[n] != r->n_hits)) return AGX_E_ARG;
+    for (uint32_t i = 0; i < n; i++) if (r->hit_off[i] > r->hit_off[i + 1] || r->hit_off[i + 1] > r->n_hits) return AGX_E_ARG;
+    try {
+        std::string o;
+        o.reserve((size_t)n * 48 + (size_t)r->n_hits * 8);
+        for (uint32_t i = 0; i < n; i++) {
+            put_u64(o, (uint64_t)unit); o += '\t'; put_u64(o, r->src_pos[i]); o += '\t'; put_u64(o, r->src_var[i]); o += '\t'; put_u64(o, r->dst_pos[i]); o += '\t';
+            put_u64(o, r->dst_var[i]); o += '\t'; put_u64(o, r->support[i]); o += '\t';
+            for (uint64_t h = r->hit_off[i]; h < r->hit_off[i + 1]; h++) { if (h != r->hit_off[i]) o += ','; put_u64(o, r->hit[h]); }
+            o += '\n';
+        }
+        char *out = (char *)malloc(o.size() + 1);
+        if (!out) return AGX_E_ARG;
+        memcpy(out, o.data(), o.size()); out[o.size()] = 0;
+        *text = out; *len = o.size();
+        return AGX_OK;
+    } catch (...) {
+        return AGX_E_ARG;
+    }
+}
+
 }  // extern "C"

@@ -57,6 +57,25 @@ struct agx_support_kargs {
     agx_u32 *unmatched;                // zeroed by the caller
     const agx_u32 *abort;              // the build's status word
 };
+// Edge reads (agx_k_edge_reads): the same pass over the tiles [tile_lo, tile_lo + n_tiles) of a CHUNK of the window, twice.  emit == 0: cnt[p] = the selected
+// contributions of chunk position p = (tile - tile_lo) * 64 + lane (written for all 64 lanes of every tile of the chunk).  emit != 0: off is the exclusive scan of cnt, and
+// the lane writes its contributions to recs[off[p] ..) as 16-byte records (src_pos, dst_pos, src_var | dst_var << 16, the hit's file number perm[place]); rec_cap: the total
+// the host read.  Reads the front, the node table and the counters; writes only cnt / recs and the error word: bit 0 a contribution without an edge, an index outside the
+// tables or a list entry without a hit; bit 1 the emit pass disagrees with the count.
+struct agx_reads_kargs {
+    agx_sweep_args S; agx_reads_tab T; const agx_u32 *perm; agx_u32 n_hits, list_cap;
+    agx_u32 tile_lo, n_tiles, emit;
+    agx_u32 *cnt, *off, *scan_tmp;     // [n_tiles * 64 + 1] each (the closing count is the host's zero), and the block sums of the multi-launch scan between the passes
+    agx_u32 *recs; agx_u32 rec_cap;    // four words per record, 16-byte aligned
+    agx_u32 *err;
+    const agx_u32 *abort;              // the build's status word
+};
+// The counters of the edges an edge-reads call listed (agx_k_edge_reads_support): edge i is (sp[i], vars[i] & 0xFFFF) -> (dp[i], vars[i] >> 16); sup[i] = its support
+// (agx_reads_counter), AGX_NONE where the node table holds no such edge or an index lies outside the tables.
+struct agx_reads_sup_args {
+    agx_reads_tab T; const agx_u32 *node_start; const agx_u16 *node_cnt; agx_u32 n_pos, pool_cap, n;
+    agx_u32 *sp, *dp, *vars, *sup;     // [n] each
+};
 // Unitig export (agx_unitig.hip): reads the node table a build left in HBM, writes only its own scratch.  Slot arrays are [pool_cap], piece arrays
 // [piece_cap], segment arrays [piece_cap + 1] (every unitig head is a piece start, so there are never more segments than pieces).
 struct agx_unitig_args {
@@ -204,6 +223,8 @@ void agx_launch_idmap_flags(const agx_unitig_region_args *, const agx_idmap_args
 void agx_launch_idmap_runs(const agx_unitig_region_args *, const agx_idmap_args *, hipStream_t);
 void agx_launch_node_sweep_huge(const agx_node_kargs *, hipStream_t);
 void agx_launch_edge_support(const agx_support_kargs *, hipStream_t);
+void agx_launch_edge_reads(const agx_reads_kargs *, hipStream_t);      // one pass (count or emit) over the chunk's tiles
+void agx_launch_edge_reads_support(const agx_reads_sup_args *, hipStream_t);
 // behind phase 3 of a region export: l_sup[i] = support of link i's edge, the last node of its source segment -> the head node of its target segment, overflow duplicates summed
 // (n_flags: the unit's, for AGX_NF_EOVF — only such tails walk the overflow list, once per link)
 void agx_launch_unitig_link_support(const agx_unitig_region_args *, const agx_u8 *n_flags, const agx_u32 *e_cnt, const agx_u32 *ovf_cnt, agx_u32 *l_sup, hipStream_t);

@@ -1023,6 +1023,81 @@ __global__ void __launch_bounds__(256) agx_k_edge_support(agx_support_kargs K) {
     const agx_u32 ev_incl = agx_wave_incl_scan(events, lane), add_incl = agx_wave_incl_scan(adds, lane);
     if (lane == 63u) { K.tile_events[tile] = ev_incl; K.tile_adds[tile] = add_incl; }
 }
+// ---- edge reads (agx_core.h): which hits name the selected edges of a window ---------------------------------------------------------------
+// agx_k_edge_support's loop with a store in place of an add, launched twice per chunk of the window's tiles: EMIT = false stores how many selected contributions each
+// position of the chunk makes, EMIT = true — behind the scan of those counts — writes one 16-byte record per contribution at the position's offset plus the lane's running
+// count.  A lane walks its tile's list in order and the list is ranked by hit number, so a position's records come out in ascending hit order whatever the schedule.
+// A single -> single lane reads the one counter its register path can name once, in front of the loop; everything else asks the counter of the slot or overflow entry
+// each contribution resolves to (agx_reads_event).  Every store is checked against the count the host read (rec_cap) and against the position's own count; a lane that
+// would write more, or ends with less, raises bit 1 of the error word and the host drops the answer.
+template <bool EMIT>
+__global__ void __launch_bounds__(256) agx_k_edge_reads(agx_reads_kargs K) {
+    AGX_RETURN_IF_ABORTED(K.abort);
+    const agx_u32 lane = threadIdx.x & 63u;
+    const agx_u32 ct = (agx_u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * AGX_WAVES_PER_BLOCK + (threadIdx.x >> 6)));      // the tile's number in the chunk
+    if (ct >= K.n_tiles || K.tile_lo + ct >= K.S.n_tiles) return;             // wave-uniform
+    const agx_u32 tile = K.tile_lo + ct, X = tile * AGX_TILE + lane, p = ct * AGX_TILE + lane;
+    const bool live = X < K.S.n_pos && agx_reads_in_window(K.T, X), has1 = live && X + 1 < K.S.n_pos;
+    agx_u32 hi = K.S.tile_off[tile + 1], lo = K.S.tile_off[tile];
+    hi = hi < K.list_cap ? hi : K.list_cap; lo = lo < hi ? lo : hi;
+    const agx_u32 own_n = live ? K.S.node_cnt[X] : 0u, own_s = live ? K.S.node_start[X] : 0u, nb_n = has1 ? K.S.node_cnt[X + 1] : 0u, nb_s = has1 ? K.S.node_start[X + 1] : 0u;
+    const bool single = own_n == 1u && nb_n == 1u && own_s < K.S.pool_cap && nb_s < K.S.pool_cap;
+    const bool ok1 = single && agx_edge_allowed(K.S, own_s, nb_s);
+    bool found1 = false;
+    const agx_u32 c1 = ok1 ? agx_reads_counter(K.T, own_s, nb_s, &found1) : 0u;      // the register path's one edge: decided here, once
+    const bool sel1 = ok1 && found1 && c1 != 0u && agx_reads_selected(K.T, c1);
+    const bool bad1 = ok1 && !(found1 && c1 != 0u);                           // (an error only if an event names it)
+    agx_u32 base = 0, mine = 0;
+    if (EMIT) { base = K.off[p]; mine = K.off[p + 1] - base; }
+    agx_u32 n = 0, bad = 0, file_no = 0;
+    uint4 *const recs = (uint4 *)K.recs;
+    auto put = [&](agx_u32 sp, agx_u32 dp, agx_u32 vars) {
+        if (EMIT) {
+            const agx_u32 at = base + n;
+            if (n < mine && at < K.rec_cap) recs[at] = make_uint4(sp, dp, vars, file_no); else bad |= 2u;
+        }
+        n++;
+    };
+    const agx_tile_recs trecs{K.S.tile_recs, K.S.dhit};
+    for (agx_u32 i = lo; i < hi; i++) {                                       // wave-uniform trip count
+        const agx_lrec r = trecs.lean(i);
+        if (r.hit >= K.n_hits) { bad |= lane == 0u ? 1u : 0u; continue; }     // wave-uniform
+        const agx_larr la = agx_lean_decode(r, lane);
+        const bool lean_event = live && la.has && !la.last;
+        const bool reg = lean_event && !la.jump && single;
+        const bool need = (r.geo >> 30) == (agx_u32)AGX_LK_GENERAL ? live : (lean_event && !reg);
+        if (__ballot(reg || need) == 0ull) continue;                          // wave-uniform: no lane of the window has an event here
+        file_no = K.perm[r.hit];                                              // (wave-uniform: a scalar load)
+        if (reg && ok1) { bad |= bad1 ? 1u : 0u; if (sel1) put(X, X + 1u, 0u); }
+        if (__ballot(need) == 0ull) continue;
+        const agx_dhit d = trecs.of_hit(r.hit);
+        if (need) {
+            const agx_arrival a = agx_decode_arrival(d, K.S.runs, X, K.S.k);
+            if (a.has && a.has_succ && a.xs < K.S.n_pos) {
+                if (single && a.xs == X + 1) { if (ok1) { bad |= bad1 ? 1u : 0u; if (sel1) put(X, X + 1u, 0u); } }
+                else bad |= agx_reads_event(K.S, K.T, X, a, true, put) ? 0u : 1u;
+            }
+        }
+    }
+    if (EMIT) { if (n != mine) bad |= 2u; }
+    else K.cnt[p] = n;
+    if (bad) atomicOr(K.err, bad);
+}
+// the counter of every listed edge (a thread per edge; every index is checked against the table it goes into)
+__global__ void __launch_bounds__(256) agx_k_edge_reads_support(agx_reads_sup_args A) {
+    const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= A.n) return;
+    const agx_u32 sp = A.sp[i], dp = A.dp[i], sv = A.vars[i] & 0xFFFFu, dv = A.vars[i] >> 16;
+    agx_u32 out = AGX_NONE;
+    if (sp < A.n_pos && dp < A.n_pos && sv < A.node_cnt[sp] && dv < A.node_cnt[dp]) {
+        const agx_u32 s0 = A.node_start[sp], d0 = A.node_start[dp];
+        if (s0 < A.pool_cap && sv < A.pool_cap - s0 && d0 < A.pool_cap && dv < A.pool_cap - d0) {
+            bool found; const agx_u32 c = agx_reads_counter(A.T, s0 + sv, d0 + dv, &found);
+            out = found ? c : AGX_NONE;
+        }
+    }
+    A.sup[i] = out;
+}
 // the special-id bitmap and its popcounts (input of the rank scan).  A wavefront takes four 64-id words — every lane one id of each, so that their loads
 // are in flight together — and writes nothing for words past the live ids: sp_bits / sp_cnt are zeroed at the start of the build (the grid covers the id
 // CAPACITY, 2.4 x the live ids of a first build: r02 spent 0.42 ms here on a 30 Mb unit, most of it rounds of threads that only found out they were idle)
@@ -1276,6 +1351,14 @@ void agx_launch_fetch_records(const agx_compact_args *A, agx_u32 first, agx_u32 
 }
 void agx_launch_edge_support(const agx_support_kargs *K, hipStream_t st) {
     if (K->S.n_tiles) hipLaunchKernelGGL(agx_k_edge_support, dim3((K->S.n_tiles + AGX_WAVES_PER_BLOCK - 1) / AGX_WAVES_PER_BLOCK), dim3(64 * AGX_WAVES_PER_BLOCK), 0, st, *K);
+}
+void agx_launch_edge_reads_support(const agx_reads_sup_args *A, hipStream_t st) {
+    if (A->n) hipLaunchKernelGGL(agx_k_edge_reads_support, dim3((A->n + 255u) / 256u), dim3(256), 0, st, *A);
+}
+void agx_launch_edge_reads(const agx_reads_kargs *K, hipStream_t st) {
+    if (!K->n_tiles) return;
+    const dim3 grid((K->n_tiles + AGX_WAVES_PER_BLOCK - 1) / AGX_WAVES_PER_BLOCK), block(64 * AGX_WAVES_PER_BLOCK);
+    if (K->emit) hipLaunchKernelGGL(agx_k_edge_reads<true>, grid, block, 0, st, *K); else hipLaunchKernelGGL(agx_k_edge_reads<false>, grid, block, 0, st, *K);
 }
 void agx_launch_reprune(const agx_reprune_args *A, agx_u32 n_tiles, hipStream_t st) {
     if (n_tiles) hipLaunchKernelGGL(agx_k_reprune, dim3((n_tiles + 3u) / 4u), dim3(256), 0, st, *A, n_tiles);

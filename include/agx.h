@@ -134,6 +134,7 @@ typedef struct {
                                                                     the counting kernel and the wait for its totals on the first call after a build, next to nothing on later ones */
     uint64_t n_support_events;                                   /* events the counting saw (agx_edge_support::n_events); 0 before the first counting call after a build */
     double ms_walk_evidence;                                     /* host wall time of the last agx_unit_walk_evidence, from entry to its tables being in the caller's memory */
+    double ms_edge_reads;                                        /* host wall time of the last agx_unit_edge_reads, from entry to its table being in the caller's memory; 0 before the first call */
 } agx_stats;
 
 /* Node/edge tables in canonical numbering (position-major, variant order), for parity tests. malloc'd; free with agx_graph_free. */
@@ -170,6 +171,19 @@ typedef struct {
  * the coverage threshold.  n_events: the events; n_contributions: the sum of edge_cnt.  malloc'd; free with agx_edge_support_free. */
 typedef struct { uint32_t n_nodes, n_edges; uint64_t n_events, n_contributions;
                  uint32_t *edge_start, *edge_dst, *edge_cnt; } agx_edge_support;
+
+/* Edge reads: the hits behind the edges of a window.  Events, named edges and support are agx_edge_support's.  An edge (s, d) is SELECTED iff the position of
+ * s lies in [pos_lo, pos_hi) and its support is <= max_support (0xFFFFFFFF: every edge whose source lies in the window; 0: none, every edge has support >= 1); the position of d
+ * may lie outside the window.  The table holds every selected edge — as (src_pos, src_var) -> (dst_pos, dst_var), var the index among ALL of the position's variants, agx_unitigs'
+ * head_var — ordered by (src_pos, src_var, dst_pos, dst_var), and for edge e its support and, in hit[hit_off[e] .. hit_off[e + 1]), the HIT NUMBER of every event that names it,
+ * ascending.  A hit number is the hit's place in the order the hits were handed over: the i-th agx_hit of all agx_unit_push_pairs batches, counted from 0 — for the file
+ * loaders the i-th (pair, hit) of tmp/_reads_genome.<u>.bowtie that passed the identity filter —, which is the index into agx_front's dhit in file order (perm[]).  One hit
+ * names an edge in one event at most (a hit has one arrival per position, and an edge's source is one position), so the numbers of an edge are distinct and
+ * hit_off[e + 1] - hit_off[e] == support[e].  The table does not depend on the coverage threshold or on a reprune.  malloc'd; free with agx_edge_reads_free. */
+typedef struct { uint32_t n_edges; uint64_t n_hits;
+                 uint32_t *src_pos, *src_var, *dst_pos, *dst_var, *support;   /* [n_edges] */
+                 uint64_t *hit_off;                                           /* [n_edges + 1] */
+                 uint32_t *hit; } agx_edge_reads;                             /* [n_hits] */
 
 /* The id map of an export (agx_unit_unitigs_mapped): which walk ids have their node in the export, and where.  Runs are sorted by id_first; walk id a lies in run r iff
  * id_first[r] <= a <= id_last[r], and its node is then node number rank_first[r] + (a - id_first[r]) of segment seg[r].  Runs are maximal (no two neighbours could be merged)
@@ -383,6 +397,18 @@ void agx_edge_support_free(agx_edge_support *s);
  * free it with agx_link_support_free (never NULL after AGX_OK, also without links). */
 int agx_unit_unitigs_support(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, uint32_t **link_support, agx_idmap *m);
 void agx_link_support_free(uint32_t *link_support);
+/* The hits behind the selected edges of a window (agx_edge_reads above).  Preconditions of agx_unit_edge_support (built; not downloaded, trimmed or released; not
+ * AGX_FLAG_ONE_SHOT; AGX_FLAG_EDGE_SUPPORT) and AGX_FLAG_KEEP_COUNTS as well (the scratch is the export's, which only such units reserve): AGX_E_ARG with the reason otherwise;
+ * pos_lo > pos_hi or pos_hi > the unit's positions: AGX_E_ARG; pos_lo == pos_hi gives an empty table.  A refused call leaves the unit as it was.  The counters are made first
+ * if need be (agx_unit_edge_support's first call).  Runs on the device over the tiles of the window only, in chunks of tiles: a count pass, a scan and an emit pass per chunk
+ * out of the export's scratch (no allocation; the chunk is halved until its records fit, AGX_EDGE_READS_CHUNK=<tiles> forces a size; a single tile whose records do not fit,
+ * and 2^32 listed hits or more, are AGX_E_UNSUPPORTED).  A contribution without an edge, or an emit pass that disagrees with its count, is AGX_E_DEVICE ("internal:").
+ * Writes nothing a walk or an export reads. */
+int  agx_unit_edge_reads(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t max_support, agx_edge_reads *r);
+void agx_edge_reads_free(agx_edge_reads *r);
+/* Host only: one line per edge, <unit> <tab> src_pos <tab> src_var <tab> dst_pos <tab> dst_var <tab> support <tab> hit,hit,... (no header line; an edge without hits ends in
+ * an empty field); *text is malloc'd, free it with agx_text_free. */
+int  agx_edge_reads_tsv(const agx_edge_reads *r, int unit, char **text, size_t *len);
 /* The stretches the last agx_unit_finish kept (AGX_FLAG_KEEP_PATHS).  Valid after a finish, also of trimmed and one-shot units, until the next finish, upload, reprune or release;
  * AGX_E_ARG without the flag or before a finish.  The caller gets copies. */
 int agx_unit_walk_paths(agx_unit *u, agx_walk_paths *w);
