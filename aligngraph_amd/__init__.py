@@ -31,6 +31,7 @@ EXPORTS = [
     "agx_unit_edge_support", "agx_edge_support_free", "agx_unit_unitigs_support", "agx_link_support_free", "agx_unitigs_gfa_support",
     "agx_unit_walk_evidence", "agx_walk_evidence_free", "agx_walk_evidence_bed",
     "agx_unit_edge_reads", "agx_edge_reads_free", "agx_edge_reads_tsv",
+    "agx_unit_pair_span", "agx_pair_span_free", "agx_unit_walk_span", "agx_walk_span_free", "agx_walk_span_bed",
     "agx_test_scan", "agx_test_zero", "agx_test_copy_out",
 ]
 
@@ -77,7 +78,8 @@ class Stats(ctypes.Structure):
                [(n, ctypes.c_uint64) for n in ("upload_bytes", "device_bytes", "pinned_bytes_cached", "device_bytes_cached", "n_spilled")] + \
                [("build_attempts", ctypes.c_uint32), ("from_cache", ctypes.c_uint32), ("dense_lists", ctypes.c_uint32), ("rows_by_reference", ctypes.c_uint32)] + \
                [("n_edge_slow", ctypes.c_uint64), ("reprune_attempts", ctypes.c_uint32), ("ms_reprune", ctypes.c_double)] + \
-               [("ms_edge_support", ctypes.c_double), ("n_support_events", ctypes.c_uint64), ("ms_walk_evidence", ctypes.c_double), ("ms_edge_reads", ctypes.c_double)]
+               [("ms_edge_support", ctypes.c_double), ("n_support_events", ctypes.c_uint64), ("ms_walk_evidence", ctypes.c_double), ("ms_edge_reads", ctypes.c_double)] + \
+               [("ms_pair_span", ctypes.c_double), ("ms_walk_span", ctypes.c_double)]
 
 
 class Graph(ctypes.Structure):
@@ -127,6 +129,22 @@ class WalkEvidence(ctypes.Structure):
                [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("depth", "votes", "step")]
 
 
+class PairSpan(ctypes.Structure):
+    _fields_ = [("pos_lo", ctypes.c_uint32), ("pos_hi", ctypes.c_uint32), ("n_kept", ctypes.c_uint64), ("n_fragments", ctypes.c_uint64), ("n_outside", ctypes.c_uint64),
+                ("span", ctypes.POINTER(ctypes.c_uint32)), ("cross", ctypes.POINTER(ctypes.c_uint32))]
+
+
+class WalkSpan(ctypes.Structure):
+    _fields_ = [("n_recs", ctypes.c_uint32), ("n_intervals", ctypes.c_uint32)] + [(n, ctypes.c_uint64) for n in ("n_graph_bases", "n_steps", "n_jump_steps", "n_steps_not_forward")] + \
+               [(n, ctypes.POINTER(ctypes.c_uint64)) for n in ("rec_graph_bases", "rec_steps", "rec_span_sum")] + \
+               [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("rec_span_min", "rec_span_min_at", "rec_step_min", "rec_step_min_at",
+                                                               "iv_rec", "iv_first", "iv_last", "iv_span_min", "iv_step_min")] + \
+               [("rec_lo", ctypes.c_uint32), ("rec_hi", ctypes.c_uint32), ("n_track", ctypes.c_uint64), ("track_off", ctypes.POINTER(ctypes.c_uint64))] + \
+               [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("pos", "span", "step")]
+
+
+REC_SPAN = ("rec_graph_bases", "rec_steps", "rec_span_sum", "rec_span_min", "rec_span_min_at", "rec_step_min", "rec_step_min_at")
+IV_SPAN = ("iv_rec", "iv_first", "iv_last", "iv_span_min", "iv_step_min")
 REC_EVIDENCE = ("rec_graph_bases", "rec_steps", "rec_depth_sum", "rec_depth_min", "rec_depth_min_at", "rec_step_min", "rec_step_min_at")
 IV_EVIDENCE = ("iv_rec", "iv_first", "iv_last", "iv_depth_min", "iv_step_min")
 
@@ -276,6 +294,13 @@ def lib():
         L.agx_walk_evidence_free.argtypes = [ctypes.POINTER(WalkEvidence)]
         L.agx_walk_evidence_free.restype = None
         L.agx_walk_evidence_bed.argtypes = [ctypes.POINTER(WalkEvidence), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+        L.agx_unit_pair_span.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(PairSpan)]
+        L.agx_pair_span_free.argtypes = [ctypes.POINTER(PairSpan)]
+        L.agx_pair_span_free.restype = None
+        L.agx_unit_walk_span.argtypes = [ctypes.c_void_p, ctypes.POINTER(WalkPaths)] + [ctypes.c_uint32] * 4 + [ctypes.POINTER(WalkSpan)]
+        L.agx_walk_span_free.argtypes = [ctypes.POINTER(WalkSpan)]
+        L.agx_walk_span_free.restype = None
+        L.agx_walk_span_bed.argtypes = [ctypes.POINTER(WalkSpan), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         L.agx_text_free.restype = None
         L.agx_unit_edge_reads.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EdgeReads)]
         L.agx_edge_reads_free.argtypes = [ctypes.POINTER(EdgeReads)]
@@ -650,6 +675,58 @@ class Unit:
         finally:
             lib().agx_walk_evidence_free(ctypes.byref(e))
 
+    def pair_span(self, region=None):
+        """The read pairs across each position (agx_unit_pair_span; needs keep_counts, before download(), trim() and release()): for region = (lo, hi) (None: every
+        position) span[x - lo], the fragments of kept hits that cover position x, and cross[x - lo], those that cover x and x + 1; n_kept, n_outside (the unit's kept
+        hits, and those of them that lie beyond its positions) and n_fragments (the fragments that meet the region); pos_lo, pos_hi."""
+        import numpy as np
+        lo, hi = region if region is not None else (0, self.stats()["n_pos"])
+        for v in (lo, hi):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise AgxError(AGX_E_ARG, "pair span: region bounds are unsigned 32-bit numbers")
+        s = PairSpan()
+        self._check(lib().agx_unit_pair_span(self._h, int(lo), int(hi), ctypes.byref(s)))
+        try:
+            n = s.pos_hi - s.pos_lo
+            def arr(p):
+                return np.ctypeslib.as_array(p, shape=(n,)).astype("uint32", copy=True) if n else np.zeros(0, "uint32")
+            return {"pos_lo": s.pos_lo, "pos_hi": s.pos_hi, "n_kept": s.n_kept, "n_fragments": s.n_fragments, "n_outside": s.n_outside, "span": arr(s.span), "cross": arr(s.cross)}
+        finally:
+            lib().agx_pair_span_free(ctypes.byref(s))
+
+    def walk_span(self, w=None, min_span=0, tracks=False, records=None):
+        """The pair span under the records of a stretch table (agx_unit_walk_span; needs keep_counts): w is a dict like walk_paths() returns (None: walk_paths() itself).
+        Per record rec_graph_bases, rec_steps, rec_span_sum, rec_span_min / _at, rec_step_min / _at; the thin intervals at min_span iv_rec, iv_first, iv_last,
+        iv_span_min, iv_step_min; the totals n_graph_bases, n_steps, n_jump_steps, n_steps_not_forward.  0xFFFFFFFF: no number.  tracks=True: also pos, span and step per
+        graph base of the records `records` = (lo, hi) (None: all) with track_off per stretch of those records, and rec_lo, rec_hi."""
+        import numpy as np
+        if w is None:
+            w = self.walk_paths()
+        ws, _keep = _walk_paths_struct(w)
+        lo, hi = (0, ws.n_recs) if records is None else records
+        for v in (min_span, lo, hi):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise AgxError(AGX_E_ARG, "walk span: the threshold and record bounds are unsigned 32-bit numbers")
+        e = WalkSpan()
+        self._check(lib().agx_unit_walk_span(self._h, ctypes.byref(ws), int(min_span), 1 if tracks else 0, int(lo), int(hi), ctypes.byref(e)))
+        try:
+            def arr(p, n, dt):
+                return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
+            out = {"n_graph_bases": e.n_graph_bases, "n_steps": e.n_steps, "n_jump_steps": e.n_jump_steps, "n_steps_not_forward": e.n_steps_not_forward}
+            for k in REC_SPAN:
+                out[k] = arr(getattr(e, k), e.n_recs, "uint64" if k in REC_SPAN[:3] else "uint32")
+            for k in IV_SPAN:
+                out[k] = arr(getattr(e, k), e.n_intervals, "uint32")
+            if tracks:
+                st = np.asarray(w["st_off"]).astype(np.int64)
+                n_st = int(st[hi] - st[lo]) if len(st) else 0
+                out.update(rec_lo=e.rec_lo, rec_hi=e.rec_hi, track_off=arr(e.track_off, n_st + 1, "uint64"))
+                for k in ("pos", "span", "step"):
+                    out[k] = arr(getattr(e, k), e.n_track, "uint32")
+            return out
+        finally:
+            lib().agx_walk_span_free(ctypes.byref(e))
+
     def gfa(self, unit=0, region=None, min_coverage=None, edge_support=False):
         """GFA 1.0 S and L lines of the unit's unitigs, segments named u<unit>_<pos>_<var> (no header line); region and min_coverage as in unitigs().
         edge_support=True: every L line also carries RC:i:<events that name the link's edge> (agx_unitigs_gfa_support)."""
@@ -763,6 +840,24 @@ def edge_reads_tsv(r, unit=0):
     rc = lib().agx_edge_reads_tsv(ctypes.byref(s), unit, ctypes.byref(p), ctypes.byref(n))
     if rc != AGX_OK:
         raise AgxError(rc, "agx_edge_reads_tsv: the table is inconsistent")
+    try:
+        return ctypes.string_at(p, n.value) if n.value else b""
+    finally:
+        lib().agx_text_free(p)
+
+
+def span_bed(e, unit=0):
+    """BED text of the thin intervals of a dict like Unit.walk_span() returns (agx_walk_span_bed; host only, needs no device)."""
+    import numpy as np
+    keep = {k: np.ascontiguousarray(e[k], dtype="uint32") for k in IV_SPAN}
+    s = WalkSpan()
+    s.n_recs, s.n_intervals = len(e["rec_graph_bases"]), len(keep["iv_rec"])
+    for k, a in keep.items():
+        setattr(s, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
+    rc = lib().agx_walk_span_bed(ctypes.byref(s), unit, ctypes.byref(p), ctypes.byref(n))
+    if rc != AGX_OK:
+        raise AgxError(rc, "agx_walk_span_bed: the interval table is inconsistent")
     try:
         return ctypes.string_at(p, n.value) if n.value else b""
     finally:

@@ -1422,6 +1422,74 @@ AGX_HD bool agx_evidence_weak(agx_u32 depth, agx_u32 step, agx_u32 min_depth, ag
     return depth == AGX_NONE || depth < min_depth || (step != AGX_NONE && step < min_support);
 }
 
+// ---- pair span: the read pairs across each position (agx_unit_pair_span) -----------------------------------------
+// The FRAGMENT of a kept hit (AGX_HF_SKIP clear) runs from the smallest to the largest reference position either mate is aligned to, whichever mate lies left: a simple
+// mate (run count 0) covers [t0, t0 + len - 1], a mate with runs the union of [t, t + n - 1] over its runs (a run of no bases covers nothing; a_runs / b_runs are not run
+// indexes where both counts are 0 and are not read then).  The upper end is clamped to n_pos - 1.  A run index is held against n_runs before the run is read.
+enum { AGX_SPAN_SKIPPED = 0, AGX_SPAN_FRAGMENT = 1, AGX_SPAN_OUTSIDE = 2 };      // not a kept hit; a fragment [*lo, *hi]; a kept hit that begins at or behind n_pos (or covers nothing)
+AGX_HD void agx_span_mate(agx_u32 t0, agx_u32 first_run, agx_u32 n_mate_runs, agx_u32 len, const agx_run *runs, agx_u32 n_runs, unsigned long long &lo, unsigned long long &hi) {
+    if (n_mate_runs == 0) {
+        if (len) { const unsigned long long a = t0, b = (unsigned long long)t0 + len - 1u; lo = a < lo ? a : lo; hi = b > hi ? b : hi; }
+        return;
+    }
+    for (agx_u32 i = 0; i < n_mate_runs; i++) {
+        const unsigned long long at = (unsigned long long)first_run + i;
+        if (at >= n_runs) break;
+        const agx_run r = runs[at];
+        if (!r.n) continue;
+        const unsigned long long a = r.t, b = (unsigned long long)r.t + r.n - 1u;
+        lo = a < lo ? a : lo; hi = b > hi ? b : hi;
+    }
+}
+// the record's fields one by one (the kernel reads a record as five 8-byte words and never holds it as a struct, as agx_k_tile_fill does)
+AGX_HD int agx_span_fragment_v(agx_u32 a_t0, agx_u32 b_t0, agx_u32 a_runs, agx_u32 b_runs, agx_u32 len, agx_u32 a_nruns, agx_u32 b_nruns, agx_u32 flags,
+                               const agx_run *runs, agx_u32 n_runs, agx_u32 n_pos, agx_u32 *f_lo, agx_u32 *f_hi) {
+    *f_lo = AGX_NONE; *f_hi = 0;
+    if (flags & AGX_HF_SKIP) return AGX_SPAN_SKIPPED;
+    unsigned long long lo = ~0ull, hi = 0;
+    agx_span_mate(a_t0, a_runs, a_nruns, len, runs, n_runs, lo, hi);
+    agx_span_mate(b_t0, b_runs, b_nruns, len, runs, n_runs, lo, hi);
+    if (lo >= n_pos) return AGX_SPAN_OUTSIDE;      // (also: neither mate covers a position, lo is still all ones)
+    *f_lo = (agx_u32)lo; *f_hi = hi < n_pos ? (agx_u32)hi : n_pos - 1u;
+    return AGX_SPAN_FRAGMENT;
+}
+AGX_HD int agx_span_fragment(const agx_dhit &d, const agx_run *runs, agx_u32 n_runs, agx_u32 n_pos, agx_u32 *f_lo, agx_u32 *f_hi) {
+    return agx_span_fragment_v(d.a_t0, d.b_t0, d.a_runs, d.b_runs, d.len, d.a_nruns, d.b_nruns, d.flags, runs, n_runs, n_pos, f_lo, f_hi);
+}
+// The window clamp: does fragment [f_lo, f_hi] meet the window [lo, hi), and if so which entry of `start` it adds to (its first position, or the window's if it begins in
+// front of it) and — *has_end — which entry of `end` (its last position, if that lies inside the window).  Both entries are below hi - lo.
+AGX_HD bool agx_span_clamp(agx_u32 f_lo, agx_u32 f_hi, agx_u32 lo, agx_u32 hi, agx_u32 *at_start, agx_u32 *at_end, bool *has_end) {
+    *at_start = 0; *at_end = 0; *has_end = false;
+    if (lo >= hi || f_lo > f_hi || f_lo >= hi || f_hi < lo) return false;
+    *at_start = (f_lo > lo ? f_lo : lo) - lo;
+    if (f_hi < hi) { *has_end = true; *at_end = f_hi - lo; }
+    return true;
+}
+// The position of a walk id: a main id is its position, a side id has it in side_xpos.  NONE: the id is no walk id of the unit, or side_xpos names no position.
+AGX_HD agx_u32 agx_span_pos(agx_u32 id, agx_u32 n_pos, agx_u32 n_ids, const agx_u32 *side_xpos) {
+    if (id < n_pos) return id;
+    if (id >= n_ids) return AGX_NONE;
+    const agx_u32 x = side_xpos[id - n_pos];
+    return x < n_pos ? x : AGX_NONE;
+}
+// A step from position x to position y: next to each other (the number is cross[x]), a jump (the number is pairs(x, y), counted over the hits), or not forward (no number)
+enum { AGX_SPAN_STEP_NEXT = 0, AGX_SPAN_STEP_JUMP = 1, AGX_SPAN_STEP_BACK = 2 };
+AGX_HD int agx_span_step_kind(agx_u32 x, agx_u32 y) {
+    if (x == AGX_NONE || y == AGX_NONE || y <= x) return AGX_SPAN_STEP_BACK;
+    return y == x + 1u ? AGX_SPAN_STEP_NEXT : AGX_SPAN_STEP_JUMP;
+}
+// One fragment [f_lo, f_hi] against the jump entries (e_x, e_y)[n_ent], sorted by (x, y): add(entry) for every entry with f_lo <= x and y <= f_hi.  The first entry with
+// x >= f_lo by bisection (32 halvings at most), then on while x < f_hi — an entry has y > x, so none behind that can lie inside the fragment; the walk ends at n_ent at the latest.
+template <class ADD>
+AGX_HD void agx_span_jump_walk(const agx_u32 *e_x, const agx_u32 *e_y, agx_u32 n_ent, agx_u32 f_lo, agx_u32 f_hi, ADD add) {
+    agx_u32 lo = 0, hi = n_ent;      // the answer lies in [lo, hi]
+    for (agx_u32 it = 0; it < 32u && lo < hi; it++) { const agx_u32 mid = lo + (hi - lo) / 2u; if (e_x[mid] < f_lo) lo = mid + 1u; else hi = mid; }
+    for (agx_u32 i = lo; i < n_ent; i++) {
+        if (e_x[i] >= f_hi) break;
+        if (e_y[i] <= f_hi) add(i);
+    }
+}
+
 // ---- walk preparation: alive-node renumbering and forced-run flags -------------------------------------------------------
 // The path walk (AG:1954-2204) only ever stands on nodes that survived the coverage prune.  After the edge sweep the
 // surviving ("alive") nodes get walk ids ("aid") laid out so that the main strand of the graph is contiguous:

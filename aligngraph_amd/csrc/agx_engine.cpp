@@ -1065,6 +1065,41 @@ size_t edge_reads_layout(size_t tiles, size_t recs, char *base, agx_reads_kargs 
     if (base) { R.err = w; if (words) *words = w; }
     return take.bytes();
 }
+// The scratch of the pair span (agx_unit_pair_span, agx_span.hip), from the front of the same buffer: the mark pass's partials (`parts` wavefronts, three words each) and
+// what one SUB-WINDOW of `sub` positions takes — start and end (span and cross in the end), the scan and its block sums, a closing entry each.  12 bytes per position.
+size_t span_layout(size_t sub, size_t parts, char *base, agx_span_args *A) {
+    Carve take{base};
+    agx_span_args T{}; agx_span_args &S = A ? *A : T;
+    take(S.part, 3 * parts); take(S.start, sub + 1); take(S.end, sub + 1); take(S.sc, sub + 1); take(S.scan_tmp, scan_words(sub + 1, 1024) + 16);
+    if (base) S.n_part = (agx_u32)parts;
+    return take.bytes();
+}
+// The scratch of the pair span under the walk's records (agx_unit_walk_span).  The whole call's: the uploaded stretch table and the per-record table as evidence_layout has
+// them, the partials, and the whole unit's span and cross (8 bytes per position).  Behind that one region that serves two uses in turn: first the scan of one SUB-WINDOW
+// of `sub` positions while span and cross are made (their start and end are the sub-window's piece of span and cross themselves), then what one CHUNK of flat graph bases
+// takes — position, span and step per base, the jump flags and the interval-start flags with their scans, the chunk's jumps as listed, as entries and as (base, entry)
+// pairs, and its intervals, each at its worst (every base a jump, every base an interval).  80 bytes per base of the chunk.
+size_t walk_span_layout(size_t n_st, size_t n_recs, size_t n_pos, size_t sub, size_t chunk, size_t parts, char *base, agx_walk_span_args *A, agx_span_args *SA, agx_u32 **words) {
+    Carve take{base};
+    agx_walk_span_args T{}; agx_walk_span_args &W = A ? *A : T; agx_span_args TS{}; agx_span_args &S = SA ? *SA : TS;
+    agx_evidence_args &E = W.E; agx_u32 *w = nullptr, *span = nullptr, *cross = nullptr, *e_x = nullptr, *e_y = nullptr, *l_base = nullptr, *l_ent = nullptr;
+    take(w, 8);
+    take(E.T.st_first, n_st); take(E.T.st_base, n_st); take(E.T.st_rec, n_st); take(E.T.st_pre, n_st + 1); take(E.T.st_join, n_st + 1);
+    take(E.r_steps, n_recs); take(E.r_dsum, n_recs); take(E.r_dmin, n_recs); take(E.r_smin, n_recs);
+    take(S.part, 3 * parts); take(span, n_pos + 1); take(cross, n_pos + 1);
+    Carve pass = take;      // the region's first use
+    pass(S.sc, sub + 1); pass(S.scan_tmp, scan_words(sub + 1, 1024) + 16);
+    take(W.c_pos, chunk); take(E.c_depth, chunk); take(E.c_step, chunk);
+    take(W.jflag, chunk + 1); take(W.joff, chunk + 1); take(E.flag, chunk + 1); take(E.foff, chunk + 1); take(E.scan_tmp, scan_words(chunk + 1, 1024) + 16);
+    take(W.jt_x, chunk); take(W.jt_y, chunk); take(W.jt_base, chunk); take(e_x, chunk); take(e_y, chunk); take(W.e_cnt, chunk); take(l_base, chunk); take(l_ent, chunk);
+    take(E.iv_rec, chunk); take(E.iv_first, chunk); take(E.iv_last, chunk); take(E.iv_dmin, chunk); take(E.iv_smin, chunk);
+    if (base) {
+        E.noedge = w + 1; E.err = w; E.c_votes = nullptr; if (words) *words = w;
+        W.span = span; W.cross = cross; W.e_x = e_x; W.e_y = e_y; W.l_base = l_base; W.l_ent = l_ent;
+        S.start = span; S.end = cross; S.n_part = (agx_u32)parts;
+    }
+    return std::max(take.bytes(), pass.bytes());
+}
 inline bool keeps_paths(const agx_unit *u) { return (u->prm.flags & (AGX_FLAG_KEEP_PATHS | AGX_FLAG_KEEP_COUNTS)) == (AGX_FLAG_KEEP_PATHS | AGX_FLAG_KEEP_COUNTS); }
 // The export buffer of a unit that keeps paths: every export of such a unit takes the same size — the larger of the two export layouts at their worst, and behind it (at `map_at`)
 // the id map's scratch for a whole-window map — so that exports of any kind in any order never take the buffer twice.
@@ -2787,30 +2822,28 @@ void agx_walk_paths_free(agx_walk_paths *w) {
     memset(w, 0, sizeof *w);
 }
 
-// Evidence under the walk's records (DESIGN.md §14): the stretch table is checked and flattened on the host, uploaded into the export's scratch, and gathered over in chunks
-// of flat graph bases on the export's own stream (agx_evidence.hip).  Two host round trips per chunk: the interval count, then the intervals (and the tracks' piece).
-static void walk_evidence(agx_unit *u, const agx_walk_paths &w, uint32_t min_depth, uint32_t min_support, bool tracks, uint32_t rec_lo, uint32_t rec_hi, agx_walk_evidence *e) {
-    const double t0 = now_ms();
-    if (!(u->prm.flags & AGX_FLAG_KEEP_COUNTS)) throw Error{E_ARG, "walk evidence: the unit was created without AGX_FLAG_KEEP_COUNTS (the depth is the kept per-node coverage)"};
-    if (!u->built || u->trimmed) throw Error{E_ARG, "walk evidence: the unit is not built (call agx_unit_build; not after agx_unit_trim or agx_unit_release)"};
-    if ((u->prm.flags & AGX_FLAG_ONE_SHOT) && (u->consumed || u->downloaded)) throw Error{E_ARG, "walk evidence: a one-shot unit is asked before its download or finish"};
-    const bool counted = (u->prm.flags & AGX_FLAG_EDGE_SUPPORT) != 0;
-    if (min_support && !counted) throw Error{E_ARG, "walk evidence: min_support needs the edge counters (the unit was created without AGX_FLAG_EDGE_SUPPORT)"};
-    // the table, before anything is uploaded
+// A caller's stretch table (agx_walk_paths), checked against the unit and flattened into the form the device reads (agx_evidence_tab): what agx_unit_walk_evidence and
+// agx_unit_walk_span both ask of a table, with the asking call's name in front of the reason.  tracks: rec_lo <= rec_hi <= n_recs is asked too.
+struct FlatTable {
+    size_t nr = 0, ns = 0; uint64_t total = 0;      // records, stretches, graph bases
+    std::vector<agx_u32> st_first, st_base, st_rec, st_pre; std::vector<agx_u8> st_join; std::vector<uint64_t> rec_bases;
+};
+static FlatTable check_walk_table(const agx_unit *u, const agx_walk_paths &w, bool tracks, uint32_t rec_lo, uint32_t rec_hi, const std::string &who) {
     const size_t nr = w.n_recs; const uint64_t ns64 = w.n_stretches;
-    auto bad = [](const std::string &why) { return Error{E_ARG, "walk evidence: " + why}; };
+    auto bad = [&](const std::string &why) { return Error{E_ARG, who + ": " + why}; };
     if (nr && (!w.rec_len || !w.st_off)) throw bad("the stretch table has records but no rec_len / st_off");
     if (ns64 && (!w.id_first || !w.id_last || !w.base_off || !w.joined || !nr)) throw bad("the stretch table has stretches but no arrays or no records");
     if (nr && (w.st_off[0] != 0 || w.st_off[nr] != ns64)) throw bad("st_off does not run from 0 to n_stretches");
     if (tracks && (rec_lo > rec_hi || rec_hi > nr)) throw bad("track records [" + std::to_string(rec_lo) + ", " + std::to_string(rec_hi) + ") are not within the table's " + std::to_string(nr));
-    if (ns64 >= 0xFFFFFFFFull) throw Error{E_UNSUPPORTED, "walk evidence: 2^32 stretches or more"};
+    if (ns64 >= 0xFFFFFFFFull) throw Error{E_UNSUPPORTED, who + ": 2^32 stretches or more"};
     const size_t ns = (size_t)ns64;
-    std::vector<agx_u32> st_first(ns), st_base(ns), st_rec(ns), st_pre(ns + 1); std::vector<agx_u8> st_join(ns + 1, 0);
-    std::vector<uint64_t> rec_bases(nr, 0);
-    uint64_t total = 0;
+    FlatTable F; F.nr = nr; F.ns = ns;
+    F.st_first.resize(ns); F.st_base.resize(ns); F.st_rec.resize(ns); F.st_pre.resize(ns + 1); F.st_join.assign(ns + 1, 0); F.rec_bases.assign(nr, 0);
+    std::vector<agx_u32> &st_first = F.st_first, &st_base = F.st_base, &st_rec = F.st_rec, &st_pre = F.st_pre; std::vector<agx_u8> &st_join = F.st_join;
+    std::vector<uint64_t> &rec_bases = F.rec_bases; uint64_t &total = F.total;
     for (size_t r = 0; r < nr; r++) if (w.st_off[r] > w.st_off[r + 1] || w.st_off[r + 1] > ns64) throw bad("st_off is not monotone at record " + std::to_string(r));
     for (size_t r = 0; r < nr; r++) {
-        if (w.st_off[r] < w.st_off[r + 1] && w.rec_len[r] > 0xFFFFFFFFull) throw Error{E_UNSUPPORTED, "walk evidence: record " + std::to_string(r) + " has 2^32 bases or more"};
+        if (w.st_off[r] < w.st_off[r + 1] && w.rec_len[r] > 0xFFFFFFFFull) throw Error{E_UNSUPPORTED, who + ": record " + std::to_string(r) + " has 2^32 bases or more"};
         uint64_t end = 0;
         for (size_t i = (size_t)w.st_off[r]; i < (size_t)w.st_off[r + 1]; i++) {
             const std::string at = "stretch " + std::to_string(i) + " of record " + std::to_string(r);
@@ -2824,10 +2857,40 @@ static void walk_evidence(agx_unit *u, const agx_walk_paths &w, uint32_t min_dep
             if (w.joined[i] && (first || w.base_off[i] != end)) throw bad(at + ": joined, but not directly behind the previous stretch of the record");
             st_first[i] = w.id_first[i]; st_base[i] = (agx_u32)w.base_off[i]; st_rec[i] = (agx_u32)r; st_pre[i] = (agx_u32)total; st_join[i] = w.joined[i];
             end = w.base_off[i] + len; total += len; rec_bases[r] += len;
-            if (total >= 0xFFFFFFFFull) throw Error{E_UNSUPPORTED, "walk evidence: 2^32 graph bases or more"};
+            if (total >= 0xFFFFFFFFull) throw Error{E_UNSUPPORTED, who + ": 2^32 graph bases or more"};
         }
     }
     st_pre[ns] = (agx_u32)total;
+    return F;
+}
+
+// The intervals of one chunk of flat bases (rec, first, last, and two minima; `cnt` of them, in order) behind those of the chunks before it: an interval cut by the chunk's
+// border — the same record, the next base offset — is one interval
+static void merge_chunk_intervals(std::vector<agx_u32> (&iv)[5], const std::vector<agx_u32> (&got)[5], agx_u32 cnt, size_t nr, uint64_t lo, const std::string &who) {
+    for (agx_u32 i = 0; i < cnt; i++) {
+        if (got[0][i] >= nr || got[1][i] > got[2][i]) throw Error{E_DEVICE, who + ": the intervals are inconsistent (chunk at base " + std::to_string(lo) + ", interval " + std::to_string(i) + ")"};
+        if (i == 0 && !iv[0].empty() && iv[0].back() == got[0][0] && (uint64_t)iv[2].back() + 1 == got[1][0]) {
+            iv[2].back() = got[2][0]; iv[3].back() = std::min(iv[3].back(), got[3][0]); iv[4].back() = std::min(iv[4].back(), got[4][0]);
+            continue;
+        }
+        for (int k = 0; k < 5; k++) iv[k].push_back(got[k][i]);
+    }
+}
+
+// Evidence under the walk's records (DESIGN.md §14): the stretch table is checked and flattened on the host, uploaded into the export's scratch, and gathered over in chunks
+// of flat graph bases on the export's own stream (agx_evidence.hip).  Two host round trips per chunk: the interval count, then the intervals (and the tracks' piece).
+static void walk_evidence(agx_unit *u, const agx_walk_paths &w, uint32_t min_depth, uint32_t min_support, bool tracks, uint32_t rec_lo, uint32_t rec_hi, agx_walk_evidence *e) {
+    const double t0 = now_ms();
+    if (!(u->prm.flags & AGX_FLAG_KEEP_COUNTS)) throw Error{E_ARG, "walk evidence: the unit was created without AGX_FLAG_KEEP_COUNTS (the depth is the kept per-node coverage)"};
+    if (!u->built || u->trimmed) throw Error{E_ARG, "walk evidence: the unit is not built (call agx_unit_build; not after agx_unit_trim or agx_unit_release)"};
+    if ((u->prm.flags & AGX_FLAG_ONE_SHOT) && (u->consumed || u->downloaded)) throw Error{E_ARG, "walk evidence: a one-shot unit is asked before its download or finish"};
+    const bool counted = (u->prm.flags & AGX_FLAG_EDGE_SUPPORT) != 0;
+    if (min_support && !counted) throw Error{E_ARG, "walk evidence: min_support needs the edge counters (the unit was created without AGX_FLAG_EDGE_SUPPORT)"};
+    // the table, before anything is uploaded
+    const FlatTable F = check_walk_table(u, w, tracks, rec_lo, rec_hi, "walk evidence");
+    const size_t nr = F.nr, ns = F.ns; const uint64_t total = F.total;
+    const std::vector<agx_u32> &st_first = F.st_first, &st_base = F.st_base, &st_rec = F.st_rec, &st_pre = F.st_pre; const std::vector<agx_u8> &st_join = F.st_join;
+    const std::vector<uint64_t> &rec_bases = F.rec_bases;
     if (counted) support_check(u);
     // the caller's tables (the per-record ones are always produced)
     auto mk = [](auto *&p, size_t n) { using T = std::remove_reference_t<decltype(*p)>; p = (T *)calloc(n + 1, sizeof(T)); if (!p) throw Error{E_ARG, "out of host memory"}; };
@@ -2886,15 +2949,7 @@ static void walk_evidence(agx_unit *u, const agx_walk_paths &w, uint32_t min_dep
                 }
             }
             E.sync();
-            for (agx_u32 i = 0; i < cnt; i++) {
-                if (got[0][i] >= nr || got[1][i] > got[2][i]) throw Error{E_DEVICE, "walk evidence: the intervals are inconsistent (chunk at base " + std::to_string(lo) + ", interval " + std::to_string(i) + ")"};
-                // an interval cut by the chunk's border: the same record, the next base offset
-                if (i == 0 && !iv[0].empty() && iv[0].back() == got[0][0] && (uint64_t)iv[2].back() + 1 == got[1][0]) {
-                    iv[2].back() = got[2][0]; iv[3].back() = std::min(iv[3].back(), got[3][0]); iv[4].back() = std::min(iv[4].back(), got[4][0]);
-                    continue;
-                }
-                for (int k = 0; k < 5; k++) iv[k].push_back(got[k][i]);
-            }
+            merge_chunk_intervals(iv, got, cnt, nr, lo, "walk evidence");
         }
         std::vector<unsigned long long> rs(nr), rd(nr), rmin(nr), smin(nr); agx_u32 wd[2] = {0, 0};
         if (nr) { E.read(rs.data(), A.r_steps, nr * 8); E.read(rd.data(), A.r_dsum, nr * 8); E.read(rmin.data(), A.r_dmin, nr * 8); E.read(smin.data(), A.r_smin, nr * 8); }
@@ -2929,6 +2984,224 @@ void agx_walk_evidence_free(agx_walk_evidence *e) {
     free(e->rec_graph_bases); free(e->rec_steps); free(e->rec_depth_sum); free(e->rec_depth_min); free(e->rec_depth_min_at); free(e->rec_step_min); free(e->rec_step_min_at);
     free(e->iv_rec); free(e->iv_first); free(e->iv_last); free(e->iv_depth_min); free(e->iv_step_min);
     free(e->track_off); free(e->depth); free(e->votes); free(e->step);
+    memset(e, 0, sizeof *e);
+}
+
+// Pair span.  What both calls refuse: the export's conditions, for the scratch, and the edge counting's but its flag — the pass reads the arrays the
+// counting reads (the derived hit records and the runs), so it may run wherever ensure_support may.
+static void span_check(const agx_unit *u, const std::string &who) {
+    if (!(u->prm.flags & AGX_FLAG_KEEP_COUNTS)) throw Error{E_ARG, who + ": the unit was created without AGX_FLAG_KEEP_COUNTS (the scratch is the export's buffer, which only such units reserve)"};
+    if (u->prm.flags & AGX_FLAG_ONE_SHOT) throw Error{E_ARG, who + ": a one-shot unit gives the arrays the pass reads away with its only download"};
+    if (!u->built || u->trimmed || u->downloaded) throw Error{E_ARG, who + ": the unit is not built (call agx_unit_build; not after agx_unit_download, agx_unit_trim or agx_unit_release)"};
+}
+
+// span and cross of positions [lo, hi) in sub-windows of `sub` positions: per sub-window place(x) says where its start / end lie (S.start, S.end: n + 1 entries each,
+// zeroed here), the kernels leave span / cross there, and done(x, n) may queue reads behind them; one host round trip each.  [lo, lo): one pass for the counts alone.
+struct SpanCounts { uint64_t kept = 0, fragments = 0, outside = 0; unsigned passes = 0; };
+static SpanCounts span_passes(const Export &E, agx_span_args &S, agx_u32 lo, agx_u32 hi, size_t sub, const std::string &who, const std::function<void(agx_u32)> &place,
+                              const std::function<void(agx_u32, agx_u32)> &done) {
+    const agx_unit *u = E.u;
+    S.dhit = u->d_dhit.p; S.runs = u->d_runs.p; S.n_hits = (agx_u32)u->nh; S.n_runs = (agx_u32)u->n_runs; S.n_pos = E.n_pos; S.win_lo = lo; S.win_hi = hi;
+    SpanCounts C;
+    std::vector<agx_u32> part((size_t)3 * S.n_part);
+    for (agx_u32 x = lo; !C.passes || x < hi;) {
+        const agx_u32 n = (agx_u32)std::min<size_t>(sub, hi - x);
+        S.lo = x; S.n = n;
+        place(x);
+        E.fill(S.start, 0, ((size_t)n + 1) * 4); E.fill(S.end, 0, ((size_t)n + 1) * 4); E.fill(S.part, 0, part.size() * 4);
+        agx_launch_pair_span(&S, E.s);
+        E.read(part.data(), S.part, part.size() * 4);
+        done(x, n);
+        E.sync();
+        HIP_OK(hipGetLastError());
+        uint64_t f = 0, k = 0, o = 0;
+        for (size_t i = 0; i < S.n_part; i++) { f += part[3 * i]; k += part[3 * i + 1]; o += part[3 * i + 2]; }
+        if (C.passes && (f != C.fragments || k != C.kept || o != C.outside)) throw Error{E_DEVICE, "internal: " + who + ": two passes over the hits disagree on their counts"};
+        C.fragments = f; C.kept = k; C.outside = o; C.passes++;
+        x += n;
+        if (!n) break;
+    }
+    return C;
+}
+
+// the sub-window a call works in: the whole window, AGX_SPAN_CHUNK's, or as many positions as `bytes_of` says fit the scratch (0: not even one)
+static size_t span_sub_window(size_t n, size_t avail, const std::function<size_t(size_t)> &bytes_of) {
+    size_t sub = std::max<size_t>(n, 1);
+    if (const char *env = getenv("AGX_SPAN_CHUNK")) { const long long v = atoll(env); if (v > 0) sub = std::min<size_t>((size_t)v, sub); }
+    while (sub > 1 && bytes_of(sub) > avail) sub = (sub + 1) / 2;
+    return bytes_of(sub) > avail ? 0 : sub;
+}
+
+static void pair_span(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, agx_pair_span *s) {
+    const double t0 = now_ms();
+    span_check(u, "pair span");
+    if (pos_lo > pos_hi || pos_hi > (agx_u32)u->V.n_pos)
+        throw Error{E_ARG, "pair span: window [" + std::to_string(pos_lo) + ", " + std::to_string(pos_hi) + ") is not within the unit's positions [0, " + std::to_string((agx_u32)u->V.n_pos) + ")"};
+    const size_t n = pos_hi - pos_lo;
+    auto mk = [](auto *&p, size_t n) { using T = std::remove_reference_t<decltype(*p)>; p = (T *)calloc(n + 1, sizeof(T)); if (!p) throw Error{E_ARG, "out of host memory"}; };
+    s->pos_lo = pos_lo; s->pos_hi = pos_hi;
+    mk(s->span, n); mk(s->cross, n);
+    Export E(u);
+    E.open(unitig_layout(E.cap, E.n_pos, E.n_ovf, nullptr, nullptr, nullptr));      // (the buffer every export of the unit takes: the room the upload reserved)
+    const size_t avail = u->d_ut.n, parts = agx_span_partials((agx_u32)u->nh);
+    const size_t sub = span_sub_window(n, avail, [&](size_t m) { return span_layout(m, parts, nullptr, nullptr); });
+    if (!sub) throw Error{E_UNSUPPORTED, "pair span: the export's scratch of " + std::to_string(avail) + " bytes does not hold one position's counts beside the partial sums of " + std::to_string(u->nh) + " hits"};
+    agx_span_args S{};
+    span_layout(sub, parts, u->d_ut.p, &S);
+    const SpanCounts C = span_passes(E, S, pos_lo, pos_hi, sub, "pair span", [](agx_u32) {}, [&](agx_u32 x, agx_u32 m) {
+        if (m) { E.read(s->span + (x - pos_lo), S.start, (size_t)m * 4); E.read(s->cross + (x - pos_lo), S.end, (size_t)m * 4); }
+    });
+    s->n_kept = C.kept; s->n_fragments = C.fragments; s->n_outside = C.outside;
+    u->stats.ms_pair_span = now_ms() - t0;
+    if (g_trace) fprintf(stderr, "[agx trace] unit %p pair span [%u, %u): %u sub-windows of %zu positions, %llu kept hits, %llu fragments\n", (void *)u, pos_lo, pos_hi, C.passes, sub,
+                         (unsigned long long)C.kept, (unsigned long long)C.fragments);
+    trace(u, "pair_span", t0, n);
+}
+
+int agx_unit_pair_span(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, agx_pair_span *s) {
+    if (!u || !s) return AGX_E_ARG;
+    memset(s, 0, sizeof *s);
+    const int rc = guarded(u, [&] { pair_span(u, pos_lo, pos_hi, s); });
+    if (rc != AGX_OK) agx_pair_span_free(s);
+    return rc;
+}
+
+void agx_pair_span_free(agx_pair_span *s) {
+    if (!s) return;
+    free(s->span); free(s->cross);
+    memset(s, 0, sizeof *s);
+}
+
+// Pair span under the walk's records: the table is checked and flattened as for the evidence, span and cross of the whole unit are made in the scratch (sub-windows where
+// need be), then the bases go through in chunks — the gather (a round trip: the jump count), where there are jumps their list (a round trip: the host sorts and merges
+// it), the count over the hits and the scatter, then the flags (a round trip: the interval count) and the intervals with the tracks' piece (a round trip).
+static void walk_span(agx_unit *u, const agx_walk_paths &w, uint32_t min_span, bool tracks, uint32_t rec_lo, uint32_t rec_hi, agx_walk_span *e) {
+    const double t0 = now_ms();
+    span_check(u, "walk span");
+    const FlatTable F = check_walk_table(u, w, tracks, rec_lo, rec_hi, "walk span");
+    const size_t nr = F.nr, ns = F.ns; const uint64_t total = F.total;
+    auto mk = [](auto *&p, size_t n) { using T = std::remove_reference_t<decltype(*p)>; p = (T *)calloc(n + 1, sizeof(T)); if (!p) throw Error{E_ARG, "out of host memory"}; };
+    e->n_recs = (uint32_t)nr; e->n_graph_bases = total;
+    mk(e->rec_graph_bases, nr); mk(e->rec_steps, nr); mk(e->rec_span_sum, nr); mk(e->rec_span_min, nr); mk(e->rec_span_min_at, nr); mk(e->rec_step_min, nr); mk(e->rec_step_min_at, nr);
+    for (size_t r = 0; r < nr; r++) { e->rec_graph_bases[r] = F.rec_bases[r]; e->rec_span_min[r] = e->rec_step_min[r] = AGX_NONE; }
+    size_t s_lo = 0, s_hi = 0; uint64_t t_lo = 0, t_hi = 0;      // the tracks' stretches and flat bases
+    if (tracks) {
+        s_lo = nr ? (size_t)w.st_off[rec_lo] : 0; s_hi = nr ? (size_t)w.st_off[rec_hi] : 0; t_lo = F.st_pre[s_lo]; t_hi = F.st_pre[s_hi];
+        e->rec_lo = rec_lo; e->rec_hi = rec_hi; e->n_track = t_hi - t_lo;
+        mk(e->track_off, s_hi - s_lo + 1); mk(e->pos, (size_t)e->n_track); mk(e->span, (size_t)e->n_track); mk(e->step, (size_t)e->n_track);
+        for (size_t i = s_lo; i <= s_hi; i++) e->track_off[i - s_lo] = F.st_pre[i] - t_lo;
+    }
+    Export E(u);
+    const agx_u32 n_pos = E.n_pos;
+    E.open(unitig_layout(E.cap, n_pos, E.n_ovf, nullptr, nullptr, nullptr));      // (the buffer every export of the unit takes: the room the upload reserved)
+    std::vector<agx_u32> iv[5];      // rec, first, last, span_min, step_min
+    unsigned n_chunks = 0, n_passes = 0; uint64_t n_entries = 0;
+    if (total) {
+        const size_t avail = u->d_ut.n, parts = agx_span_partials((agx_u32)u->nh);
+        auto bytes_of = [&](size_t sub, size_t chunk) { return walk_span_layout(ns, nr, n_pos, sub, chunk, parts, nullptr, nullptr, nullptr, nullptr); };
+        if (bytes_of(1, 64) > avail)
+            throw Error{E_UNSUPPORTED, "walk span: the unit's span and cross (" + std::to_string(n_pos) + " positions) and the stretch table (" + std::to_string(ns) + " stretches, " + std::to_string(nr) +
+                                       " records) do not fit the export's scratch of " + std::to_string(avail) + " bytes"};
+        const size_t sub = span_sub_window(n_pos, avail, [&](size_t m) { return bytes_of(m, 64); });
+        size_t chunk = std::min<size_t>(((size_t)total + 63) & ~(size_t)63, (size_t)1 << 30);
+        if (const char *env = getenv("AGX_SPAN_BASE_CHUNK")) { const long long v = atoll(env); if (v > 0) chunk = std::min<size_t>(((size_t)v + 63) & ~(size_t)63, (size_t)1 << 30); }
+        while (chunk > 64 && bytes_of(1, chunk) > avail) chunk = ((chunk / 2) + 63) & ~(size_t)63;
+        agx_walk_span_args A{}; agx_span_args S{}; agx_u32 *words = nullptr;
+        walk_span_layout(ns, nr, n_pos, sub, chunk, parts, u->d_ut.p, &A, &S, &words);
+        agx_evidence_args &V = A.E; agx_evidence_tab &T = V.T;
+        T.n_st = (agx_u32)ns; T.n_flat = (agx_u32)total;
+        T.a_nid = u->d_a_nid.p; T.n_ids = u->n_ids; T.pool_cap = E.cap; T.n_counts = u->d_counts.p; T.n_next = u->d_next.p; T.n_flags = u->d_flags.p; T.ovf = u->d_ovf.p; T.n_ovf = E.n_ovf;
+        T.e_cnt = nullptr; T.ovf_cnt = nullptr;
+        V.min_depth = min_span; V.min_support = min_span; V.n_recs = (agx_u32)nr;
+        A.dhit = u->d_dhit.p; A.runs = u->d_runs.p; A.n_hits = (agx_u32)u->nh; A.n_runs = (agx_u32)u->n_runs; A.n_pos = n_pos; A.side_xpos = u->d_side_xpos.p;
+        auto up = [&](const void *dst, const void *src, size_t b) { if (b) HIP_OK(hipMemcpyAsync(const_cast<void *>(dst), src, b, hipMemcpyHostToDevice, E.s)); };
+        up(T.st_first, F.st_first.data(), ns * 4); up(T.st_base, F.st_base.data(), ns * 4); up(T.st_rec, F.st_rec.data(), ns * 4); up(T.st_pre, F.st_pre.data(), (ns + 1) * 4); up(T.st_join, F.st_join.data(), ns + 1);
+        E.fill(words, 0, 32); E.fill(V.r_steps, 0, nr * 8); E.fill(V.r_dsum, 0, nr * 8); E.fill(V.r_dmin, 0xFF, nr * 8); E.fill(V.r_smin, 0xFF, nr * 8);
+        // the whole unit's span and cross: a sub-window's start and end are its piece of the two arrays
+        agx_u32 *const span_all = S.start, *const cross_all = S.end;
+        n_passes = span_passes(E, S, 0, n_pos, sub, "walk span", [&](agx_u32 x) { S.start = span_all + x; S.end = cross_all + x; }, [](agx_u32, agx_u32) {}).passes;
+        std::vector<agx_u32> got[5], jt[3];
+        SpanJumps J;
+        for (uint64_t lo = 0; lo < total; lo += chunk) {
+            const agx_u32 n = (agx_u32)std::min<uint64_t>(chunk, total - lo);
+            V.lo = (agx_u32)lo; V.n = n; V.iv_cap = 0; A.jt_cap = 0; A.n_ent = 0; A.n_list = 0;
+            agx_launch_walk_span_gather(&A, E.s);
+            agx_u32 nj = 0;
+            E.read(&nj, A.joff + n, 4); E.sync();
+            if (nj > n) throw Error{E_DEVICE, "internal: walk span: more jumps than bases"};
+            if (nj) {
+                A.jt_cap = nj;
+                agx_launch_walk_span_emit(&A, E.s);
+                agx_u32 *src[3] = {A.jt_x, A.jt_y, A.jt_base};
+                for (int k = 0; k < 3; k++) { jt[k].resize(nj); E.read(jt[k].data(), src[k], (size_t)nj * 4); }
+                agx_u32 w0 = 0;
+                E.read(&w0, words, 4); E.sync();
+                if (w0 || !span_jump_entries(jt[0].data(), jt[1].data(), jt[2].data(), nj, J)) throw Error{E_DEVICE, "internal: walk span: the jump list is inconsistent (error word " + std::to_string(w0) + ")"};
+                const size_t ne = J.e_x.size();
+                up(A.e_x, J.e_x.data(), ne * 4); up(A.e_y, J.e_y.data(), ne * 4); up(A.l_base, J.l_base.data(), (size_t)nj * 4); up(A.l_ent, J.l_ent.data(), (size_t)nj * 4);
+                E.fill(A.e_cnt, 0, ne * 4);
+                A.n_ent = (agx_u32)ne; A.n_list = nj;
+                agx_launch_walk_span_jumps(&A, E.s);
+                e->n_jump_steps += nj; n_entries += ne;
+            }
+            agx_launch_walk_span_flags(&A, E.s);
+            agx_u32 cnt = 0;
+            E.read(&cnt, V.foff + n, 4); E.sync();
+            if (cnt > n) throw Error{E_DEVICE, "internal: walk span: more intervals than bases"};
+            if (cnt) {
+                V.iv_cap = cnt;
+                E.fill(V.iv_dmin, 0xFF, (size_t)cnt * 4); E.fill(V.iv_smin, 0xFF, (size_t)cnt * 4);
+                agx_launch_evidence_runs(&V, E.s);
+                agx_u32 *src[5] = {V.iv_rec, V.iv_first, V.iv_last, V.iv_dmin, V.iv_smin};
+                for (int k = 0; k < 5; k++) { got[k].resize(cnt); E.read(got[k].data(), src[k], (size_t)cnt * 4); }
+            }
+            if (tracks) {      // the piece of the tracks that lies in this chunk
+                const uint64_t a = std::max<uint64_t>(lo, t_lo), b = std::min<uint64_t>(lo + n, t_hi);
+                if (a < b) {
+                    E.read(e->pos + (a - t_lo), A.c_pos + (a - lo), (size_t)(b - a) * 4); E.read(e->span + (a - t_lo), V.c_depth + (a - lo), (size_t)(b - a) * 4);
+                    E.read(e->step + (a - t_lo), V.c_step + (a - lo), (size_t)(b - a) * 4);
+                }
+            }
+            E.sync();
+            merge_chunk_intervals(iv, got, cnt, nr, lo, "walk span");
+            n_chunks++;
+        }
+        std::vector<unsigned long long> rs(nr), rd(nr), rmin(nr), smin(nr); agx_u32 wd[2] = {0, 0};
+        if (nr) { E.read(rs.data(), V.r_steps, nr * 8); E.read(rd.data(), V.r_dsum, nr * 8); E.read(rmin.data(), V.r_dmin, nr * 8); E.read(smin.data(), V.r_smin, nr * 8); }
+        E.read(wd, words, 8); E.sync();
+        HIP_OK(hipGetLastError());
+        if (wd[0]) throw Error{E_DEVICE, "internal: walk span: the interval or jump numbers are inconsistent (error word " + std::to_string(wd[0]) + ")"};
+        e->n_steps_not_forward = wd[1];
+        for (size_t r = 0; r < nr; r++) {
+            e->rec_steps[r] = rs[r]; e->rec_span_sum[r] = rd[r]; e->n_steps += rs[r];
+            if (rmin[r] != ~0ull) { e->rec_span_min[r] = (uint32_t)(rmin[r] >> 32); e->rec_span_min_at[r] = (uint32_t)rmin[r]; }
+            if (smin[r] != ~0ull) { e->rec_step_min[r] = (uint32_t)(smin[r] >> 32); e->rec_step_min_at[r] = (uint32_t)smin[r]; }
+        }
+    }
+    const size_t ni = iv[0].size();
+    e->n_intervals = (uint32_t)ni;
+    mk(e->iv_rec, ni); mk(e->iv_first, ni); mk(e->iv_last, ni); mk(e->iv_span_min, ni); mk(e->iv_step_min, ni);
+    uint32_t *dst[5] = {e->iv_rec, e->iv_first, e->iv_last, e->iv_span_min, e->iv_step_min};
+    for (int k = 0; k < 5; k++) if (ni) memcpy(dst[k], iv[k].data(), ni * 4);
+    u->stats.ms_walk_span = now_ms() - t0;
+    if (g_trace) fprintf(stderr, "[agx trace] unit %p walk span (min %u): %u sub-windows, %u chunks of bases, %llu jump steps in %llu entries, %zu intervals\n", (void *)u, min_span, n_passes, n_chunks,
+                         (unsigned long long)e->n_jump_steps, (unsigned long long)n_entries, ni);
+    trace(u, "walk_span", t0, (size_t)total);
+}
+
+int agx_unit_walk_span(agx_unit *u, const agx_walk_paths *w, uint32_t min_span, uint32_t want_tracks, uint32_t rec_lo, uint32_t rec_hi, agx_walk_span *e) {
+    if (!u || !w || !e) return AGX_E_ARG;
+    memset(e, 0, sizeof *e);
+    const int rc = guarded(u, [&] { walk_span(u, *w, min_span, want_tracks != 0, rec_lo, rec_hi, e); });
+    if (rc != AGX_OK) agx_walk_span_free(e);
+    return rc;
+}
+
+void agx_walk_span_free(agx_walk_span *e) {
+    if (!e) return;
+    free(e->rec_graph_bases); free(e->rec_steps); free(e->rec_span_sum); free(e->rec_span_min); free(e->rec_span_min_at); free(e->rec_step_min); free(e->rec_step_min_at);
+    free(e->iv_rec); free(e->iv_first); free(e->iv_last); free(e->iv_span_min); free(e->iv_step_min);
+    free(e->track_off); free(e->pos); free(e->span); free(e->step);
     memset(e, 0, sizeof *e);
 }
 

@@ -214,22 +214,22 @@ int agx_unitigs_gfa_support(const agx_unitigs *t, const uint32_t *link_support, 
     return gfa_text(t, link_support, unit, text, len);
 }
 
-// The weak intervals of agx_unit_walk_evidence as BED, one line per interval in the table's order:
-//   p<unit>_<rec>	<base_first>	<base_last + 1>	weak	0	+	dm:i:<depth_min>	sm:i:<step_min>      ("." for a number that is 0xFFFFFFFF)
-int agx_walk_evidence_bed(const agx_walk_evidence *e, int unit, char **text, size_t *len) {
-    if (!e || !text || !len || unit < 0) return AGX_E_ARG;
+// An interval table as BED, one line per interval in the table's order (the weak intervals of §14, the thin ones of §16):
+//   p<unit>_<rec>	<base_first>	<base_last + 1>	<label>	0	+	<tag_a><min_a>	<tag_b><min_b>      ("." for a number that is 0xFFFFFFFF)
+static int intervals_bed(uint32_t n, uint32_t n_recs, const uint32_t *rec, const uint32_t *first, const uint32_t *last, const uint32_t *min_a, const uint32_t *min_b,
+                         const char *label, const char *tag_a, const char *tag_b, int unit, char **text, size_t *len) {
+    if (!text || !len || unit < 0) return AGX_E_ARG;
     *text = nullptr; *len = 0;
-    const uint32_t n = e->n_intervals;
-    if (n && (!e->iv_rec || !e->iv_first || !e->iv_last || !e->iv_depth_min || !e->iv_step_min)) return AGX_E_ARG;
-    for (uint32_t i = 0; i < n; i++) if (e->iv_last[i] < e->iv_first[i] || e->iv_rec[i] >= e->n_recs) return AGX_E_ARG;
+    if (n && (!rec || !first || !last || !min_a || !min_b)) return AGX_E_ARG;
+    for (uint32_t i = 0; i < n; i++) if (last[i] < first[i] || rec[i] >= n_recs) return AGX_E_ARG;
     try {
         const std::string prefix = "p" + std::to_string(unit) + "_";
         std::string o;
         o.reserve((size_t)n * 64);
         auto put_or_dot = [&](uint32_t v) { if (v == 0xFFFFFFFFu) o += '.'; else put_u64(o, v); };
         for (uint32_t i = 0; i < n; i++) {
-            o += prefix; put_u64(o, e->iv_rec[i]); o += '\t'; put_u64(o, e->iv_first[i]); o += '\t'; put_u64(o, (uint64_t)e->iv_last[i] + 1);
-            o += "\tweak\t0\t+\tdm:i:"; put_or_dot(e->iv_depth_min[i]); o += "\tsm:i:"; put_or_dot(e->iv_step_min[i]); o += '\n';
+            o += prefix; put_u64(o, rec[i]); o += '\t'; put_u64(o, first[i]); o += '\t'; put_u64(o, (uint64_t)last[i] + 1);
+            o += '\t'; o += label; o += "\t0\t+\t"; o += tag_a; put_or_dot(min_a[i]); o += '\t'; o += tag_b; put_or_dot(min_b[i]); o += '\n';
         }
         char *out = (char *)malloc(o.size() + 1);
         if (!out) return AGX_E_ARG;
@@ -239,6 +239,20 @@ int agx_walk_evidence_bed(const agx_walk_evidence *e, int unit, char **text, siz
     } catch (...) {
         return AGX_E_ARG;
     }
+}
+
+// The weak intervals of agx_unit_walk_evidence as BED:
+//   p<unit>_<rec>	<base_first>	<base_last + 1>	weak	0	+	dm:i:<depth_min>	sm:i:<step_min>
+int agx_walk_evidence_bed(const agx_walk_evidence *e, int unit, char **text, size_t *len) {
+    if (!e) return AGX_E_ARG;
+    return intervals_bed(e->n_intervals, e->n_recs, e->iv_rec, e->iv_first, e->iv_last, e->iv_depth_min, e->iv_step_min, "weak", "dm:i:", "sm:i:", unit, text, len);
+}
+
+// The thin intervals of agx_unit_walk_span as BED:
+//   p<unit>_<rec>	<base_first>	<base_last + 1>	thin	0	+	pm:i:<span_min>	jm:i:<step_min>
+int agx_walk_span_bed(const agx_walk_span *e, int unit, char **text, size_t *len) {
+    if (!e) return AGX_E_ARG;
+    return intervals_bed(e->n_intervals, e->n_recs, e->iv_rec, e->iv_first, e->iv_last, e->iv_span_min, e->iv_step_min, "thin", "pm:i:", "jm:i:", unit, text, len);
 }
 
 // The edges of agx_unit_edge_reads with the hits behind them, one line per edge in the table's order:

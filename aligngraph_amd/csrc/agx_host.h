@@ -307,4 +307,21 @@ struct Assistant {          // (helpers(): how many threads there are; `who` pic
 };
 void walk_join_scaffold(const UnitView &V, const GraphView &G, UnitOutput &out, Assistant *assistant = nullptr);
 
+// The jump table of agx_unit_walk_span (host only, here so that the engine and the tests' serial replay run the same function): the n jumps of a chunk as
+// the device listed them (positions x < y, flat base) sorted by (x, y, base) and merged into entries, one per distinct (x, y), in the form agx_k_sp_jumps and
+// agx_k_sp_scatter read: e_x / e_y per entry, and per jump its base and its entry.  false: a listed jump is not forward (the device's list is inconsistent).
+struct SpanJumps { std::vector<agx_u32> e_x, e_y, l_base, l_ent; };
+inline bool span_jump_entries(const agx_u32 *x, const agx_u32 *y, const agx_u32 *base, size_t n, SpanJumps &J) {
+    J.e_x.clear(); J.e_y.clear(); J.l_base.assign(n, 0); J.l_ent.assign(n, 0);
+    std::vector<size_t> order(n);
+    for (size_t i = 0; i < n; i++) { if (y[i] <= x[i]) return false; order[i] = i; }
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return x[a] != x[b] ? x[a] < x[b] : y[a] != y[b] ? y[a] < y[b] : base[a] < base[b]; });
+    for (size_t k = 0; k < n; k++) {
+        const size_t i = order[k];
+        if (J.e_x.empty() || J.e_x.back() != x[i] || J.e_y.back() != y[i]) { J.e_x.push_back(x[i]); J.e_y.push_back(y[i]); }
+        J.l_base[k] = base[i]; J.l_ent[k] = (agx_u32)(J.e_x.size() - 1);
+    }
+    return true;
+}
+
 }  // namespace agx

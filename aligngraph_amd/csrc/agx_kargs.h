@@ -149,6 +149,35 @@ struct agx_evidence_args {
     agx_u32 *err;                              // bit 0: an interval number beyond iv_cap
 };
 
+// Pair span (agx_span.hip, agx_unit_pair_span): one launch set per SUB-WINDOW [lo, lo + n) of the call's window [win_lo, win_hi).  The mark pass goes over all
+// hit records whatever the sub-window (it clamps every fragment to it); its counts are those of the call's window and are the same in every sub-window's pass.
+struct agx_span_args {
+    const agx_dhit *dhit; const agx_run *runs; agx_u32 n_hits, n_runs, n_pos;
+    agx_u32 win_lo, win_hi;                    // the call's window: the fragments counted are those that meet it
+    agx_u32 lo, n;                             // the sub-window
+    agx_u32 *start, *end;                      // [n + 1] fragments that begin at (or in front of and reach) / end on each position; zeroed; start becomes span, end becomes cross
+    agx_u32 *sc, *scan_tmp;                    // [n + 1] the scan of start[x] - end[x - 1], and the scan's block sums
+    agx_u32 *part; agx_u32 n_part;             // [3 * n_part] per wavefront of the mark pass: fragments that meet the window, kept hits, kept hits outside the unit
+};
+#define AGX_SPAN_BLOCKS 1024u   // workgroups of the mark pass at most (its lanes stride over the hits): 4096 partials of three words
+
+// Pair span under the walk's records (agx_unit_walk_span): one launch set per CHUNK of flat graph bases, §14's shape.  E is the evidence kernels' own argument struct with
+// span in the place of depth (c_depth = the chunk's span, r_dsum / r_dmin the span sums and minima, min_depth = min_support = min_span, noedge = the steps that are not
+// forward), so that agx_k_ev_runs serves the thin intervals unchanged.  span / cross are the whole unit's.  A JUMP is a step between positions x and y > x + 1: the gather
+// flags it, the emit pass lists it behind the flags' scan, the host sorts and merges the list into ENTRIES (x, y) ascending, each with the flat bases that take it, and
+// agx_k_sp_jumps counts per entry the fragments with f_lo <= x and y <= f_hi.
+struct agx_walk_span_args {
+    agx_evidence_args E;
+    const agx_dhit *dhit; const agx_run *runs; agx_u32 n_hits, n_runs, n_pos;
+    const agx_u32 *side_xpos;                  // [n_ids - n_pos] the position of every side id
+    const agx_u32 *span, *cross;               // [n_pos]
+    agx_u32 *c_pos;                            // [n] the position of every base of the chunk
+    agx_u32 *jflag, *joff;                     // [n + 1] jump flags (closing zero) and their exclusive scan; the scan's block sums are E.scan_tmp
+    agx_u32 *jt_x, *jt_y, *jt_base; agx_u32 jt_cap;      // [jt_cap] the chunk's jumps as the emit pass lists them: positions and flat base
+    const agx_u32 *e_x, *e_y; agx_u32 *e_cnt; agx_u32 n_ent;      // [n_ent] the entries, sorted by (x, y), and their counters (zeroed)
+    const agx_u32 *l_base, *l_ent; agx_u32 n_list;       // [n_list] every jump once more: its flat base and its entry
+};
+
 #define AGX_SLOW_WAVES 8192u   // wavefronts of the per-hit edge pass if the occupancy query fails (normally: as many as are resident at once)
 
 extern "C" {
@@ -232,4 +261,14 @@ void agx_launch_unitig_link_support(const agx_unitig_region_args *, const agx_u8
 // and the interval minima filled with ones, the intervals
 void agx_launch_evidence_gather(const agx_evidence_args *, hipStream_t);
 void agx_launch_evidence_runs(const agx_evidence_args *, hipStream_t);
+// pair span of one sub-window: the mark pass over all hits (start, end and part zeroed by the caller), the difference, its scan, and span / cross in place of start / end
+agx_u32 agx_span_partials(agx_u32 n_hits);      // wavefronts of the mark pass = entries of `part` / 3
+void agx_launch_pair_span(const agx_span_args *, hipStream_t);
+// pair span under the records, one chunk: the gather with the jump flags and their scan (the host reads joff[n]); with jt_cap set the jump list; with the entries uploaded and
+// their counters zeroed the count over all hits and the scatter to the bases' steps; then the record summaries, the interval-start flags and their scan (the host reads
+// E.foff[n] and goes on with agx_launch_evidence_runs on E)
+void agx_launch_walk_span_gather(const agx_walk_span_args *, hipStream_t);
+void agx_launch_walk_span_emit(const agx_walk_span_args *, hipStream_t);
+void agx_launch_walk_span_jumps(const agx_walk_span_args *, hipStream_t);
+void agx_launch_walk_span_flags(const agx_walk_span_args *, hipStream_t);
 }

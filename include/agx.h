@@ -135,6 +135,8 @@ typedef struct {
     uint64_t n_support_events;                                   /* events the counting saw (agx_edge_support::n_events); 0 before the first counting call after a build */
     double ms_walk_evidence;                                     /* host wall time of the last agx_unit_walk_evidence, from entry to its tables being in the caller's memory */
     double ms_edge_reads;                                        /* host wall time of the last agx_unit_edge_reads, from entry to its table being in the caller's memory; 0 before the first call */
+    double ms_pair_span;                                         /* host wall time of the last agx_unit_pair_span, from entry to its table being in the caller's memory; 0 before the first call */
+    double ms_walk_span;                                         /* the same of the last agx_unit_walk_span */
 } agx_stats;
 
 /* Node/edge tables in canonical numbering (position-major, variant order), for parity tests. malloc'd; free with agx_graph_free. */
@@ -427,6 +429,45 @@ void agx_walk_evidence_free(agx_walk_evidence *e);
 /* Host only: the weak intervals as BED, one line per interval: p<unit>_<rec> <tab> base_first <tab> base_last + 1 <tab> weak <tab> 0 <tab> + <tab> dm:i:<depth_min> <tab>
  * sm:i:<step_min>, "." in place of a number that is 0xFFFFFFFF; *text is malloc'd, free it with agx_text_free. */
 int agx_walk_evidence_bed(const agx_walk_evidence *e, int unit, char **text, size_t *len);
+/* Pair span: the read pairs across each position.  A KEPT hit is one whose derived record has AGX_HF_SKIP clear (the hits that make events, §13).  Its
+ * FRAGMENT runs from f_lo, the smallest, to f_hi, the largest reference position either mate is aligned to (a simple mate: [t0, t0 + len - 1]; a mate with runs: the
+ * union of [t, t + n - 1] over its runs), whichever mate lies left; f_hi is clamped to n_pos - 1, and a kept hit with f_lo >= n_pos has no fragment and is counted in
+ * n_outside (0 for anything the loaders make).  pairs(x, y), x < y: the fragments with f_lo <= x and y <= f_hi.  span[x - pos_lo]: the fragments with f_lo <= x <= f_hi;
+ * cross[x - pos_lo] = pairs(x, x + 1) = span less the fragments that end on x (0 at n_pos - 1).  n_kept and n_outside are the unit's, n_fragments counts the fragments
+ * that meet the window.  Nothing depends on the coverage threshold, on a reprune or on the node table.  malloc'd; free with agx_pair_span_free. */
+typedef struct { uint32_t pos_lo, pos_hi; uint64_t n_kept, n_fragments, n_outside;
+                 uint32_t *span, *cross; } agx_pair_span;                            /* [pos_hi - pos_lo] each */
+/* The pair span of positions [pos_lo, pos_hi): pos_lo <= pos_hi <= n_pos (AGX_E_ARG otherwise; pos_lo == pos_hi: an empty table with the unit's n_kept and n_outside).
+ * Needs AGX_FLAG_KEEP_COUNTS (the scratch is the export's buffer) and the arrays the edge counting reads: the unit is built, not one-shot, and neither downloaded by
+ * agx_unit_download nor trimmed nor released (AGX_E_ARG with the reason); allowed after agx_unit_finish; AGX_FLAG_EDGE_SUPPORT and AGX_FLAG_KEEP_PATHS are not needed.
+ * On the device, out of the export's scratch: no allocation, about 12 bytes per position of the window; a window that does not fit goes through in sub-windows (halved
+ * until they fit; AGX_SPAN_CHUNK=<positions> forces a size), each one more pass over all hits.  Nothing is kept between calls; nothing a walk or an export reads is
+ * written; a refused call leaves the unit as it was. */
+int  agx_unit_pair_span(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, agx_pair_span *s);
+void agx_pair_span_free(agx_pair_span *s);
+/* Pair span under the records of a stretch table w (layout, checks, "graph base" and "step" exactly as agx_walk_evidence above).  The POSITION of walk id a is a for
+ * a < n_pos, else the side id's position; an id needs no node to have one, so every graph base has a span.  A step from a base at position x to one at position y has
+ * step = pairs(x, y) when y > x — it needs no edge in the node table —, else 0xFFFFFFFF, counted in n_steps_not_forward (0 for the stretches of a finish); n_jump_steps
+ * counts the steps with y > x + 1.  A base is THIN iff its span is below min_span or its step is a number below min_span; the thin intervals are maximal runs of thin
+ * bases of one record at consecutive base offsets, by (rec, first), with the smallest span and the smallest numbered step inside (min_span = 0: none).  Per record: graph
+ * bases, numbered steps, the span summed, the smallest span and the smallest numbered step, each with the smallest base offset that has it (value 0xFFFFFFFF, offset 0:
+ * none).  Tracks (want_tracks): pos, span and step per graph base of the records [rec_lo, rec_hi) in stretch order, track_off as in agx_walk_evidence.
+ * malloc'd; free with agx_walk_span_free. */
+typedef struct { uint32_t n_recs, n_intervals; uint64_t n_graph_bases, n_steps, n_jump_steps, n_steps_not_forward;
+                 /* [n_recs] */ uint64_t *rec_graph_bases, *rec_steps, *rec_span_sum; uint32_t *rec_span_min, *rec_span_min_at, *rec_step_min, *rec_step_min_at;
+                 /* [n_intervals] */ uint32_t *iv_rec, *iv_first, *iv_last, *iv_span_min, *iv_step_min;
+                 /* tracks, want_tracks only */ uint32_t rec_lo, rec_hi; uint64_t n_track; uint64_t *track_off; uint32_t *pos, *span, *step; } agx_walk_span;
+/* The pair span under the records of w: the table checks of agx_unit_walk_evidence and the preconditions of agx_unit_pair_span (AGX_E_ARG with the reason).  On the device
+ * out of the export's scratch: the whole unit's span and cross (8 bytes per position, made as agx_unit_pair_span makes them, in sub-windows where need be) beside the
+ * arrays of one chunk of graph bases (AGX_SPAN_BASE_CHUNK=<bases> forces a chunk size); a unit whose fixed part does not fit is AGX_E_UNSUPPORTED.  The jumps of a chunk
+ * go to the host once, are sorted and merged there, and cost one more pass over all hits (skipped for a chunk without jumps): the cost of a table with jumps grows with
+ * the number of chunks — a forced chunk of 64 bases means up to one pass over the hits per 64 bases —, and inside the pass a hit walks every entry whose x lies in its fragment.  Nothing is kept between calls; nothing a
+ * walk or an export reads is written; a refused call leaves the unit as it was. */
+int  agx_unit_walk_span(agx_unit *u, const agx_walk_paths *w, uint32_t min_span, uint32_t want_tracks, uint32_t rec_lo, uint32_t rec_hi, agx_walk_span *e);
+void agx_walk_span_free(agx_walk_span *e);
+/* Host only: the thin intervals as BED, one line per interval: p<unit>_<rec> <tab> base_first <tab> base_last + 1 <tab> thin <tab> 0 <tab> + <tab> pm:i:<span_min> <tab>
+ * jm:i:<step_min>, "." in place of a number that is 0xFFFFFFFF; *text is malloc'd, free it with agx_text_free. */
+int  agx_walk_span_bed(const agx_walk_span *e, int unit, char **text, size_t *len);
 void agx_unitigs_free(agx_unitigs *t);
 /* Host only: the S and L lines of GFA 1.0 for unit `unit` (no header line), as DESIGN.md §11 defines them; *text is malloc'd, free it with agx_text_free. */
 int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len);
