@@ -182,7 +182,7 @@ __global__ void __launch_bounds__(256) agx_k_sp_flags(agx_walk_span_args A) {
 }
 
 inline dim3 sp_grid(agx_u32 n) { return dim3((n + 255u) / 256u); }
-inline agx_u32 sp_hit_blocks(agx_u32 n_hits) { const agx_u32 b = (n_hits + 255u) / 256u; return b < 1u ? 1u : b > AGX_SPAN_BLOCKS ? AGX_SPAN_BLOCKS : b; }
+inline agx_u32 sp_hit_blocks(agx_u32 n_hits) { const agx_u32 b = n_hits / 256u + (n_hits % 256u ? 1u : 0u); return b < 1u ? 1u : b > AGX_SPAN_BLOCKS ? AGX_SPAN_BLOCKS : b; }      // (n_hits + 255 would wrap within 255 of 2^32)
 
 }  // namespace
 

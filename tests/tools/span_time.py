@@ -6,8 +6,9 @@
   - the shapes: hits, kept hits, fragments, the largest span; records, stretches, graph bases, numbered steps, jump steps, steps not forward, thin intervals;
   - for comparison in the same trace, one Unit.edge_support() (agx_k_edge_support) and one Unit.walk_evidence() (agx_k_ev_gather) — the unit is created with edge_support
     for that alone: the pair span does not need it;
-  - consistency at this size (the model's loops are for the small units of the tests): cross <= span, cross at the last position is 0, a window equals the whole
-    unit's slice, forced sub-windows and forced base chunks equal the plain calls.
+  - the whole unit's span, cross and counts against tests/span_wide.py (sorted endpoints, fast at this size) on the front Unit.front() copies out: a reference, where the
+    model's loops are for the small units of the tests;
+  - consistency: cross <= span, cross at the last position is 0, a window equals the whole unit's slice, forced sub-windows and forced base chunks equal the plain calls.
 Prints every value.  Not a test: nothing here asserts a time.
 Usage (GPU box): python tests/tools/span_time.py [--work DIR]      (under rocprofv3 --kernel-trace --stats for the kernels of agx_span.hip)"""
 import argparse
@@ -24,6 +25,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import harness as H          # noqa: E402
 import aligngraph_amd as A   # noqa: E402
 import span_model as SM      # noqa: E402
+import span_wide as SW       # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--work", default="/tmp/agx_span_time")
@@ -61,6 +63,11 @@ s1 = u.stats()
 print("first call: ms_pair_span %.3f; device_bytes %d" % (s1["ms_pair_span"], s1["device_bytes"]), flush=True)
 print("pair span: %d kept hits, %d fragments, %d outside; largest span %d, mean span %.2f; cross <= span everywhere: %s; cross at the last position %d" %
       (first["n_kept"], first["n_fragments"], first["n_outside"], int(first["span"].max()), float(first["span"].mean()), bool((first["cross"] <= first["span"]).all()), int(first["cross"][-1])), flush=True)
+t_front, front = ms(u.front)
+t_ref, ref = ms(lambda: SW.pair_span({k: front[k] for k in ("n_pos", "dhit", "runs")}))
+print("the whole unit against span_wide on the front of %d hit records and %d runs (front %.0f ms, reference %.0f ms): first differing field %s; equal to the wide reference: %s" %
+      (len(front["dhit"]), len(front["runs"]), t_front, t_ref, SM.same_span(first, ref), SM.same_span(first, ref) is None), flush=True)
+del front
 whole, window, wall = [], [], []
 mid = (n_pos // 2, n_pos // 2 + 100000)
 for _ in range(a.rounds):
