@@ -32,6 +32,7 @@ EXPORTS = [
     "agx_unit_walk_evidence", "agx_walk_evidence_free", "agx_walk_evidence_bed",
     "agx_unit_edge_reads", "agx_edge_reads_free", "agx_edge_reads_tsv",
     "agx_unit_pair_span", "agx_pair_span_free", "agx_unit_walk_span", "agx_walk_span_free", "agx_walk_span_bed",
+    "agx_unit_mate_links", "agx_mate_links_free", "agx_mate_links_tsv",
     "agx_test_scan", "agx_test_zero", "agx_test_copy_out",
 ]
 
@@ -143,6 +144,16 @@ class WalkSpan(ctypes.Structure):
                [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("pos", "span", "step")]
 
 
+class MateLinks(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_kept", "n_outside", "n_fragments", "n_unowned", "n_inside", "n_open", "n_link_pairs", "n_links_all", "n_owned", "n_shadowed")] + \
+               [(n, ctypes.c_uint32) for n in ("n_recs", "n_links", "n_passes", "n_slots")] + [("ms", ctypes.c_double)] + \
+               [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("rec_inside", "rec_open_left", "rec_open_right", "rec_links_out", "rec_links_in", "a", "b", "n_pairs")] + \
+               [("len_sum", ctypes.POINTER(ctypes.c_uint64))] + [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("lo_min", "lo_max", "hi_min", "hi_max")]
+
+
+TOTALS_LINKS = ("n_kept", "n_outside", "n_fragments", "n_unowned", "n_inside", "n_open", "n_link_pairs", "n_links_all", "n_owned", "n_shadowed", "n_passes", "n_slots")
+REC_LINKS = ("rec_inside", "rec_open_left", "rec_open_right", "rec_links_out", "rec_links_in")
+LINK_LINKS = ("a", "b", "n_pairs", "len_sum", "lo_min", "lo_max", "hi_min", "hi_max")
 REC_SPAN = ("rec_graph_bases", "rec_steps", "rec_span_sum", "rec_span_min", "rec_span_min_at", "rec_step_min", "rec_step_min_at")
 IV_SPAN = ("iv_rec", "iv_first", "iv_last", "iv_span_min", "iv_step_min")
 REC_EVIDENCE = ("rec_graph_bases", "rec_steps", "rec_depth_sum", "rec_depth_min", "rec_depth_min_at", "rec_step_min", "rec_step_min_at")
@@ -301,6 +312,10 @@ def lib():
         L.agx_walk_span_free.argtypes = [ctypes.POINTER(WalkSpan)]
         L.agx_walk_span_free.restype = None
         L.agx_walk_span_bed.argtypes = [ctypes.POINTER(WalkSpan), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+        L.agx_unit_mate_links.argtypes = [ctypes.c_void_p, ctypes.POINTER(WalkPaths), ctypes.c_uint32, ctypes.POINTER(MateLinks)]
+        L.agx_mate_links_free.argtypes = [ctypes.POINTER(MateLinks)]
+        L.agx_mate_links_free.restype = None
+        L.agx_mate_links_tsv.argtypes = [ctypes.POINTER(MateLinks), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         L.agx_text_free.restype = None
         L.agx_unit_edge_reads.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EdgeReads)]
         L.agx_edge_reads_free.argtypes = [ctypes.POINTER(EdgeReads)]
@@ -727,6 +742,32 @@ class Unit:
         finally:
             lib().agx_walk_span_free(ctypes.byref(e))
 
+    def mate_links(self, w=None, min_pairs=1):
+        """The read pairs that join two records of a stretch table (agx_unit_mate_links; needs keep_counts): w is a dict like walk_paths() returns (None: walk_paths()
+        itself).  The totals n_kept, n_outside, n_fragments, n_unowned, n_inside, n_open, n_link_pairs, n_links_all, n_owned, n_shadowed; per record rec_inside,
+        rec_open_left, rec_open_right, rec_links_out, rec_links_in; per link with n_pairs >= min_pairs, by (a, b): a, b, n_pairs, len_sum, lo_min, lo_max, hi_min, hi_max;
+        n_passes and n_slots: the passes over the hits the call took and the slots of its table; ms: the call's host wall time."""
+        import numpy as np
+        if w is None:
+            w = self.walk_paths()
+        ws, _keep = _walk_paths_struct(w)
+        if not 0 <= int(min_pairs) <= 0xFFFFFFFF:
+            raise AgxError(AGX_E_ARG, "mate links: the threshold is an unsigned 32-bit number")
+        l = MateLinks()
+        self._check(lib().agx_unit_mate_links(self._h, ctypes.byref(ws), int(min_pairs), ctypes.byref(l)))
+        try:
+            def arr(p, n, dt):
+                return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
+            out = {k: int(getattr(l, k)) for k in TOTALS_LINKS}
+            out["ms"] = float(l.ms)
+            for k in REC_LINKS:
+                out[k] = arr(getattr(l, k), l.n_recs, "uint32")
+            for k in LINK_LINKS:
+                out[k] = arr(getattr(l, k), l.n_links, "uint64" if k == "len_sum" else "uint32")
+            return out
+        finally:
+            lib().agx_mate_links_free(ctypes.byref(l))
+
     def gfa(self, unit=0, region=None, min_coverage=None, edge_support=False):
         """GFA 1.0 S and L lines of the unit's unitigs, segments named u<unit>_<pos>_<var> (no header line); region and min_coverage as in unitigs().
         edge_support=True: every L line also carries RC:i:<events that name the link's edge> (agx_unitigs_gfa_support)."""
@@ -858,6 +899,24 @@ def span_bed(e, unit=0):
     rc = lib().agx_walk_span_bed(ctypes.byref(s), unit, ctypes.byref(p), ctypes.byref(n))
     if rc != AGX_OK:
         raise AgxError(rc, "agx_walk_span_bed: the interval table is inconsistent")
+    try:
+        return ctypes.string_at(p, n.value) if n.value else b""
+    finally:
+        lib().agx_text_free(p)
+
+
+def links_tsv(l, unit=0):
+    """Text of the links of a dict like Unit.mate_links() returns, one line per link (agx_mate_links_tsv; host only, needs no device)."""
+    import numpy as np
+    keep = {k: np.ascontiguousarray(l[k], dtype="uint64" if k == "len_sum" else "uint32") for k in LINK_LINKS}
+    s = MateLinks()
+    s.n_recs, s.n_links = len(l["rec_inside"]), len(keep["a"])
+    for k, a in keep.items():
+        setattr(s, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64 if k == "len_sum" else ctypes.c_uint32)))
+    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
+    rc = lib().agx_mate_links_tsv(ctypes.byref(s), unit, ctypes.byref(p), ctypes.byref(n))
+    if rc != AGX_OK:
+        raise AgxError(rc, "agx_mate_links_tsv: the link table is inconsistent")
     try:
         return ctypes.string_at(p, n.value) if n.value else b""
     finally:

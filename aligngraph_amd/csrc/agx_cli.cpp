@@ -52,6 +52,9 @@ struct Options {
     // --spanOut <file> [--spanMin n]: the thin intervals of every unit's pre-extended records — too few read pairs across a base or a step — as BED (agx_unit_walk_span,
     // DESIGN.md §16); the threshold defaults to 2
     int tagSpan = 0; string span; int tagSpanMin = 0, spanMin = 2;
+    // --linksOut <file> [--linksMin n]: the links between every unit's pre-extended records — the read pairs with one end under one record and the other under another — as
+    // TSV (agx_unit_mate_links); the threshold defaults to 2 pairs
+    int tagLinks = 0; string links; int tagLinksMin = 0, linksMin = 2;
     // --graphEdgeReads <file> [--graphEdgeReadsMax n]: the edges of support <= n (default 2) of every unit — with --graphRegion: of that unit's positions [lo, hi) — with the
     // numbers of the hits behind them, as TSV (agx_unit_edge_reads)
     int tagEdgeReads = 0; string edgeReads; int tagEdgeReadsMax = 0, edgeReadsMax = 2;
@@ -147,6 +150,8 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--evidenceMinSupport") { integer(i, o.tagEvSupport, o.evSupport); if (o.evSupport < 0) die_usage(); }
         else if (b == "--spanOut") outfile(i, o.tagSpan, o.span);
         else if (b == "--spanMin") { integer(i, o.tagSpanMin, o.spanMin); if (o.spanMin < 0) die_usage(); }
+        else if (b == "--linksOut") outfile(i, o.tagLinks, o.links);
+        else if (b == "--linksMin") { integer(i, o.tagLinksMin, o.linksMin); if (o.linksMin < 0) die_usage(); }
         else if (b == "--kMer") integer(i, o.tagK, o.k);
         else if (b == "--insertVariation") integer(i, o.tagIV, o.insertVariation);
         else if (b == "--coverage") integer(i, o.tagCov, o.coverage);
@@ -164,6 +169,7 @@ void parse_params(const string &file, Options &o) {
     if (o.tagEdgeReadsMax && !o.tagEdgeReads) die_usage();
     if ((o.tagEvDepth || o.tagEvSupport) && !o.tagEvidence) die_usage();
     if (o.tagSpanMin && !o.tagSpan) die_usage();
+    if (o.tagLinksMin && !o.tagLinks) die_usage();
 }
 
 // tmp/_evidence.<u>.d<depth>.s<support>.bed, the thresholds in the name: a --resume run merges only intervals that were made under its own settings
@@ -172,6 +178,9 @@ string evidence_part_path(const Options &o, int u) { return "tmp/_evidence." + i
 
 // tmp/_span.<u>.m<min>.bed, the threshold in the name: a --resume run merges only intervals that were made under its own setting
 string span_part_path(const Options &o, int u) { return "tmp/_span." + itoa(u) + ".m" + itoa(o.spanMin) + ".bed"; }
+
+// tmp/_links.<u>.m<min>.tsv, the threshold in the name: a --resume run merges only links that were made under its own setting
+string links_part_path(const Options &o, int u) { return "tmp/_links." + itoa(u) + ".m" + itoa(o.linksMin) + ".tsv"; }
 
 // tmp/_edge_reads.<u>.m<max>.tsv, with the region in the name when one is given: a --resume run merges only lines that were made under its own settings
 string edge_reads_part_path(const Options &o, int u) {
@@ -1211,9 +1220,9 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                 // (--graphEdgeSupport: the counting reads the front of the build, which a one-shot unit does not promise to keep — such a run's units are ordinary ones, with the edge counters)
                 // (--evidenceOut: ordinary units too, with the counts, the stretches and the edge counters: the evidence is asked for after the finish)
                 // (--graphEdgeReads: as for --graphEdgeSupport, with the counts as well: the listing's scratch is the export's buffer)
-                // (--spanOut: ordinary units with the counts and the stretches, no edge counters: the pass reads the hit records behind the finish)
-                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, (o.graphSupport || o.tagEvidence || o.tagEdgeReads ? AGX_FLAG_EDGE_SUPPORT : o.tagSpan ? 0u : AGX_FLAG_ONE_SHOT) |
-                                (o.tagGraph || o.tagEvidence || o.tagEdgeReads || o.tagSpan ? AGX_FLAG_KEEP_COUNTS : 0u) | (o.graphPaths || o.tagEvidence || o.tagSpan ? AGX_FLAG_KEEP_PATHS : 0u)};
+                // (--spanOut, --linksOut: ordinary units with the counts and the stretches, no edge counters: the pass reads the hit records behind the finish)
+                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, (o.graphSupport || o.tagEvidence || o.tagEdgeReads ? AGX_FLAG_EDGE_SUPPORT : o.tagSpan || o.tagLinks ? 0u : AGX_FLAG_ONE_SHOT) |
+                                (o.tagGraph || o.tagEvidence || o.tagEdgeReads || o.tagSpan || o.tagLinks ? AGX_FLAG_KEEP_COUNTS : 0u) | (o.graphPaths || o.tagEvidence || o.tagSpan || o.tagLinks ? AGX_FLAG_KEEP_PATHS : 0u)};
                 agx_result r; memset(&r, 0, sizeof r); char err[512]; err[0] = 0;
                 agx_unit *un = nullptr;
                 int rc = agx_unit_create(&p, &un);
@@ -1269,7 +1278,7 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                     }
                     agx_text_free(text);
                 }
-                bool wanted = false; if (rc == AGX_OK) { std::lock_guard<std::mutex> g(mem_mu); wanted = waiting[d] > 0 && !o.tagEvidence && !o.tagSpan; }      // (--evidenceOut, --spanOut: never trimmed before the finish, they read the unit's arrays behind it)
+                bool wanted = false; if (rc == AGX_OK) { std::lock_guard<std::mutex> g(mem_mu); wanted = waiting[d] > 0 && !o.tagEvidence && !o.tagSpan && !o.tagLinks; }      // (--evidenceOut, --spanOut, --linksOut: never trimmed before the finish, they read the unit's arrays behind it)
                 if (rc == AGX_OK && wanted) {      // r05: somebody waits for room on this device — the whole download first, then what the walk cannot ask the device for goes back: the next unit is admitted while this one is walked on the host
                     rc = agx_unit_download(un);
                     uint64_t freed = 0;
@@ -1311,6 +1320,20 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                     agx_walk_paths_free(&wp); agx_walk_span_free(&sp);
                     if (rc == AGX_OK) {
                         FILE *f = fopen(span_part_path(o, u).c_str(), "wb"); bool ok = f != nullptr;
+                        if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
+                        if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
+                    }
+                    agx_text_free(text);
+                }
+                if (rc == AGX_OK && o.tagLinks) {      // --linksOut: the links between the records just written, into tmp/_links.<u>.m<min>.tsv
+                    agx_walk_paths wp; agx_mate_links ml; char *text = nullptr; size_t len = 0;
+                    memset(&ml, 0, sizeof ml);
+                    rc = agx_unit_walk_paths(un, &wp);
+                    if (rc == AGX_OK) rc = agx_unit_mate_links(un, &wp, (uint32_t)o.linksMin, &ml);
+                    if (rc == AGX_OK) { rc = agx_mate_links_tsv(&ml, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "TSV FORMATTING FAILED"); }
+                    agx_walk_paths_free(&wp); agx_mate_links_free(&ml);
+                    if (rc == AGX_OK) {
+                        FILE *f = fopen(links_part_path(o, u).c_str(), "wb"); bool ok = f != nullptr;
                         if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
                         if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
                     }
@@ -1460,6 +1483,20 @@ int main(int argc, char **argv) {
         if (g) ok = (fclose(g) == 0) && ok;
         if (!ok) die("CANNOT OPEN FILE!");
         stage("span output");
+    }
+    if (o.tagLinks) {                                                         // --linksOut: every unit's links, in unit order (a --resume run finds the earlier units' files in tmp/)
+        FILE *g = fopen(o.links.c_str(), "wb");
+        bool ok = g != nullptr;
+        for (int u = 0; ok && u < units; u++) {
+            FILE *f = fopen(links_part_path(o, u).c_str(), "rb");
+            if (!f) { ok = false; break; }
+            char buf[1 << 16]; size_t n;
+            while (ok && (n = fread(buf, 1, sizeof buf, f)) > 0) ok = fwrite(buf, 1, n, g) == n;
+            fclose(f);
+        }
+        if (g) ok = (fclose(g) == 0) && ok;
+        if (!ok) die("CANNOT OPEN FILE!");
+        stage("links output");
     }
     refinement(o, units, genomeIds, contigIds);
     stage("refinement");

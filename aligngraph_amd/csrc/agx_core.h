@@ -1490,6 +1490,33 @@ AGX_HD void agx_span_jump_walk(const agx_u32 *e_x, const agx_u32 *e_y, agx_u32 n
     }
 }
 
+// ---- mate links: the read pairs that join two records (agx_unit_mate_links) --------------------------------------
+// own[x] is the smallest record with a graph base at position x (NONE: nobody).  A fragment [f_lo, f_hi] (above) with A = own[f_lo], B = own[f_hi] falls into one class:
+enum { AGX_LINKS_UNOWNED = 0, AGX_LINKS_INSIDE = 1, AGX_LINKS_OPEN_RIGHT = 2, AGX_LINKS_OPEN_LEFT = 3, AGX_LINKS_LINK = 4 };
+AGX_HD int agx_links_class(agx_u32 own_lo, agx_u32 own_hi) {
+    if (own_lo == AGX_NONE) return own_hi == AGX_NONE ? AGX_LINKS_UNOWNED : AGX_LINKS_OPEN_LEFT;      // open to the left: counted on the record under the right end
+    if (own_hi == AGX_NONE) return AGX_LINKS_OPEN_RIGHT;
+    return own_lo == own_hi ? AGX_LINKS_INSIDE : AGX_LINKS_LINK;
+}
+// The key of link (A, B), A the record under the LEFT end: (A, B) and (B, A) are two links.  A != B and a record is never NONE, so no key is all ones: the empty slot.
+#define AGX_LINKS_EMPTY (~0ull)
+AGX_HD unsigned long long agx_links_key(agx_u32 a, agx_u32 b) { return ((unsigned long long)a << 32) | b; }
+// the home slot of a key in a table of 2^log2_slots slots (1 <= log2_slots <= 31): a fixed multiply-shift, the same on the host and on the device
+AGX_HD agx_u32 agx_links_hash(unsigned long long key, agx_u32 log2_slots) { return (agx_u32)((key * 0x9E3779B97F4A7C15ull) >> (64u - log2_slots)); }
+// The probe loop, linear, over `slots` = 2^log2_slots slots, at most `slots` probes.  claim(slot, key) puts key into the slot if it is empty and returns what the slot held
+// before (the kernel: a 64-bit compare-and-swap; the replay: a plain store); a slot that was empty or held the key already is the key's: accumulate(slot).  No slot left:
+// give_up().
+template <class CLAIM, class ACC, class GIVE_UP>
+AGX_HD void agx_links_insert(unsigned long long key, agx_u32 slots, agx_u32 log2_slots, CLAIM claim, ACC accumulate, GIVE_UP give_up) {
+    agx_u32 s = agx_links_hash(key, log2_slots) & (slots - 1u);
+    for (agx_u32 p = 0; p < slots; p++) {
+        const unsigned long long was = claim(s, key);
+        if (was == AGX_LINKS_EMPTY || was == key) { accumulate(s); return; }
+        s = (s + 1u) & (slots - 1u);
+    }
+    give_up();
+}
+
 // ---- walk preparation: alive-node renumbering and forced-run flags -------------------------------------------------------
 // The path walk (AG:1954-2204) only ever stands on nodes that survived the coverage prune.  After the edge sweep the
 // surviving ("alive") nodes get walk ids ("aid") laid out so that the main strand of the graph is contiguous:

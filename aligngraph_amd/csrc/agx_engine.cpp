@@ -1100,6 +1100,22 @@ size_t walk_span_layout(size_t n_st, size_t n_recs, size_t n_pos, size_t sub, si
     }
     return std::max(take.bytes(), pass.bytes());
 }
+// The scratch of the mate links (agx_unit_mate_links, agx_links.hip), from the front of the same buffer.  The whole call's: the uploaded stretch table as evidence_layout
+// has it, own (4 bytes per position), the five per-record counters and the partials of the pass and of the shadow count.  One pass's: the table of `slots` slots as a
+// structure of arrays (36 bytes per slot: key and length sum of 8, count and four extents of 4), the kept slots' flags with their scan, and the compacted output at its
+// worst (every slot kept).  80 bytes per slot.
+size_t links_layout(size_t n_st, size_t n_recs, size_t n_pos, size_t parts, size_t sparts, size_t slots, char *base, agx_links_args *A) {
+    Carve take{base};
+    agx_links_args T{}; agx_links_args &L = A ? *A : T;
+    take(L.words, 8);
+    take(L.T.st_first, n_st); take(L.T.st_base, n_st); take(L.T.st_rec, n_st); take(L.T.st_pre, n_st + 1); take(L.T.st_join, n_st + 1);
+    take(L.own, n_pos); take(L.rec, 5 * n_recs); take(L.part, 6 * parts); take(L.spart, 2 * sparts);
+    take(L.t_key, slots); take(L.t_len, slots); take(L.t_n, slots); take(L.t_lo_min, slots); take(L.t_lo_max, slots); take(L.t_hi_min, slots); take(L.t_hi_max, slots);
+    take(L.flag, slots + 1); take(L.off, slots + 1); take(L.scan_tmp, scan_words(slots + 1, 1024) + 16);
+    take(L.o_key, slots); take(L.o_len, slots); take(L.o_n, slots); take(L.o_lo_min, slots); take(L.o_lo_max, slots); take(L.o_hi_min, slots); take(L.o_hi_max, slots);
+    if (base) { L.n_part = (agx_u32)parts; L.n_spart = (agx_u32)sparts; L.out_cap = (agx_u32)slots; }
+    return take.bytes();
+}
 inline bool keeps_paths(const agx_unit *u) { return (u->prm.flags & (AGX_FLAG_KEEP_PATHS | AGX_FLAG_KEEP_COUNTS)) == (AGX_FLAG_KEEP_PATHS | AGX_FLAG_KEEP_COUNTS); }
 // The export buffer of a unit that keeps paths: every export of such a unit takes the same size — the larger of the two export layouts at their worst, and behind it (at `map_at`)
 // the id map's scratch for a whole-window map — so that exports of any kind in any order never take the buffer twice.
@@ -3203,6 +3219,129 @@ void agx_walk_span_free(agx_walk_span *e) {
     free(e->iv_rec); free(e->iv_first); free(e->iv_last); free(e->iv_span_min); free(e->iv_step_min);
     free(e->track_off); free(e->pos); free(e->span); free(e->step);
     memset(e, 0, sizeof *e);
+}
+
+// Mate links: the table is checked and flattened as for the evidence and uploaded; own, the shadow count and the first pass over all hits (the per-record
+// counters and the totals) go in one queue; every pass ends in one host round trip (the error and overflow words and the kept count) and, if it fit, a second (its links).
+// Each pass is one more read of all hits: a table that fits the links needs one.
+static void mate_links(agx_unit *u, const agx_walk_paths &w, uint32_t min_pairs, agx_mate_links *l) {
+    const double t0 = now_ms();
+    span_check(u, "mate links");
+    const FlatTable F = check_walk_table(u, w, false, 0, 0, "mate links");
+    const size_t nr = F.nr, ns = F.ns;
+    size_t forced = 0;
+    if (const char *env = getenv("AGX_LINKS_SLOTS")) {
+        char *end = nullptr; const unsigned long long v = strtoull(env, &end, 10);
+        if (!*env || *end || v < 2 || v > (1ull << 31) || (v & (v - 1))) throw Error{E_ARG, std::string("mate links: AGX_LINKS_SLOTS=") + env + " is not a power of two from 2 to 2^31"};
+        forced = (size_t)v;
+    }
+    auto mk = [](auto *&p, size_t n) { using T = std::remove_reference_t<decltype(*p)>; p = (T *)calloc(n + 1, sizeof(T)); if (!p) throw Error{E_ARG, "out of host memory"}; };
+    l->n_recs = (uint32_t)nr;
+    mk(l->rec_inside, nr); mk(l->rec_open_left, nr); mk(l->rec_open_right, nr); mk(l->rec_links_out, nr); mk(l->rec_links_in, nr);
+    Export E(u);
+    const agx_u32 n_pos = E.n_pos;
+    E.open(unitig_layout(E.cap, n_pos, E.n_ovf, nullptr, nullptr, nullptr));      // (the buffer every export of the unit takes: the room the upload reserved)
+    const size_t avail = u->d_ut.n, parts = agx_links_partials((agx_u32)u->nh), sparts = agx_links_partials((agx_u32)std::max<uint64_t>(F.total, n_pos));
+    auto bytes_of = [&](size_t slots) { return links_layout(ns, nr, n_pos, parts, sparts, slots, nullptr, nullptr); };
+    // the natural size: twice the keys there can be at most — a key per hit, a key per ordered pair of records — as a power of two
+    const unsigned long long most = std::min<unsigned long long>(u->nh, (unsigned long long)nr * (nr ? nr - 1 : 0));
+    size_t slots = 2;
+    while (slots < 2 * most && slots < ((size_t)1 << 31)) slots <<= 1;
+    if (forced) slots = forced;
+    else while (slots > 2 && bytes_of(slots) > avail) slots >>= 1;
+    if (bytes_of(slots) > avail)
+        throw Error{E_UNSUPPORTED, "mate links: own (" + std::to_string(n_pos) + " positions), the stretch table (" + std::to_string(ns) + " stretches, " + std::to_string(nr) + " records) and a table of " +
+                                   std::to_string(slots) + " slots do not fit the export's scratch of " + std::to_string(avail) + " bytes"};
+    agx_u32 log2_slots = 0; while (((size_t)1 << log2_slots) < slots) log2_slots++;
+    agx_links_args A{};
+    links_layout(ns, nr, n_pos, parts, sparts, slots, u->d_ut.p, &A);
+    agx_evidence_tab &T = A.T;
+    T.n_st = (agx_u32)ns; T.n_flat = (agx_u32)F.total;
+    T.a_nid = u->d_a_nid.p; T.n_ids = u->n_ids; T.pool_cap = E.cap; T.n_counts = u->d_counts.p; T.n_next = u->d_next.p; T.n_flags = u->d_flags.p; T.ovf = u->d_ovf.p; T.n_ovf = E.n_ovf;
+    T.e_cnt = nullptr; T.ovf_cnt = nullptr;
+    A.dhit = u->d_dhit.p; A.runs = u->d_runs.p; A.n_hits = (agx_u32)u->nh; A.n_runs = (agx_u32)u->n_runs; A.n_pos = n_pos; A.side_xpos = u->d_side_xpos.p;
+    A.n_recs = (agx_u32)nr; A.min_pairs = min_pairs; A.slots = (agx_u32)slots; A.log2_slots = log2_slots;
+    auto up = [&](const void *dst, const void *src, size_t b) { if (b) HIP_OK(hipMemcpyAsync(const_cast<void *>(dst), src, b, hipMemcpyHostToDevice, E.s)); };
+    up(T.st_first, F.st_first.data(), ns * 4); up(T.st_base, F.st_base.data(), ns * 4); up(T.st_rec, F.st_rec.data(), ns * 4); up(T.st_pre, F.st_pre.data(), (ns + 1) * 4); up(T.st_join, F.st_join.data(), ns + 1);
+    std::vector<unsigned long long> keys, lens, g_key, g_len; std::vector<agx_u32> nums[5], g_num[5];      // n_pairs, lo_min, lo_max, hi_min, hi_max
+    uint64_t distinct = 0;
+    agx_u32 stuck = 0, stuck_dropped = 0;
+    const long passes = links_plan((agx_u32)nr, [&](agx_u32 a_lo, agx_u32 a_hi, bool first) {
+        A.a_lo = a_lo; A.a_hi = a_hi; A.count = first ? 1u : 0u; A.init_all = A.count;
+        E.fill(A.words, 0, 32);
+        if (first) { E.fill(A.part, 0, 6 * parts * 4); E.fill(A.spart, 0, 2 * sparts * 4); }
+        agx_launch_links_init(&A, E.s);
+        if (first) agx_launch_links_own(&A, E.s);
+        agx_launch_links_pass(&A, E.s);
+        agx_u32 wd[3] = {0, 0, 0}, kept = 0;
+        E.read(wd, A.words, 12); E.read(&kept, A.off + slots, 4);
+        E.sync();
+        HIP_OK(hipGetLastError());
+        if (wd[0]) throw Error{E_DEVICE, "internal: mate links: the owners or the kept slots are inconsistent (error word " + std::to_string(wd[0]) + ")"};
+        if (wd[1]) { stuck_dropped = wd[1]; return false; }      // the pass is discarded
+        if (wd[2] > slots || kept > wd[2]) throw Error{E_DEVICE, "internal: mate links: " + std::to_string(kept) + " kept of " + std::to_string(wd[2]) + " slots in use of " + std::to_string(slots)};
+        distinct += wd[2];
+        if (kept) {
+            g_key.resize(kept); g_len.resize(kept);
+            E.read(g_key.data(), A.o_key, (size_t)kept * 8); E.read(g_len.data(), A.o_len, (size_t)kept * 8);
+            agx_u32 *src[5] = {A.o_n, A.o_lo_min, A.o_lo_max, A.o_hi_min, A.o_hi_max};
+            for (int k = 0; k < 5; k++) { g_num[k].resize(kept); E.read(g_num[k].data(), src[k], (size_t)kept * 4); }
+            E.sync();
+            keys.insert(keys.end(), g_key.begin(), g_key.end()); lens.insert(lens.end(), g_len.begin(), g_len.end());
+            for (int k = 0; k < 5; k++) nums[k].insert(nums[k].end(), g_num[k].begin(), g_num[k].end());
+        }
+        return true;
+    }, &stuck);
+    if (passes < 0)
+        throw Error{E_UNSUPPORTED, "mate links: the links that leave record " + std::to_string(stuck) + " alone do not fit a table of " + std::to_string(slots) + " slots (" + std::to_string(stuck_dropped) +
+                                   " pairs found none); the scratch holds no larger one"};
+    {   // the counters and the totals: the first pass's, whether it fit or not — they never depended on the table, and the later passes added to none of them
+        std::vector<agx_u32> part(6 * parts), spart(2 * sparts), rec(5 * nr + 1);
+        E.read(part.data(), A.part, part.size() * 4); E.read(spart.data(), A.spart, spart.size() * 4);
+        if (nr) E.read(rec.data(), A.rec, 5 * nr * 4);
+        E.sync();
+        uint64_t t[6] = {0, 0, 0, 0, 0, 0};
+        for (size_t i = 0; i < parts; i++) for (int k = 0; k < 6; k++) t[k] += part[6 * i + k];
+        for (size_t i = 0; i < sparts; i++) { l->n_shadowed += spart[2 * i]; l->n_owned += spart[2 * i + 1]; }
+        l->n_kept = t[0]; l->n_outside = t[1]; l->n_fragments = t[0] - t[1]; l->n_unowned = t[2]; l->n_inside = t[3]; l->n_open = t[4]; l->n_link_pairs = t[5];
+        if (t[1] > t[0] || t[2] + t[3] + t[4] + t[5] != l->n_fragments)
+            throw Error{E_DEVICE, "internal: mate links: the classes (" + std::to_string(t[2]) + " + " + std::to_string(t[3]) + " + " + std::to_string(t[4]) + " + " + std::to_string(t[5]) +
+                                  ") do not add up to the " + std::to_string(l->n_fragments) + " fragments"};
+        uint32_t *dst[5] = {l->rec_inside, l->rec_open_left, l->rec_open_right, l->rec_links_out, l->rec_links_in};
+        for (int k = 0; k < 5; k++) if (nr) memcpy(dst[k], rec.data() + k * nr, nr * 4);
+    }
+    const size_t nl = keys.size();
+    if (nl >= 0xFFFFFFFFull) throw Error{E_UNSUPPORTED, "mate links: 2^32 links or more"};
+    // the ranges are disjoint in A: sorting the concatenated lists by (A, B) is all the merge there is
+    std::vector<size_t> order(nl);
+    for (size_t i = 0; i < nl; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return keys[a] < keys[b]; });
+    for (size_t i = 1; i < nl; i++) if (keys[order[i - 1]] == keys[order[i]]) throw Error{E_DEVICE, "internal: mate links: a link came out of two slots"};
+    l->n_links = (uint32_t)nl; l->n_links_all = distinct; l->n_passes = (uint32_t)passes; l->n_slots = (uint32_t)slots;
+    mk(l->a, nl); mk(l->b, nl); mk(l->n_pairs, nl); mk(l->len_sum, nl); mk(l->lo_min, nl); mk(l->lo_max, nl); mk(l->hi_min, nl); mk(l->hi_max, nl);
+    for (size_t i = 0; i < nl; i++) {
+        const size_t j = order[i];
+        l->a[i] = (uint32_t)(keys[j] >> 32); l->b[i] = (uint32_t)keys[j]; l->len_sum[i] = lens[j];
+        l->n_pairs[i] = nums[0][j]; l->lo_min[i] = nums[1][j]; l->lo_max[i] = nums[2][j]; l->hi_min[i] = nums[3][j]; l->hi_max[i] = nums[4][j];
+    }
+    l->ms = now_ms() - t0;
+    if (g_trace) fprintf(stderr, "[agx trace] unit %p mate links (min %u): %ld passes, %zu slots, %llu distinct keys, %zu kept links\n", (void *)u, min_pairs, passes, slots, (unsigned long long)distinct, nl);
+    trace(u, "mate_links", t0, u->nh);
+}
+
+int agx_unit_mate_links(agx_unit *u, const agx_walk_paths *w, uint32_t min_pairs, agx_mate_links *l) {
+    if (!u || !w || !l) return AGX_E_ARG;
+    memset(l, 0, sizeof *l);
+    const int rc = guarded(u, [&] { mate_links(u, *w, min_pairs, l); });
+    if (rc != AGX_OK) agx_mate_links_free(l);
+    return rc;
+}
+
+void agx_mate_links_free(agx_mate_links *l) {
+    if (!l) return;
+    free(l->rec_inside); free(l->rec_open_left); free(l->rec_open_right); free(l->rec_links_out); free(l->rec_links_in);
+    free(l->a); free(l->b); free(l->n_pairs); free(l->len_sum); free(l->lo_min); free(l->lo_max); free(l->hi_min); free(l->hi_max);
+    memset(l, 0, sizeof *l);
 }
 
 int agx_run_unit(const agx_params *p, const char *tmp_dir, int unit, int write_files, agx_result *r, char *err, size_t err_len) {

@@ -284,4 +284,30 @@ int agx_edge_reads_tsv(const agx_edge_reads *r, int unit, char **text, size_t *l
     }
 }
 
+// The links of agx_unit_mate_links, one line per link in the table's order, no header line:
+//   p<unit>_<a>	p<unit>_<b>	<n_pairs>	<len_sum>	<lo_min>	<lo_max>	<hi_min>	<hi_max>
+int agx_mate_links_tsv(const agx_mate_links *l, int unit, char **text, size_t *len) {
+    if (!l || !text || !len || unit < 0) return AGX_E_ARG;
+    *text = nullptr; *len = 0;
+    const uint32_t n = l->n_links;
+    if (n && (!l->a || !l->b || !l->n_pairs || !l->len_sum || !l->lo_min || !l->lo_max || !l->hi_min || !l->hi_max)) return AGX_E_ARG;
+    for (uint32_t i = 0; i < n; i++) if (l->a[i] >= l->n_recs || l->b[i] >= l->n_recs || l->a[i] == l->b[i]) return AGX_E_ARG;
+    try {
+        const std::string prefix = "p" + std::to_string(unit) + "_";
+        std::string o;
+        o.reserve((size_t)n * 64);
+        for (uint32_t i = 0; i < n; i++) {
+            o += prefix; put_u64(o, l->a[i]); o += '\t'; o += prefix; put_u64(o, l->b[i]); o += '\t'; put_u64(o, l->n_pairs[i]); o += '\t'; put_u64(o, l->len_sum[i]); o += '\t';
+            put_u64(o, l->lo_min[i]); o += '\t'; put_u64(o, l->lo_max[i]); o += '\t'; put_u64(o, l->hi_min[i]); o += '\t'; put_u64(o, l->hi_max[i]); o += '\n';
+        }
+        char *out = (char *)malloc(o.size() + 1);
+        if (!out) return AGX_E_ARG;
+        memcpy(out, o.data(), o.size()); out[o.size()] = 0;
+        *text = out; *len = o.size();
+        return AGX_OK;
+    } catch (...) {
+        return AGX_E_ARG;
+    }
+}
+
 }  // extern "C"

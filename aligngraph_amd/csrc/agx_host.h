@@ -324,4 +324,24 @@ inline bool span_jump_entries(const agx_u32 *x, const agx_u32 *y, const agx_u32 
     return true;
 }
 
+// The passes of agx_unit_mate_links (host only, here so that the engine and the tests' serial replay run the same function).  pass(a_lo, a_hi, first) runs one
+// pass over all hits for the links whose left record lies in [a_lo, a_hi) and says whether every pair found a slot; a pass that did not is discarded by its caller and its
+// range halved.  The ranges that fit come in ascending order and are disjoint.  Returns the passes run, or -1 with *stuck the record whose links alone do not fit the table.
+template <class PASS>
+inline long links_plan(agx_u32 n_recs, PASS pass, agx_u32 *stuck) {
+    std::vector<std::pair<agx_u32, agx_u32>> todo{{0u, n_recs}};
+    long passes = 0;
+    while (!todo.empty()) {
+        const std::pair<agx_u32, agx_u32> r = todo.back();
+        todo.pop_back();
+        const bool fit = pass(r.first, r.second, passes == 0);
+        passes++;
+        if (fit) continue;
+        if (r.second - r.first <= 1u) { *stuck = r.first; return -1; }
+        const agx_u32 mid = r.first + (r.second - r.first) / 2u;
+        todo.push_back({mid, r.second}); todo.push_back({r.first, mid});
+    }
+    return passes;
+}
+
 }  // namespace agx

@@ -178,6 +178,26 @@ struct agx_walk_span_args {
     const agx_u32 *l_base, *l_ent; agx_u32 n_list;       // [n_list] every jump once more: its flat base and its entry
 };
 
+// Mate links (agx_links.hip, agx_unit_mate_links).  T is §14's flat stretch table (only its stretch arrays and n_ids are read here).  own and the per-record
+// counters are the call's; the slot table, its flags and the compacted output are one PASS's: a pass inserts the links whose left record lies in [a_lo, a_hi).
+struct agx_links_args {
+    agx_evidence_tab T;
+    const agx_dhit *dhit; const agx_run *runs; agx_u32 n_hits, n_runs, n_pos;
+    const agx_u32 *side_xpos;                  // [n_ids - n_pos] the position of every side id
+    agx_u32 *own;                              // [n_pos] the smallest record with a graph base on the position; NONE: nobody
+    agx_u32 *rec; agx_u32 n_recs;              // [5 * n_recs] per record: inside, open to the left, open to the right, pairs of links out, pairs of links in
+    agx_u32 *part; agx_u32 n_part;             // [6 * n_part] per wavefront of the pass: kept hits, kept hits outside the unit, unowned, inside, open, link pairs
+    agx_u32 *spart; agx_u32 n_spart;           // [2 * n_spart] per wavefront of the shadow pass: shadowed graph bases, owned positions
+    agx_u32 count;                             // the pass adds to rec and part (the call's first pass only)
+    agx_u32 a_lo, a_hi, min_pairs;
+    agx_u32 init_all;                          // agx_k_ln_init: own and rec too, not the slots alone
+    unsigned long long *t_key, *t_len; agx_u32 *t_n, *t_lo_min, *t_lo_max, *t_hi_min, *t_hi_max;      // [slots] the table, a structure of arrays
+    agx_u32 slots, log2_slots;                 // slots = 2^log2_slots >= 2
+    agx_u32 *flag, *off, *scan_tmp;            // [slots + 1] the kept slots' flags (closing zero) and their exclusive scan, and the scan's block sums
+    unsigned long long *o_key, *o_len; agx_u32 *o_n, *o_lo_min, *o_lo_max, *o_hi_min, *o_hi_max; agx_u32 out_cap;      // [out_cap] the kept slots, dense, in slot order
+    agx_u32 *words;                            // 0: error bits (1: own names no record, 2: an emit beyond out_cap); 1: pairs that found no slot; 2: slots in use
+};
+
 #define AGX_SLOW_WAVES 8192u   // wavefronts of the per-hit edge pass if the occupancy query fails (normally: as many as are resident at once)
 
 extern "C" {
@@ -271,4 +291,10 @@ void agx_launch_walk_span_gather(const agx_walk_span_args *, hipStream_t);
 void agx_launch_walk_span_emit(const agx_walk_span_args *, hipStream_t);
 void agx_launch_walk_span_jumps(const agx_walk_span_args *, hipStream_t);
 void agx_launch_walk_span_flags(const agx_walk_span_args *, hipStream_t);
+// mate links: wavefronts of a strided pass over n items (entries of part / 6, of spart / 2); the init (own, rec and the slots, or the slots alone); own and the shadow
+// count (own initialised); one pass over all hits into the initialised slots, the flags of the kept slots, their scan and the dense copy (the host reads words and off[slots])
+agx_u32 agx_links_partials(agx_u32 n);
+void agx_launch_links_init(const agx_links_args *, hipStream_t);
+void agx_launch_links_own(const agx_links_args *, hipStream_t);
+void agx_launch_links_pass(const agx_links_args *, hipStream_t);
 }

@@ -468,6 +468,30 @@ void agx_walk_span_free(agx_walk_span *e);
 /* Host only: the thin intervals as BED, one line per interval: p<unit>_<rec> <tab> base_first <tab> base_last + 1 <tab> thin <tab> 0 <tab> + <tab> pm:i:<span_min> <tab>
  * jm:i:<step_min>, "." in place of a number that is 0xFFFFFFFF; *text is malloc'd, free it with agx_text_free. */
 int  agx_walk_span_bed(const agx_walk_span *e, int unit, char **text, size_t *len);
+/* Mate links: the read pairs that join two records of a stretch table w (layout, checks and "graph base" exactly as agx_walk_evidence above; position of
+ * a walk id, kept hit, fragment [f_lo, f_hi], n_kept and n_outside as in the pair span).  own[x] is the smallest record with a graph base at position x, or none: n_owned
+ * counts the positions with an owner, n_shadowed the graph bases whose record does not own their position.  With A = own[f_lo] and B = own[f_hi] a fragment is UNOWNED (both
+ * none), INSIDE (A == B, a record), OPEN TO THE RIGHT (B none; counted on A), OPEN TO THE LEFT (A none; counted on B) or a pair of the LINK (A, B), A the record under the left
+ * end: (A, B) and (B, A) are two links.  n_fragments = n_kept - n_outside = n_unowned + n_inside + n_open + n_link_pairs; n_links_all counts the distinct links.  Per record
+ * the pairs inside, open to either side, and of the links that leave it (it is A) and reach it (it is B), all before any threshold.  Per link of the table: the pairs, the
+ * sum of f_hi - f_lo + 1, and the smallest and largest f_lo and f_hi.  The table holds the links with n_pairs >= min_pairs (0 and 1: all) by (a, b); nothing else depends on
+ * min_pairs.  Nothing depends on the coverage threshold, on a reprune or on the node table.  n_passes, n_slots, ms: how the call went (below); agx_stats is as it was.  malloc'd; free with
+ * agx_mate_links_free. */
+typedef struct { uint64_t n_kept, n_outside, n_fragments, n_unowned, n_inside, n_open, n_link_pairs, n_links_all, n_owned, n_shadowed;
+                 uint32_t n_recs, n_links, n_passes, n_slots; double ms;      /* ms: host wall time of the call, from entry to the tables being in the caller's memory */
+                 /* [n_recs] */ uint32_t *rec_inside, *rec_open_left, *rec_open_right, *rec_links_out, *rec_links_in;
+                 /* [n_links] */ uint32_t *a, *b, *n_pairs; uint64_t *len_sum; uint32_t *lo_min, *lo_max, *hi_min, *hi_max; } agx_mate_links;
+/* The mate links of w: the table checks of agx_unit_walk_evidence and the preconditions of agx_unit_pair_span (AGX_E_ARG with the reason).  On the device out of the
+ * export's scratch, no allocation: own (4 bytes per position), the per-record counters, and a hash table of the links keyed by (A, B) at 80 bytes per slot with its
+ * compacted copy — twice the keys there can be, or the largest power of two that fits; AGX_LINKS_SLOTS=<n> forces a slot count (a power of two from 2; AGX_E_ARG
+ * otherwise).  One pass over all hits fills it.  A pass in which a pair finds no slot is discarded and the records it took links from are halved: EVERY PASS IS ONE MORE
+ * READ OF ALL HITS (n_passes); a single record whose links do not fit, a unit whose own and table do not fit the scratch, and 2^32 links or more are AGX_E_UNSUPPORTED.
+ * Nothing is kept between calls; nothing a walk or an export reads is written; a refused call leaves the unit as it was. */
+int  agx_unit_mate_links(agx_unit *u, const agx_walk_paths *w, uint32_t min_pairs, agx_mate_links *l);
+void agx_mate_links_free(agx_mate_links *l);
+/* Host only: the links as text, one line per link in the table's order and no header line: p<unit>_<a> <tab> p<unit>_<b> <tab> n_pairs <tab> len_sum <tab> lo_min <tab>
+ * lo_max <tab> hi_min <tab> hi_max (the names are the BED's and the P lines'); *text is malloc'd, free it with agx_text_free. */
+int  agx_mate_links_tsv(const agx_mate_links *l, int unit, char **text, size_t *len);
 void agx_unitigs_free(agx_unitigs *t);
 /* Host only: the S and L lines of GFA 1.0 for unit `unit` (no header line), as DESIGN.md §11 defines them; *text is malloc'd, free it with agx_text_free. */
 int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len);
