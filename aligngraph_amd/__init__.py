@@ -172,18 +172,36 @@ WALK_RECORD = [("next", "<u4", (4,)), ("off0", "<u4"), ("xpos", "<u4"), ("sref_s
 WALK_HOP = [("str_off", "<u4"), ("len", "<u4"), ("end_pos", "<u4")]
 
 
+def _arr(p, n, dt):
+    """n entries at p as a numpy array of its own: p is a typed ctypes pointer, whose entries are converted to dt, or an address (a c_void_p field) of entries of dt."""
+    import numpy as np
+    if not p or not n:
+        return np.zeros(0, dt)
+    if isinstance(p, int):
+        return np.frombuffer(ctypes.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy()
+    return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True)
+
+
+def _text(fn, *args, what):
+    """The text one of the library's writers makes of args, as bytes; what: the message when it refuses them."""
+    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
+    rc = fn(*args, ctypes.byref(p), ctypes.byref(n))
+    if rc != AGX_OK:
+        raise AgxError(rc, what)
+    try:
+        return ctypes.string_at(p, n.value) if n.value else b""
+    finally:
+        lib().agx_text_free(p)
+
+
 def walk_graph_arrays(g):
     """An agx_walk_graph-shaped ctypes struct (this library's, or the test executor's) as a dict of numpy arrays; str and chain_str as bytes."""
-    import numpy as np
-
-    def arr(p, n, dt):
-        return np.frombuffer(ctypes.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy() if p and n else np.zeros(0, dt)
     ni, nw = g.n_ids, g.n_ids // 64 + 1
-    return {"n_pos": g.n_pos, "n_ids": ni, "n_special": g.n_special, "meta": arr(g.meta, ni, "u1"), "str": ctypes.string_at(g.str, ni) if g.str else b"",
-            "side_xpos": arr(g.side_xpos, ni - g.n_pos, "<u4"), "sp_bits": arr(g.sp_bits, nw, "<u8"), "sp_rank": arr(g.sp_rank, nw, "<u4"),
-            "sp_node": arr(g.sp_node, g.n_special, WALK_RECORD), "sp_hop": arr(g.sp_hop, g.n_special, WALK_HOP), "ovf": arr(g.ovf, g.n_ovf * 2, "<u4").reshape(-1, 2),
+    return {"n_pos": g.n_pos, "n_ids": ni, "n_special": g.n_special, "meta": _arr(g.meta, ni, "u1"), "str": ctypes.string_at(g.str, ni) if g.str else b"",
+            "side_xpos": _arr(g.side_xpos, ni - g.n_pos, "<u4"), "sp_bits": _arr(g.sp_bits, nw, "<u8"), "sp_rank": _arr(g.sp_rank, nw, "<u4"),
+            "sp_node": _arr(g.sp_node, g.n_special, WALK_RECORD), "sp_hop": _arr(g.sp_hop, g.n_special, WALK_HOP), "ovf": _arr(g.ovf, g.n_ovf * 2, "<u4").reshape(-1, 2),
             "chain_str": ctypes.string_at(g.chain_str, g.n_chain_str) if g.chain_str else b"",
-            "all_node": arr(g.all_node, ni, WALK_RECORD) if g.all_node else None}
+            "all_node": _arr(g.all_node, ni, WALK_RECORD) if g.all_node else None}
 
 
 class Front(ctypes.Structure):
@@ -205,17 +223,13 @@ FRONT_CMHEAD = [("cid", "<u4"), ("coff", "<u4"), ("n", "<u4"), ("start", "<u4")]
 def front_arrays(f):
     """An agx_front-shaped ctypes struct (this library's, or the test executor's) as a dict: the counts and form flags as ints, ref as bytes, the arrays as numpy arrays
     (records as structured arrays with the fields of FRONT_*; vcodes as [n_rows, stride])."""
-    import numpy as np
-
-    def arr(p, n, dt):
-        return np.frombuffer(ctypes.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy() if p and n else np.zeros(0, dt)
     out = {n: int(getattr(f, n)) for n, t in Front._fields_ if t is ctypes.c_uint32}
     nt = f.n_tiles
-    out.update({"ref": ctypes.string_at(f.ref, f.n_pos) if f.ref else b"", "vcodes": arr(f.vcodes, f.n_rows * f.stride, "u1").reshape(f.n_rows, f.stride),
-                "runs": arr(f.runs, f.n_runs, FRONT_RUN), "cm_start": arr(f.cm_start, f.n_pos + 1, "<u4"), "cm": arr(f.cm, f.n_cm, FRONT_CMKEY),
-                "cm_head": arr(f.cm_head, f.n_pos + 1, FRONT_CMHEAD), "dhit": arr(f.dhit, f.n_hits, FRONT_DHIT), "perm": arr(f.perm, f.n_hits, "<u4"),
-                "tile_first": arr(f.tile_first, nt + 1, "<u4"), "ckey": arr(f.ckey, f.n_hits, "<u4"), "tile_cnt": arr(f.tile_cnt, nt + 1, "<u4"),
-                "tile_off": arr(f.tile_off, nt + 1, "<u4"), "tile_recs": arr(f.tile_recs, f.n_entries, FRONT_LREC), "long_list": arr(f.long_list, f.n_long, "<u4")})
+    out.update({"ref": ctypes.string_at(f.ref, f.n_pos) if f.ref else b"", "vcodes": _arr(f.vcodes, f.n_rows * f.stride, "u1").reshape(f.n_rows, f.stride),
+                "runs": _arr(f.runs, f.n_runs, FRONT_RUN), "cm_start": _arr(f.cm_start, f.n_pos + 1, "<u4"), "cm": _arr(f.cm, f.n_cm, FRONT_CMKEY),
+                "cm_head": _arr(f.cm_head, f.n_pos + 1, FRONT_CMHEAD), "dhit": _arr(f.dhit, f.n_hits, FRONT_DHIT), "perm": _arr(f.perm, f.n_hits, "<u4"),
+                "tile_first": _arr(f.tile_first, nt + 1, "<u4"), "ckey": _arr(f.ckey, f.n_hits, "<u4"), "tile_cnt": _arr(f.tile_cnt, nt + 1, "<u4"),
+                "tile_off": _arr(f.tile_off, nt + 1, "<u4"), "tile_recs": _arr(f.tile_recs, f.n_entries, FRONT_LREC), "long_list": _arr(f.long_list, f.n_long, "<u4")})
     return out
 
 
@@ -506,16 +520,13 @@ class Unit:
         return {n: getattr(s, n) for n, _ in Stats._fields_}
 
     def graph(self):
-        import numpy as np
         g = Graph()
         self._check(lib().agx_unit_graph(self._h, ctypes.byref(g)))
 
-        def arr(p, n, dt):
-            return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
         out = {"n_pos": g.n_pos, "n_nodes": g.n_nodes, "n_edges": g.n_edges,
-               "node_start": arr(g.node_start, g.n_pos + 1, "uint32"), "node_key": arr(g.node_key, g.n_nodes * 6, "uint32").reshape(-1, 6),
-               "node_cnt": arr(g.node_cnt, g.n_nodes * 6, "int32").reshape(-1, 6), "node_slen": arr(g.node_slen, g.n_nodes, "uint32"),
-               "edge_start": arr(g.edge_start, g.n_nodes + 1, "uint32"), "edge_dst": arr(g.edge_dst, g.n_edges, "uint32")}
+               "node_start": _arr(g.node_start, g.n_pos + 1, "uint32"), "node_key": _arr(g.node_key, g.n_nodes * 6, "uint32").reshape(-1, 6),
+               "node_cnt": _arr(g.node_cnt, g.n_nodes * 6, "int32").reshape(-1, 6), "node_slen": _arr(g.node_slen, g.n_nodes, "uint32"),
+               "edge_start": _arr(g.edge_start, g.n_nodes + 1, "uint32"), "edge_dst": _arr(g.edge_dst, g.n_edges, "uint32")}
         lib().agx_graph_free(ctypes.byref(g))
         return out
 
@@ -560,14 +571,11 @@ class Unit:
         """How many events name each edge of the built graph (agx_unit_edge_support; the unit was created with edge_support=True): edge_start and edge_dst are graph()'s,
         edge_cnt[e] the support of edge e, n_events the events counted and n_contributions the sum of edge_cnt.  The first call after a build counts on the device; later
         calls reuse the counters."""
-        import numpy as np
         s = EdgeSupport()
         self._check(lib().agx_unit_edge_support(self._h, ctypes.byref(s)))
         try:
-            def arr(p, n):
-                return np.ctypeslib.as_array(p, shape=(n,)).astype("uint32", copy=True) if n else np.zeros(0, "uint32")
             return {"n_nodes": s.n_nodes, "n_edges": s.n_edges, "n_events": s.n_events, "n_contributions": s.n_contributions,
-                    "edge_start": arr(s.edge_start, s.n_nodes + 1), "edge_dst": arr(s.edge_dst, s.n_edges), "edge_cnt": arr(s.edge_cnt, s.n_edges)}
+                    "edge_start": _arr(s.edge_start, s.n_nodes + 1, "uint32"), "edge_dst": _arr(s.edge_dst, s.n_edges, "uint32"), "edge_cnt": _arr(s.edge_cnt, s.n_edges, "uint32")}
         finally:
             lib().agx_edge_support_free(ctypes.byref(s))
 
@@ -576,7 +584,6 @@ class Unit:
         lies in region = (lo, hi) (None: every position) and whose support is <= max_support (None: every edge), as src_pos, src_var, dst_pos, dst_var, support per edge in
         the order (src_pos, src_var, dst_pos, dst_var), and the hit numbers of the events that name edge e, ascending, in hit[hit_off[e]:hit_off[e + 1]].  A hit number is
         the hit's place in file order: the index into front()["dhit"] after undoing perm, the i-th hit handed to push_pairs."""
-        import numpy as np
         lo, hi = region if region is not None else (0, self.stats()["n_pos"])
         top = 0xFFFFFFFF if max_support is None else max_support
         for v in (lo, hi, top):
@@ -585,10 +592,8 @@ class Unit:
         r = EdgeReads()
         self._check(lib().agx_unit_edge_reads(self._h, int(lo), int(hi), int(top), ctypes.byref(r)))
         try:
-            def arr(p, n, dt):
-                return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
-            out = {k: arr(getattr(r, k), r.n_edges, "uint32") for k in EDGE_READS_EDGE}
-            out.update(hit_off=arr(r.hit_off, r.n_edges + 1, "uint64"), hit=arr(r.hit, r.n_hits, "uint32"))
+            out = {k: _arr(getattr(r, k), r.n_edges, "uint32") for k in EDGE_READS_EDGE}
+            out.update(hit_off=_arr(r.hit_off, r.n_edges + 1, "uint64"), hit=_arr(r.hit, r.n_hits, "uint32"))
             return out
         finally:
             lib().agx_edge_reads_free(ctypes.byref(r))
@@ -645,15 +650,12 @@ class Unit:
     def walk_paths(self):
         """The graph stretches of the records the last finish() wrote to "pre" (agx_unit_walk_paths; needs keep_paths): rec_len, st_off per record, id_first, id_last,
         base_off, joined per stretch, as numpy arrays."""
-        import numpy as np
         w = WalkPaths()
         self._check(lib().agx_unit_walk_paths(self._h, ctypes.byref(w)))
         try:
-            def arr(p, n, dt):
-                return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
             nr, ns = w.n_recs, w.n_stretches
-            return {"rec_len": arr(w.rec_len, nr, "uint64"), "st_off": arr(w.st_off, nr + 1, "uint64"), "id_first": arr(w.id_first, ns, "uint32"),
-                    "id_last": arr(w.id_last, ns, "uint32"), "base_off": arr(w.base_off, ns, "uint64"), "joined": arr(w.joined, ns, "uint8")}
+            return {"rec_len": _arr(w.rec_len, nr, "uint64"), "st_off": _arr(w.st_off, nr + 1, "uint64"), "id_first": _arr(w.id_first, ns, "uint32"),
+                    "id_last": _arr(w.id_last, ns, "uint32"), "base_off": _arr(w.base_off, ns, "uint64"), "joined": _arr(w.joined, ns, "uint8")}
         finally:
             lib().agx_walk_paths_free(ctypes.byref(w))
 
@@ -662,39 +664,42 @@ class Unit:
         returns (None: walk_paths() itself).  Per record rec_graph_bases, rec_steps, rec_depth_sum, rec_depth_min / _at, rec_step_min / _at; the weak intervals at the
         thresholds iv_rec, iv_first, iv_last, iv_depth_min, iv_step_min; the totals n_graph_bases, n_steps, n_steps_without_edge.  0xFFFFFFFF: no number.  tracks=True:
         also depth, votes and step per graph base of the records `records` = (lo, hi) (None: all) with track_off per stretch of those records, and rec_lo, rec_hi."""
+        return self._under_records(w, (min_depth, min_support), tracks, records, "walk evidence: thresholds and record bounds are unsigned 32-bit numbers", WalkEvidence, "walk_evidence",
+                                   ("n_graph_bases", "n_steps", "n_steps_without_edge"), REC_EVIDENCE, IV_EVIDENCE, ("depth", "votes", "step"))
+
+    def _under_records(self, w, thresholds, tracks, records, bad, struct, call, totals, rec_names, iv_names, track_names):
+        """walk_evidence and walk_span: the stretch table as a struct, the 32-bit checks (bad: the message), agx_unit_<call> into a `struct`, and its totals, per-record
+        arrays (the first three 64-bit), intervals and tracks, by their names, as the dict the two return."""
         import numpy as np
         if w is None:
             w = self.walk_paths()
         ws, _keep = _walk_paths_struct(w)
         lo, hi = (0, ws.n_recs) if records is None else records
-        for v in (min_depth, min_support, lo, hi):
+        for v in thresholds + (lo, hi):
             if not 0 <= int(v) <= 0xFFFFFFFF:
-                raise AgxError(AGX_E_ARG, "walk evidence: thresholds and record bounds are unsigned 32-bit numbers")
-        e = WalkEvidence()
-        self._check(lib().agx_unit_walk_evidence(self._h, ctypes.byref(ws), int(min_depth), int(min_support), 1 if tracks else 0, int(lo), int(hi), ctypes.byref(e)))
+                raise AgxError(AGX_E_ARG, bad)
+        e = struct()
+        self._check(getattr(lib(), "agx_unit_" + call)(self._h, ctypes.byref(ws), *(int(v) for v in thresholds), 1 if tracks else 0, int(lo), int(hi), ctypes.byref(e)))
         try:
-            def arr(p, n, dt):
-                return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
-            out = {"n_graph_bases": e.n_graph_bases, "n_steps": e.n_steps, "n_steps_without_edge": e.n_steps_without_edge}
-            for k in REC_EVIDENCE:
-                out[k] = arr(getattr(e, k), e.n_recs, "uint64" if k in REC_EVIDENCE[:3] else "uint32")
-            for k in IV_EVIDENCE:
-                out[k] = arr(getattr(e, k), e.n_intervals, "uint32")
+            out = {k: getattr(e, k) for k in totals}
+            for k in rec_names:
+                out[k] = _arr(getattr(e, k), e.n_recs, "uint64" if k in rec_names[:3] else "uint32")
+            for k in iv_names:
+                out[k] = _arr(getattr(e, k), e.n_intervals, "uint32")
             if tracks:
                 st = np.asarray(w["st_off"]).astype(np.int64)
                 n_st = int(st[hi] - st[lo]) if len(st) else 0
-                out.update(rec_lo=e.rec_lo, rec_hi=e.rec_hi, track_off=arr(e.track_off, n_st + 1, "uint64"))
-                for k in ("depth", "votes", "step"):
-                    out[k] = arr(getattr(e, k), e.n_track, "uint32")
+                out.update(rec_lo=e.rec_lo, rec_hi=e.rec_hi, track_off=_arr(e.track_off, n_st + 1, "uint64"))
+                for k in track_names:
+                    out[k] = _arr(getattr(e, k), e.n_track, "uint32")
             return out
         finally:
-            lib().agx_walk_evidence_free(ctypes.byref(e))
+            getattr(lib(), "agx_" + call + "_free")(ctypes.byref(e))
 
     def pair_span(self, region=None):
         """The read pairs across each position (agx_unit_pair_span; needs keep_counts, before download(), trim() and release()): for region = (lo, hi) (None: every
         position) span[x - lo], the fragments of kept hits that cover position x, and cross[x - lo], those that cover x and x + 1; n_kept, n_outside (the unit's kept
         hits, and those of them that lie beyond its positions) and n_fragments (the fragments that meet the region); pos_lo, pos_hi."""
-        import numpy as np
         lo, hi = region if region is not None else (0, self.stats()["n_pos"])
         for v in (lo, hi):
             if not 0 <= int(v) <= 0xFFFFFFFF:
@@ -703,9 +708,7 @@ class Unit:
         self._check(lib().agx_unit_pair_span(self._h, int(lo), int(hi), ctypes.byref(s)))
         try:
             n = s.pos_hi - s.pos_lo
-            def arr(p):
-                return np.ctypeslib.as_array(p, shape=(n,)).astype("uint32", copy=True) if n else np.zeros(0, "uint32")
-            return {"pos_lo": s.pos_lo, "pos_hi": s.pos_hi, "n_kept": s.n_kept, "n_fragments": s.n_fragments, "n_outside": s.n_outside, "span": arr(s.span), "cross": arr(s.cross)}
+            return {"pos_lo": s.pos_lo, "pos_hi": s.pos_hi, "n_kept": s.n_kept, "n_fragments": s.n_fragments, "n_outside": s.n_outside, "span": _arr(s.span, n, "uint32"), "cross": _arr(s.cross, n, "uint32")}
         finally:
             lib().agx_pair_span_free(ctypes.byref(s))
 
@@ -714,40 +717,14 @@ class Unit:
         Per record rec_graph_bases, rec_steps, rec_span_sum, rec_span_min / _at, rec_step_min / _at; the thin intervals at min_span iv_rec, iv_first, iv_last,
         iv_span_min, iv_step_min; the totals n_graph_bases, n_steps, n_jump_steps, n_steps_not_forward.  0xFFFFFFFF: no number.  tracks=True: also pos, span and step per
         graph base of the records `records` = (lo, hi) (None: all) with track_off per stretch of those records, and rec_lo, rec_hi."""
-        import numpy as np
-        if w is None:
-            w = self.walk_paths()
-        ws, _keep = _walk_paths_struct(w)
-        lo, hi = (0, ws.n_recs) if records is None else records
-        for v in (min_span, lo, hi):
-            if not 0 <= int(v) <= 0xFFFFFFFF:
-                raise AgxError(AGX_E_ARG, "walk span: the threshold and record bounds are unsigned 32-bit numbers")
-        e = WalkSpan()
-        self._check(lib().agx_unit_walk_span(self._h, ctypes.byref(ws), int(min_span), 1 if tracks else 0, int(lo), int(hi), ctypes.byref(e)))
-        try:
-            def arr(p, n, dt):
-                return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
-            out = {"n_graph_bases": e.n_graph_bases, "n_steps": e.n_steps, "n_jump_steps": e.n_jump_steps, "n_steps_not_forward": e.n_steps_not_forward}
-            for k in REC_SPAN:
-                out[k] = arr(getattr(e, k), e.n_recs, "uint64" if k in REC_SPAN[:3] else "uint32")
-            for k in IV_SPAN:
-                out[k] = arr(getattr(e, k), e.n_intervals, "uint32")
-            if tracks:
-                st = np.asarray(w["st_off"]).astype(np.int64)
-                n_st = int(st[hi] - st[lo]) if len(st) else 0
-                out.update(rec_lo=e.rec_lo, rec_hi=e.rec_hi, track_off=arr(e.track_off, n_st + 1, "uint64"))
-                for k in ("pos", "span", "step"):
-                    out[k] = arr(getattr(e, k), e.n_track, "uint32")
-            return out
-        finally:
-            lib().agx_walk_span_free(ctypes.byref(e))
+        return self._under_records(w, (min_span,), tracks, records, "walk span: the threshold and record bounds are unsigned 32-bit numbers", WalkSpan, "walk_span",
+                                   ("n_graph_bases", "n_steps", "n_jump_steps", "n_steps_not_forward"), REC_SPAN, IV_SPAN, ("pos", "span", "step"))
 
     def mate_links(self, w=None, min_pairs=1):
         """The read pairs that join two records of a stretch table (agx_unit_mate_links; needs keep_counts): w is a dict like walk_paths() returns (None: walk_paths()
         itself).  The totals n_kept, n_outside, n_fragments, n_unowned, n_inside, n_open, n_link_pairs, n_links_all, n_owned, n_shadowed; per record rec_inside,
         rec_open_left, rec_open_right, rec_links_out, rec_links_in; per link with n_pairs >= min_pairs, by (a, b): a, b, n_pairs, len_sum, lo_min, lo_max, hi_min, hi_max;
         n_passes and n_slots: the passes over the hits the call took and the slots of its table; ms: the call's host wall time."""
-        import numpy as np
         if w is None:
             w = self.walk_paths()
         ws, _keep = _walk_paths_struct(w)
@@ -756,14 +733,12 @@ class Unit:
         l = MateLinks()
         self._check(lib().agx_unit_mate_links(self._h, ctypes.byref(ws), int(min_pairs), ctypes.byref(l)))
         try:
-            def arr(p, n, dt):
-                return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
             out = {k: int(getattr(l, k)) for k in TOTALS_LINKS}
             out["ms"] = float(l.ms)
             for k in REC_LINKS:
-                out[k] = arr(getattr(l, k), l.n_recs, "uint32")
+                out[k] = _arr(getattr(l, k), l.n_recs, "uint32")
             for k in LINK_LINKS:
-                out[k] = arr(getattr(l, k), l.n_links, "uint64" if k == "len_sum" else "uint32")
+                out[k] = _arr(getattr(l, k), l.n_links, "uint64" if k == "len_sum" else "uint32")
             return out
         finally:
             lib().agx_mate_links_free(ctypes.byref(l))
@@ -789,23 +764,17 @@ class Unit:
 def _unitigs_arrays(t):
     import numpy as np
 
-    def arr(p, n, dt):
-        return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
     ns, nl = t.n_segs, t.n_links
-    return {"head_pos": arr(t.head_pos, ns, "uint32"), "head_var": arr(t.head_var, ns, "uint32"), "n_nodes": arr(t.n_nodes, ns, "uint32"),
-            "last_pos": arr(t.last_pos, ns, "uint32"), "coverage": arr(t.coverage, ns, "uint64"),
-            "seq_off": arr(t.seq_off, ns + 1, "uint64") if ns else np.zeros(1, "uint64"),
+    return {"head_pos": _arr(t.head_pos, ns, "uint32"), "head_var": _arr(t.head_var, ns, "uint32"), "n_nodes": _arr(t.n_nodes, ns, "uint32"),
+            "last_pos": _arr(t.last_pos, ns, "uint32"), "coverage": _arr(t.coverage, ns, "uint64"),
+            "seq_off": _arr(t.seq_off, ns + 1, "uint64") if ns else np.zeros(1, "uint64"),
             "seq": ctypes.string_at(t.seq, t.n_bases) if t.seq and t.n_bases else b"",
-            "link_from": arr(t.link_from, nl, "uint32"), "link_to": arr(t.link_to, nl, "uint32")}
+            "link_from": _arr(t.link_from, nl, "uint32"), "link_to": _arr(t.link_to, nl, "uint32")}
 
 
 def _idmap_arrays(m):
-    import numpy as np
-
-    def arr(p, n):
-        return np.ctypeslib.as_array(p, shape=(n,)).astype("uint32", copy=True) if n else np.zeros(0, "uint32")
     n = m.n_runs
-    return {"n_pos": m.n_pos, "n_ids": m.n_ids, "id_first": arr(m.id_first, n), "id_last": arr(m.id_last, n), "seg": arr(m.seg, n), "rank_first": arr(m.rank_first, n)}
+    return {"n_pos": m.n_pos, "n_ids": m.n_ids, "id_first": _arr(m.id_first, n, "uint32"), "id_last": _arr(m.id_last, n, "uint32"), "seg": _arr(m.seg, n, "uint32"), "rank_first": _arr(m.rank_first, n, "uint32")}
 
 
 def gfa_paths(t, w, unit=0):
@@ -819,20 +788,8 @@ def gfa_paths(t, w, unit=0):
     m.n_runs, m.n_pos, m.n_ids = len(mk["id_first"]), int(im["n_pos"]), int(im["n_ids"])
     for k, a in mk.items():
         setattr(m, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
-    wk = {k: np.ascontiguousarray(w[k], dtype=dt) for k, dt in (("rec_len", "uint64"), ("st_off", "uint64"), ("id_first", "uint32"), ("id_last", "uint32"),
-                                                                 ("base_off", "uint64"), ("joined", "uint8"))}
-    ws = WalkPaths()
-    ws.n_recs, ws.n_stretches = len(wk["rec_len"]), len(wk["id_first"])
-    for k, a in wk.items():
-        setattr(ws, k, a.ctypes.data_as(ctypes.POINTER({"uint64": ctypes.c_uint64, "uint32": ctypes.c_uint32, "uint8": ctypes.c_uint8}[a.dtype.name])))
-    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
-    rc = lib().agx_unitigs_paths_gfa(ctypes.byref(ts), ctypes.byref(m), ctypes.byref(ws), unit, ctypes.byref(p), ctypes.byref(n))
-    if rc != AGX_OK:
-        raise AgxError(rc, "agx_unitigs_paths_gfa: the unitig table, the id map and the stretches do not agree")
-    try:
-        return ctypes.string_at(p, n.value) if n.value else b""
-    finally:
-        lib().agx_text_free(p)
+    ws, _keep_w = _walk_paths_struct(w)
+    return _text(lib().agx_unitigs_paths_gfa, ctypes.byref(ts), ctypes.byref(m), ctypes.byref(ws), unit, what="agx_unitigs_paths_gfa: the unitig table, the id map and the stretches do not agree")
 
 
 def _walk_paths_struct(w):
@@ -855,14 +812,7 @@ def evidence_bed(e, unit=0):
     s.n_recs, s.n_intervals = len(e["rec_graph_bases"]), len(keep["iv_rec"])
     for k, a in keep.items():
         setattr(s, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
-    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
-    rc = lib().agx_walk_evidence_bed(ctypes.byref(s), unit, ctypes.byref(p), ctypes.byref(n))
-    if rc != AGX_OK:
-        raise AgxError(rc, "agx_walk_evidence_bed: the interval table is inconsistent")
-    try:
-        return ctypes.string_at(p, n.value) if n.value else b""
-    finally:
-        lib().agx_text_free(p)
+    return _text(lib().agx_walk_evidence_bed, ctypes.byref(s), unit, what="agx_walk_evidence_bed: the interval table is inconsistent")
 
 
 def edge_reads_tsv(r, unit=0):
@@ -877,14 +827,7 @@ def edge_reads_tsv(r, unit=0):
         raise AgxError(AGX_E_ARG, "agx_edge_reads_tsv: one entry per edge, and one offset more")
     for k, a in keep.items():
         setattr(s, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64 if k == "hit_off" else ctypes.c_uint32)))
-    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
-    rc = lib().agx_edge_reads_tsv(ctypes.byref(s), unit, ctypes.byref(p), ctypes.byref(n))
-    if rc != AGX_OK:
-        raise AgxError(rc, "agx_edge_reads_tsv: the table is inconsistent")
-    try:
-        return ctypes.string_at(p, n.value) if n.value else b""
-    finally:
-        lib().agx_text_free(p)
+    return _text(lib().agx_edge_reads_tsv, ctypes.byref(s), unit, what="agx_edge_reads_tsv: the table is inconsistent")
 
 
 def span_bed(e, unit=0):
@@ -895,14 +838,7 @@ def span_bed(e, unit=0):
     s.n_recs, s.n_intervals = len(e["rec_graph_bases"]), len(keep["iv_rec"])
     for k, a in keep.items():
         setattr(s, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
-    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
-    rc = lib().agx_walk_span_bed(ctypes.byref(s), unit, ctypes.byref(p), ctypes.byref(n))
-    if rc != AGX_OK:
-        raise AgxError(rc, "agx_walk_span_bed: the interval table is inconsistent")
-    try:
-        return ctypes.string_at(p, n.value) if n.value else b""
-    finally:
-        lib().agx_text_free(p)
+    return _text(lib().agx_walk_span_bed, ctypes.byref(s), unit, what="agx_walk_span_bed: the interval table is inconsistent")
 
 
 def links_tsv(l, unit=0):
@@ -913,29 +849,15 @@ def links_tsv(l, unit=0):
     s.n_recs, s.n_links = len(l["rec_inside"]), len(keep["a"])
     for k, a in keep.items():
         setattr(s, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64 if k == "len_sum" else ctypes.c_uint32)))
-    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
-    rc = lib().agx_mate_links_tsv(ctypes.byref(s), unit, ctypes.byref(p), ctypes.byref(n))
-    if rc != AGX_OK:
-        raise AgxError(rc, "agx_mate_links_tsv: the link table is inconsistent")
-    try:
-        return ctypes.string_at(p, n.value) if n.value else b""
-    finally:
-        lib().agx_text_free(p)
+    return _text(lib().agx_mate_links_tsv, ctypes.byref(s), unit, what="agx_mate_links_tsv: the link table is inconsistent")
 
 
 def _gfa_text(t, unit, link_support=None):
     """link_support: a ctypes uint32 pointer for the RC tags (agx_unitigs_gfa_support), or None"""
-    p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
+    what = "agx_unitigs_gfa: the unitig table is inconsistent"
     if link_support is None:
-        rc = lib().agx_unitigs_gfa(ctypes.byref(t), unit, ctypes.byref(p), ctypes.byref(n))
-    else:
-        rc = lib().agx_unitigs_gfa_support(ctypes.byref(t), link_support, unit, ctypes.byref(p), ctypes.byref(n))
-    if rc != AGX_OK:
-        raise AgxError(rc, "agx_unitigs_gfa: the unitig table is inconsistent")
-    try:
-        return ctypes.string_at(p, n.value) if n.value else b""
-    finally:
-        lib().agx_text_free(p)
+        return _text(lib().agx_unitigs_gfa, ctypes.byref(t), unit, what=what)
+    return _text(lib().agx_unitigs_gfa_support, ctypes.byref(t), link_support, unit, what=what)
 
 
 def _unitigs_struct(u):

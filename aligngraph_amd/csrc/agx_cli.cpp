@@ -199,6 +199,30 @@ string graph_part_path(const Options &o, int u) {
     return s + ".gfa";
 }
 
+// One unit's part of an output file ("wb"; "ab": behind what the unit wrote there before); what goes wrong becomes the unit's error
+void write_part(const string &path, const char *mode, const char *text, size_t len, int &rc, char (&err)[512]) {
+    if (rc != AGX_OK) return;
+    FILE *f = fopen(path.c_str(), mode); bool ok = f != nullptr;
+    if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
+    if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
+}
+
+// An output file: the header line, if any, and every unit's part in unit order (a --resume run finds the earlier units' parts in tmp/); only >= 0: only that unit has one
+void join_parts(const Options &o, int units, const string &out_path, const char *header, string (*part_path)(const Options &, int), int only) {
+    FILE *g = fopen(out_path.c_str(), "wb");
+    bool ok = g != nullptr && (!header || fputs(header, g) >= 0);
+    for (int u = 0; ok && u < units; u++) {
+        if (only >= 0 && u != only) continue;
+        FILE *f = fopen(part_path(o, u).c_str(), "rb");
+        if (!f) { ok = false; break; }
+        char buf[1 << 16]; size_t n;
+        while (ok && (n = fread(buf, 1, sizeof buf, f)) > 0) ok = fwrite(buf, 1, n, g) == n;
+        fclose(f);
+    }
+    if (g) ok = (fclose(g) == 0) && ok;
+    if (!ok) die("CANNOT OPEN FILE!");
+}
+
 // A text file mapped read-only and read the way the reference's `getline` loops read theirs: lines without their '\n'; past the last byte a
 // read gives an empty line and the stream stops being good; a last line without '\n' is delivered and ends the stream too.  The multi-gigabyte
 // inputs (reads, SAM) go through this at memchr speed instead of through ifstream::getline + a vector of strings.
@@ -1256,12 +1280,7 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                     if (rc == AGX_OK) { rc = o.graphSupport ? agx_unitigs_gfa_support(&ut, sup, u, &text, &len) : agx_unitigs_gfa(&ut, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "GFA FORMATTING FAILED"); }
                     agx_link_support_free(sup);
                     if (!o.graphPaths) agx_unitigs_free(&ut);
-                    if (rc == AGX_OK) {
-                        const string path = graph_part_path(o, u);
-                        FILE *f = fopen(path.c_str(), "wb"); bool ok = f != nullptr;
-                        if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
-                        if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
-                    }
+                    write_part(graph_part_path(o, u), "wb", text, len, rc, err);
                     agx_text_free(text);
                 }
                 if (rc == AGX_OK && o.tagEdgeReads && (!o.tagRegion || u == o.regionUnit)) {      // --graphEdgeReads: the hits behind the weak edges, before the download, into tmp/_edge_reads.<u>...tsv
@@ -1271,11 +1290,7 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                     if (rc == AGX_OK) rc = agx_unit_edge_reads(un, o.tagRegion ? o.regionLo : 0u, o.tagRegion ? o.regionHi : (uint32_t)st.n_pos, (uint32_t)o.edgeReadsMax, &er);
                     if (rc == AGX_OK) { rc = agx_edge_reads_tsv(&er, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "TSV FORMATTING FAILED"); }
                     agx_edge_reads_free(&er);
-                    if (rc == AGX_OK) {
-                        FILE *f = fopen(edge_reads_part_path(o, u).c_str(), "wb"); bool ok = f != nullptr;
-                        if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
-                        if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
-                    }
+                    write_part(edge_reads_part_path(o, u), "wb", text, len, rc, err);
                     agx_text_free(text);
                 }
                 bool wanted = false; if (rc == AGX_OK) { std::lock_guard<std::mutex> g(mem_mu); wanted = waiting[d] > 0 && !o.tagEvidence && !o.tagSpan && !o.tagLinks; }      // (--evidenceOut, --spanOut, --linksOut: never trimmed before the finish, they read the unit's arrays behind it)
@@ -1285,61 +1300,42 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                     if (rc == AGX_OK && agx_unit_trim(un, &freed) == AGX_OK && freed) { { std::lock_guard<std::mutex> g(mem_mu); const double f = std::min(est, (double)freed); used[d] -= f; est -= f; } mem_cv.notify_all(); }
                 }
                 if (rc == AGX_OK) rc = agx_unit_finish(un, &r);      // (r06: nothing downloaded yet — nobody waits for this unit's HBM — : the download is streamed and the walk begins on what has landed)
+                agx_walk_paths wp; memset(&wp, 0, sizeof wp);      // the stretch table of the records just written: fetched once for the outputs behind the finish that are asked for
+                if (rc == AGX_OK && ((graph_here && o.graphPaths) || o.tagEvidence || o.tagSpan || o.tagLinks)) rc = agx_unit_walk_paths(un, &wp);
                 if (rc == AGX_OK && graph_here && o.graphPaths) {      // the P lines behind the unit's S and L lines
-                    agx_walk_paths wp; char *text = nullptr; size_t len = 0;
-                    rc = agx_unit_walk_paths(un, &wp);
-                    if (rc == AGX_OK) { rc = agx_unitigs_paths_gfa(&ut, &im, &wp, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "GFA FORMATTING FAILED"); }
-                    agx_walk_paths_free(&wp);
-                    if (rc == AGX_OK) {
-                        FILE *f = fopen(graph_part_path(o, u).c_str(), "ab"); bool ok = f != nullptr;
-                        if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
-                        if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
-                    }
+                    char *text = nullptr; size_t len = 0;
+                    rc = agx_unitigs_paths_gfa(&ut, &im, &wp, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "GFA FORMATTING FAILED");
+                    write_part(graph_part_path(o, u), "ab", text, len, rc, err);
                     agx_text_free(text);
                 }
                 if (rc == AGX_OK && o.tagEvidence) {      // --evidenceOut: the weak intervals of the records just written, into tmp/_evidence.<u>.d<depth>.s<support>.bed
-                    agx_walk_paths wp; agx_walk_evidence ev; char *text = nullptr; size_t len = 0;
+                    agx_walk_evidence ev; char *text = nullptr; size_t len = 0;
                     memset(&ev, 0, sizeof ev);
-                    rc = agx_unit_walk_paths(un, &wp);
-                    if (rc == AGX_OK) rc = agx_unit_walk_evidence(un, &wp, evidence_depth(o), (uint32_t)o.evSupport, 0, 0, 0, &ev);
+                    rc = agx_unit_walk_evidence(un, &wp, evidence_depth(o), (uint32_t)o.evSupport, 0, 0, 0, &ev);
                     if (rc == AGX_OK) { rc = agx_walk_evidence_bed(&ev, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "BED FORMATTING FAILED"); }
-                    agx_walk_paths_free(&wp); agx_walk_evidence_free(&ev);
-                    if (rc == AGX_OK) {
-                        FILE *f = fopen(evidence_part_path(o, u).c_str(), "wb"); bool ok = f != nullptr;
-                        if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
-                        if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
-                    }
+                    agx_walk_evidence_free(&ev);
+                    write_part(evidence_part_path(o, u), "wb", text, len, rc, err);
                     agx_text_free(text);
                 }
                 if (rc == AGX_OK && o.tagSpan) {      // --spanOut: the thin intervals of the records just written, into tmp/_span.<u>.m<min>.bed
-                    agx_walk_paths wp; agx_walk_span sp; char *text = nullptr; size_t len = 0;
+                    agx_walk_span sp; char *text = nullptr; size_t len = 0;
                     memset(&sp, 0, sizeof sp);
-                    rc = agx_unit_walk_paths(un, &wp);
-                    if (rc == AGX_OK) rc = agx_unit_walk_span(un, &wp, (uint32_t)o.spanMin, 0, 0, 0, &sp);
+                    rc = agx_unit_walk_span(un, &wp, (uint32_t)o.spanMin, 0, 0, 0, &sp);
                     if (rc == AGX_OK) { rc = agx_walk_span_bed(&sp, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "BED FORMATTING FAILED"); }
-                    agx_walk_paths_free(&wp); agx_walk_span_free(&sp);
-                    if (rc == AGX_OK) {
-                        FILE *f = fopen(span_part_path(o, u).c_str(), "wb"); bool ok = f != nullptr;
-                        if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
-                        if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
-                    }
+                    agx_walk_span_free(&sp);
+                    write_part(span_part_path(o, u), "wb", text, len, rc, err);
                     agx_text_free(text);
                 }
                 if (rc == AGX_OK && o.tagLinks) {      // --linksOut: the links between the records just written, into tmp/_links.<u>.m<min>.tsv
-                    agx_walk_paths wp; agx_mate_links ml; char *text = nullptr; size_t len = 0;
+                    agx_mate_links ml; char *text = nullptr; size_t len = 0;
                     memset(&ml, 0, sizeof ml);
-                    rc = agx_unit_walk_paths(un, &wp);
-                    if (rc == AGX_OK) rc = agx_unit_mate_links(un, &wp, (uint32_t)o.linksMin, &ml);
+                    rc = agx_unit_mate_links(un, &wp, (uint32_t)o.linksMin, &ml);
                     if (rc == AGX_OK) { rc = agx_mate_links_tsv(&ml, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "TSV FORMATTING FAILED"); }
-                    agx_walk_paths_free(&wp); agx_mate_links_free(&ml);
-                    if (rc == AGX_OK) {
-                        FILE *f = fopen(links_part_path(o, u).c_str(), "wb"); bool ok = f != nullptr;
-                        if (f) { ok = len == 0 || fwrite(text, 1, len, f) == len; ok = (fclose(f) == 0) && ok; }
-                        if (!ok) { rc = AGX_E_IO; snprintf(err, sizeof err, "CANNOT OPEN FILE!"); }
-                    }
+                    agx_mate_links_free(&ml);
+                    write_part(links_part_path(o, u), "wb", text, len, rc, err);
                     agx_text_free(text);
                 }
-                agx_unitigs_free(&ut); agx_idmap_free(&im);
+                agx_unitigs_free(&ut); agx_idmap_free(&im); agx_walk_paths_free(&wp);
                 if (rc != AGX_OK && un && !err[0]) snprintf(err, sizeof err, "%s", agx_unit_error(un));
                 agx_unit_destroy(un);                                          // (its HBM goes back before the next unit is admitted)
                 if (admitted) { { std::lock_guard<std::mutex> g(mem_mu); used[d] -= est; if (used[d] < 1.0) used[d] = 0.0; } mem_cv.notify_all(); }
@@ -1426,78 +1422,12 @@ int main(int argc, char **argv) {
     stage("resume / ratio check");
     if (cp < units) run_units(o, cp, units, wcp);
     stage("unit loop");
-    if (o.tagGraph) {                                                         // --graphOut: the header and every unit's lines, in unit order (a --resume run finds the earlier units' files in tmp/)
-        FILE *g = fopen(o.graph.c_str(), "wb");
-        bool ok = g != nullptr && fputs("H\tVN:Z:1.0\n", g) >= 0;
-        for (int u = 0; ok && u < units; u++) {
-            if (o.tagRegion && u != o.regionUnit) continue;      // (with a region only the named unit has lines)
-            FILE *f = fopen(graph_part_path(o, u).c_str(), "rb");
-            if (!f) { ok = false; break; }
-            char buf[1 << 16]; size_t n;
-            while (ok && (n = fread(buf, 1, sizeof buf, f)) > 0) ok = fwrite(buf, 1, n, g) == n;
-            fclose(f);
-        }
-        if (g) ok = (fclose(g) == 0) && ok;
-        if (!ok) die("CANNOT OPEN FILE!");
-        stage("graph output");
-    }
-    if (o.tagEdgeReads) {                                                     // --graphEdgeReads: every unit's lines, in unit order (a --resume run finds the earlier units' files in tmp/)
-        FILE *g = fopen(o.edgeReads.c_str(), "wb");
-        bool ok = g != nullptr;
-        for (int u = 0; ok && u < units; u++) {
-            if (o.tagRegion && u != o.regionUnit) continue;      // (with a region only the named unit has lines)
-            FILE *f = fopen(edge_reads_part_path(o, u).c_str(), "rb");
-            if (!f) { ok = false; break; }
-            char buf[1 << 16]; size_t n;
-            while (ok && (n = fread(buf, 1, sizeof buf, f)) > 0) ok = fwrite(buf, 1, n, g) == n;
-            fclose(f);
-        }
-        if (g) ok = (fclose(g) == 0) && ok;
-        if (!ok) die("CANNOT OPEN FILE!");
-        stage("edge reads output");
-    }
-    if (o.tagEvidence) {                                                      // --evidenceOut: every unit's intervals, in unit order (a --resume run finds the earlier units' files in tmp/)
-        FILE *g = fopen(o.evidence.c_str(), "wb");
-        bool ok = g != nullptr;
-        for (int u = 0; ok && u < units; u++) {
-            FILE *f = fopen(evidence_part_path(o, u).c_str(), "rb");
-            if (!f) { ok = false; break; }
-            char buf[1 << 16]; size_t n;
-            while (ok && (n = fread(buf, 1, sizeof buf, f)) > 0) ok = fwrite(buf, 1, n, g) == n;
-            fclose(f);
-        }
-        if (g) ok = (fclose(g) == 0) && ok;
-        if (!ok) die("CANNOT OPEN FILE!");
-        stage("evidence output");
-    }
-    if (o.tagSpan) {                                                          // --spanOut: every unit's intervals, in unit order (a --resume run finds the earlier units' files in tmp/)
-        FILE *g = fopen(o.span.c_str(), "wb");
-        bool ok = g != nullptr;
-        for (int u = 0; ok && u < units; u++) {
-            FILE *f = fopen(span_part_path(o, u).c_str(), "rb");
-            if (!f) { ok = false; break; }
-            char buf[1 << 16]; size_t n;
-            while (ok && (n = fread(buf, 1, sizeof buf, f)) > 0) ok = fwrite(buf, 1, n, g) == n;
-            fclose(f);
-        }
-        if (g) ok = (fclose(g) == 0) && ok;
-        if (!ok) die("CANNOT OPEN FILE!");
-        stage("span output");
-    }
-    if (o.tagLinks) {                                                         // --linksOut: every unit's links, in unit order (a --resume run finds the earlier units' files in tmp/)
-        FILE *g = fopen(o.links.c_str(), "wb");
-        bool ok = g != nullptr;
-        for (int u = 0; ok && u < units; u++) {
-            FILE *f = fopen(links_part_path(o, u).c_str(), "rb");
-            if (!f) { ok = false; break; }
-            char buf[1 << 16]; size_t n;
-            while (ok && (n = fread(buf, 1, sizeof buf, f)) > 0) ok = fwrite(buf, 1, n, g) == n;
-            fclose(f);
-        }
-        if (g) ok = (fclose(g) == 0) && ok;
-        if (!ok) die("CANNOT OPEN FILE!");
-        stage("links output");
-    }
+    const int only = o.tagRegion ? o.regionUnit : -1;      // (with a region only the named unit has graph lines and edge reads)
+    if (o.tagGraph) { join_parts(o, units, o.graph, "H\tVN:Z:1.0\n", graph_part_path, only); stage("graph output"); }                   // --graphOut
+    if (o.tagEdgeReads) { join_parts(o, units, o.edgeReads, nullptr, edge_reads_part_path, only); stage("edge reads output"); }       // --graphEdgeReads
+    if (o.tagEvidence) { join_parts(o, units, o.evidence, nullptr, evidence_part_path, -1); stage("evidence output"); }               // --evidenceOut
+    if (o.tagSpan) { join_parts(o, units, o.span, nullptr, span_part_path, -1); stage("span output"); }                               // --spanOut
+    if (o.tagLinks) { join_parts(o, units, o.links, nullptr, links_part_path, -1); stage("links output"); }                           // --linksOut
     refinement(o, units, genomeIds, contigIds);
     stage("refinement");
     if (o.misassemblyRemoval == 1) {                                          // AG:4787-4792

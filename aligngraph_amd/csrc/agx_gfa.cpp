@@ -92,6 +92,15 @@ struct PathWriter {
     }
 };
 
+// a finished text into the caller's hands: malloc'd and terminated (agx_text_free)
+int give_text(const std::string &o, char **text, size_t *len) {
+    char *out = (char *)malloc(o.size() + 1);
+    if (!out) return AGX_E_ARG;
+    memcpy(out, o.data(), o.size()); out[o.size()] = 0;
+    *text = out; *len = o.size();
+    return AGX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -143,11 +152,7 @@ int agx_unitigs_paths_gfa(const agx_unitigs *t, const agx_idmap *m, const agx_wa
             }
             pw.close();
         }
-        char *out = (char *)malloc(o.size() + 1);
-        if (!out) return AGX_E_ARG;
-        memcpy(out, o.data(), o.size()); out[o.size()] = 0;
-        *text = out; *len = o.size();
-        return AGX_OK;
+        return give_text(o, text, len);
     } catch (...) {
         return AGX_E_ARG;
     }
@@ -231,11 +236,7 @@ static int intervals_bed(uint32_t n, uint32_t n_recs, const uint32_t *rec, const
             o += prefix; put_u64(o, rec[i]); o += '\t'; put_u64(o, first[i]); o += '\t'; put_u64(o, (uint64_t)last[i] + 1);
             o += '\t'; o += label; o += "\t0\t+\t"; o += tag_a; put_or_dot(min_a[i]); o += '\t'; o += tag_b; put_or_dot(min_b[i]); o += '\n';
         }
-        char *out = (char *)malloc(o.size() + 1);
-        if (!out) return AGX_E_ARG;
-        memcpy(out, o.data(), o.size()); out[o.size()] = 0;
-        *text = out; *len = o.size();
-        return AGX_OK;
+        return give_text(o, text, len);
     } catch (...) {
         return AGX_E_ARG;
     }
@@ -274,11 +275,7 @@ int agx_edge_reads_tsv(const agx_edge_reads *r, int unit, char **text, size_t *l
             for (uint64_t h = r->hit_off[i]; h < r->hit_off[i + 1]; h++) { if (h != r->hit_off[i]) o += ','; put_u64(o, r->hit[h]); }
             o += '\n';
         }
-        char *out = (char *)malloc(o.size() + 1);
-        if (!out) return AGX_E_ARG;
-        memcpy(out, o.data(), o.size()); out[o.size()] = 0;
-        *text = out; *len = o.size();
-        return AGX_OK;
+        return give_text(o, text, len);
     } catch (...) {
         return AGX_E_ARG;
     }
@@ -300,11 +297,7 @@ int agx_mate_links_tsv(const agx_mate_links *l, int unit, char **text, size_t *l
             o += prefix; put_u64(o, l->a[i]); o += '\t'; o += prefix; put_u64(o, l->b[i]); o += '\t'; put_u64(o, l->n_pairs[i]); o += '\t'; put_u64(o, l->len_sum[i]); o += '\t';
             put_u64(o, l->lo_min[i]); o += '\t'; put_u64(o, l->lo_max[i]); o += '\t'; put_u64(o, l->hi_min[i]); o += '\t'; put_u64(o, l->hi_max[i]); o += '\n';
         }
-        char *out = (char *)malloc(o.size() + 1);
-        if (!out) return AGX_E_ARG;
-        memcpy(out, o.data(), o.size()); out[o.size()] = 0;
-        *text = out; *len = o.size();
-        return AGX_OK;
+        return give_text(o, text, len);
     } catch (...) {
         return AGX_E_ARG;
     }

@@ -1,5 +1,5 @@
 // edge_reads_shim.cpp — TEST-ONLY: agx_reads_lane (csrc/agx_core.h) run serially over every (tile list entry, lane) of plain arrays, the way agx_k_edge_reads runs it on
-// the device, and a serial replay of what surrounds it in agx_unit_edge_reads (csrc/agx_engine.cpp): per chunk of the window's tiles a COUNT pass (selected contributions
+// the device, and a serial replay of what surrounds it in agx_unit_edge_reads (csrc/agx_export.cpp): per chunk of the window's tiles a COUNT pass (selected contributions
 // per position of the chunk), the exclusive scan of the counts and an EMIT pass that writes every record at its position's offset plus the lane's running count, each
 // store checked against the position's count and the chunk's total; a chunk whose records do not fit `room` is counted again over half its tiles, a single tile that does
 // not fit is refused (-3).  The counters e_cnt / ovf_cnt are the counting pass's (tests/edge_support_shim.cpp fills them from the same tables).

@@ -1,4 +1,4 @@
-"""Hand-made units that pin the unitig export (agx_unitig.hip; export_body / region_export, agx_engine.cpp; the id map behind --graphPaths) arm by arm.
+"""Hand-made units that pin the unitig export (agx_unitig.hip; export_body / region_export, agx_export.cpp; the id map behind --graphPaths) arm by arm.
 
 The units are lean_units.Unit's / walk_units.WUnit's written by walk_units.write_unit, so the CPU twin (tests/test_unitig_cases.py) and the GPU file
 (tests/test_gpu_unitig_cases.py) build exactly the same inputs.  What is correct is decided by tests/unitig_model.py, tests/unitig_region_model.py and
@@ -97,7 +97,7 @@ def piece_model(graph, lo, hi, cov):
         P.chains.append(chain)
     assert (P.seg_of >= 0).all() and sum(len(c) for c in P.chains) == P.np
     P.rounds = 1
-    while P.rounds < 32 and (1 << (P.rounds - 1)) < P.np:                   # ceil(log2 np) + 1: restated from export_body (agx_engine.cpp)
+    while P.rounds < 32 and (1 << (P.rounds - 1)) < P.np:                   # ceil(log2 np) + 1: restated from export_body (agx_export.cpp)
         P.rounds += 1
     ext = ~internal
     P.links = sorted(zip(s[ext].tolist(), d[ext].tolist()))
