@@ -90,6 +90,100 @@ AGX_HD agx_hit agx_unpack_hit(const agx_whit &w, const agx_wside *sides) {
     }
     return h;
 }
+// ---- compact wire forms: what crosses PCIe of the hit and side records; the device makes the arrays above of them once per upload (agx_k_expand_hits, agx_k_side_*) ----
+// Hits travel in blocks of 64 in the upload's order: a header and 8 bytes per hit.  A slot holds the record's `row` field whole (the hit's number in the tile order: random
+// there) and a word: bits 0-5 the six flags, bit 6 "len is the unit's longest read", bit 7 "back is 0", bits 8-31 the positions —
+//   * no mate with runs: the left mate's position as 12 bits above the block's base, the other mate's as 12 bits of signed distance from the left one (biased by 2048);
+//   * a mate with runs: the side index (the field of the first mate that has runs) travels whole in the block's piece of the list of extra words, in slot order; the
+//     other field in the 24 bits — above the base if it is a position, as it is (a zero, from the loaders) if that mate has runs too.
+// A hit that does not fit — another len, a back, a flag bit beyond the six, a position out of reach — travels whole in the escape list, in slot order, and its slot is
+// zero: bits 6 and 7 both set is what marks a compact slot.  So every agx_whit value comes back exactly, whatever the packer chose as the base.
+#define AGX_CH_BLOCK 64u
+enum { AGX_CH_LEN = 64, AGX_CH_BACK0 = 128, AGX_CH_MARK = AGX_CH_LEN | AGX_CH_BACK0, AGX_CH_LO = 4096, AGX_CH_REL = 2048, AGX_CH_FAR = 1 << 24 };
+struct agx_chit_block { agx_u32 base, esc, ext, pad; agx_u32 num[AGX_CH_BLOCK], word[AGX_CH_BLOCK]; };      // esc / ext: the block's first entry in the escape list / in the extra words
+AGX_HD bool agx_chit_escaped(agx_u32 word) { return (word & (agx_u32)AGX_CH_MARK) != (agx_u32)AGX_CH_MARK; }
+AGX_HD bool agx_chit_has_side(agx_u32 word) { return (word & (agx_u32)(AGX_WF_RUNS1 | AGX_WF_RUNS2)) != 0; }      // (of a compact slot)
+// the position a hit is measured from its block's base by; false: it has none (both mates have runs) or it escapes whatever the base
+AGX_HD bool agx_chit_anchor(const agx_whit &w, agx_u32 maxlen, agx_u32 &pos) {
+    const agx_u32 f = w.flags, runs = f & (agx_u32)(AGX_WF_RUNS1 | AGX_WF_RUNS2);
+    if ((f & ~63u) || w.len != maxlen || w.back != 0 || runs == (agx_u32)(AGX_WF_RUNS1 | AGX_WF_RUNS2)) return false;
+    pos = runs ? ((f & AGX_WF_RUNS1) ? w.b : w.a) : ((f & AGX_WF_LEFT2) ? w.b : w.a);
+    return true;
+}
+AGX_HD bool agx_chit_encode(const agx_whit &w, agx_u32 base, agx_u32 maxlen, agx_u32 &word) {      // false: the hit escapes
+    const agx_u32 f = w.flags, runs = f & (agx_u32)(AGX_WF_RUNS1 | AGX_WF_RUNS2);
+    if ((f & ~63u) || w.len != maxlen || w.back != 0) return false;
+    agx_u32 pay;
+    if (!runs) {
+        const agx_u32 left = (f & AGX_WF_LEFT2) ? w.b : w.a, other = (f & AGX_WF_LEFT2) ? w.a : w.b;
+        const agx_u32 lo = left - base, rel = other - left + (agx_u32)AGX_CH_REL;
+        if (lo >= (agx_u32)AGX_CH_LO || rel >= 2u * AGX_CH_REL) return false;
+        pay = lo | rel << 12;
+    } else {
+        const agx_u32 v = (f & AGX_WF_RUNS1) ? w.b : w.a;
+        pay = runs == (agx_u32)(AGX_WF_RUNS1 | AGX_WF_RUNS2) ? v : v - base;
+        if (pay >= (agx_u32)AGX_CH_FAR) return false;
+    }
+    word = f | (agx_u32)AGX_CH_MARK | pay << 8;
+    return true;
+}
+AGX_HD agx_whit agx_chit_decode(agx_u32 num, agx_u32 word, agx_u32 base, agx_u32 maxlen, agx_u32 side) {      // a compact slot; side: its extra word, if it has one
+    const agx_u32 f = word & 63u, runs = f & (agx_u32)(AGX_WF_RUNS1 | AGX_WF_RUNS2), pay = word >> 8;
+    agx_whit w; w.row = num; w.len = (agx_u16)maxlen; w.flags = (agx_u8)f; w.back = 0;
+    if (!runs) {
+        const agx_u32 left = base + (pay & (agx_u32)(AGX_CH_LO - 1)), other = left + (pay >> 12) - (agx_u32)AGX_CH_REL;
+        w.a = (f & AGX_WF_LEFT2) ? other : left; w.b = (f & AGX_WF_LEFT2) ? left : other;
+    } else {
+        const agx_u32 v = runs == (agx_u32)(AGX_WF_RUNS1 | AGX_WF_RUNS2) ? pay : base + pay;
+        w.a = (f & AGX_WF_RUNS1) ? side : v; w.b = (f & AGX_WF_RUNS1) ? v : side;
+    }
+    return w;
+}
+// One block from its n <= 64 hits: the base is the lowest position any of them is measured by.  esc / ext: where the block's escapes and extra words go; their numbers come
+// back in n_esc / n_ext (the caller keeps the running sums that the headers hold).
+AGX_HD void agx_chit_pack_block(const agx_whit *hits, agx_u32 n, agx_u32 maxlen, agx_chit_block &B, agx_whit *esc, agx_u32 &n_esc, agx_u32 *ext, agx_u32 &n_ext) {
+    agx_u32 base = 0xFFFFFFFFu, pos = 0; n_esc = n_ext = 0;
+    for (agx_u32 i = 0; i < n; i++) if (agx_chit_anchor(hits[i], maxlen, pos) && pos < base) base = pos;
+    B.base = base; B.pad = 0;
+    for (agx_u32 i = 0; i < AGX_CH_BLOCK; i++) {
+        agx_u32 word = 0;
+        if (i < n && agx_chit_encode(hits[i], base, maxlen, word)) { B.num[i] = hits[i].row; B.word[i] = word; if (agx_chit_has_side(word)) ext[n_ext++] = (word & AGX_WF_RUNS1) ? hits[i].a : hits[i].b; }
+        else { B.num[i] = 0; B.word[i] = 0; if (i < n) esc[n_esc++] = hits[i]; }
+    }
+}
+// and back, slot by slot (the device counts the escapes and extra words in front of a lane with a ballot: agx_k_expand_hits)
+AGX_HD void agx_chit_unpack_block(const agx_chit_block &B, agx_u32 n, agx_u32 maxlen, const agx_whit *esc_list, const agx_u32 *ext_list, agx_whit *out) {
+    agx_u32 e = B.esc, x = B.ext;
+    for (agx_u32 i = 0; i < n; i++) {
+        const agx_u32 word = B.word[i];
+        if (agx_chit_escaped(word)) out[i] = esc_list[e++];
+        else out[i] = agx_chit_decode(B.num[i], word, B.base, maxlen, agx_chit_has_side(word) ? ext_list[x++] : 0u);
+    }
+}
+// Sides travel as their two counts, a byte each; runs1 / runs2 are running sums of the counts where the run pool lies in side order and a mate without runs holds a zero
+// (agx_sides_consecutive: the loaders' layout; a unit for which it does not hold sends its side records as they are), rebuilt by a scan on the device.  A side with a count beyond a byte carries the mark
+// and its nruns word travels in a list of (side, nruns) that a second kernel writes over it.
+#define AGX_CS_ESC 0xFFFFu
+struct agx_cside_esc { agx_u32 side, nruns; };
+AGX_HD agx_u32 agx_cside_pack(agx_u32 nruns) { const agx_u32 n1 = nruns & 0xFFFFu, n2 = nruns >> 16; return (n1 < 256u && n2 < 256u && (n1 | n2 << 8) != AGX_CS_ESC) ? (n1 | n2 << 8) : AGX_CS_ESC; }
+AGX_HD agx_u32 agx_cside_nruns(agx_u32 c) { return (c & 0xFFu) | (c >> 8) << 16; }
+AGX_HD agx_u32 agx_cside_total(agx_u32 nruns) { return (nruns & 0xFFFFu) + (nruns >> 16); }
+// before: the counts of the sides in front.  A mate without runs names no place in the pool: its field is the loaders' zero
+AGX_HD agx_wside agx_cside_rebuild(agx_u32 first, agx_u32 before, agx_u32 nruns) { const agx_u32 n1 = nruns & 0xFFFFu, r1 = first + before; return agx_wside{n1 ? r1 : 0u, (nruns >> 16) ? r1 + n1 : 0u, nruns}; }
+// one step of the check that the run pool lies in side order: side sd where `at` runs lie in front of it (at: a 64-bit sum that must stay below 2^32)
+AGX_HD bool agx_cside_in_order(const agx_wside &sd, unsigned long long &at) {
+    const agx_u32 n1 = sd.nruns & 0xFFFFu, n2 = sd.nruns >> 16;
+    const bool fine = sd.runs1 == (n1 ? at : 0ull) && sd.runs2 == (n2 ? at + n1 : 0ull);
+    at += n1 + n2;
+    return fine && at <= 0xFFFFFFFFull;
+}
+AGX_HD agx_u32 agx_cside_first(const agx_wside *sides, size_t n) { return !n ? 0u : (sides[0].nruns & 0xFFFFu) ? sides[0].runs1 : (sides[0].nruns >> 16) ? sides[0].runs2 : 0u; }      // where the pool's first listed run lies
+AGX_HD bool agx_sides_consecutive(const agx_wside *sides, size_t n, agx_u32 &first) {
+    first = agx_cside_first(sides, n);
+    unsigned long long at = first;
+    for (size_t i = 0; i < n; i++) if (!agx_cside_in_order(sides[i], at)) return false;
+    return true;
+}
 // reference bases: 2 bits each (A, C, G, T = 0..3, four per byte, position x in bits 2 * (x & 3) of byte x >> 2) + the stretches that are anything
 // else (N runs, lower case), as runs of one byte value
 struct agx_refx { agx_u32 pos, len, byte; };

@@ -262,9 +262,10 @@ inline GraphCounts landing_estimate(size_t n_pos) { const size_t ni = n_pos + n_
 
 // The staged blocks that a one-shot unit's download may land in, in the order download_buffers cuts from them, the largest first: its inputs, dead once they are in HBM
 // (`input`), and the landing block that reserve_landing sizes by what the inputs lack.
-const int LANDING_ROOMS = 8;
+const int LANDING_ROOMS = 10;
 template <class F> void landing_rooms(agx_unit *u, F f) {
     f(u->s_codes, true); f(u->s_hits, true); f(u->s_landing, false); f(u->s_codes_t, true); f(u->s_hits_t, true); f(u->s_runs, true); f(u->s_sides, true); f(u->s_other, true);
+    f(u->s_wire, true); f(u->s_csides, true);      // (the compact wire forms; the tile-ordered records they stand for are ordinary memory then and count for nothing)
 }
 
 // A one-shot unit's download lands in the pinned memory of its staged inputs, which are dead once they are in HBM (do_download).  Since r03 those are packed
@@ -315,6 +316,88 @@ void stage_order(agx_unit *u, unsigned threads) {
     order_hits(u->s_hits.p, u->nh, u->s_sides.p, u->s_runs.p, u->s_jump.p, u->n_jump, n_pos, threads, u->s_perm.p, u->s_tfirst.p, u->s_jump_at.p);
     if (getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] hits in tile order: %.1f ms (%zu hits, %zu tiles, window of %u tiles)\n", now_ms() - t0, u->nh, n_tiles, u->lookback);
 }
+// The hit and side records of the upload in their compact wire forms (agx_core.h "compact wire forms"): 16 -> about 9.5 bytes per hit and 12 -> 2 per side cross PCIe, in
+// front of everything else a unit sends, and the device makes d_whits / d_wsides of them at the head of the unit's first build (agx_k_expand_hits, agx_k_side_*).
+// AGX_WIRE_PLAIN=1: the records as they are (A/B, tests).
+inline bool want_compact() { const char *e = getenv("AGX_WIRE_PLAIN"); return !(e && atoi(e) != 0); }
+// The hits, a block at a time as its 64 records stand in the upload's order `hits` (tile order: stage_tiled writes them in its loop and hands each block over while it
+// is in the cache; r05's file order: stage_wire_hits).  Thread t of T packs the blocks [first(t), first(t + 1)); its escapes and extra words collect in lists of its own and
+// the headers hold places in those until finish() has put the lists behind one another.  Everything lands in ONE pinned buffer of the size the records would have taken
+// (s_wire: blocks, escapes, extra words — they are used only where they are fewer bytes): a unit pins what it pinned, and a one-shot unit's download finds the room it found.
+struct HitPacker {
+    agx_unit *u; unsigned T; size_t n_blocks; bool on; std::vector<std::vector<agx_whit>> esc; std::vector<std::vector<agx_u32>> ext;
+    HitPacker(agx_unit *unit, unsigned threads) : u(unit), T(threads), n_blocks((unit->nh + AGX_CH_BLOCK - 1) / AGX_CH_BLOCK), esc(threads), ext(threads) {
+        on = want_compact() && n_blocks * sizeof(agx_chit_block) < u->nh * sizeof(agx_whit);      // (a few dozen hits: the last block's empty slots outweigh the rest)
+        if (on) { u->s_wire.alloc((u->nh + 1) * sizeof(agx_whit)); for (unsigned t = 0; t < T; t++) { esc[t].reserve(u->nh / T / 8 + 64); ext[t].reserve(u->nh / T / 2 + 64); } }
+    }
+    agx_chit_block *blocks() const { return (agx_chit_block *)u->s_wire.p; }
+    size_t first(unsigned t) const { return n_blocks * t / T; }
+    void block(unsigned t, size_t b, const agx_whit *hits) {
+        const size_t lo = b * AGX_CH_BLOCK; const agx_u32 n = (agx_u32)std::min<size_t>(AGX_CH_BLOCK, u->nh - lo);
+        agx_whit e[AGX_CH_BLOCK]; agx_u32 x[AGX_CH_BLOCK], ne = 0, nx = 0;
+        agx_chit_block &B = blocks()[b];
+        agx_chit_pack_block(hits + lo, n, u->maxlen, B, e, ne, x, nx);
+        B.esc = (agx_u32)esc[t].size(); B.ext = (agx_u32)ext[t].size();
+        esc[t].insert(esc[t].end(), e, e + ne); ext[t].insert(ext[t].end(), x, x + nx);
+    }
+    bool finish(double t0) {      // false: the blocks would be no fewer bytes than the records (hits all over the unit: file order) — the unit sends its records
+        if (!on) return false;
+        size_t ne = 0, nx = 0;
+        for (unsigned t = 0; t < T; t++) { for (size_t b = first(t); b < first(t + 1); b++) { blocks()[b].esc += (agx_u32)ne; blocks()[b].ext += (agx_u32)nx; } ne += esc[t].size(); nx += ext[t].size(); }
+        const size_t bytes = n_blocks * sizeof(agx_chit_block) + ne * sizeof(agx_whit) + nx * 4;
+        const bool gain = bytes < u->nh * sizeof(agx_whit);
+        if (getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] compact hit records (with the forms they are made beside): %.1f ms, 16 -> %.2f bytes per hit, %.2f %% escaped, %.2f %% with an extra word%s\n", now_ms() - t0,
+                                              (double)bytes / u->nh, 100.0 * ne / u->nh, 100.0 * nx / u->nh, gain ? "" : ": not used");
+        if (!gain) return false;
+        agx_whit *e_at = (agx_whit *)(u->s_wire.p + n_blocks * sizeof(agx_chit_block)); agx_u32 *x_at = (agx_u32 *)(e_at + ne);      // (a block is a multiple of 16 bytes)
+        u->wire_esc = e_at; u->wire_ext = x_at;
+        for (unsigned t = 0; t < T; t++) {
+            if (!esc[t].empty()) memcpy(e_at, esc[t].data(), esc[t].size() * sizeof(agx_whit));
+            if (!ext[t].empty()) memcpy(x_at, ext[t].data(), ext[t].size() * 4);
+            e_at += esc[t].size(); x_at += ext[t].size();
+        }
+        u->n_cblocks = n_blocks; u->n_cesc = ne; u->n_cext = nx;
+        return true;
+    }
+};
+void release_wire_hits(agx_unit *u) { u->hits_compact = false; u->n_cblocks = u->n_cesc = u->n_cext = 0; u->wire_esc = nullptr; u->wire_ext = nullptr; u->s_wire.release(); }
+// a unit that uploads r05's file-order forms: the same blocks over s_hits
+void stage_wire_hits(agx_unit *u, unsigned threads) {
+    release_wire_hits(u);
+    if (u->nh == 0) return;
+    const double t0 = now_ms();
+    const unsigned T = std::max(1u, std::min(threads, 16u));
+    HitPacker P(u, T);
+    if (P.on) on_threads(T, [&](unsigned t) { for (size_t b = P.first(t); b < P.first(t + 1); b++) P.block(t, b, u->s_hits.p); });
+    u->hits_compact = P.finish(t0);
+    if (!u->hits_compact) u->s_wire.release();
+}
+// The sides as their counts, the listed sides behind them in one pinned buffer.  The run pool lies in side order (both loaders write a hit's runs where the last hit's end) or
+// the unit sends the records themselves.
+void stage_wire_sides(agx_unit *u) {
+    u->sides_compact = false; u->n_csesc = 0; u->side_first = 0; u->wire_listed = nullptr;
+    const size_t n = u->n_sides;
+    const double t0 = now_ms();
+    bool fine = want_compact() && n != 0;
+    if (fine) {
+        const agx_wside *sd = u->s_sides.p; size_t listed = 0;
+        u->side_first = agx_cside_first(sd, n); unsigned long long at = u->side_first;
+        for (size_t i = 0; i < n && fine; i++) { fine = agx_cside_in_order(sd[i], at); listed += agx_cside_pack(sd[i].nruns) == AGX_CS_ESC; }      // (agx_sides_consecutive)
+        const size_t counts_bytes = (n * 2 + 7) & ~(size_t)7, bytes = n * 2 + listed * sizeof(agx_cside_esc);
+        if (fine && bytes >= n * sizeof(agx_wside)) fine = false;
+        if (fine) {
+            u->s_csides.alloc(counts_bytes + (listed + 1) * sizeof(agx_cside_esc));
+            agx_u16 *c = (agx_u16 *)u->s_csides.p; agx_cside_esc *l = (agx_cside_esc *)(u->s_csides.p + counts_bytes);
+            u->wire_listed = l; u->n_csesc = listed;
+            for (size_t i = 0; i < n; i++) { const agx_u32 v = agx_cside_pack(sd[i].nruns); c[i] = (agx_u16)v; if (v == AGX_CS_ESC) *l++ = agx_cside_esc{(agx_u32)i, sd[i].nruns}; }
+        }
+        if (getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] compact side records: %.1f ms, 12 -> %.2f bytes per side, %.2f %% listed%s\n", now_ms() - t0, (double)bytes / n,
+                                              100.0 * listed / n, fine ? "" : ": not used (the run pool is not in side order, or nothing gained)");
+    }
+    if (!fine) { u->s_csides.release(); return; }
+    u->sides_compact = true;
+}
+
 // r06: what the device is sent of the read alignments, in the order of the hits' first tiles (stage_order's permutation applied on the host).
 //   * the wire records: s_hits_t[i] = hit perm[i], its `row` field carrying the hit's NUMBER (the key the tile lists are ranked by) — the 4 bytes per hit of the permutation no
 //     longer cross PCIe, the device reads the records in order instead of gathering them — and AGX_WF_DUP what the rule of AG:1650-1655 says about it (it needs the hit's FILE
@@ -331,7 +414,10 @@ void stage_tiled(agx_unit *u, unsigned threads) {
     // (rows that were to cross as differences and do not — nothing gained — cross tile-ordered)
     if (u->rows_diffed || getenv("AGX_NO_TILED_UPLOAD") || nh == 0 || u->n_rows == 0) { u->s_hits_t.release(); u->s_codes_t.release(); u->s_other_t.release(); return; }
     const double t0 = now_ms();
-    u->s_hits_t.alloc(nh + 1); u->s_codes_t.alloc(nh * s4 + 16); u->slot_row.resize(nh);
+    // (records that cross in their compact blocks are only ever read by the host: ordinary memory)
+    const bool compact = want_compact();
+    if (compact) u->s_hits_t.alloc_plain(nh + 1); else u->s_hits_t.alloc(nh + 1);
+    u->s_codes_t.alloc(nh * s4 + 16); u->slot_row.resize(nh);
     const agx_whit *wh = u->s_hits.p; const agx_wside *sd = u->s_sides.p; const agx_wrun *wr = u->s_runs.p; const agx_u32 *perm = u->s_perm.p;
     // rows that carry a listed base (few): one bit per row
     const size_t n_rows = u->n_rows; std::vector<agx_u8> has_other((n_rows + 7) / 8, 0);
@@ -343,10 +429,13 @@ void stage_tiled(agx_unit *u, unsigned threads) {
     };
     const unsigned T = std::max(1u, std::min(threads, 16u));
     std::vector<std::vector<unsigned long long>> others(T);
+    release_wire_hits(u);
+    HitPacker packer(u, T);
+    const size_t n_blocks = (nh + AGX_CH_BLOCK - 1) / AGX_CH_BLOCK;      // (a thread takes whole blocks of 64 hits)
     on_threads(T, [&](unsigned t) {
         // (two dependent random reads per hit — its record, then its row: asked for a few hits ahead, or every hit costs two cache misses in a row: 0.16 s of cfg3's load)
         const size_t AHEAD = 48, NEAR = 24;
-        for (size_t i = nh * t / T, hi = nh * (t + 1) / T; i < hi; i++) {
+        for (size_t i = (n_blocks * t / T) * AGX_CH_BLOCK, hi = std::min<size_t>(nh, (n_blocks * (t + 1) / T) * AGX_CH_BLOCK); i < hi; i++) {
             if (i + AHEAD < hi) __builtin_prefetch(wh + perm[i + AHEAD]);
             if (i + NEAR < hi) { const char *c = (const char *)(u->s_codes.p + (size_t)wh[perm[i + NEAR]].row * s4); __builtin_prefetch(c); if (s4 > 40) __builtin_prefetch(c + 64); }
             const agx_u32 h = perm[i]; agx_whit w = wh[h];
@@ -357,6 +446,7 @@ void stage_tiled(agx_unit *u, unsigned threads) {
             if (w.back) { const agx_u32 me = idx0(w); for (agx_u32 e = 1; e <= w.back && !dup; e++) dup = agx_absdiff(me, idx0(wh[h - e])) < (int)w.len; }      // agx_hit_dup_by
             w.row = h; if (dup) w.flags |= (agx_u8)AGX_WF_DUP;
             u->s_hits_t.p[i] = w;
+            if (packer.on && ((i & (AGX_CH_BLOCK - 1)) == AGX_CH_BLOCK - 1 || i + 1 == nh)) packer.block(t, i / AGX_CH_BLOCK, u->s_hits_t.p);
             if (has_other[row >> 3] & (1u << (row & 7))) {
                 const unsigned long long lo = (unsigned long long)row * u->stride, *b = u->s_other.p, *e = b + u->n_other;
                 for (const unsigned long long *at = std::lower_bound(b, e, lo); at != e && *at < lo + u->stride; ++at) others[t].push_back((unsigned long long)i * u->stride + (*at - lo));
@@ -367,6 +457,11 @@ void stage_tiled(agx_unit *u, unsigned threads) {
     u->s_other_t.alloc(no + 1); u->n_other_t = no;
     { size_t at = 0; for (auto &v : others) { if (!v.empty()) memcpy(u->s_other_t.p + at, v.data(), v.size() * 8); at += v.size(); } }
     u->tiled = true;
+    u->hits_compact = packer.finish(t0);
+    if (compact && !u->hits_compact) {      // nothing gained: the records into the pinned buffer that the blocks would have filled
+        u->s_wire.alloc((nh + 1) * sizeof(agx_whit));
+        on_threads(T, [&](unsigned t) { const size_t lo = nh * t / T, hi = nh * (t + 1) / T; if (hi > lo) memcpy(u->s_wire.p + lo * sizeof(agx_whit), u->s_hits_t.p + lo, (hi - lo) * sizeof(agx_whit)); });
+    }
     // windows of the first build's sweep: about 8 M positions each, eight at most (AGX_UPLOAD_WINDOWS forces a number: tests), cut at tiles
     const size_t n_pos = u->V.n_pos ? u->V.n_pos : u->T.ref.size(), n_tiles = (n_pos + AGX_TILE - 1) / AGX_TILE;
     size_t W = getenv("AGX_UPLOAD_WINDOWS") ? (size_t)atoi(getenv("AGX_UPLOAD_WINDOWS")) : n_pos / 8000000u;
@@ -405,6 +500,8 @@ void finish_staging(agx_unit *u, unsigned threads_rows, unsigned threads) {
     stage_rows(u, threads_rows);
     stage_order(u, threads);
     stage_tiled(u, threads);
+    if (!u->tiled) stage_wire_hits(u, threads);
+    stage_wire_sides(u);
     stage_rows_tiled(u, threads);
     u->V.slot_row = u->tiled ? u->slot_row.data() : nullptr;
     reserve_landing(u);
@@ -733,6 +830,8 @@ template <class U> void fixed_bufs(U *u, Take &t) {
     t(u->d_runs, u->n_runs + 1); t(u->d_vcodes, codes_bytes(u) * 4 + 16); t(u->d_other, others_up(u) + 1);
     if (u->rows_diffed) { t(u->d_units, u->n_units + 2); t(u->d_rowcnt, u->n_rowcnt); t(u->d_blockoff, u->n_blockoff); t(u->d_blockfirst, u->n_blockfirst); t(u->d_anchor, u->n_anchor); }
     else t(u->d_codes, codes_bytes(u) + 16);
+    if (u->hits_compact) { t(u->d_chits, u->n_cblocks + 1); t(u->d_cesc, u->n_cesc + 1); t(u->d_cext, u->n_cext + 1); }
+    if (u->sides_compact) { t(u->d_csides, u->n_sides + 1); t(u->d_csesc, u->n_csesc + 1); t(u->d_cside_scan, agx_side_scan_words(u->n_sides)); }
     t(u->d_whits, nh + 1); t(u->d_wsides, u->n_sides + 1); t(u->d_wruns, u->n_runs + 1); t(u->d_jump, u->n_jump + 1);
     if (u->ref_packed) { t(u->d_wref, (n_pos + 3) / 4 + 32); t(u->d_refx, u->n_refx + 1); }
     t(u->d_dhit, nh + 1);
@@ -835,7 +934,11 @@ void do_upload(agx_unit *u) {
         };
         up(u->d_segs.p, u->s_segs.p, u->n_segs * sizeof(agx_cmseg)); up(u->d_cntruns.p, u->s_cntruns.p, u->n_cntruns * sizeof(agx_cntrun));
         up(u->d_cntchunks.p, u->s_cntchunks.p, u->n_cntchunks * sizeof(agx_chunk)); up(u->d_segchunks.p, u->s_segchunks.p, u->n_segchunks * sizeof(agx_chunk)); up(u->d_segindex.p, u->s_segindex.p, u->n_segindex * 4);
-        up(u->d_whits.p, u->tiled ? u->s_hits_t.p : u->s_hits.p, nh * sizeof(agx_whit)); up(u->d_wsides.p, u->s_sides.p, u->n_sides * sizeof(agx_wside)); up(u->d_wruns.p, u->s_runs.p, u->n_runs * sizeof(agx_wrun)); up(u->d_jump.p, u->s_jump_at.p, u->n_jump * 4);
+        if (u->hits_compact) { up(u->d_chits.p, u->s_wire.p, u->n_cblocks * sizeof(agx_chit_block)); up(u->d_cesc.p, u->wire_esc, u->n_cesc * sizeof(agx_whit)); up(u->d_cext.p, u->wire_ext, u->n_cext * 4); }
+        else up(u->d_whits.p, !u->tiled ? (const void *)u->s_hits.p : u->s_wire.p ? (const void *)u->s_wire.p : (const void *)u->s_hits_t.p, nh * sizeof(agx_whit));      // (s_wire: the tile-ordered records of a unit that gained nothing from the blocks)
+        if (u->sides_compact) { up(u->d_csides.p, u->s_csides.p, u->n_sides * 2); up(u->d_csesc.p, u->wire_listed, u->n_csesc * sizeof(agx_cside_esc)); }
+        else up(u->d_wsides.p, u->s_sides.p, u->n_sides * sizeof(agx_wside));
+        up(u->d_wruns.p, u->s_runs.p, u->n_runs * sizeof(agx_wrun)); up(u->d_jump.p, u->s_jump_at.p, u->n_jump * 4);
         if (!u->tiled) up(u->d_perm.p, u->s_perm.p, nh * 4);      // (tile-ordered records carry their hit numbers: agx_k_hit_prep writes the array)
         up(u->d_tfirst.p, u->s_tfirst.p, ((size_t)u->n_tiles + 2) * 4);
         HIP_OK(hipEventRecord(u->ev_hits, st));         // what the front of the build needs (conti-mer tables, hit preparation, binning) is there: it starts while the rest still travels
@@ -985,6 +1088,8 @@ void do_build(agx_unit *u) {
         if (turn.n) HIP_OK(hipStreamWaitEvent(st, (u->ev.all || turn.prev_exclusive) ? turn.build_done[(turn.n - 1) & 1] : turn.sweep_done[(turn.n - 1) & 1], 0));
         if (u->ev.all) HIP_OK(hipEventRecord(u->ev.first, st));      // (every event record costs the stream a few microseconds: untimed builds record only what orders them)
         if (!u->expanded) {   // the unit's first build: the hits and runs out of their wire forms, then the conti-mer tables from their runs (agx_cmseg: count per position, scan, keys, heads); the read bases follow behind the binning
+            if (u->hits_compact) agx_launch_expand_hits(u->d_chits.p, u->d_cesc.p, u->d_cext.p, u->d_whits.p, nh, u->maxlen, st);
+            if (u->sides_compact) agx_launch_expand_sides(u->d_csides.p, u->d_csesc.p, (agx_u32)u->n_csesc, u->d_wsides.p, (agx_u32)u->n_sides, u->side_first, u->d_cside_scan.p, st);
             agx_launch_expand_runs(u->d_wruns.p, u->d_runs.p, (agx_u32)u->n_runs, st);
             agx_launch_cm_tables(u->d_cntruns.p, u->d_cntchunks.p, (agx_u32)u->n_cntchunks, u->d_segs.p, u->d_segchunks.p, (agx_u32)u->n_segchunks, u->d_cm_start.p, u->d_cm.p, u->d_cm_head.p, n_pos, (agx_u32)u->n_cm, st);
         }

@@ -214,6 +214,10 @@ void agx_launch_expand_rows(const void *whits, agx_u32 nh, const void *wsides, c
                             const agx_u16 *units, const void *wref, void *vcodes, agx_u32 n_rows, agx_u32 stride, const unsigned long long *other, size_t n_other, hipStream_t);
 void agx_launch_patch_codes(const unsigned long long *other, size_t n_other, void *vcodes, hipStream_t);      // the listed bases alone (indices into the whole vote-code array)
 void agx_launch_expand_runs(const void *wruns, agx_run *runs, agx_u32 n_runs, hipStream_t);      // wire formats (agx_core.h) -> working arrays
+// compact wire forms (agx_core.h) -> the wire records, once per upload.  The sides' scratch: their runs and the scan's output, n + 1 words each, then the scan's own words
+void agx_launch_expand_hits(const agx_chit_block *blocks, const void *esc, const agx_u32 *ext, void *whits, agx_u32 nh, agx_u32 maxlen, hipStream_t);
+inline size_t agx_side_scan_words(size_t n) { const size_t nb = (n + 1 + 4095) / 4096, nb2 = (nb + 4095) / 4096; return 2 * (n + 1) + 2 * (nb + 1) + 2 * (nb2 + 1); }
+void agx_launch_expand_sides(const agx_u16 *counts, const agx_cside_esc *list, agx_u32 n_list, void *sides, agx_u32 n, agx_u32 first, agx_u32 *scan, hipStream_t);
 void agx_launch_expand_ref(const void *packed, void *ref, size_t n_pos16, const void *refx, agx_u32 n_refx, hipStream_t);      // 2-bit reference bases + the stretches of other bytes -> letters; n_pos16 a multiple of 16
 void agx_launch_hit_prep(const agx_prep_args *, hipStream_t);
 // exclusive scan of in[0..n] (n+1 entries; in[n] is read, its value reaches no output) into out[0..n]; out[n] = total.  tmp: 2*(nb+1) + 2*(nb2+1) words, nb = ceil((n+1)/4096), nb2 = ceil(nb/4096)

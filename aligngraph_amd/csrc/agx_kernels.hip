@@ -121,6 +121,34 @@ __global__ void __launch_bounds__(256) agx_k_expand_runs(const agx_wrun *wruns, 
     const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
     if (i < n_runs) { const agx_wrun r = wruns[i]; runs[i] = agx_run{r.q, r.t, r.n}; }
 }
+// The hit records out of their blocks (agx_core.h "compact wire forms"): a wavefront per block, a lane per slot.  The slots' two words are consecutive across the lanes, the
+// header is wave-uniform; a lane finds its place in the block's escapes or extra words by counting the lanes in front of it in a ballot.  Each lane stores its 16-byte
+// record whole: a wavefront writes 1 KB of consecutive bytes.
+__global__ void __launch_bounds__(256) agx_k_expand_hits(const agx_chit_block *blocks, const uint4 *esc, const agx_u32 *ext, uint4 *whits, agx_u32 nh, agx_u32 maxlen) {
+    const agx_u32 i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+    const bool valid = i < nh;
+    const agx_chit_block *B = blocks + (i >> 6);
+    const agx_u32 num = valid ? B->num[lane] : 0u, word = valid ? B->word[lane] : 0u;
+    const bool escaped = valid && agx_chit_escaped(word), side = valid && !escaped && agx_chit_has_side(word);
+    const unsigned long long front = (1ull << lane) - 1ull, em = __ballot(escaped), xm = __ballot(side);
+    if (!valid) return;
+    if (escaped) { whits[i] = esc[B->esc + (agx_u32)__popcll(em & front)]; return; }
+    const agx_whit w = agx_chit_decode(num, word, B->base, maxlen, side ? ext[B->ext + (agx_u32)__popcll(xm & front)] : 0u);
+    whits[i] = make_uint4(w.a, w.b, w.row, (agx_u32)w.len | (agx_u32)w.flags << 16 | (agx_u32)w.back << 24);
+}
+// The side records from their counts: the nruns word and the side's runs (the scan's input) per side, the listed sides over them, and behind the scan the two firsts.
+__global__ void __launch_bounds__(256) agx_k_side_counts(const agx_u16 *counts, agx_wside *sides, agx_u32 *total, agx_u32 n) {
+    const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) { const agx_u32 nr = agx_cside_nruns(counts[i]); sides[i].nruns = nr; total[i] = agx_cside_total(nr); }
+}
+__global__ void __launch_bounds__(256) agx_k_side_listed(const agx_cside_esc *list, agx_u32 n_list, agx_wside *sides, agx_u32 *total) {
+    const agx_u32 j = blockIdx.x * 256u + threadIdx.x;
+    if (j < n_list) { const agx_cside_esc e = list[j]; sides[e.side].nruns = e.nruns; total[e.side] = agx_cside_total(e.nruns); }
+}
+__global__ void __launch_bounds__(256) agx_k_side_firsts(const agx_u32 *before, agx_wside *sides, agx_u32 n, agx_u32 first) {
+    const agx_u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) sides[i] = agx_cside_rebuild(first, before[i], sides[i].nruns);
+}
 // 16 positions per thread: one packed word in, sixteen letters out
 __global__ void __launch_bounds__(256) agx_k_expand_ref(const agx_u32 *packed, uint4 *ref, size_t n16) {
     const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
@@ -1235,6 +1263,17 @@ void agx_launch_expand_rows(const void *whits, agx_u32 nh, const void *wsides, c
 }
 void agx_launch_expand_runs(const void *wruns, agx_run *runs, agx_u32 n_runs, hipStream_t st) {
     if (n_runs) hipLaunchKernelGGL(agx_k_expand_runs, dim3((n_runs + 255) / 256), dim3(256), 0, st, (const agx_wrun *)wruns, runs, n_runs);
+}
+void agx_launch_expand_hits(const agx_chit_block *blocks, const void *esc, const agx_u32 *ext, void *whits, agx_u32 nh, agx_u32 maxlen, hipStream_t st) {
+    if (nh) hipLaunchKernelGGL(agx_k_expand_hits, dim3((nh + 255) / 256), dim3(256), 0, st, blocks, (const uint4 *)esc, ext, (uint4 *)whits, nh, maxlen);
+}
+void agx_launch_expand_sides(const agx_u16 *counts, const agx_cside_esc *list, agx_u32 n_list, void *sides, agx_u32 n, agx_u32 first, agx_u32 *scan, hipStream_t st) {
+    if (!n) return;
+    agx_u32 *total = scan, *before = scan + n + 1, *tmp = before + n + 1;      // (agx_side_scan_words)
+    hipLaunchKernelGGL(agx_k_side_counts, dim3((n + 255) / 256), dim3(256), 0, st, counts, (agx_wside *)sides, total, n);
+    if (n_list) hipLaunchKernelGGL(agx_k_side_listed, dim3((n_list + 255) / 256), dim3(256), 0, st, list, n_list, (agx_wside *)sides, total);
+    agx_launch_exclusive_scan(total, before, n, tmp, st);
+    hipLaunchKernelGGL(agx_k_side_firsts, dim3((n + 255) / 256), dim3(256), 0, st, before, (agx_wside *)sides, n, first);
 }
 void agx_launch_expand_ref(const void *packed, void *ref, size_t n_pos16, const void *refx, agx_u32 n_refx, hipStream_t st) {
     const size_t n16 = n_pos16 / 16;

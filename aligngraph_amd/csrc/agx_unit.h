@@ -146,6 +146,10 @@ struct agx_unit {
     PBuf<agx_u32> s_chain_end, s_region_off; PBuf<agx_cmseg> s_segs; size_t n_segs = 0;
     // r06, tile-ordered upload (stage_tiled): the wire records and the read rows in the order of the hits' first tiles — what the device is sent instead of s_hits / s_perm / s_codes / s_other
     PBuf<agx_whit> s_hits_t; PBuf<agx_u8> s_codes_t; PBuf<unsigned long long> s_other_t; size_t n_other_t = 0; bool tiled = false; std::vector<agx_u32> slot_row;      // slot_row[i] = staged row of the i-th hit's left mate (the walk's k-mer tails)
+    // the hit and side records in their compact wire forms (agx_core.h; made at the end of staging: stage_wire_hits / stage_wire_sides).  hits_compact / sides_compact = false:
+    // the unit sends the 16- and 12-byte records themselves (nothing gained, a run pool that is not in side order, AGX_WIRE_PLAIN=1)
+    // s_wire: the hits' blocks, escapes and extra words in one pinned buffer of the records' size (or, tile-ordered with nothing gained, the records); s_csides: counts, then the listed sides
+    PBuf<char> s_wire, s_csides; const agx_whit *wire_esc = nullptr; const agx_u32 *wire_ext = nullptr; const agx_cside_esc *wire_listed = nullptr; size_t n_cblocks = 0, n_cesc = 0, n_cext = 0, n_csesc = 0; agx_u32 side_first = 0; bool hits_compact = false, sides_compact = false;
     agx_u32 front_windows = 1;      // windows the last build's node sweep ran in (agx_unit_front)
     agx_u32 n_win = 1, win_tile[9] = {};      // a unit's first build sweeps windows of tiles as their rows land: window w = tiles [win_tile[w], win_tile[w + 1])
     hipEvent_t ev_rows[8] = {}, ev_win[8] = {}, ev_sw0[8] = {}, ev_sw1[8] = {};      // rows of window w in HBM / expanded; around window w's sweep (its time is the sum over the windows)
@@ -167,6 +171,7 @@ struct agx_unit {
     DBuf<agx_run> d_runs; DBuf<agx_u8> d_codes, d_vcodes; DBuf<unsigned long long> d_other;
     DBuf<agx_u16> d_units; DBuf<agx_u8> d_rowcnt; DBuf<agx_u32> d_blockoff, d_blockfirst, d_anchor;
     DBuf<agx_cntrun> d_cntruns; DBuf<agx_chunk> d_cntchunks, d_segchunks; DBuf<agx_u32> d_jump, d_segindex;
+    DBuf<agx_chit_block> d_chits; DBuf<agx_whit> d_cesc; DBuf<agx_u32> d_cext, d_cside_scan; DBuf<agx_u16> d_csides; DBuf<agx_cside_esc> d_csesc;      // the compact forms of the next line's first two, until the first build has expanded them
     DBuf<agx_whit> d_whits; DBuf<agx_wside> d_wsides; DBuf<agx_wrun> d_wruns; DBuf<agx_u8> d_wref; DBuf<agx_refx> d_refx;      // what was uploaded, until the first build has expanded it
     // derived
     DBuf<agx_dhit> d_dhit; DBuf<agx_u32> d_tile_cnt, d_tile_off, d_cursor, d_unsorted, d_tile_recs, d_scan_tmp, d_words; DBuf<unsigned long long> d_scan_desc; size_t scan_desc_n = 0;      // descriptors of the three one-launch scans   // d_words: counters/status

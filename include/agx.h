@@ -116,7 +116,7 @@ typedef struct {
     double ms_build_span;                                        /* with AGX_FLAG_TIME_SECTIONS: device time from the first to the last command of the build (all kernels and the gaps between them) */
     double ms_stage;                                             /* packing the handed-over arrays into pinned upload buffers (agx_unit_stage) */
     double ms_upload_dev;                                        /* with AGX_FLAG_TIME_SECTIONS: device time of the unit's upload copies on the device's upload stream */
-    uint64_t upload_bytes, device_bytes;                         /* bytes copied host -> HBM by the upload; HBM held by the unit */
+    uint64_t upload_bytes, device_bytes;                         /* bytes copied host -> HBM by the upload (AGX_WIRE_PLAIN=1: hit and side records as they are, not in their compact wire forms); HBM held by the unit */
     uint64_t pinned_bytes_cached, device_bytes_cached;           /* free blocks in the library's pinned-host and device caches (agx_pool_trim releases them) */
     uint64_t n_spilled;                                          /* node ids taken from the pool's spill area (regions whose slice was full) */
     uint32_t build_attempts, from_cache;                         /* build_attempts: 1 unless a capacity had to grow and the build was repeated; from_cache: the unit was
