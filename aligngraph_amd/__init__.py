@@ -33,6 +33,7 @@ EXPORTS = [
     "agx_unit_edge_reads", "agx_edge_reads_free", "agx_edge_reads_tsv",
     "agx_unit_pair_span", "agx_pair_span_free", "agx_unit_walk_span", "agx_walk_span_free", "agx_walk_span_bed",
     "agx_unit_mate_links", "agx_mate_links_free", "agx_mate_links_tsv",
+    "agx_unit_bubbles", "agx_unitigs_bubbles", "agx_bubbles_free", "agx_bubbles_tsv",
     "agx_test_scan", "agx_test_zero", "agx_test_copy_out",
 ]
 
@@ -151,6 +152,19 @@ class MateLinks(ctypes.Structure):
                [("len_sum", ctypes.POINTER(ctypes.c_uint64))] + [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("lo_min", "lo_max", "hi_min", "hi_max")]
 
 
+class Bubbles(ctypes.Structure):
+    _fields_ = [("n_segs", ctypes.c_uint32), ("n_links", ctypes.c_uint32)] + \
+               [(n, ctypes.c_uint64) for n in ("n_forks", "n_bubbles_all", "n_tip", "n_nested", "n_sinks_differ", "n_sink_shared")] + \
+               [(n, ctypes.c_uint32) for n in ("longest_branch", "max_nodes", "has_support", "n_bubbles", "n_branches")] + \
+               [("n_bases", ctypes.c_uint64), ("bytes_down", ctypes.c_uint64), ("ms", ctypes.c_double)] + \
+               [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("src_pos", "src_var", "src_last", "sink_pos", "sink_var", "br_off", "br_pos", "br_var", "br_nodes")] + \
+               [(n, ctypes.POINTER(ctypes.c_uint64)) for n in ("br_cov", "br_seq_off")] + [(n, ctypes.POINTER(ctypes.c_uint32)) for n in ("br_sup_in", "br_sup_out")] + \
+               [("seq", ctypes.c_void_p)]
+
+
+TOTALS_BUBBLES = ("n_segs", "n_links", "n_forks", "n_bubbles_all", "n_tip", "n_nested", "n_sinks_differ", "n_sink_shared", "longest_branch", "max_nodes")
+BUBBLE_BUBBLES = ("src_pos", "src_var", "src_last", "sink_pos", "sink_var")
+BRANCH_BUBBLES = ("br_pos", "br_var", "br_nodes", "br_cov")
 TOTALS_LINKS = ("n_kept", "n_outside", "n_fragments", "n_unowned", "n_inside", "n_open", "n_link_pairs", "n_links_all", "n_owned", "n_shadowed", "n_passes", "n_slots")
 REC_LINKS = ("rec_inside", "rec_open_left", "rec_open_right", "rec_links_out", "rec_links_in")
 LINK_LINKS = ("a", "b", "n_pairs", "len_sum", "lo_min", "lo_max", "hi_min", "hi_max")
@@ -334,6 +348,11 @@ def lib():
         L.agx_unit_edge_reads.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EdgeReads)]
         L.agx_edge_reads_free.argtypes = [ctypes.POINTER(EdgeReads)]
         L.agx_edge_reads_free.restype = None
+        L.agx_unit_bubbles.argtypes = [ctypes.c_void_p] + [ctypes.c_uint32] * 5 + [ctypes.POINTER(Bubbles)]
+        L.agx_unitigs_bubbles.argtypes = [ctypes.POINTER(Unitigs), ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(Bubbles)]
+        L.agx_bubbles_free.argtypes = [ctypes.POINTER(Bubbles)]
+        L.agx_bubbles_free.restype = None
+        L.agx_bubbles_tsv.argtypes = [ctypes.POINTER(Bubbles), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         L.agx_edge_reads_tsv.argtypes = [ctypes.POINTER(EdgeReads), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         L.agx_run_unit.argtypes = [ctypes.POINTER(Params), ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Result), ctypes.c_char_p, ctypes.c_size_t]
         _lib = L
@@ -743,6 +762,22 @@ class Unit:
         finally:
             lib().agx_mate_links_free(ctypes.byref(l))
 
+    def bubbles(self, region=None, min_coverage=None, max_nodes=None, edge_support=False):
+        """The variant sites of the unit's graph, found on the device (agx_unit_bubbles; needs keep_counts): the forks of the graph unitigs(region, min_coverage) gives,
+        counted by class — n_forks, n_bubbles_all, n_tip, n_nested, n_sinks_differ, n_sink_shared, longest_branch, with n_segs and n_links —, and the table of the bubbles
+        whose branch segments have max_nodes nodes at most (None: all), by source segment: src_pos, src_var, src_last, sink_pos, sink_var, br_off per bubble (one offset
+        more); br_pos, br_var (0xFFFFFFFF: a direct branch), br_nodes, br_cov, br_seq_off (one offset more) per branch row; seq, the branch segments' bases, as bytes.
+        edge_support=True (the unit was created with edge_support=True): also br_sup_in, br_sup_out.  ms and bytes_down: the call's host wall time and download."""
+        mx = 0xFFFFFFFF if max_nodes is None else int(max_nodes)
+        if not 0 <= mx <= 0xFFFFFFFF:
+            raise AgxError(AGX_E_ARG, "bubbles: max_nodes is an unsigned 32-bit number")
+        b = Bubbles()
+        self._check(lib().agx_unit_bubbles(self._h, *self._window(region, min_coverage), mx, 1 if edge_support else 0, ctypes.byref(b)))
+        try:
+            return _bubbles_arrays(b)
+        finally:
+            lib().agx_bubbles_free(ctypes.byref(b))
+
     def gfa(self, unit=0, region=None, min_coverage=None, edge_support=False):
         """GFA 1.0 S and L lines of the unit's unitigs, segments named u<unit>_<pos>_<var> (no header line); region and min_coverage as in unitigs().
         edge_support=True: every L line also carries RC:i:<events that name the link's edge> (agx_unitigs_gfa_support)."""
@@ -850,6 +885,65 @@ def links_tsv(l, unit=0):
     for k, a in keep.items():
         setattr(s, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64 if k == "len_sum" else ctypes.c_uint32)))
     return _text(lib().agx_mate_links_tsv, ctypes.byref(s), unit, what="agx_mate_links_tsv: the link table is inconsistent")
+
+
+def _bubbles_arrays(b):
+    out = {k: int(getattr(b, k)) for k in TOTALS_BUBBLES}
+    out.update(ms=float(b.ms), bytes_down=int(b.bytes_down), has_support=bool(b.has_support))
+    for k in BUBBLE_BUBBLES:
+        out[k] = _arr(getattr(b, k), b.n_bubbles, "uint32")
+    out["br_off"] = _arr(b.br_off, b.n_bubbles + 1, "uint32")
+    for k in BRANCH_BUBBLES:
+        out[k] = _arr(getattr(b, k), b.n_branches, "uint64" if k == "br_cov" else "uint32")
+    out["br_seq_off"] = _arr(b.br_seq_off, b.n_branches + 1, "uint64")
+    if b.has_support:
+        out["br_sup_in"], out["br_sup_out"] = _arr(b.br_sup_in, b.n_branches, "uint32"), _arr(b.br_sup_out, b.n_branches, "uint32")
+    out["seq"] = ctypes.string_at(b.seq, b.n_bases) if b.seq and b.n_bases else b""
+    return out
+
+
+def unitigs_bubbles(t, link_support=None, max_nodes=None):
+    """The bubbles of a unitig table given as the dict Unit.unitigs() returns, as Unit.bubbles() gives them for the same graph (agx_unitigs_bubbles; host only, needs no
+    device).  link_support: one number per link (Unit.unitigs(edge_support=True)["link_support"]) for br_sup_in and br_sup_out, or None."""
+    import numpy as np
+    ts, _keep = _unitigs_struct(t)
+    sup = None
+    if link_support is not None:
+        sup = np.ascontiguousarray(link_support, dtype="uint32")
+        if len(sup) != ts.n_links:
+            raise AgxError(AGX_E_ARG, "agx_unitigs_bubbles: one number per link")
+        sup = np.concatenate([sup, np.zeros(1, "uint32")])      # (never a null pointer, also without links)
+    mx = 0xFFFFFFFF if max_nodes is None else int(max_nodes)
+    if not 0 <= mx <= 0xFFFFFFFF:
+        raise AgxError(AGX_E_ARG, "agx_unitigs_bubbles: max_nodes is an unsigned 32-bit number")
+    b = Bubbles()
+    rc = lib().agx_unitigs_bubbles(ctypes.byref(ts), sup.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if sup is not None else None, mx, ctypes.byref(b))
+    if rc != AGX_OK:
+        raise AgxError(rc, "agx_unitigs_bubbles: the unitig table is inconsistent")
+    try:
+        return _bubbles_arrays(b)
+    finally:
+        lib().agx_bubbles_free(ctypes.byref(b))
+
+
+def bubbles_tsv(b, unit=0):
+    """Text of the bubbles of a dict like Unit.bubbles() returns, one line per bubble (agx_bubbles_tsv; host only, needs no device)."""
+    import numpy as np
+    keep = {k: np.ascontiguousarray(b[k], dtype="uint32") for k in BUBBLE_BUBBLES + ("br_off", "br_pos", "br_var", "br_nodes")}
+    keep.update({k: np.ascontiguousarray(b[k], dtype="uint64") for k in ("br_cov", "br_seq_off")})
+    sup = "br_sup_in" in b and b["br_sup_in"] is not None
+    if sup:
+        keep.update({k: np.concatenate([np.ascontiguousarray(b[k], dtype="uint32"), np.zeros(1, "uint32")]) for k in ("br_sup_in", "br_sup_out")})
+    seq = ctypes.create_string_buffer(bytes(b["seq"]), max(1, len(b["seq"])))
+    s = Bubbles()
+    s.n_bubbles, s.n_branches, s.n_bases, s.has_support = len(keep["src_pos"]), len(keep["br_pos"]), len(b["seq"]), 1 if sup else 0
+    if len(keep["br_off"]) != s.n_bubbles + 1 or len(keep["br_seq_off"]) != s.n_branches + 1 or any(len(keep[k]) != s.n_bubbles for k in BUBBLE_BUBBLES) or \
+            any(len(keep[k]) != s.n_branches for k in BRANCH_BUBBLES) or (sup and any(len(keep[k]) != s.n_branches + 1 for k in ("br_sup_in", "br_sup_out"))):
+        raise AgxError(AGX_E_ARG, "agx_bubbles_tsv: one entry per bubble and per branch row, and one offset more")
+    for k, a in keep.items():
+        setattr(s, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64 if a.dtype == np.uint64 else ctypes.c_uint32)))
+    s.seq = ctypes.cast(seq, ctypes.c_void_p).value
+    return _text(lib().agx_bubbles_tsv, ctypes.byref(s), unit, what="agx_bubbles_tsv: the bubble table is inconsistent")
 
 
 def _gfa_text(t, unit, link_support=None):

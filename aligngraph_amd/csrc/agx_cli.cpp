@@ -58,7 +58,10 @@ struct Options {
     // --graphEdgeReads <file> [--graphEdgeReadsMax n]: the edges of support <= n (default 2) of every unit — with --graphRegion: of that unit's positions [lo, hi) — with the
     // numbers of the hits behind them, as TSV (agx_unit_edge_reads)
     int tagEdgeReads = 0; string edgeReads; int tagEdgeReadsMax = 0, edgeReadsMax = 2;
-    int graphSupport = 0;               // --graphEdgeSupport (only with --graphOut): RC:i:<events that name the link's edge> on every L line (agx_unit_unitigs_support)
+    int graphSupport = 0;               // --graphEdgeSupport (only with --graphOut or --graphBubbles): RC:i:<events that name the link's edge> on every L line (agx_unit_unitigs_support); the support of every branch of a bubble
+    // --graphBubbles <file> [--graphBubblesMax n]: the bubbles of every unit's graph — with --graphRegion: of that unit's positions [lo, hi); with --graphMinCoverage: at that
+    // threshold — whose branch segments have n nodes at most (default: all), as TSV (agx_unit_bubbles); needs no --graphOut
+    int tagBubbles = 0; string bubbles; int tagBubblesMax = 0, bubblesMax = 0;
     int fastMap = 0, ratioCheck = 0, uniqueExtension = 0, iterativeMap = 0, misassemblyRemoval = 0, resume = 0;
     int k = 5, distanceLow = 0, distanceHigh = 99999, coverage = 20, insertVariation = 50, part = 1;      // defaults of AG:4701
 };
@@ -145,6 +148,8 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--graphEdgeSupport") flag(o.graphSupport);
         else if (b == "--graphEdgeReads") outfile(i, o.tagEdgeReads, o.edgeReads);
         else if (b == "--graphEdgeReadsMax") { integer(i, o.tagEdgeReadsMax, o.edgeReadsMax); if (o.edgeReadsMax < 0) die_usage(); }
+        else if (b == "--graphBubbles") outfile(i, o.tagBubbles, o.bubbles);
+        else if (b == "--graphBubblesMax") { integer(i, o.tagBubblesMax, o.bubblesMax); if (o.bubblesMax < 0) die_usage(); }
         else if (b == "--evidenceOut") outfile(i, o.tagEvidence, o.evidence);
         else if (b == "--evidenceMinDepth") { integer(i, o.tagEvDepth, o.evDepth); if (o.evDepth < 0) die_usage(); }
         else if (b == "--evidenceMinSupport") { integer(i, o.tagEvSupport, o.evSupport); if (o.evSupport < 0) die_usage(); }
@@ -164,8 +169,10 @@ void parse_params(const string &file, Options &o) {
         else if (b == "--resume") { if (o.resume == 1 || count != 1) die_usage(); o.resume = 1; }
         else die_usage();
     }
-    if ((o.tagGraphCov || o.graphPaths || o.graphSupport) && !o.tagGraph) die_usage();
-    if (o.tagRegion && !o.tagGraph && !o.tagEdgeReads) die_usage();
+    if ((o.tagGraphCov || o.graphSupport) && !o.tagGraph && !o.tagBubbles) die_usage();
+    if (o.graphPaths && !o.tagGraph) die_usage();
+    if (o.tagRegion && !o.tagGraph && !o.tagEdgeReads && !o.tagBubbles) die_usage();
+    if (o.tagBubblesMax && !o.tagBubbles) die_usage();
     if (o.tagEdgeReadsMax && !o.tagEdgeReads) die_usage();
     if ((o.tagEvDepth || o.tagEvSupport) && !o.tagEvidence) die_usage();
     if (o.tagSpanMin && !o.tagSpan) die_usage();
@@ -187,6 +194,17 @@ string edge_reads_part_path(const Options &o, int u) {
     string s = "tmp/_edge_reads." + itoa(u);
     if (o.tagRegion) s += "." + itoa(o.regionLo) + "-" + itoa(o.regionHi);
     return s + ".m" + itoa(o.edgeReadsMax) + ".tsv";
+}
+
+// tmp/_bubbles.<u>.tsv, with the region, the threshold, --graphEdgeSupport (.s) and the largest branch (.m<max>) in the name when they are given: a --resume run merges only
+// lines that were made under its own settings
+string bubbles_part_path(const Options &o, int u) {
+    string s = "tmp/_bubbles." + itoa(u);
+    if (o.tagRegion) s += "." + itoa(o.regionLo) + "-" + itoa(o.regionHi);
+    if (o.tagGraphCov) s += ".c" + itoa(o.graphCov);
+    if (o.graphSupport) s += ".s";
+    if (o.tagBubblesMax) s += ".m" + itoa(o.bubblesMax);
+    return s + ".tsv";
 }
 
 // tmp/_graph.<u>.gfa, with the region, the threshold, --graphPaths (.p) and --graphEdgeSupport (.s) in the name when they are given: a --resume run merges only lines that were made under its own settings
@@ -1245,8 +1263,9 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                 // (--evidenceOut: ordinary units too, with the counts, the stretches and the edge counters: the evidence is asked for after the finish)
                 // (--graphEdgeReads: as for --graphEdgeSupport, with the counts as well: the listing's scratch is the export's buffer)
                 // (--spanOut, --linksOut: ordinary units with the counts and the stretches, no edge counters: the pass reads the hit records behind the finish)
-                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, (o.graphSupport || o.tagEvidence || o.tagEdgeReads ? AGX_FLAG_EDGE_SUPPORT : o.tagSpan || o.tagLinks ? 0u : AGX_FLAG_ONE_SHOT) |
-                                (o.tagGraph || o.tagEvidence || o.tagEdgeReads || o.tagSpan || o.tagLinks ? AGX_FLAG_KEEP_COUNTS : 0u) | (o.graphPaths || o.tagEvidence || o.tagSpan || o.tagLinks ? AGX_FLAG_KEEP_PATHS : 0u)};
+                // (--graphBubbles: ordinary units with the counts; the edge counters only with --graphEdgeSupport)
+                agx_params p = {(uint32_t)o.k, (uint32_t)o.insertVariation, (uint32_t)o.coverage, 0, d, (o.graphSupport || o.tagEvidence || o.tagEdgeReads ? AGX_FLAG_EDGE_SUPPORT : o.tagSpan || o.tagLinks || o.tagBubbles ? 0u : AGX_FLAG_ONE_SHOT) |
+                                (o.tagGraph || o.tagEvidence || o.tagEdgeReads || o.tagSpan || o.tagLinks || o.tagBubbles ? AGX_FLAG_KEEP_COUNTS : 0u) | (o.graphPaths || o.tagEvidence || o.tagSpan || o.tagLinks ? AGX_FLAG_KEEP_PATHS : 0u)};
                 agx_result r; memset(&r, 0, sizeof r); char err[512]; err[0] = 0;
                 agx_unit *un = nullptr;
                 int rc = agx_unit_create(&p, &un);
@@ -1291,6 +1310,17 @@ void run_units(const Options &o, int first, int units, std::ofstream &wcp) {
                     if (rc == AGX_OK) { rc = agx_edge_reads_tsv(&er, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "TSV FORMATTING FAILED"); }
                     agx_edge_reads_free(&er);
                     write_part(edge_reads_part_path(o, u), "wb", text, len, rc, err);
+                    agx_text_free(text);
+                }
+                if (rc == AGX_OK && o.tagBubbles && (!o.tagRegion || u == o.regionUnit)) {      // --graphBubbles: the variant sites of the unit's graph, before the download, into tmp/_bubbles.<u>...tsv
+                    agx_bubbles bb; char *text = nullptr; size_t len = 0; agx_stats st;
+                    memset(&bb, 0, sizeof bb); memset(&st, 0, sizeof st);
+                    rc = agx_unit_stats(un, &st);
+                    if (rc == AGX_OK) rc = agx_unit_bubbles(un, o.tagRegion ? o.regionLo : 0u, o.tagRegion ? o.regionHi : (uint32_t)st.n_pos, (uint32_t)(o.tagGraphCov ? o.graphCov : o.coverage),
+                                                            o.tagBubblesMax ? (uint32_t)o.bubblesMax : 0xFFFFFFFFu, o.graphSupport ? 1u : 0u, &bb);
+                    if (rc == AGX_OK) { rc = agx_bubbles_tsv(&bb, u, &text, &len); if (rc != AGX_OK) snprintf(err, sizeof err, "TSV FORMATTING FAILED"); }
+                    agx_bubbles_free(&bb);
+                    write_part(bubbles_part_path(o, u), "wb", text, len, rc, err);
                     agx_text_free(text);
                 }
                 bool wanted = false; if (rc == AGX_OK) { std::lock_guard<std::mutex> g(mem_mu); wanted = waiting[d] > 0 && !o.tagEvidence && !o.tagSpan && !o.tagLinks; }      // (--evidenceOut, --spanOut, --linksOut: never trimmed before the finish, they read the unit's arrays behind it)
@@ -1422,9 +1452,10 @@ int main(int argc, char **argv) {
     stage("resume / ratio check");
     if (cp < units) run_units(o, cp, units, wcp);
     stage("unit loop");
-    const int only = o.tagRegion ? o.regionUnit : -1;      // (with a region only the named unit has graph lines and edge reads)
+    const int only = o.tagRegion ? o.regionUnit : -1;      // (with a region only the named unit has graph lines, edge reads and bubbles)
     if (o.tagGraph) { join_parts(o, units, o.graph, "H\tVN:Z:1.0\n", graph_part_path, only); stage("graph output"); }                   // --graphOut
     if (o.tagEdgeReads) { join_parts(o, units, o.edgeReads, nullptr, edge_reads_part_path, only); stage("edge reads output"); }       // --graphEdgeReads
+    if (o.tagBubbles) { join_parts(o, units, o.bubbles, nullptr, bubbles_part_path, only); stage("bubbles output"); }                 // --graphBubbles
     if (o.tagEvidence) { join_parts(o, units, o.evidence, nullptr, evidence_part_path, -1); stage("evidence output"); }               // --evidenceOut
     if (o.tagSpan) { join_parts(o, units, o.span, nullptr, span_part_path, -1); stage("span output"); }                               // --spanOut
     if (o.tagLinks) { join_parts(o, units, o.links, nullptr, links_part_path, -1); stage("links output"); }                           // --linksOut

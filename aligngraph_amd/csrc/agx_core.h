@@ -1611,6 +1611,50 @@ AGX_HD void agx_links_insert(unsigned long long key, agx_u32 slots, agx_u32 log2
     give_up();
 }
 
+// ---- bubbles: the forks of a region export's graph and what closes them (agx_unit_bubbles, agx_unitigs_bubbles) ----
+// The graph is a segment table's: out(s) = l_to[l_off[s] .. l_off[s + 1]) (by target), s_in[s] = the links that enter s, s_len[s] = its nodes.  A FORK is a segment with
+// k >= 2 links.  A target X with s_in[X] == 1 is a BRANCH SEGMENT, its exit the target of its one link; a target with s_in[X] >= 2 is a DIRECT branch, its exit X itself.
+// The class of a fork is the first of these that applies: TIP (a branch segment without a link), NESTED (one with two or more), SINKS_DIFFER (the exits are not one
+// segment), SINK_SHARED (s_in of the common exit > k), BUBBLE.  BAD: the table broke a precondition (an offset that falls or passes n_links, a segment past n_segs, a
+// target nothing enters) — nothing behind the offending index was read.
+enum { AGX_BB_NONE = 0, AGX_BB_BUBBLE = 1, AGX_BB_TIP = 2, AGX_BB_NESTED = 3, AGX_BB_SINKS_DIFFER = 4, AGX_BB_SINK_SHARED = 5, AGX_BB_BAD = 6 };
+struct agx_bubble { agx_u32 cls, sink, k, longest, bases; };      // sink: a BUBBLE's, else NONE; longest / bases: the most nodes of one branch segment / of all of them (0 without one)
+AGX_HD agx_bubble agx_bubble_class(agx_u32 s, const agx_u32 *l_off, const agx_u32 *l_to, const agx_u32 *s_in, const agx_u32 *s_len, agx_u32 n_segs, agx_u32 n_links) {
+    agx_bubble b{AGX_BB_BAD, AGX_NONE, 0u, 0u, 0u};
+    if (s >= n_segs) return b;
+    const agx_u32 lo = l_off[s], hi = l_off[s + 1];
+    if (lo > hi || hi > n_links) return b;
+    b.k = hi - lo;
+    if (b.k < 2u) { b.cls = AGX_BB_NONE; return b; }
+    bool tip = false, nested = false, differ = false;
+    agx_u32 exit0 = AGX_NONE;
+    for (agx_u32 i = lo; i < hi; i++) {
+        const agx_u32 x = l_to[i];
+        if (x >= n_segs) return b;
+        const agx_u32 in = s_in[x];
+        if (!in) return b;                                   // (the link itself enters x)
+        agx_u32 exit = x;
+        if (in == 1u) {
+            const agx_u32 xl = l_off[x], xh = l_off[x + 1];
+            if (xl > xh || xh > n_links) return b;
+            const agx_u32 n = s_len[x];
+            b.longest = n > b.longest ? n : b.longest;
+            b.bases = b.bases + n < b.bases ? AGX_NONE : b.bases + n;      // (saturates: a table's bases are counted in 32 bits)
+            if (xh == xl) { tip = true; continue; }
+            if (xh - xl > 1u) { nested = true; continue; }
+            exit = l_to[xl];
+            if (exit >= n_segs) return b;
+        }
+        if (exit0 == AGX_NONE) exit0 = exit; else differ = differ || exit != exit0;
+    }
+    if (tip) b.cls = AGX_BB_TIP;
+    else if (nested) b.cls = AGX_BB_NESTED;
+    else if (differ) b.cls = AGX_BB_SINKS_DIFFER;
+    else if (s_in[exit0] != b.k) b.cls = s_in[exit0] > b.k ? AGX_BB_SINK_SHARED : AGX_BB_BAD;      // (k distinct links enter the exit: fewer is a broken table)
+    else { b.cls = AGX_BB_BUBBLE; b.sink = exit0; }
+    return b;
+}
+
 // ---- walk preparation: alive-node renumbering and forced-run flags -------------------------------------------------------
 // The path walk (AG:1954-2204) only ever stands on nodes that survived the coverage prune.  After the edge sweep the
 // surviving ("alive") nodes get walk ids ("aid") laid out so that the main strand of the graph is contiguous:

@@ -1,6 +1,6 @@
 // agx_export.cpp — the calls that answer a question about a built unit on request, out of the scratch the unit's block reserves for them (d_ut) and on a stream of their
 // own: the layouts that carve that buffer, Export and ensure_support, the unitig exports, edge support, edge reads, the walk's stretch table (FlatTable), the evidence and
-// the pair span under its records (records_body), pair span and mate links.  None touches the build path: that, and the calls that copy build state out, is agx_engine.cpp.
+// the pair span under its records (records_body), pair span, mate links and bubbles.  None touches the build path: that, and the calls that copy build state out, is agx_engine.cpp.
 #include "agx_unit.h"
 
 namespace agx {
@@ -167,6 +167,47 @@ size_t mapped_scratch(size_t cap, size_t n_pos, size_t n_nodes, size_t n_ids, si
     return front + idmap_layout(n_pos + sides, std::min(kept, n_pos + sides), nullptr, nullptr);
 }
 
+// What a region export no longer reads once its phase 3 (and, on request, agx_k_utr_link_support) has run: of everything unitig_region_layout carves from l_slot on, only the
+// tables themselves stay live — s_hpos, s_hvar, s_last, s_len and s_cov at `ns` segments, s_off and l_off at ns + 1, the first `nl` words of l_to and the first `nb` bytes
+// of seq.  The rest is free: l_slot, pos_of, the links' room behind nl, indeg, what succ has behind the bases, osucc, nxt, haspred, the piece and head counts with their
+// scans, the pointer jumping's arrays behind the two offset scans, p_seg, s_links, every per-segment array behind its ns entries, and whatever the buffer holds behind the
+// layout (the id map's scratch of a unit that keeps paths: a bubble call makes no map).  Gaps lists those stretches in address order and hands arrays out of them first
+// fit, each at the next multiple of 256 bytes.
+struct Gaps {
+    std::vector<std::pair<char *, char *> > free;
+    Gaps(char *lo, char *hi, std::vector<std::pair<const void *, size_t> > live) {
+        std::sort(live.begin(), live.end());
+        char *at = lo;
+        for (const auto &l : live) {
+            char *p = (char *)const_cast<void *>(l.first);
+            if (p > at) free.emplace_back(at, std::min(p, hi));
+            at = std::max(at, p + l.second);
+        }
+        if (at < hi) free.emplace_back(at, hi);
+    }
+    template <class T> void operator()(T *&p, size_t n) {
+        const size_t bytes = (n ? n : 1) * sizeof(T);
+        for (auto &z : free) {
+            char *a = (char *)(((uintptr_t)z.first + 255) & ~(uintptr_t)255);
+            if (a <= z.second && bytes <= (size_t)(z.second - a)) { p = (T *)a; z.first = a + bytes; return; }
+        }
+        throw Error{E_UNSUPPORTED, "bubbles: the export's scratch has no " + std::to_string(bytes) + " bytes left behind the segment table"};
+    }
+};
+// The scratch of the bubbles (agx_unit_bubbles, agx_bubbles.hip) out of those gaps, in two steps.  rows == false: what the class pass takes — the in-degrees, three
+// counts and three scans per segment (a closing entry each) and the wavefronts' partials, 28 bytes per segment and 32 per wavefront.  rows == true, with the three totals
+// read: the bubble rows (24 bytes each), the branch rows (40) and the bases.
+void bubbles_layout(Gaps &take, bool rows, agx_bubbles_args &A) {
+    if (!rows) {
+        const size_t n = (size_t)A.n_segs + 1;
+        take(A.tot, 8); take(A.s_in, n); take(A.flag, n); take(A.kcnt, n); take(A.bcnt, n); take(A.boff, n); take(A.koff, n); take(A.baoff, n); take(A.part, 8 * (size_t)A.n_part);
+        return;
+    }
+    const size_t nb = A.bub_cap, nr = A.row_cap;
+    take(A.b_spos, nb); take(A.b_svar, nb); take(A.b_slast, nb); take(A.b_tpos, nb); take(A.b_tvar, nb); take(A.b_broff, nb);
+    take(A.r_pos, nr); take(A.r_var, nr); take(A.r_nodes, nr); take(A.r_seqoff, nr); take(A.r_seg, nr); take(A.r_in, nr); take(A.r_out, nr); take(A.r_cov, nr); take(A.o_seq, A.base_cap);
+}
+
 }  // namespace agx
 
 namespace {
@@ -268,7 +309,10 @@ static void ensure_support(const Export &E) {
 // error word at `words`; R: the region export A is the local view of (nullptr: the whole export, whose head counts per position are cleared here); max_nodes bounds the bases;
 // J: also the export's id map — flags read with the totals, runs beside phase 3, four more copies
 // S (region exports only): also the support of every link, and where the caller wants the array — one kernel behind phase 3 and one more copy; without it the body queues what it queued before
-static void export_body(const Export &E, agx_unitig_args &A, const agx_unitig_region_args *R, agx_u32 *words, agx_u32 np, agx_u32 max_nodes, agx_unitigs *t, MapJob *J, uint32_t **S = nullptr) {
+// tail (region exports only): the body stops behind phase 3 and hands the tables over where they lie, on the device — no download is queued and t stays empty (agx_unit_bubbles)
+using ExportTail = std::function<void(const Export &, const agx_unitig_region_args &, agx_u32 *words, agx_u32 ns, agx_u32 nb, agx_u32 nl)>;
+static void export_body(const Export &E, agx_unitig_args &A, const agx_unitig_region_args *R, agx_u32 *words, agx_u32 np, agx_u32 max_nodes, agx_unitigs *t, MapJob *J, uint32_t **S = nullptr,
+                        const ExportTail *tail = nullptr) {
     A.piece_cap = np;
     agx_u32 rounds = 1; while (rounds < 32 && (1ull << (rounds - 1)) < np) rounds++;      // ceil(log2 np) + 1
     E.fill(A.p_seg, 0xFF, (size_t)np * 4);
@@ -297,6 +341,7 @@ static void export_body(const Export &E, agx_unitig_args &A, const agx_unitig_re
         E.u->d_lsup.alloc(E.u->arena, (size_t)nl + nl / 2 + 64); E.u->stats.device_bytes = E.u->arena.capacity();
         agx_launch_unitig_link_support(R, E.u->d_flags.p, E.u->d_e_cnt.p, E.u->d_ovf_cnt.p, E.u->d_lsup.p, E.s);
     }
+    if (tail && R) { (*tail)(E, *R, words, ns, nb, nl); return; }
     // the compact arrays (per-node arrays never leave the device) into pinned memory, then into the caller's malloc'd table
     const size_t o_hp = 0, o_hv = o_hp + 4 * (size_t)ns, o_ln = o_hv + 4 * (size_t)ns, o_lp = o_ln + 4 * (size_t)ns, o_cov = (o_lp + 4 * (size_t)ns + 7) & ~(size_t)7,
                  o_so = o_cov + 8 * (size_t)ns, o_lo = o_so + 4 * ((size_t)ns + 1), o_lt = o_lo + 4 * ((size_t)ns + 1), o_seq = o_lt + 4 * (size_t)nl,
@@ -376,7 +421,8 @@ int agx_unit_unitigs(agx_unit *u, agx_unitigs *t) {
 // whole export above comes through the same body with one trip less in front of it.
 // (m: also the id map of the export, agx_unit_unitigs_mapped; nullptr: every command and copy is agx_unit_unitigs_region's; link_support: also the links' support,
 // agx_unit_unitigs_support — the counters are made first if this is the first request since the build)
-static void region_export(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, agx_idmap *m, uint32_t **link_support = nullptr) {
+// (tail: export_body's — the front runs unchanged and the tables stay on the device)
+static void region_export(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t, agx_idmap *m, uint32_t **link_support = nullptr, const ExportTail *tail = nullptr) {
     if (link_support) support_check(u);
     export_check(u, m != nullptr);
     window_check(u, pos_lo, pos_hi, "unitigs: region");
@@ -430,7 +476,7 @@ static void region_export(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_
     if (h[0]) throw Error{E_DEVICE, "unitigs: the node table is inconsistent (error word " + std::to_string(h[0]) + ")"};
     const agx_u32 np = h[1];
     if (!np || np > kept || h[2] > np) throw Error{E_DEVICE, "unitigs: piece and head counts out of range"};
-    export_body(E, A, &R, words, np, kept, t, m ? &J : nullptr, link_support);
+    export_body(E, A, &R, words, np, kept, t, m ? &J : nullptr, link_support, tail);
 }
 
 int agx_unit_unitigs_region(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, agx_unitigs *t) {
@@ -1128,6 +1174,85 @@ void agx_mate_links_free(agx_mate_links *l) {
     free(l->rec_inside); free(l->rec_open_left); free(l->rec_open_right); free(l->rec_links_out); free(l->rec_links_in);
     free(l->a); free(l->b); free(l->n_pairs); free(l->len_sum); free(l->lo_min); free(l->lo_max); free(l->hi_min); free(l->hi_max);
     memset(l, 0, sizeof *l);
+}
+
+// Bubbles: the region export's front as far as its phase 3 — the export's own round trips up to the totals —, then, where the tables lie: the in-degrees, the
+// classes and the three scans (a round trip: the totals by class and the three counts), the rows (another: the table comes down).  No segment table is downloaded.
+static void unit_bubbles(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, uint32_t max_nodes, bool support, agx_bubbles *b) {
+    const double t0 = now_ms();
+    b->max_nodes = max_nodes; b->has_support = support ? 1u : 0u;
+    uint64_t n_bub = 0, n_rows = 0, n_bases = 0;
+    PBuf<char> pin;
+    size_t o_b = 0, o_r = 0, o_cov = 0, o_sup = 0, o_seq = 0;
+    const ExportTail tail = [&](const Export &E, const agx_unitig_region_args &R, agx_u32 *words, agx_u32 ns, agx_u32 nb, agx_u32 nl) {
+        const agx_unitig_args &X = R.U;
+        b->n_segs = ns; b->n_links = nl;
+        if (!ns) return;
+        const size_t seg4 = 4 * (size_t)ns;
+        Gaps take((char *)R.l_slot, u->d_ut.p + u->d_ut.n, {{X.s_hpos, seg4}, {X.s_hvar, seg4}, {X.s_last, seg4}, {X.s_len, seg4}, {X.s_cov, 2 * seg4}, {X.s_off, seg4 + 4}, {X.l_off, seg4 + 4},
+                                                            {X.l_to, 4 * (size_t)nl}, {X.seq, nb}});
+        agx_bubbles_args A{};
+        A.s_hpos = X.s_hpos; A.s_hvar = X.s_hvar; A.s_last = X.s_last; A.s_len = X.s_len; A.s_off = X.s_off; A.l_off = X.l_off; A.l_to = X.l_to; A.s_cov = X.s_cov; A.seq = X.seq;
+        A.l_sup = support && nl ? u->d_lsup.p : nullptr;
+        A.n_segs = ns; A.n_links = nl; A.n_bases = nb; A.max_nodes = max_nodes; A.scan_tmp = X.scan_tmp; A.err = words; A.n_part = agx_bubbles_partials(ns);
+        bubbles_layout(take, false, A);
+        E.fill(A.s_in, 0, seg4 + 4);
+        agx_launch_bubbles_class(&A, E.s);
+        agx_u32 tot[8] = {0, 0, 0, 0, 0, 0, 0, 0}, h[4] = {0, 0, 0, 0};
+        E.read(tot, A.tot, 32); E.read(h, A.boff + ns, 4); E.read(h + 1, A.koff + ns, 4); E.read(h + 2, A.baoff + ns, 4); E.read(h + 3, words, 4); E.sync();
+        HIP_OK(hipGetLastError());
+        if (h[3] & ~16u) throw Error{E_DEVICE, "unitigs: the segments are inconsistent (error word " + std::to_string(h[3]) + ")"};
+        if (h[3] || tot[7]) throw Error{E_DEVICE, "internal: bubbles: " + std::to_string(tot[7]) + " segments of the table the export left do not describe themselves (error word " + std::to_string(h[3]) + ")"};
+        if ((uint64_t)tot[0] != (uint64_t)tot[1] + tot[2] + tot[3] + tot[4] + tot[5])
+            throw Error{E_DEVICE, "internal: bubbles: " + std::to_string(tot[0]) + " forks, but their classes add up to " + std::to_string((uint64_t)tot[1] + tot[2] + tot[3] + tot[4] + tot[5])};
+        b->n_forks = tot[0]; b->n_bubbles_all = tot[1]; b->n_tip = tot[2]; b->n_nested = tot[3]; b->n_sinks_differ = tot[4]; b->n_sink_shared = tot[5]; b->longest_branch = tot[6];
+        if (h[0] > tot[1] || h[1] > nl || h[2] > nb || (h[0] && h[1] < 2ull * h[0])) throw Error{E_DEVICE, "internal: bubbles: the table's counts are out of range"};
+        n_bub = h[0]; n_rows = h[1]; n_bases = h[2];
+        if (!n_bub) return;
+        A.bub_cap = h[0]; A.row_cap = h[1]; A.base_cap = h[2];
+        bubbles_layout(take, true, A);
+        agx_launch_bubbles_emit(&A, E.s);
+        // the rows into pinned memory: six words per bubble, five per branch row and its coverage, the support on request, the bases
+        o_r = o_b + 24 * (size_t)n_bub; o_cov = (o_r + 16 * (size_t)n_rows + 7) & ~(size_t)7; o_sup = o_cov + 8 * (size_t)n_rows; o_seq = o_sup + (A.l_sup ? 8 * (size_t)n_rows : 0);
+        pin.alloc(o_seq + n_bases + 8);
+        const agx_u32 *bsrc[6] = {A.b_spos, A.b_svar, A.b_slast, A.b_tpos, A.b_tvar, A.b_broff}, *rsrc[4] = {A.r_pos, A.r_var, A.r_nodes, A.r_seqoff};
+        for (int i = 0; i < 6; i++) E.read(pin.p + o_b + 4 * (size_t)n_bub * i, bsrc[i], 4 * (size_t)n_bub);
+        for (int i = 0; i < 4; i++) E.read(pin.p + o_r + 4 * (size_t)n_rows * i, rsrc[i], 4 * (size_t)n_rows);
+        E.read(pin.p + o_cov, A.r_cov, 8 * (size_t)n_rows);
+        if (A.l_sup) { E.read(pin.p + o_sup, A.r_in, 4 * (size_t)n_rows); E.read(pin.p + o_sup + 4 * (size_t)n_rows, A.r_out, 4 * (size_t)n_rows); }
+        if (n_bases) E.read(pin.p + o_seq, A.o_seq, n_bases);
+        E.read(h + 3, words, 4); E.sync();
+        HIP_OK(hipGetLastError());
+        if (h[3]) throw Error{E_DEVICE, "internal: bubbles: the rows disagree with their counts (error word " + std::to_string(h[3]) + ")"};
+        b->bytes_down = 48 + o_seq + n_bases + 4;
+    };
+    agx_unitigs none{}; uint32_t *lsup = nullptr;
+    region_export(u, pos_lo, pos_hi, min_coverage, &none, nullptr, support ? &lsup : nullptr, &tail);
+    host_array(b->src_pos, n_bub); host_array(b->src_var, n_bub); host_array(b->src_last, n_bub); host_array(b->sink_pos, n_bub); host_array(b->sink_var, n_bub); host_array(b->br_off, n_bub);
+    host_array(b->br_pos, n_rows); host_array(b->br_var, n_rows); host_array(b->br_nodes, n_rows); host_array(b->br_cov, n_rows); host_array(b->br_seq_off, n_rows); host_array(b->seq, n_bases);
+    if (support) { host_array(b->br_sup_in, n_rows); host_array(b->br_sup_out, n_rows); }
+    if (n_bub) {
+        uint32_t *bdst[6] = {b->src_pos, b->src_var, b->src_last, b->sink_pos, b->sink_var, b->br_off}, *rdst[3] = {b->br_pos, b->br_var, b->br_nodes};
+        for (int i = 0; i < 6; i++) memcpy(bdst[i], pin.p + o_b + 4 * (size_t)n_bub * i, 4 * (size_t)n_bub);
+        for (int i = 0; i < 3; i++) memcpy(rdst[i], pin.p + o_r + 4 * (size_t)n_rows * i, 4 * (size_t)n_rows);
+        const agx_u32 *so = (const agx_u32 *)(pin.p + o_r + 12 * (size_t)n_rows);
+        for (size_t r = 0; r < n_rows; r++) b->br_seq_off[r] = so[r];
+        memcpy(b->br_cov, pin.p + o_cov, 8 * (size_t)n_rows);
+        if (support && b->n_links) { memcpy(b->br_sup_in, pin.p + o_sup, 4 * (size_t)n_rows); memcpy(b->br_sup_out, pin.p + o_sup + 4 * (size_t)n_rows, 4 * (size_t)n_rows); }
+        memcpy(b->seq, pin.p + o_seq, n_bases);
+        // what the kernels wrote must be a table: rows and bases in order, each bubble two rows at least
+        for (size_t i = 0; i < n_bub; i++)
+            if (b->br_off[i] > n_rows || (i && b->br_off[i] < b->br_off[i - 1] + 2u)) throw Error{E_DEVICE, "internal: bubbles: the branch offsets are inconsistent (bubble " + std::to_string(i) + ")"};
+        for (size_t r = 0; r < n_rows; r++)
+            if (b->br_seq_off[r] + b->br_nodes[r] != (r + 1 < n_rows ? b->br_seq_off[r + 1] : n_bases)) throw Error{E_DEVICE, "internal: bubbles: the base offsets are inconsistent (row " + std::to_string(r) + ")"};
+    }
+    b->br_off[n_bub] = (uint32_t)n_rows; b->br_seq_off[n_rows] = n_bases;
+    b->n_bubbles = (uint32_t)n_bub; b->n_branches = (uint32_t)n_rows; b->n_bases = n_bases;
+    b->ms = now_ms() - t0;
+}
+
+int agx_unit_bubbles(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, uint32_t max_nodes, uint32_t want_support, agx_bubbles *b) {
+    return answer(u, b, agx_bubbles_free, true, [&] { unit_bubbles(u, pos_lo, pos_hi, min_coverage, max_nodes, want_support != 0, b); });
 }
 
 }  // extern "C"

@@ -303,4 +303,111 @@ int agx_mate_links_tsv(const agx_mate_links *l, int unit, char **text, size_t *l
     }
 }
 
+// The bubbles of an export the caller holds: the host-only twin of agx_unit_bubbles and its CPU replay.  The link offsets and in-degrees are made from the
+// table, every segment is classed by agx_bubble_class — the function the kernels call —, and the rows are written as agx_k_bb_emit writes them.
+int agx_unitigs_bubbles(const agx_unitigs *t, const uint32_t *link_support, uint32_t max_nodes, agx_bubbles *b) {
+    if (!t || !b) return AGX_E_ARG;
+    memset(b, 0, sizeof *b);
+    if (!table_ok(t) || t->n_bases > 0xFFFFFFFFull) return AGX_E_ARG;
+    const uint32_t ns = t->n_segs, nl = t->n_links;
+    for (uint32_t i = 1; i < nl; i++) if (t->link_from[i - 1] > t->link_from[i]) return AGX_E_ARG;      // (the offsets below are those of links ordered by source)
+    try {
+        std::vector<agx_u32> l_off((size_t)ns + 1, 0u), s_in(ns, 0u);
+        for (uint32_t i = 0; i < nl; i++) { l_off[(size_t)t->link_from[i] + 1]++; s_in[t->link_to[i]]++; }
+        for (uint32_t s = 0; s < ns; s++) l_off[(size_t)s + 1] += l_off[s];
+        b->n_segs = ns; b->n_links = nl; b->max_nodes = max_nodes; b->has_support = link_support ? 1u : 0u;
+        std::vector<agx_bubble> cls(ns);
+        uint64_t n_bub = 0, n_rows = 0, n_bases = 0;
+        for (uint32_t s = 0; s < ns; s++) {
+            const agx_bubble c = cls[s] = agx_bubble_class(s, l_off.data(), t->link_to, s_in.data(), t->n_nodes, ns, nl);
+            if (c.cls == AGX_BB_BAD) { agx_bubbles_free(b); return AGX_E_ARG; }
+            if (c.cls == AGX_BB_NONE) continue;
+            b->n_forks++;
+            if (c.cls == AGX_BB_TIP) b->n_tip++; else if (c.cls == AGX_BB_NESTED) b->n_nested++; else if (c.cls == AGX_BB_SINKS_DIFFER) b->n_sinks_differ++;
+            else if (c.cls == AGX_BB_SINK_SHARED) b->n_sink_shared++;
+            else {
+                b->n_bubbles_all++; b->longest_branch = std::max(b->longest_branch, c.longest);
+                if (c.longest <= max_nodes) { n_bub++; n_rows += c.k; n_bases += c.bases; }
+            }
+        }
+        auto arr = [](size_t n, size_t sz) { void *p = calloc(n + 1, sz); if (!p) throw std::bad_alloc(); return p; };
+        b->src_pos = (uint32_t *)arr(n_bub, 4); b->src_var = (uint32_t *)arr(n_bub, 4); b->src_last = (uint32_t *)arr(n_bub, 4); b->sink_pos = (uint32_t *)arr(n_bub, 4);
+        b->sink_var = (uint32_t *)arr(n_bub, 4); b->br_off = (uint32_t *)arr(n_bub, 4);
+        b->br_pos = (uint32_t *)arr(n_rows, 4); b->br_var = (uint32_t *)arr(n_rows, 4); b->br_nodes = (uint32_t *)arr(n_rows, 4); b->br_cov = (uint64_t *)arr(n_rows, 8);
+        b->br_seq_off = (uint64_t *)arr(n_rows, 8); b->seq = (char *)arr(n_bases, 1);
+        if (link_support) { b->br_sup_in = (uint32_t *)arr(n_rows, 4); b->br_sup_out = (uint32_t *)arr(n_rows, 4); }
+        uint32_t at = 0, r = 0; uint64_t base = 0;
+        for (uint32_t s = 0; s < ns; s++) {
+            const agx_bubble &c = cls[s];
+            if (c.cls != AGX_BB_BUBBLE || c.longest > max_nodes) continue;
+            b->src_pos[at] = t->head_pos[s]; b->src_var[at] = t->head_var[s]; b->src_last[at] = t->last_pos[s]; b->sink_pos[at] = t->head_pos[c.sink]; b->sink_var[at] = t->head_var[c.sink];
+            b->br_off[at++] = r;
+            for (uint32_t i = l_off[s]; i < l_off[(size_t)s + 1]; i++, r++) {
+                const uint32_t x = t->link_to[i];
+                b->br_seq_off[r] = base;
+                if (s_in[x] == 1u) {
+                    b->br_pos[r] = t->head_pos[x]; b->br_var[r] = t->head_var[x]; b->br_nodes[r] = t->n_nodes[x]; b->br_cov[r] = t->coverage[x];
+                    memcpy(b->seq + base, t->seq + t->seq_off[x], t->n_nodes[x]); base += t->n_nodes[x];
+                    if (link_support) { b->br_sup_in[r] = link_support[i]; b->br_sup_out[r] = link_support[l_off[x]]; }
+                } else {
+                    b->br_pos[r] = b->br_var[r] = 0xFFFFFFFFu;
+                    if (link_support) b->br_sup_in[r] = b->br_sup_out[r] = link_support[i];
+                }
+            }
+        }
+        b->br_off[at] = r; b->br_seq_off[r] = base;
+        b->n_bubbles = at; b->n_branches = r; b->n_bases = base;
+        return AGX_OK;
+    } catch (...) {
+        agx_bubbles_free(b);
+        return AGX_E_ARG;
+    }
+}
+
+void agx_bubbles_free(agx_bubbles *b) {
+    if (!b) return;
+    free(b->src_pos); free(b->src_var); free(b->src_last); free(b->sink_pos); free(b->sink_var); free(b->br_off);
+    free(b->br_pos); free(b->br_var); free(b->br_nodes); free(b->br_cov); free(b->br_seq_off); free(b->br_sup_in); free(b->br_sup_out); free(b->seq);
+    memset(b, 0, sizeof *b);
+}
+
+// The bubbles as text, one line per bubble in the table's order, no header line:
+//   <source>	<sink>	<source's last position>	<sink's head position>	<k>	<names>	<nodes>	<coverage>	<support_in>	<support_out>	<bases>
+// the last six as comma lists with an entry per branch; a direct branch has * for its name and bases; without support both support lists are "."
+int agx_bubbles_tsv(const agx_bubbles *b, int unit, char **text, size_t *len) {
+    if (!b || !text || !len || unit < 0) return AGX_E_ARG;
+    *text = nullptr; *len = 0;
+    const uint32_t n = b->n_bubbles, nr = b->n_branches;
+    if (n && (!b->src_pos || !b->src_var || !b->src_last || !b->sink_pos || !b->sink_var || !b->br_off)) return AGX_E_ARG;
+    if (nr && (!b->br_pos || !b->br_var || !b->br_nodes || !b->br_cov || !b->br_seq_off || !n)) return AGX_E_ARG;
+    if (b->has_support && nr && (!b->br_sup_in || !b->br_sup_out)) return AGX_E_ARG;
+    if (n && (b->br_off[0] != 0 || b->br_off[n] != nr)) return AGX_E_ARG;
+    for (uint32_t i = 0; i < n; i++) if (b->br_off[i] > b->br_off[i + 1] || b->br_off[i + 1] > nr) return AGX_E_ARG;
+    for (uint32_t r = 0; r < nr; r++)
+        if (b->br_seq_off[r] > b->br_seq_off[r + 1] || b->br_seq_off[r + 1] > b->n_bases || b->br_seq_off[r + 1] - b->br_seq_off[r] != b->br_nodes[r] || (b->br_nodes[r] && !b->seq)) return AGX_E_ARG;
+    try {
+        const std::string prefix = "u" + std::to_string(unit) + "_";
+        std::string o;
+        o.reserve((size_t)n * 64 + (size_t)nr * 48 + (size_t)b->n_bases);
+        auto name = [&](uint32_t pos, uint32_t var) { o += prefix; put_u64(o, pos); o += '_'; put_u64(o, var); };
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t lo = b->br_off[i], hi = b->br_off[i + 1];
+            name(b->src_pos[i], b->src_var[i]); o += '\t'; name(b->sink_pos[i], b->sink_var[i]); o += '\t'; put_u64(o, b->src_last[i]); o += '\t'; put_u64(o, b->sink_pos[i]); o += '\t';
+            put_u64(o, hi - lo);
+            auto list = [&](auto put) { o += '\t'; for (uint32_t r = lo; r < hi; r++) { if (r != lo) o += ','; put(r); } };
+            auto direct = [&](uint32_t r) { return b->br_pos[r] == 0xFFFFFFFFu && b->br_var[r] == 0xFFFFFFFFu; };
+            list([&](uint32_t r) { if (direct(r)) o += '*'; else name(b->br_pos[r], b->br_var[r]); });
+            list([&](uint32_t r) { put_u64(o, b->br_nodes[r]); });
+            list([&](uint32_t r) { put_u64(o, b->br_cov[r]); });
+            if (b->has_support) { list([&](uint32_t r) { put_u64(o, b->br_sup_in[r]); }); list([&](uint32_t r) { put_u64(o, b->br_sup_out[r]); }); }
+            else o += "\t.\t.";
+            list([&](uint32_t r) { if (direct(r)) o += '*'; else o.append(b->seq + b->br_seq_off[r], (size_t)b->br_nodes[r]); });
+            o += '\n';
+        }
+        return give_text(o, text, len);
+    } catch (...) {
+        return AGX_E_ARG;
+    }
+}
+
 }  // extern "C"

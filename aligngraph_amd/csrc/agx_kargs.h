@@ -198,7 +198,26 @@ struct agx_links_args {
     agx_u32 *words;                            // 0: error bits (1: own names no record, 2: an emit beyond out_cap); 1: pairs that found no slot; 2: slots in use
 };
 
-#define AGX_SLOW_WAVES 8192u   // wavefronts of the per-hit edge pass if the occupancy query fails (normally: as many as are resident at once)
+// Bubbles (agx_bubbles.hip, agx_unit_bubbles): behind phase 3 of a region export, over the segment and link tables it left in the export's scratch
+// (read only: s_* [n_segs], s_off / l_off [n_segs + 1], l_to [n_links], seq [n_bases], l_sup [n_links] with support).  Everything written is the call's own, carved from
+// what the export no longer reads.  Per segment [n_segs + 1] (a closing zero each): flag (a bubble whose branch segments have max_nodes nodes at most), kcnt / bcnt (its
+// branch rows / the bases of its branch segments, 0 when not flagged) and their exclusive scans boff / koff / baoff.  The table: bubble rows [bub_cap], branch rows
+// [row_cap], bases [base_cap] — the three totals the host read.
+struct agx_bubbles_args {
+    const agx_u32 *s_hpos, *s_hvar, *s_last, *s_len, *s_off, *l_off, *l_to; const unsigned long long *s_cov; const char *seq; const agx_u32 *l_sup;
+    agx_u32 n_segs, n_links, n_bases, max_nodes;
+    agx_u32 *s_in;                                           // [n_segs] links that enter each segment (zeroed by the caller)
+    agx_u32 *flag, *kcnt, *bcnt, *boff, *koff, *baoff, *scan_tmp;
+    agx_u32 *part; agx_u32 n_part;                           // [8 * n_part] per wavefront of the class kernel: forks, bubbles, TIP, NESTED, SINKS_DIFFER, SINK_SHARED, the longest branch of a bubble, broken segments
+    agx_u32 *tot;                                            // [8] the same, summed (the longest: the maximum)
+    agx_u32 bub_cap, row_cap, base_cap;
+    agx_u32 *b_spos, *b_svar, *b_slast, *b_tpos, *b_tvar, *b_broff;      // [bub_cap]
+    agx_u32 *r_pos, *r_var, *r_nodes, *r_seqoff, *r_seg, *r_in, *r_out; unsigned long long *r_cov;      // [row_cap]; r_seg: the branch segment (NONE: direct); r_in / r_out: the two links' numbers, then (agx_k_bb_support) their support
+    char *o_seq;                                             // [base_cap]
+    agx_u32 *err;                                            // bit 4 (16): an index outside the tables or a store beyond a capacity
+};
+
+#define AGX_SLOW_WAVES 8192u  // wavefronts of the per-hit edge pass if the occupancy query fails (normally: as many as are resident at once)
 
 extern "C" {
 // one kernel that zeroes up to eight u32 ranges
@@ -301,4 +320,9 @@ agx_u32 agx_links_partials(agx_u32 n);
 void agx_launch_links_init(const agx_links_args *, hipStream_t);
 void agx_launch_links_own(const agx_links_args *, hipStream_t);
 void agx_launch_links_pass(const agx_links_args *, hipStream_t);
+// bubbles: wavefronts of the class kernel (entries of part / 8); the in-degrees, the classes with their totals and the three scans (s_in zeroed; the host reads tot and
+// the scans' last entries); with the three capacities set the rows and their bases; with l_sup set the rows' support
+agx_u32 agx_bubbles_partials(agx_u32 n_segs);
+void agx_launch_bubbles_class(const agx_bubbles_args *, hipStream_t);
+void agx_launch_bubbles_emit(const agx_bubbles_args *, hipStream_t);
 }

@@ -492,6 +492,37 @@ void agx_mate_links_free(agx_mate_links *l);
 /* Host only: the links as text, one line per link in the table's order and no header line: p<unit>_<a> <tab> p<unit>_<b> <tab> n_pairs <tab> len_sum <tab> lo_min <tab>
  * lo_max <tab> hi_min <tab> hi_max (the names are the BED's and the P lines'); *text is malloc'd, free it with agx_text_free. */
 int  agx_mate_links_tsv(const agx_mate_links *l, int unit, char **text, size_t *len);
+/* Bubbles: the forks of a region export's graph and what closes them.  The graph is exactly agx_unit_unitigs_region's for the same window and threshold, in its
+ * numbering: out(s) are the links that leave segment s in the table's order (by target), in(s) the number of links that enter it.  A FORK is a segment S with k = |out(S)| >= 2.
+ * A target X of S with in(X) == 1 is a BRANCH SEGMENT, and its exit is the target of its one link when |out(X)| == 1; a target with in(X) >= 2 is a DIRECT branch (no segment)
+ * with exit X itself.  The class of a fork is the first that applies of: TIP (a branch segment has no link), NESTED (a branch segment has two links or more), SINKS_DIFFER (the
+ * exits are not all one segment), SINK_SHARED (the common exit T has in(T) > k), BUBBLE with sink T.  n_forks = n_bubbles_all + n_tip + n_nested + n_sinks_differ + n_sink_shared;
+ * longest_branch: the most nodes of a branch segment of any bubble.  None of these depends on max_nodes.  The table holds the bubbles whose every branch segment has at most
+ * max_nodes nodes (0xFFFFFFFF: all), ordered by source segment; bubble i has the branch rows br_off[i] .. br_off[i + 1), in out(S)'s order.  A direct branch's row has br_pos =
+ * br_var = 0xFFFFFFFF, no nodes, coverage or bases; br_sup_in is the support of the link S -> X, br_sup_out of the link X -> T (a direct branch: the same link), both NULL without
+ * support.  Positions and variants are the whole unit's (the S lines' names), so nothing depends on the window or threshold except through the sub-graph: a fork cut by the
+ * window's border is a TIP, or no fork.  ms, bytes_down: how the call went (agx_unit_bubbles; 0 from the host-only twin).  malloc'd; free with agx_bubbles_free. */
+typedef struct { uint32_t n_segs, n_links;                       /* the sub-graph's */
+                 uint64_t n_forks, n_bubbles_all, n_tip, n_nested, n_sinks_differ, n_sink_shared;
+                 uint32_t longest_branch, max_nodes, has_support, n_bubbles, n_branches; uint64_t n_bases, bytes_down; double ms;
+                 /* [n_bubbles] */ uint32_t *src_pos, *src_var, *src_last, *sink_pos, *sink_var; /* [n_bubbles + 1] */ uint32_t *br_off;
+                 /* [n_branches] */ uint32_t *br_pos, *br_var, *br_nodes; uint64_t *br_cov; /* [n_branches + 1] */ uint64_t *br_seq_off; uint32_t *br_sup_in, *br_sup_out;
+                 char *seq; } agx_bubbles;                        /* [n_bases] the branch segments' bases, row after row */
+/* The bubbles of the window [pos_lo, pos_hi) at min_coverage, found on the device: the region export's front up to its phase 3, then a pass over the links and one over the
+ * segments where they lie, three scans, and the rows — the segment table is never downloaded.  Preconditions and refusals of agx_unit_unitigs_region; want_support != 0:
+ * also those of agx_unit_edge_support (AGX_FLAG_EDGE_SUPPORT; the counters are made first if need be).  Three more arrays per segment and the rows are carved from what the
+ * export no longer reads behind phase 3: no allocation (with support: the per-link array agx_unit_unitigs_support keeps); a graph whose rows do not fit there is
+ * AGX_E_UNSUPPORTED.  Totals that break the identity above, or a table index out of range, are AGX_E_DEVICE ("internal:").  agx_stats is as it was (the wall time is the
+ * answer's ms); nothing a walk or an export reads is written; a refused call leaves the unit as it was. */
+int  agx_unit_bubbles(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_coverage, uint32_t max_nodes, uint32_t want_support, agx_bubbles *b);
+/* Host only, the same table from an export the caller holds (and the CPU replay of the call above: both class a fork with one function, agx_bubble_class).  link_support: the
+ * array agx_unit_unitigs_support gave with t, or NULL.  AGX_E_ARG for a table that does not describe itself: links not ordered by source, a segment past n_segs, offsets that fall. */
+int  agx_unitigs_bubbles(const agx_unitigs *t, const uint32_t *link_support /* may be NULL */, uint32_t max_nodes, agx_bubbles *b);
+void agx_bubbles_free(agx_bubbles *b);
+/* Host only: one line per bubble in the table's order and no header line, tab-separated: source name, sink name (u<unit>_<pos>_<var>, the S lines'), the source's last
+ * position, the sink's head position, k, then six comma lists with an entry per branch: name (* for a direct branch), nodes, coverage, support_in, support_out (. without
+ * support), bases (* for a direct branch); *text is malloc'd, free it with agx_text_free. */
+int  agx_bubbles_tsv(const agx_bubbles *b, int unit, char **text, size_t *len);
 void agx_unitigs_free(agx_unitigs *t);
 /* Host only: the S and L lines of GFA 1.0 for unit `unit` (no header line), as DESIGN.md §11 defines them; *text is malloc'd, free it with agx_text_free. */
 int agx_unitigs_gfa(const agx_unitigs *t, int unit, char **text, size_t *len);
