@@ -856,11 +856,30 @@ void do_release(agx_unit *u);
 // Capacities of a unit's first build and the HBM they add up to (what do_upload reserves as one block; AlignGraph_amd admits a unit to a device by it:
 // agx_unit_hbm_needed).  From the staged counts: positions, hits, runs, conti-mers, read rows.
 struct Plan { agx_u32 pool_cap, list_cap, ovf_cap, sp_cap; size_t exact, total; };      // exact: what the five groups take; total: with the room to regrow in and the export's scratch
-// first row of window w's piece of a tile-ordered upload (w = n_win: all rows): the place in the tile order of the first hit of the window's first tile, rounded up to 16 rows —
-// a piece then begins on a 16-byte boundary of the packed classes and on a multiple of 16 bases (agx_k_expand_codes takes 16 bases per thread); the few rows of the next window's
-// hits that ride in this piece only arrive early
-inline size_t win_row(const agx_unit *u, agx_u32 w) { const size_t a = u->rows_diffed ? 63 : 15;      // (rows as differences: whole 64-row blocks of the stream)
-    return w == 0 ? 0 : w >= u->n_win ? u->nh : std::min<size_t>(u->nh, ((size_t)u->s_tfirst.p[u->win_tile[w]] + a) & ~a); }
+// The read rows of windows [w_lo, w_hi) of a tile-ordered unit ((0, n_win): all of them), named ONCE for both sides of the upload: do_upload copies what a piece names and
+// records ev_rows[w]; the unit's first build expands the same piece into d_vcodes behind that event and records ev_win[w] (build_front).  File-order units have none.
+struct RowPiece { size_t r_lo, r_hi,      // the rows: those of the hits whose first tile lies in the windows (a tile's list also names hits that begin in earlier tiles: earlier pieces)
+    code_lo, code_hi,      // 2-bit rows: their bytes in s_codes_t / d_codes
+    cnt_lo, cnt_hi, blk_lo, blk_hi, unit_lo, unit_hi,      // rows as differences: count bytes (s_rowcnt / d_rowcnt), whole 64-row blocks (d_blockoff, d_blockfirst), their 16-bit units (s_units / d_units)
+    v_lo, v_hi, o_lo, o_hi; };      // the bases of d_vcodes they are expanded to; the listed bases among them: entries of s_other_t / d_other
+RowPiece row_piece(const agx_unit *u, agx_u32 w_lo, agx_u32 w_hi) {
+    // a window's first row: the place in the tile order of the first hit of its first tile, rounded up to 16 rows — a piece then begins on a 16-byte boundary of the packed
+    // classes and on a multiple of 16 bases (agx_k_expand_codes takes 16 bases per thread) —, to 64 where the rows cross as differences (whole blocks of the stream); the few
+    // rows of the next window's hits that ride in this piece only arrive early
+    const size_t a = u->rows_diffed ? 63 : 15, s4 = u->stride / 4, nh = u->nh;
+    auto first_row = [&](agx_u32 w) { return w == 0 ? 0 : w >= u->n_win ? nh : std::min(nh, ((size_t)u->s_tfirst.p[u->win_tile[w]] + a) & ~a); };
+    const unsigned long long *ob = u->s_other_t.p, *oe = ob + u->n_other_t;
+    auto listed_at = [&](size_t row) { return (size_t)(std::lower_bound(ob, oe, (unsigned long long)row * u->stride) - ob); };
+    RowPiece p{}; p.r_lo = first_row(w_lo); p.r_hi = first_row(w_hi); p.o_lo = listed_at(p.r_lo); p.o_hi = listed_at(p.r_hi);
+    if (u->rows_diffed) {
+        p.blk_lo = p.r_lo / 64; p.blk_hi = (p.r_hi + 63) / 64; p.cnt_lo = p.r_lo; p.cnt_hi = std::min<size_t>(u->n_rowcnt, p.blk_hi * 64);
+        p.unit_lo = u->s_blockoff.p[p.blk_lo]; p.unit_hi = u->s_blockoff.p[p.blk_hi];
+    } else { p.code_lo = p.r_lo * s4; p.code_hi = p.r_hi * s4; }
+    // the piece that holds the LAST row — not always the last window's: a unit with few hits has windows without rows — is padded to whole 16-base groups like the whole array
+    // (r06's fuzz found the unpadded form: the last row's last bases stayed unexpanded where an earlier window already reached the last row)
+    p.v_lo = p.r_lo * s4 * 4; p.v_hi = p.r_hi == nh ? (codes_bytes(u) * 4 + 15) / 16 * 16 : p.r_hi * s4 * 4;
+    return p;
+}
 // Room behind the exact sum, in the same block: a group that proves too small on the device is taken again at its larger size, and while that fits here the unit stays
 // in ONE block — it holds no more HBM than it was admitted with, and agx_unit_trim can still give its tail back.  A 64th of the unit; the constant is what small units
 // (AGX_TEST_SMALL_CAPS ones above all) regrow in.
@@ -954,14 +973,10 @@ void do_upload(agx_unit *u) {
         if (u->tiled) {
             small();
             if (u->rows_diffed) tables();
-            const size_t s4 = u->stride / 4;
-            for (agx_u32 w = 0; w < u->n_win; w++) {      // rows of the hits whose first tile lies in window w (a tile's list also names hits that begin in earlier tiles: earlier pieces)
-                const size_t r_lo = win_row(u, w), r_hi = win_row(u, w + 1);
-                if (u->rows_diffed) {                     // the window's count bytes and its piece of the stream of differences (whole 64-row blocks)
-                    const size_t b_lo = r_lo / 64, b_hi = (r_hi + 63) / 64, c_hi = std::min<size_t>(u->n_rowcnt, b_hi * 64);
-                    up(u->d_rowcnt.p + r_lo, u->s_rowcnt.p + r_lo, c_hi - r_lo);
-                    up(u->d_units.p + u->s_blockoff.p[b_lo], u->s_units.p + u->s_blockoff.p[b_lo], ((size_t)u->s_blockoff.p[b_hi] - u->s_blockoff.p[b_lo]) * 2);
-                } else up(u->d_codes.p + r_lo * s4, u->s_codes_t.p + r_lo * s4, (r_hi - r_lo) * s4);
+            for (agx_u32 w = 0; w < u->n_win; w++) {      // window w's piece of the rows, then its event
+                const RowPiece p = row_piece(u, w, w + 1);
+                if (u->rows_diffed) { up(u->d_rowcnt.p + p.cnt_lo, u->s_rowcnt.p + p.cnt_lo, p.cnt_hi - p.cnt_lo); up(u->d_units.p + p.unit_lo, u->s_units.p + p.unit_lo, (p.unit_hi - p.unit_lo) * 2); }
+                else up(u->d_codes.p + p.code_lo, u->s_codes_t.p + p.code_lo, p.code_hi - p.code_lo);
                 HIP_OK(hipEventRecord(u->ev_rows[w], st));
             }
         } else {
@@ -1028,6 +1043,29 @@ void start_helper(agx_unit *u) {
     u->helper.submit(UnitHelper::OUT, [u] { const double th0 = now_ms(); prepare_outputs(u); trace(u, "helper: output buffers", th0, u->V.n_pos); });      // (no helper: finish prepares the outputs itself)
 }
 
+// The three exclusive scans of a build (0: the tile histogram, 1: the side counts per tile, 2: the special ids per word), by the one-launch form with the scan's own
+// descriptors or — no descriptors — by the three-launch form over d_scan_tmp (AGX_SCAN_LEGACY)
+inline unsigned long long *scan_desc(agx_unit *u, int which) { return g_scan1 ? u->d_scan_desc.p + which * u->scan_desc_n : nullptr; }
+inline void queue_scan(agx_unit *u, const agx_u32 *in, agx_u32 *out, agx_u32 n, int which, hipStream_t st) {
+    if (unsigned long long *desc = scan_desc(u, which)) agx_launch_exclusive_scan1(in, out, n, desc, st); else agx_launch_exclusive_scan(in, out, n, u->d_scan_tmp.p, st);
+}
+// What queue_walk_prep assumes zeroed (see there): segments `at` .. `at + 3` of the caller's ONE zeroing launch (first_scan: with scan 0's descriptors, a build's) and the
+// fill of a_mark: two commands.
+void queue_zero(agx_unit *u, agx_zero_args &Z, int at, bool first_scan, hipStream_t st) {
+    auto seg = [&](void *ptr, size_t words) { Z.p[at] = (agx_u32 *)ptr; Z.n[at++] = (agx_u32)words; };
+    seg(u->d_tile_side.p + u->n_tiles, 1); seg(u->d_sp_cnt.p, (size_t)u->n_words + 1);
+    seg(u->d_scan_desc.p + (first_scan ? 0 : u->scan_desc_n), (first_scan ? 6 : 4) * u->scan_desc_n); seg(u->d_sp_bits.p, 2 * ((size_t)u->n_words + 1));
+    agx_launch_zero(&Z, st); HIP_OK(hipMemsetAsync(u->d_a_mark.p, 0, u->V.n_pos + u->pool_cap + 2, st));
+}
+// The tail of a build's and a reprune's verdict: more special ids than the sparse record table holds — it is taken again, larger, and the caller goes round again (true) —,
+// or the unit's ids and special ids are counted.
+bool walk_ids_verdict(agx_unit *u, const agx_u32 *w) {
+    if (w[W_N + 2] > u->sp_cap) { Take grow{&u->arena}; sparse_bufs(u, w[W_N + 2] + w[W_N + 2] / 8 + 1024, grow); return true; }
+    const unsigned long long ids = (unsigned long long)u->V.n_pos + w[W_N + 1];
+    if (ids >= 0xFFFFFF00ull) throw Error{E_OVERFLOW, "walk graph exceeds 2^32 ids"};
+    u->n_ids = (agx_u32)ids; u->n_special = w[W_N + 2]; return false;
+}
+
 // The back of a build behind its edge passes, and all of a reprune behind its kernel: the walk preparation over the side counts in side_pk / tile_side (side counts ->
 // scan -> walk ids, node records, rewritten edges, forced-run flags -> special ids with the stream cuts), then the counters to the host by a kernel at the end of the chain
 // and the event their reader waits for.  before_counters: what the caller records between the two (a build: its section mark and the device's build_done event).
@@ -1044,12 +1082,11 @@ template <class F> void queue_walk_prep(agx_unit *u, hipStream_t st, F before_co
     C.a_mark = u->d_a_mark.p; C.side_xpos = u->d_side_xpos.p; C.sparse_min = (u->prm.flags & AGX_FLAG_SPARSE_MIN) ? 1u : 0u;
     C.sp_bits = u->d_sp_bits.p; C.sp_cnt = u->d_sp_cnt.p; C.sp_rank = u->d_sp_rank.p; C.sp_node = u->d_sp_node.p; C.sp_cap = u->sp_cap;
     C.segs = u->d_segs.p; C.n_seg0 = u->n_seg0; C.cm_start = u->d_cm_start.p; C.sp_hop = u->d_sp_hop.p; C.seg_index = u->d_segindex.p;
-    if (g_scan1) agx_launch_exclusive_scan1(u->d_tile_side.p, u->d_tile_side_start.p, u->n_tiles, u->d_scan_desc.p + u->scan_desc_n, st);
-    else agx_launch_exclusive_scan(u->d_tile_side.p, u->d_tile_side_start.p, u->n_tiles, u->d_scan_tmp.p, st);      // per tile: the sweep has scanned inside the tiles
+    queue_scan(u, u->d_tile_side.p, u->d_tile_side_start.p, u->n_tiles, 1, st);      // per tile: the sweep has scanned inside the tiles
     agx_launch_compact(&C, u->d_chain_end.p, u->n_chain_end, u->d_words.p + W_OVFCOUNT, u->ovf_cap, st);
     AGX_CHECKPOINT("compact");
     u->cuts = stream_cuts(n_pos); u->cuts.cut_out = u->d_words.p + W_CUT;
-    agx_launch_special(&C, u->n_words, u->d_sp_rank.p, u->d_scan_tmp.p, g_scan1 ? u->d_scan_desc.p + 2 * u->scan_desc_n : nullptr,
+    agx_launch_special(&C, u->n_words, u->d_sp_rank.p, u->d_scan_tmp.p, scan_desc(u, 2),
                        u->d_words.p + W_N, u->d_tile_off.p + u->n_tiles, u->d_tile_side_start.p + u->n_tiles, u->d_pool_cnt.p, u->n_regions, u->d_words.p + W_POOL, u->cuts.n ? &u->cuts : nullptr, st);
     u->walk_args = C;
     AGX_CHECKPOINT("special");
@@ -1059,227 +1096,195 @@ template <class F> void queue_walk_prep(agx_unit *u, hipStream_t st, F before_co
     HIP_OK(hipEventRecord(u->ev_built, st));
 }
 
-// All kernels of one build are queued back to back with the current buffer capacities; the counters they produce (tile-list
-// entries, nodes, overflowed tiles, edge overflow, side variants) are read after ONE synchronisation.  A capacity that proved too
-// small is grown and the build repeats — the first guesses (do_upload) are made so that this is rare.
+// All kernels of one build are queued back to back with the current buffer capacities; the counters they produce (tile-list entries, nodes, overflowed tiles, edge overflow,
+// side variants) are read after ONE synchronisation.  A capacity that proved too small is grown and the build repeats — the first guesses (do_upload) make that rare.  An
+// attempt is the stages below, queued in this order by do_build under the device's turn; each stage's head names the stream it queues on, the events it waits for and
+// records, and what it takes to be in HBM.  What an attempt is planned by, when it takes the turn:
+struct Attempt { DeviceTurn &turn;
+    bool early;      // a unit's first build starts on the arrays that arrive first (ev_hits); the read bases are waited for on the device, in front of their first use (not in builds that time their sections: those would time the wait)
+    bool windows;    // r06: a tile-ordered unit's first build expands its read rows and sweeps its tiles WINDOW BY WINDOW, each when its piece of the upload (RowPiece) has landed: the sweep of the unit's front runs beside the upload of its back
+    agx_u32 n_win;   // in so many windows (a build that has waited for the whole upload on the host — timed sections — has nothing to overlap: one window, no boundaries to pay for)
+    double t_queue; hipEvent_t trace_from; };      // host time when the turn was asked for; AGX_TRACE_GAP: the end of the device's previous sweep
+// WAIT AND TAKE THE TURN.  Host: waits for ev_hits (early) or ev_uploaded — the build streams are shared by all units of the device: nothing that could wait long is queued
+// on them —, then locks the device's turn: no other stage does, and do_build unlocks it behind the attempt's last command.  Front stream: waits for the previous build's
+// sweep_done (build_done where either build times its sections): a front may run beside that build's edge passes and walk preparation, not beside its sweep.
+std::unique_lock<std::mutex> build_take_turn(agx_unit *u, int attempt, Attempt &A) {
+    const double tb0 = now_ms(); DeviceTurn &turn = A.turn;
+    A.early = !u->expanded && attempt == 0 && !u->ev.all; A.windows = !u->expanded && u->tiled; A.n_win = (A.windows && A.early) ? u->n_win : 1u;
+    HIP_OK(wait_event(A.early ? u->ev_hits : u->ev_uploaded));
+    trace(u, "build: wait for upload", tb0, u->V.n_pos);
+    A.t_queue = now_ms();
+    std::unique_lock<std::mutex> my_turn(turn.m);
+    if (turn.n) HIP_OK(hipStreamWaitEvent(turn.front, (u->ev.all || turn.prev_exclusive) ? turn.build_done[(turn.n - 1) & 1] : turn.sweep_done[(turn.n - 1) & 1], 0));
+    return my_turn;
+}
+// FRONT, all of it on the front stream.  In HBM: what ev_hits stands for (hit, side and run records, conti-mer runs, tile_first).  An early build also waits for ev_uploaded
+// (file order) or ev_rows[0] (tile order: the reference, the listed bases and the region layout travel in front of the first rows), then for ev_rows[w] in front of window
+// w's rows.  Queues a first build's expansions out of the wire forms, the zeroing, hit_prep, the scan of the tile histogram, the tile lists, the reference and the file-order
+// rows; records ev_front; then expands the tile-ordered rows piece by piece and records ev_win[w] behind each.
+void build_front(agx_unit *u, const Attempt &A) {
+    hipStream_t st = A.turn.front; const agx_u32 n_pos = (agx_u32)u->V.n_pos, nh = (agx_u32)u->nh;
+    if (u->ev.all) HIP_OK(hipEventRecord(u->ev.first, st));      // (every event record costs the stream a few microseconds: untimed builds record only what orders them)
+    if (!u->expanded) {   // the unit's first build: the hits and runs out of their wire forms, then the conti-mer tables from their runs (agx_cmseg: count per position, scan, keys, heads); the read bases follow behind the binning
+        if (u->hits_compact) agx_launch_expand_hits(u->d_chits.p, u->d_cesc.p, u->d_cext.p, u->d_whits.p, nh, u->maxlen, st);
+        if (u->sides_compact) agx_launch_expand_sides(u->d_csides.p, u->d_csesc.p, (agx_u32)u->n_csesc, u->d_wsides.p, (agx_u32)u->n_sides, u->side_first, u->d_cside_scan.p, st);
+        agx_launch_expand_runs(u->d_wruns.p, u->d_runs.p, (agx_u32)u->n_runs, st);
+        agx_launch_cm_tables(u->d_cntruns.p, u->d_cntchunks.p, (agx_u32)u->n_cntchunks, u->d_segs.p, u->d_segchunks.p, (agx_u32)u->n_segchunks, u->d_cm_start.p, u->d_cm.p, u->d_cm_head.p, n_pos, (agx_u32)u->n_cm, st);
+    }
+    agx_zero_args Z; memset(&Z, 0, sizeof Z);
+    Z.p[0] = u->d_words.p; Z.n[0] = W_TOTAL; Z.p[1] = u->d_tile_cnt.p; Z.n[1] = u->n_tiles + 1; Z.p[2] = u->d_cursor.p; Z.n[2] = u->n_tiles + 1; Z.p[3] = u->d_pool_cnt.p; Z.n[3] = u->n_regions * AGX_REGION_PAD;
+    queue_zero(u, Z, 4, true, st);
+    u->ev.begin(); u->ev.mark(B_START, st);
+    agx_prep_args PA{(const agx_whit *)u->d_whits.p, (const agx_wside *)u->d_wsides.p, u->d_runs.p, u->d_dhit.p, nh, u->prm.k, n_pos, u->d_tile_cnt.p, u->d_words.p + W_ERR,
+                     u->d_perm.p, u->d_tfirst.p, u->d_ckey.p, u->lookback, u->d_long.p, u->d_words.p + W_LONGCOUNT, u->tiled ? 1u : 0u, u->d_perm.p};
+    agx_launch_hit_prep(&PA, st);
+    AGX_CHECKPOINT("hit_prep");
+    u->ev.mark(B_PREP, st);
+    queue_scan(u, u->d_tile_cnt.p, u->d_tile_off.p, u->n_tiles, 0, st);
+    agx_fill_args FA{u->d_tile_off.p, u->d_tfirst.p, u->d_perm.p, u->d_ckey.p, u->d_dhit.p, u->d_runs.p, u->d_tile_recs.p, u->d_unsorted.p, u->n_tiles, u->list_cap, u->prm.k, u->lookback,
+                     u->d_long.p, u->d_words.p + W_LONGCOUNT, u->d_words.p + W_ERR, u->d_words.p + W_STATUS, u->dense ? 1u : 0u};
+    agx_launch_tile_fill(&FA, st);                  // every tile's list from its window of the tile order
+    if (u->dense) {                                 // the fallback for a unit with more long hits than a list's window scan takes: queued once a build has met them (an idle launch of a kernel per tile costs 0.1 ms)
+        agx_bin_args BA{u->d_dhit.p, nh, u->d_tile_off.p, u->d_cursor.p, u->d_unsorted.p, u->list_cap, u->d_words.p + W_LONGCOUNT};
+        agx_launch_bin_fill(&BA, st);
+        agx_launch_tile_sort(&FA, st);
+    }
+    AGX_CHECKPOINT("tile_sort");
+    if (!u->expanded) {   // the vote codes (and the region layout, the last copy of the upload) are first needed by the sweep
+        if (!u->tiled) {  // the file-order forms: no windows, the rows whole with their listed bases
+            if (A.early) HIP_OK(hipStreamWaitEvent(st, u->ev_uploaded, 0));      // (at most the tail of this unit's own upload: a build stream never waits for anything else)
+            if (u->rows_diffed) agx_launch_expand_rows(u->d_whits.p, nh, u->d_wsides.p, u->d_wruns.p, u->d_anchor.p, u->d_blockfirst.p, u->d_rowcnt.p, u->d_blockoff.p, u->d_units.p, u->d_wref.p, u->d_vcodes.p, u->n_rows, u->stride, u->d_other.p, u->n_other, st);
+            else agx_launch_expand_codes(u->d_codes.p, u->d_vcodes.p, (codes_bytes(u) * 4 + 15) / 16 * 16, u->d_other.p, u->n_other, st);
+        } else if (A.early) HIP_OK(hipStreamWaitEvent(st, u->ev_rows[0], 0));
+        if (u->ref_packed) agx_launch_expand_ref(u->d_wref.p, u->d_ref.p, ((size_t)n_pos + 15) / 16 * 16, u->d_refx.p, (agx_u32)u->n_refx, st);      // (the letters are first read by the sweep's write-out)
+        u->expanded = true;
+    }
+    HIP_OK(hipEventRecord(u->ev_front, st));
+    for (agx_u32 w = 0; A.windows && w < A.n_win; w++) {      // behind ev_front: the rows of window w out of their upload form when they are in, then the listed bases among them
+        const RowPiece p = A.n_win == 1 ? row_piece(u, 0, u->n_win) : row_piece(u, w, w + 1);
+        if (A.early && w) HIP_OK(hipStreamWaitEvent(st, u->ev_rows[w], 0));
+        if (p.r_hi > p.r_lo) {
+            if (u->rows_diffed) agx_launch_expand_rows(u->d_whits.p, nh, u->d_wsides.p, u->d_wruns.p, u->d_anchor.p, u->d_blockfirst.p + p.blk_lo, u->d_rowcnt.p + p.cnt_lo, u->d_blockoff.p + p.blk_lo, u->d_units.p, u->d_wref.p,
+                                                       u->d_vcodes.p + p.v_lo, (agx_u32)(p.r_hi - p.r_lo), u->stride, nullptr, 0, st);      // (every row's anchor is its own hit: the anchor bits are all ones)
+            else agx_launch_expand_codes(u->d_codes.p + p.code_lo, u->d_vcodes.p + p.v_lo, p.v_hi - p.v_lo, nullptr, 0, st);
+            agx_launch_patch_codes(u->d_other.p + p.o_lo, p.o_hi - p.o_lo, u->d_vcodes.p, st);
+        }
+        HIP_OK(hipEventRecord(u->ev_win[w], st));
+    }
+}
+// SWEEP, all of it on the main stream.  Waits for ev_front (the lists, the reference, file-order or resident rows) and for ev_win[w] in front of window w's tiles.  Queues
+// pass 0 — every tile with small LDS buckets — per window between ev_sw0[w] and ev_sw1[w], records the device's sweep_done (the next build's front may start), then the
+// tiles that overflowed: with wider buckets and, once a build has met such a tile, with global scratch (device-side lists).
+void build_sweep(agx_unit *u, Attempt &A) {
+    hipStream_t st = A.turn.main; HIP_OK(hipStreamWaitEvent(st, u->ev_front, 0)); u->ev.mark(B_BIN, st);
+    agx_node_kargs K; fill_node_args(u, K);
+    for (agx_u32 w = 0; w < A.n_win; w++) {
+        K.tile_lo = A.n_win == 1 ? 0u : u->win_tile[w]; K.tile_hi = A.n_win == 1 ? u->n_tiles : u->win_tile[w + 1];
+        if (A.windows) { HIP_OK(hipStreamWaitEvent(st, u->ev_win[w], 0)); HIP_OK(hipEventRecord(u->ev_sw0[w], st)); }      // (behind the wait: the sweep's time must not hold the rows' journey)
+        agx_launch_node_sweep(&K, st);
+        if (A.windows) HIP_OK(hipEventRecord(u->ev_sw1[w], st));
+    }
+    AGX_CHECKPOINT("node_sweep");
+    u->ev.mark(B_NODE, st); u->stats.node_sweep_launches++;
+    A.trace_from = A.turn.prev_node; A.turn.prev_node = u->ev.e[B_NODE]; HIP_OK(hipEventRecord(A.turn.sweep_done[A.turn.n & 1], st));
+    agx_launch_node_sweep_big(&K, st);      // the two fallback passes: they find their (usually empty) tile lists on the device.  A unit is built once, so they
+    if (u->huge) agx_launch_node_sweep_huge(&K, st);
+    AGX_CHECKPOINT("node_sweep_big");       // are always queued: two idle launches cost less than repeating the build of a unit that turns out to need them
+    u->ev.mark(B_BIG, st);
+}
+// EDGES: passes A and B on the main stream.  Passes J and B insert edges out of different sources (positions with one variant / with several) and both wait on memory more
+// than they compute: J goes to the front stream, behind pass A (ev_passA) and in front of the next build's front, and runs beside B; the main stream waits for it (ev_passJ)
+// behind B.  Timed builds and AGX_DEBUG_SYNC keep all three on the main stream.
+void build_edges(agx_unit *u, const Attempt &A) {
+    hipStream_t st = A.turn.main, front = A.turn.front;
+    agx_edge_kargs E; fill_edge_args(u, E);
+    const bool side_j = !u->ev.all && !g_debug_sync;
+    agx_launch_edge_sweep(&E, st);
+    AGX_CHECKPOINT("edge_sweep");
+    if (side_j) {
+        HIP_OK(hipEventRecord(u->ev_passA, st)); HIP_OK(hipStreamWaitEvent(front, u->ev_passA, 0));
+        agx_launch_edge_jump(&E, front);
+        HIP_OK(hipEventRecord(u->ev_passJ, front));
+    } else { agx_launch_edge_jump(&E, st); AGX_CHECKPOINT("edge_jump"); }
+    u->ev.mark(B_EDGE, st);
+    agx_launch_edge_slow(&E, st);
+    AGX_CHECKPOINT("edge_slow");
+    u->ev.mark(B_SLOW, st);
+    if (side_j) HIP_OK(hipStreamWaitEvent(st, u->ev_passJ, 0));
+}
+// VERDICT, on the host behind ev_built, over the counters in h_words: throws the input's and the internal errors; grows the ONE capacity that proved too small (the arena
+// keeps the old buffer) and says "again" (true), or stores the unit's counts.  Whatever a retry changes on the device goes through the download
+// stream and a fresh ev_uploaded — recorded only here — which the next attempt waits for.
+bool build_verdict(agx_unit *u, const Attempt &A, int attempt) {
+    hipStream_t down = A.turn.down; const agx_u32 *w = u->h_words.p;
+    if (w[W_ERR] & 1u) throw Error{E_ALIGNMENT, "BOWTIE ALIGNMENT ERROR"};
+    if (w[W_ERR] & 2u) throw Error{E_UNSUPPORTED, "read alignment beyond the end of the unit sequence"};
+    if (w[W_ERR] & (4u | 8u)) throw Error{E_DEVICE, (w[W_ERR] & 4u) ? "internal: the staged order of the hits is not the order of their first tiles" : "internal: a tile's list does not hold what its histogram counted"};
+    u->n_tile_entries = w[W_N];
+    bool again = true; Take grow{&u->arena};
+    if ((w[W_STATUS] & 16u) && !u->dense) u->dense = true;      // more long hits than the window scan takes: again, with the scatter fallback queued
+    else if (u->n_tile_entries > u->list_cap) list_bufs(u, u->n_tile_entries + u->n_tile_entries / 8 + 1024, grow);
+    else if ((w[W_STATUS] & 2u) && !u->huge) {     // a position beyond the 64 variants of pass 2 (deep repeats under a wide --distanceHigh): queue pass 3 and build again
+        u->huge = true; u->d_huge_list.alloc(u->arena, (size_t)u->n_tiles + 1); u->d_scratch_huge.alloc(u->arena, (size_t)AGX_HUGE_WAVES * AGX_NF * AGX_MAXV_HUGE * 64);
+    } else if (w[W_STATUS] & 2u) throw Error{E_OVERFLOW, "more than " + std::to_string(AGX_MAXV_HUGE) + " node variants at one position"};
+    else if (w[W_STATUS] & 1u) {                   // the node pool ran out: cut the slices to what the regions asked for
+        std::vector<agx_u32> padded((size_t)u->n_regions * AGX_REGION_PAD), demand(u->n_regions);
+        HIP_OK(hipMemcpyAsync(padded.data(), u->d_pool_cnt.p, padded.size() * 4, hipMemcpyDeviceToHost, down)); HIP_OK(hipStreamSynchronize(down));
+        for (agx_u32 r = 0; r < u->n_regions; r++) demand[r] = padded[(size_t)r * AGX_REGION_PAD];
+        const unsigned long long need = layout_regions(u, demand.data(), 0, false, down);
+        if (need >= 0xFFFFFF00ull) throw Error{E_OVERFLOW, "node table exceeds 2^32 entries"};
+        if (need > u->pool_cap) pool_bufs(u, (agx_u32)need, grow);
+        layout_regions(u, demand.data(), 0, true, down);
+    } else if (w[W_OVFCOUNT] > u->ovf_cap) ovf_bufs(u, w[W_OVFCOUNT] + w[W_OVFCOUNT] / 2 + 1024, grow);
+    else again = walk_ids_verdict(u, w);
+    if (again) { HIP_OK(hipEventRecord(u->ev_uploaded, down)); return true; }
+    u->n_nodes = w[W_POOL]; u->n_big = w[W_BIGCOUNT]; u->n_mid = w[W_MIDCOUNT]; u->n_ovf = w[W_OVFCOUNT]; u->n_slow = w[W_SLOWCOUNT];
+    u->stats.build_attempts = (uint32_t)attempt + 1; u->stats.n_spilled = w[W_SPILL]; u->stats.dense_lists = w[W_LONGCOUNT] > AGX_LONG_MAX ? 2u : w[W_LONGCOUNT] ? 1u : 0u;
+#ifdef AGX_SWEEP_STATS
+    {   const agx_u32 *c = w + W_N + 6;
+        fprintf(stderr, "[agx sweep stats] wave-entries %u (lanes with an arrival %u = %.1f per entry); leave the fast path: %u entries / %u lanes; of those not a first store: %u / %u; "
+                        "variant 0 incompatible: %u / %u; several candidate keys: %u / %u; entries with a multi-run record %u\n",
+                c[0], c[3], c[0] ? (double)c[3] / c[0] : 0.0, c[4], c[5], c[6], c[7], c[8], c[9], c[10], c[11], c[12]); }
+#endif
+    return false;
+}
+// STATISTICS of a converged build, from its last attempt's events
+void build_stats(agx_unit *u, const Attempt &A) {
+    u->stats.ms_build_span = u->ev.all ? u->ev.span() : 0.0;
+    u->stats.ms_prep = u->ev.ms(B_PREP); u->stats.ms_bin = u->ev.ms(B_BIN); u->stats.ms_node_sweep = u->ev.ms(B_NODE);
+    if (A.windows) {      // the sweep's time is the sum over its windows (between them the stream may have waited for rows that were still travelling)
+        u->stats.ms_node_sweep = 0; for (agx_u32 w = 0; w < A.n_win; w++) { float f = 0; if (hipEventElapsedTime(&f, u->ev_sw0[w], u->ev_sw1[w]) == hipSuccess) u->stats.ms_node_sweep += f; else (void)hipGetLastError(); } }
+    u->stats.ms_node_big = u->ev.ms(B_BIG); u->stats.ms_edge_fast = u->ev.ms(B_EDGE); u->stats.ms_edge_slow = u->ev.ms(B_SLOW); u->stats.ms_edge_sweep = u->stats.ms_edge_fast + u->stats.ms_edge_slow; u->stats.ms_compact = u->ev.ms(B_COMPACT);
+    if (u->up_timed) { float f = 0; if (hipEventElapsedTime(&f, u->ev_up0, u->ev_uploaded) == hipSuccess) u->stats.ms_upload_dev = f; else (void)hipGetLastError(); }
+}
 void do_build(agx_unit *u) {
     if (!u->uploaded) do_upload(u);
     HIP_OK(hipSetDevice(u->prm.device));
-    const agx_u32 n_pos = (agx_u32)u->V.n_pos, nh = (agx_u32)u->nh;
-    hipStream_t st = nullptr;              // the device's build stream, taken with the turn
     u->stats.node_sweep_launches = u->stats.edge_sweep_launches = 0;
     u->support_valid = false; u->stats.n_support_events = 0;      // (the edge counters are the last build's: counted again on the next request)
-    agx_u32 swept_windows = 1; bool swept_timed = false;      // of the last attempt
+    DeviceTurn &turn = turn_of(u->prm.device);
     for (int attempt = 0;; attempt++) {
         if (attempt > 8) throw Error{E_DEVICE, "build did not converge"};
-        const size_t ids_cap = (size_t)n_pos + u->pool_cap;                       // side variants <= nodes <= pool_cap
-
-        // The build streams are shared by all units of the device: nothing is queued on them that could wait long.  The unit's upload is
-        // awaited here, on the host, before the turn is taken.
-        const double tb0 = now_ms();
-        const bool early = !u->expanded && attempt == 0 && !u->ev.all;      // a unit's first build starts on the arrays that arrive first; the read bases are waited for on the device, in front of their first use (not in builds that time their sections: those would time the wait)
-        HIP_OK(wait_event(early ? u->ev_hits : u->ev_uploaded));
-        trace(u, "build: wait for upload", tb0, n_pos);
-        const double tb1 = now_ms();
-        DeviceTurn &turn = turn_of(u->prm.device);
-        std::unique_lock<std::mutex> my_turn(turn.m);
-        // ---- front (its own stream): may run beside the previous build's edge passes and walk preparation, not beside its sweep ----
-        st = turn.front;
-        if (turn.n) HIP_OK(hipStreamWaitEvent(st, (u->ev.all || turn.prev_exclusive) ? turn.build_done[(turn.n - 1) & 1] : turn.sweep_done[(turn.n - 1) & 1], 0));
-        if (u->ev.all) HIP_OK(hipEventRecord(u->ev.first, st));      // (every event record costs the stream a few microseconds: untimed builds record only what orders them)
-        if (!u->expanded) {   // the unit's first build: the hits and runs out of their wire forms, then the conti-mer tables from their runs (agx_cmseg: count per position, scan, keys, heads); the read bases follow behind the binning
-            if (u->hits_compact) agx_launch_expand_hits(u->d_chits.p, u->d_cesc.p, u->d_cext.p, u->d_whits.p, nh, u->maxlen, st);
-            if (u->sides_compact) agx_launch_expand_sides(u->d_csides.p, u->d_csesc.p, (agx_u32)u->n_csesc, u->d_wsides.p, (agx_u32)u->n_sides, u->side_first, u->d_cside_scan.p, st);
-            agx_launch_expand_runs(u->d_wruns.p, u->d_runs.p, (agx_u32)u->n_runs, st);
-            agx_launch_cm_tables(u->d_cntruns.p, u->d_cntchunks.p, (agx_u32)u->n_cntchunks, u->d_segs.p, u->d_segchunks.p, (agx_u32)u->n_segchunks, u->d_cm_start.p, u->d_cm.p, u->d_cm_head.p, n_pos, (agx_u32)u->n_cm, st);
-        }
-        {   // everything a build counts into or marks, zeroed by one kernel and one fill (every command on the stream costs a few microseconds)
-            agx_zero_args Z; memset(&Z, 0, sizeof Z);
-            auto seg = [&](int i, agx_u32 *ptr, size_t words) { Z.p[i] = ptr; Z.n[i] = (agx_u32)words; };
-            seg(0, u->d_words.p, W_TOTAL); seg(1, u->d_tile_cnt.p, (size_t)u->n_tiles + 1); seg(2, u->d_cursor.p, (size_t)u->n_tiles + 1);
-            seg(3, u->d_pool_cnt.p, (size_t)u->n_regions * AGX_REGION_PAD); seg(4, u->d_tile_side.p + u->n_tiles, 1); seg(5, u->d_sp_cnt.p, (size_t)u->n_words + 1);
-            seg(6, reinterpret_cast<agx_u32 *>(u->d_scan_desc.p), 6 * u->scan_desc_n); seg(7, reinterpret_cast<agx_u32 *>(u->d_sp_bits.p), 2 * ((size_t)u->n_words + 1));      // (the special-id kernels write and read the words of the live ids only)
-            agx_launch_zero(&Z, st);
-            HIP_OK(hipMemsetAsync(u->d_a_mark.p, 0, ids_cap + 2, st));
-        }
-        // ---- hit_prep + tile histogram ----
-        u->ev.begin(); u->ev.mark(B_START, st);
-        agx_prep_args PA{(const agx_whit *)u->d_whits.p, (const agx_wside *)u->d_wsides.p, u->d_runs.p, u->d_dhit.p, nh, u->prm.k, n_pos, u->d_tile_cnt.p, u->d_words.p + W_ERR,
-                         u->d_perm.p, u->d_tfirst.p, u->d_ckey.p, u->lookback, u->d_long.p, u->d_words.p + W_LONGCOUNT, u->tiled ? 1u : 0u, u->d_perm.p};
-        agx_launch_hit_prep(&PA, st);
-        AGX_CHECKPOINT("hit_prep");
-        u->ev.mark(B_PREP, st);
-        // ---- tile lists ----
-        if (g_scan1) agx_launch_exclusive_scan1(u->d_tile_cnt.p, u->d_tile_off.p, u->n_tiles, u->d_scan_desc.p, st);
-        else agx_launch_exclusive_scan(u->d_tile_cnt.p, u->d_tile_off.p, u->n_tiles, u->d_scan_tmp.p, st);
-        agx_fill_args FA{u->d_tile_off.p, u->d_tfirst.p, u->d_perm.p, u->d_ckey.p, u->d_dhit.p, u->d_runs.p, u->d_tile_recs.p, u->d_unsorted.p, u->n_tiles, u->list_cap, u->prm.k, u->lookback,
-                         u->d_long.p, u->d_words.p + W_LONGCOUNT, u->d_words.p + W_ERR, u->d_words.p + W_STATUS, u->dense ? 1u : 0u};
-        agx_launch_tile_fill(&FA, st);                  // every tile's list from its window of the tile order
-        if (u->dense) {                                 // the fallback for a unit with more long hits than a list's window scan takes: queued once a build has met them (an idle launch of a kernel per tile costs 0.1 ms)
-            agx_bin_args BA{u->d_dhit.p, nh, u->d_tile_off.p, u->d_cursor.p, u->d_unsorted.p, u->list_cap, u->d_words.p + W_LONGCOUNT};
-            agx_launch_bin_fill(&BA, st);
-            agx_launch_tile_sort(&FA, st);
-        }
-        AGX_CHECKPOINT("tile_sort");
-        // r06: a tile-ordered unit's first build expands its read rows and sweeps its tiles WINDOW BY WINDOW, each when its piece of the upload has landed (the rows of a window's
-        // hits are one piece, in front of which lie the rows of every earlier tile: stage_tiled) — the sweep of the unit's front runs beside the upload of its back
-        const bool windows = !u->expanded && u->tiled;
-        const agx_u32 n_win = (windows && early) ? u->n_win : 1u;      // (a build that has waited for the whole upload on the host — timed sections — has nothing to overlap: one window, no boundaries to pay for)
-        agx_u32 wt[9]; size_t wr[9];                                   // the windows' tiles and rows
-        for (agx_u32 w = 0; w <= n_win; w++) { wt[w] = n_win == 1 ? (w ? u->n_tiles : 0u) : u->win_tile[w]; wr[w] = n_win == 1 ? (w ? (size_t)nh : 0) : win_row(u, w); }
-        swept_windows = windows ? n_win : 1u; swept_timed = windows;
-        if (!u->expanded) {   // the vote codes (and the region layout, the last copy of the upload) are first needed by the sweep
-            if (!windows) {
-                const size_t n_bases = codes_bytes(u) * 4;
-                if (early) HIP_OK(hipStreamWaitEvent(st, u->ev_uploaded, 0));      // (at most the tail of this unit's own upload: nothing else is ever waited for on a build stream)
-                if (u->rows_diffed) agx_launch_expand_rows(u->d_whits.p, (agx_u32)nh, u->d_wsides.p, u->d_wruns.p, u->d_anchor.p, u->d_blockfirst.p, u->d_rowcnt.p, u->d_blockoff.p, u->d_units.p, u->d_wref.p, u->d_vcodes.p, u->n_rows, u->stride, u->d_other.p, u->n_other, st);
-                else agx_launch_expand_codes(u->d_codes.p, u->d_vcodes.p, (n_bases + 15) / 16 * 16, u->d_other.p, u->n_other, st);
-                if (u->ref_packed) agx_launch_expand_ref(u->d_wref.p, u->d_ref.p, ((size_t)n_pos + 15) / 16 * 16, u->d_refx.p, (agx_u32)u->n_refx, st);      // (the letters are first read by the sweep's write-out)
-            } else {
-                if (early) HIP_OK(hipStreamWaitEvent(st, u->ev_rows[0], 0));       // (the small arrays travel in front of the first piece of rows: with it the reference and the region layout are in)
-                if (u->ref_packed) agx_launch_expand_ref(u->d_wref.p, u->d_ref.p, ((size_t)n_pos + 15) / 16 * 16, u->d_refx.p, (agx_u32)u->n_refx, st);
-            }
-            u->expanded = true;
-        }
-        HIP_OK(hipEventRecord(u->ev_front, st));
-        if (windows) {      // still on the front stream, behind ev_front: the rows of window w out of their 2-bit form when they are in, then the listed bases among them
-            const size_t s4 = u->stride / 4;
-            for (agx_u32 w = 0; w < n_win; w++) {
-                const size_t r_lo = wr[w], r_hi = wr[w + 1];
-                if (early && w) HIP_OK(hipStreamWaitEvent(st, u->ev_rows[w], 0));
-                const unsigned long long *ob = u->s_other_t.p, *oe = ob + u->n_other_t;
-                const size_t o_lo = (size_t)(std::lower_bound(ob, oe, (unsigned long long)r_lo * u->stride) - ob), o_hi = (size_t)(std::lower_bound(ob, oe, (unsigned long long)r_hi * u->stride) - ob);
-                // (pieces begin at multiples of 16 rows: whole 16-base groups, 16-byte aligned stores; the last piece is padded like the whole array was)
-                // (the piece that holds the LAST row — not always the last window's: a unit with few hits has windows without rows — is padded like the whole array was; r06's fuzz found the
-                // unpadded form: the last row's last bases stayed unexpanded where an earlier window already reached the last row)
-                const size_t b_lo = r_lo * s4 * 4, b_hi = r_hi == (size_t)nh ? (codes_bytes(u) * 4 + 15) / 16 * 16 : r_hi * s4 * 4;
-                if (r_hi <= r_lo) { HIP_OK(hipEventRecord(u->ev_win[w], st)); continue; }
-                if (u->rows_diffed) agx_launch_expand_rows(u->d_whits.p, (agx_u32)nh, u->d_wsides.p, u->d_wruns.p, u->d_anchor.p, u->d_blockfirst.p + r_lo / 64, u->d_rowcnt.p + r_lo, u->d_blockoff.p + r_lo / 64, u->d_units.p, u->d_wref.p,
-                                                           u->d_vcodes.p + b_lo, (agx_u32)(r_hi - r_lo), u->stride, nullptr, 0, st);      // (every row's anchor is its own hit: the anchor bits are all ones)
-                else agx_launch_expand_codes(u->d_codes.p + r_lo * s4, u->d_vcodes.p + b_lo, b_hi - b_lo, nullptr, 0, st);
-                agx_launch_patch_codes(u->d_other.p + o_lo, o_hi - o_lo, u->d_vcodes.p, st);
-                HIP_OK(hipEventRecord(u->ev_win[w], st));
-            }
-        }
-        // ---- main stream ----
-        st = turn.main;
-        HIP_OK(hipStreamWaitEvent(st, u->ev_front, 0));
-        u->ev.mark(B_BIN, st);
-        // ---- node sweep: every tile with small LDS buckets, then the tiles that overflowed with wider ones, then with global scratch (device-side lists) ----
-        agx_node_kargs K; fill_sweep_args(u, K.S);
-#ifdef AGX_SWEEP_STATS
-        K.S.sweep_stats = u->d_words.p + W_N + 6;
-#endif
-        K.pool_cnt = u->d_pool_cnt.p; K.region_off = u->d_region_off.p; K.spill_lo = u->spill_lo; K.spill_cnt = u->d_words.p + W_SPILL;
-        K.mid_count = u->d_words.p + W_MIDCOUNT; K.mid_list = u->d_mid_list.p; K.mid_n = u->d_words.p + W_MIDCOUNT;
-        K.big_count = u->d_words.p + W_BIGCOUNT; K.big_list = u->d_big_list.p; K.status = u->d_words.p + W_STATUS;
-        K.list_cap = u->list_cap; K.big_n = u->d_words.p + W_BIGCOUNT; K.scratch = u->d_scratch.p;
-        K.slow_list = u->d_slow_list.p; K.slow_count = u->d_words.p + W_SLOWCOUNT; K.fallback_queued = 1u;
-        K.huge_count = u->d_words.p + W_HUGECOUNT; K.huge_n = u->d_words.p + W_HUGECOUNT; K.huge_list = u->d_huge_list.p; K.scratch_huge = u->d_scratch_huge.p; K.huge_queued = u->huge ? 1u : 0u;
-        for (agx_u32 w = 0; w < n_win; w++) {
-            K.tile_lo = windows ? wt[w] : 0u; K.tile_hi = windows ? wt[w + 1] : u->n_tiles;
-            if (windows) { HIP_OK(hipStreamWaitEvent(st, u->ev_win[w], 0)); HIP_OK(hipEventRecord(u->ev_sw0[w], st)); }      // (behind the wait: the sweep's time must not hold the rows' journey)
-            agx_launch_node_sweep(&K, st);
-            if (windows) HIP_OK(hipEventRecord(u->ev_sw1[w], st));
-        }
-        AGX_CHECKPOINT("node_sweep");
-        u->ev.mark(B_NODE, st); u->stats.node_sweep_launches++;
-        hipEvent_t trace_from = turn.prev_node; turn.prev_node = u->ev.e[B_NODE];
-        HIP_OK(hipEventRecord(turn.sweep_done[turn.n & 1], st));
-        agx_launch_node_sweep_big(&K, st);      // the two fallback passes: they find their (usually empty) tile lists on the device.  A unit is built once, so they
-        if (u->huge) agx_launch_node_sweep_huge(&K, st);
-        AGX_CHECKPOINT("node_sweep_big");       // are always queued: two idle launches cost less than repeating the build of a unit that turns out to need them
-        u->ev.mark(B_BIG, st);
-        // ---- edge sweep ----
-        agx_edge_kargs E; fill_sweep_args(u, E.S); E.ovf = u->d_ovf.p; E.ovf_count = u->d_words.p + W_OVFCOUNT; E.ovf_cap = u->ovf_cap; E.list_cap = u->list_cap;
-        E.n_hits = nh; E.jump_list = u->d_jump.p; E.n_jump = (agx_u32)u->n_jump; E.abort = u->d_words.p + W_STATUS; E.big_list = u->d_big_list.p; E.big_n = u->d_words.p + W_BIGCOUNT; E.slow_list = u->d_slow_list.p; E.slow_count = u->d_words.p + W_SLOWCOUNT;
-        agx_launch_edge_sweep(&E, st);
-        AGX_CHECKPOINT("edge_sweep");
-        // Passes J and B insert edges out of different sources (positions with one variant / with several) and both wait on memory more than
-        // they compute: J goes to the front stream, behind pass A and in front of the next build's front, and runs beside B.  (Timed builds
-        // keep everything on the main stream.)
-        const bool side_j = !u->ev.all && !g_debug_sync;
-        if (side_j) {
-            HIP_OK(hipEventRecord(u->ev_passA, st));
-            HIP_OK(hipStreamWaitEvent(turn.front, u->ev_passA, 0));
-            agx_launch_edge_jump(&E, turn.front);
-            HIP_OK(hipEventRecord(u->ev_passJ, turn.front));
-        } else {
-            agx_launch_edge_jump(&E, st);
-            AGX_CHECKPOINT("edge_jump");
-        }
-        u->ev.mark(B_EDGE, st);
-        agx_launch_edge_slow(&E, st);
-        AGX_CHECKPOINT("edge_slow");
-        u->ev.mark(B_SLOW, st);
-        if (side_j) HIP_OK(hipStreamWaitEvent(st, u->ev_passJ, 0));
-        // ---- walk preparation, then the one synchronisation ----
-        queue_walk_prep(u, st, [&] {
-            u->ev.mark(B_COMPACT, st);
-            u->stats.edge_sweep_launches++;
-            if (u->ev.all) HIP_OK(hipEventRecord(u->ev.last, st));
-            HIP_OK(hipEventRecord(turn.build_done[turn.n & 1], st));               // (a stream wait binds to the record that precedes it: the handle may be recorded again later)
+        Attempt A{turn, false, false, 1u, 0.0, nullptr};
+        std::unique_lock<std::mutex> my_turn = build_take_turn(u, attempt, A);
+        build_front(u, A); build_sweep(u, A); build_edges(u, A);
+        queue_walk_prep(u, turn.main, [&] {      // WALK PREPARATION, main stream; records build_done, ev_built
+            u->ev.mark(B_COMPACT, turn.main); u->stats.edge_sweep_launches++;
+            if (u->ev.all) HIP_OK(hipEventRecord(u->ev.last, turn.main));
+            HIP_OK(hipEventRecord(turn.build_done[turn.n & 1], turn.main));               // (a stream wait binds to the record that precedes it: the handle may be recorded again later)
         });
         turn.n++; turn.prev_exclusive = u->ev.all;
         my_turn.unlock();
-        trace(u, "build: queue kernels", tb1, n_pos);
+        trace(u, "build: queue kernels", A.t_queue, u->V.n_pos);
         const double tb2 = now_ms();
-        HIP_OK(wait_event(u->ev_built));
-        trace(u, "build: wait for kernels", tb2, n_pos);
-        HIP_OK(hipGetLastError());
-        if (g_trace_gap && trace_from && trace_from != u->ev.e[B_NODE]) {      // diagnostic (units must outlive each other's builds): end of the previous sweep -> start of this one
-            float f = 0; if (hipEventElapsedTime(&f, trace_from, u->ev.e[B_BIN]) == hipSuccess) fprintf(stderr, "[agx gap] %.3f ms between sweeps, %.3f ms sweep\n", f, u->ev.ms(B_NODE)); else (void)hipGetLastError(); }
-        const agx_u32 *w = u->h_words.p;
-        if (w[W_ERR] & 1u) throw Error{E_ALIGNMENT, "BOWTIE ALIGNMENT ERROR"};
-        if (w[W_ERR] & 2u) throw Error{E_UNSUPPORTED, "read alignment beyond the end of the unit sequence"};
-        if (w[W_ERR] & (4u | 8u)) throw Error{E_DEVICE, (w[W_ERR] & 4u) ? "internal: the staged order of the hits is not the order of their first tiles" : "internal: a tile's list does not hold what its histogram counted"};
-        u->n_tile_entries = w[W_N];
-        // a capacity that was too small: take a larger buffer (the arena keeps the old one until the unit is released) and build again.
-        // Whatever a retry changes on the device goes through the download stream and a fresh ev_uploaded, which the next attempt waits for.
-        bool again = false; Take grow{&u->arena};
-        if ((w[W_STATUS] & 16u) && !u->dense) { u->dense = true; HIP_OK(hipEventRecord(u->ev_uploaded, turn.down)); continue; }      // more long hits than the window scan takes: again, with the scatter fallback queued
-        if (u->n_tile_entries > u->list_cap) { list_bufs(u, u->n_tile_entries + u->n_tile_entries / 8 + 1024, grow); again = true; }
-        else {
-            if ((w[W_STATUS] & 2u) && !u->huge) {     // a position beyond the 64 variants of pass 2 (deep repeats under a wide --distanceHigh): queue pass 3 and build again
-                u->huge = true; u->d_huge_list.alloc(u->arena, (size_t)u->n_tiles + 1); u->d_scratch_huge.alloc(u->arena, (size_t)AGX_HUGE_WAVES * AGX_NF * AGX_MAXV_HUGE * 64);
-                HIP_OK(hipEventRecord(u->ev_uploaded, turn.down)); continue;
-            }
-            if (w[W_STATUS] & 2u) throw Error{E_OVERFLOW, "more than " + std::to_string(AGX_MAXV_HUGE) + " node variants at one position"};
-            if (w[W_STATUS] & 1u) {                  // the node pool ran out: cut the slices to what the regions asked for
-                std::vector<agx_u32> padded((size_t)u->n_regions * AGX_REGION_PAD), demand(u->n_regions);
-                HIP_OK(hipMemcpyAsync(padded.data(), u->d_pool_cnt.p, padded.size() * 4, hipMemcpyDeviceToHost, turn.down)); HIP_OK(hipStreamSynchronize(turn.down));
-                for (agx_u32 r = 0; r < u->n_regions; r++) demand[r] = padded[(size_t)r * AGX_REGION_PAD];
-                const unsigned long long need = layout_regions(u, demand.data(), 0, false, turn.down);
-                if (need >= 0xFFFFFF00ull) throw Error{E_OVERFLOW, "node table exceeds 2^32 entries"};
-                if (need > u->pool_cap) pool_bufs(u, (agx_u32)need, grow);
-                layout_regions(u, demand.data(), 0, true, turn.down);
-                again = true;
-            } else if (w[W_OVFCOUNT] > u->ovf_cap) { ovf_bufs(u, w[W_OVFCOUNT] + w[W_OVFCOUNT] / 2 + 1024, grow); again = true; }
-            else if (w[W_N + 2] > u->sp_cap) { sparse_bufs(u, w[W_N + 2] + w[W_N + 2] / 8 + 1024, grow); again = true; }
-        }
-        if (again) { HIP_OK(hipEventRecord(u->ev_uploaded, turn.down)); continue; }
-        u->n_nodes = w[W_POOL]; u->n_big = w[W_BIGCOUNT]; u->n_mid = w[W_MIDCOUNT]; u->n_ovf = w[W_OVFCOUNT]; u->n_slow = w[W_SLOWCOUNT];
-        const unsigned long long ids = (unsigned long long)n_pos + w[W_N + 1];
-        if (ids >= 0xFFFFFF00ull) throw Error{E_OVERFLOW, "walk graph exceeds 2^32 ids"};
-        u->n_ids = (agx_u32)ids; u->n_special = w[W_N + 2];
-        u->stats.build_attempts = (uint32_t)attempt + 1; u->stats.n_spilled = w[W_SPILL]; u->stats.dense_lists = w[W_LONGCOUNT] > AGX_LONG_MAX ? 2u : w[W_LONGCOUNT] ? 1u : 0u;
-#ifdef AGX_SWEEP_STATS
-        {   const agx_u32 *c = w + W_N + 6;
-            fprintf(stderr, "[agx sweep stats] wave-entries %u (lanes with an arrival %u = %.1f per entry); leave the fast path: %u entries / %u lanes; of those not a first store: %u / %u; "
-                            "variant 0 incompatible: %u / %u; several candidate keys: %u / %u; entries with a multi-run record %u\n",
-                    c[0], c[3], c[0] ? (double)c[3] / c[0] : 0.0, c[4], c[5], c[6], c[7], c[8], c[9], c[10], c[11], c[12]); }
-#endif
-        break;
+        HIP_OK(wait_event(u->ev_built)); HIP_OK(hipGetLastError());
+        trace(u, "build: wait for kernels", tb2, u->V.n_pos);
+        if (g_trace_gap && A.trace_from && A.trace_from != u->ev.e[B_NODE]) {      // diagnostic (units must outlive each other's builds): end of the previous sweep -> start of this one
+            float f = 0; if (hipEventElapsedTime(&f, A.trace_from, u->ev.e[B_BIN]) == hipSuccess) fprintf(stderr, "[agx gap] %.3f ms between sweeps, %.3f ms sweep\n", f, u->ev.ms(B_NODE)); else (void)hipGetLastError(); }
+        if (build_verdict(u, A, attempt)) continue;
+        u->built = true; u->downloaded = false; u->trimmed = false; u->front_windows = A.n_win;
+        return build_stats(u, A);
     }
-    u->built = true; u->downloaded = false; u->trimmed = false; u->front_windows = swept_windows;
-    u->stats.ms_build_span = u->ev.all ? u->ev.span() : 0.0;
-    u->stats.ms_prep = u->ev.ms(B_PREP); u->stats.ms_bin = u->ev.ms(B_BIN); u->stats.ms_node_sweep = u->ev.ms(B_NODE);
-    if (swept_windows >= 1 && swept_timed) {      // a windowed first build: the sweep's time is the sum over its windows (between them the stream may have waited for rows that were still travelling)
-        double sum = 0; for (agx_u32 w = 0; w < swept_windows; w++) { float f = 0; if (hipEventElapsedTime(&f, u->ev_sw0[w], u->ev_sw1[w]) == hipSuccess) sum += f; else (void)hipGetLastError(); }
-        u->stats.ms_node_sweep = sum;
-    }
-    u->stats.ms_node_big = u->ev.ms(B_BIG); u->stats.ms_edge_fast = u->ev.ms(B_EDGE); u->stats.ms_edge_slow = u->ev.ms(B_SLOW); u->stats.ms_edge_sweep = u->stats.ms_edge_fast + u->stats.ms_edge_slow; u->stats.ms_compact = u->ev.ms(B_COMPACT);
-    if (u->up_timed) { float f = 0; if (hipEventElapsedTime(&f, u->ev_up0, u->ev_uploaded) == hipSuccess) u->stats.ms_upload_dev = f; else (void)hipGetLastError(); }
 }
 
 void stream_wait_all(agx_unit *u);
@@ -1304,16 +1309,12 @@ void do_reprune(agx_unit *u, uint32_t coverage) {
     struct Failed { agx_unit *u; bool armed; ~Failed() { if (armed) u->built = false; } } failed{u, true};      // (an error behind the first launch leaves flags nobody has counted: the next build makes them again)
     for (int attempt = 0;; attempt++) {
         if (attempt > 2) throw Error{E_DEVICE, "reprune did not converge"};
-        const size_t ids_cap = (size_t)n_pos + u->pool_cap;
         {
             std::unique_lock<std::mutex> my_turn(turn.m);
             hipStream_t st = turn.main;
             agx_zero_args Z; memset(&Z, 0, sizeof Z);
-            auto seg = [&](int i, agx_u32 *ptr, size_t words) { Z.p[i] = ptr; Z.n[i] = (agx_u32)words; };
-            seg(0, u->d_words.p + W_N, W_TOTAL - W_N); seg(1, u->d_tile_side.p + u->n_tiles, 1); seg(2, u->d_sp_cnt.p, (size_t)u->n_words + 1);
-            seg(3, reinterpret_cast<agx_u32 *>(u->d_scan_desc.p + u->scan_desc_n), 4 * u->scan_desc_n); seg(4, reinterpret_cast<agx_u32 *>(u->d_sp_bits.p), 2 * ((size_t)u->n_words + 1));
-            agx_launch_zero(&Z, st);
-            HIP_OK(hipMemsetAsync(u->d_a_mark.p, 0, ids_cap + 2, st));
+            Z.p[0] = u->d_words.p + W_N; Z.n[0] = W_TOTAL - W_N;
+            queue_zero(u, Z, 1, false, st);
             agx_reprune_args R; memset(&R, 0, sizeof R);
             R.node_start = u->d_node_start.p; R.node_cnt = u->d_node_cnt.p; R.nk_cid = u->d_cid.p; R.n_counts = u->d_counts.p; R.n_flags = u->d_flags.p;
             R.side_pk = u->d_side_pk.p; R.tile_side = u->d_tile_side.p; R.n_pos = n_pos; R.pool_cap = u->pool_cap; R.coverage = (int)coverage; R.abort = u->d_words.p + W_STATUS;
@@ -1326,10 +1327,7 @@ void do_reprune(agx_unit *u, uint32_t coverage) {
         const agx_u32 *w = u->h_words.p;
         if (w[W_STATUS]) throw Error{E_DEVICE, "internal: reprune of a unit whose build left a status word"};      // (the kernels have returned at once)
         u->stats.reprune_attempts = (uint32_t)attempt + 1;
-        if (w[W_N + 2] > u->sp_cap) { Take grow{&u->arena}; sparse_bufs(u, w[W_N + 2] + w[W_N + 2] / 8 + 1024, grow); u->stats.device_bytes = u->arena.capacity(); continue; }
-        const unsigned long long ids = (unsigned long long)n_pos + w[W_N + 1];
-        if (ids >= 0xFFFFFF00ull) throw Error{E_OVERFLOW, "walk graph exceeds 2^32 ids"};
-        u->n_ids = (agx_u32)ids; u->n_special = w[W_N + 2];
+        if (walk_ids_verdict(u, w)) { u->stats.device_bytes = u->arena.capacity(); continue; }
         break;
     }
     failed.armed = false;

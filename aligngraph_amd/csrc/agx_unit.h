@@ -228,6 +228,25 @@ inline void fill_sweep_args(agx_unit *u, agx_sweep_args &S) {
     S.pool_cap = u->pool_cap;
     S.sweep_stats = nullptr;
 }
+// what the three passes of a build's node sweep take (the window of tiles of pass 0 is the caller's: tile_lo / tile_hi), and its three edge passes
+inline void fill_node_args(agx_unit *u, agx_node_kargs &K) {
+    agx_u32 *w = u->d_words.p;
+    fill_sweep_args(u, K.S);
+#ifdef AGX_SWEEP_STATS
+    K.S.sweep_stats = w + W_N + 6;
+#endif
+    K.pool_cnt = u->d_pool_cnt.p; K.region_off = u->d_region_off.p; K.spill_lo = u->spill_lo; K.spill_cnt = w + W_SPILL;
+    K.mid_count = w + W_MIDCOUNT; K.mid_list = u->d_mid_list.p; K.mid_n = w + W_MIDCOUNT;
+    K.big_count = w + W_BIGCOUNT; K.big_list = u->d_big_list.p; K.status = w + W_STATUS;
+    K.list_cap = u->list_cap; K.big_n = w + W_BIGCOUNT; K.scratch = u->d_scratch.p;
+    K.slow_list = u->d_slow_list.p; K.slow_count = w + W_SLOWCOUNT; K.fallback_queued = 1u;
+    K.huge_count = w + W_HUGECOUNT; K.huge_n = w + W_HUGECOUNT; K.huge_list = u->d_huge_list.p; K.scratch_huge = u->d_scratch_huge.p; K.huge_queued = u->huge ? 1u : 0u;
+}
+inline void fill_edge_args(agx_unit *u, agx_edge_kargs &E) {
+    agx_u32 *w = u->d_words.p;
+    fill_sweep_args(u, E.S); E.ovf = u->d_ovf.p; E.ovf_count = w + W_OVFCOUNT; E.ovf_cap = u->ovf_cap; E.list_cap = u->list_cap;
+    E.n_hits = (agx_u32)u->nh; E.jump_list = u->d_jump.p; E.n_jump = (agx_u32)u->n_jump; E.abort = w + W_STATUS; E.big_list = u->d_big_list.p; E.big_n = w + W_BIGCOUNT; E.slow_list = u->d_slow_list.p; E.slow_count = w + W_SLOWCOUNT;
+}
 
 template <class F> int guarded(agx_unit *u, F f) {
     try { f(); return AGX_OK; }

@@ -34,7 +34,7 @@ pytestmark = pytest.mark.gpu
 
 CASES = {c.name: c for c in FU.cases()}
 FORMS = {"tiled": {}, "file_order": {"AGX_NO_TILED_UPLOAD": "1"}, "rowdiff_tiled": {"AGX_ROW_DIFF": "1"}, "rowdiff_file_order": {"AGX_ROW_DIFF": "1", "AGX_NO_TILED_UPLOAD": "1"},
-         "ref_raw": {"AGX_REF_RAW": "1"}, "windows3": {"AGX_UPLOAD_WINDOWS": "3"}}
+         "ref_raw": {"AGX_REF_RAW": "1"}, "windows3": {"AGX_UPLOAD_WINDOWS": "3"}, "rowdiff_windows3": {"AGX_ROW_DIFF": "1", "AGX_UPLOAD_WINDOWS": "3"}}
 SWITCHES = ("AGX_NO_TILED_UPLOAD", "AGX_ROW_DIFF", "AGX_REF_RAW", "AGX_UPLOAD_WINDOWS", "AGX_TEST_SMALL_CAPS")
 ARRAYS = ("ref", "vcodes", "runs", "cm_start", "cm", "cm_head", "dhit", "perm", "tile_first", "ckey", "tile_cnt", "tile_off", "tile_recs")
 GEOMETRY = ("qoff1", "boff1", "qoff2", "boff2", "lenjs", "geo")
@@ -191,7 +191,7 @@ def test_front_matches_the_executor_and_the_model(agx, unit_of, name, form, monk
         assert d["tiled"] == (0 if "AGX_NO_TILED_UPLOAD" in env else 1)
         assert d["ref_packed"] == (0 if "AGX_REF_RAW" in env else case.device.get("ref_packed", 1))
         # (the windows are the FIRST attempt's: a build that had to repeat — long_1025 — converges on an attempt that sweeps the resident rows in one piece)
-        assert d["swept_windows"] == (3 if form == "windows3" and st["build_attempts"] == 1 else 1) and d["w_status"] & 16 == 0
+        assert d["swept_windows"] == (3 if "AGX_UPLOAD_WINDOWS" in env and st["build_attempts"] == 1 else 1) and d["w_status"] & 16 == 0
         if "AGX_ROW_DIFF" not in env:
             assert d["rows_diffed"] == 0 and st["rows_by_reference"] == 0
         elif case.row_diff:
@@ -209,6 +209,23 @@ def test_front_matches_the_executor_and_the_model(agx, unit_of, name, form, monk
     for key in ("initial", "pre", "extended"):
         assert out[key] == o[key], key
     assert graph_mismatch(o["graph"], g) is None
+
+
+def test_rowdiff_windows3_sends_rows_as_differences_and_sweeps_three_windows(agx, unit_of, monkeypatch):
+    """The form counts only where a unit keeps both: the encoder drops the differences where they gain nothing, and then the form is windows3 again.  The rows_* cases keep
+    them (row_diff: asserted per case above, as under rowdiff_tiled); rows_130 has rows in all three windows — pieces that begin at blocks 0, 1 and 2 of the stream."""
+    tmp, v, o = unit_of("rows_130")
+    for key in SWITCHES:
+        monkeypatch.delenv(key, raising=False)
+    for key, val in FORMS["rowdiff_windows3"].items():
+        monkeypatch.setenv(key, val)
+    with agx.Unit(k=LU.K, insert_variation=LU.IV, coverage=1, keep_counts=True) as u:
+        u.load_files(tmp, 0)
+        u.upload()
+        u.build()
+        d = u.front()
+        assert d["rows_diffed"] == 1 and d["swept_windows"] == 3 and d["tiled"] == 1
+        assert front_mismatch(v, d, u.stats()) is None
 
 
 def test_front_is_refused_where_the_arrays_are_not_there(agx, unit_of):
