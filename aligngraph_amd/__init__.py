@@ -34,7 +34,7 @@ EXPORTS = [
     "agx_unit_pair_span", "agx_pair_span_free", "agx_unit_walk_span", "agx_walk_span_free", "agx_walk_span_bed",
     "agx_unit_mate_links", "agx_mate_links_free", "agx_mate_links_tsv",
     "agx_unit_bubbles", "agx_unitigs_bubbles", "agx_bubbles_free", "agx_bubbles_tsv",
-    "agx_test_scan", "agx_test_zero", "agx_test_copy_out",
+    "agx_test_scan", "agx_test_zero", "agx_test_copy_out", "agx_test_poison",
 ]
 
 
@@ -281,6 +281,7 @@ def lib():
                                     ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
         L.agx_test_zero.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
         L.agx_test_copy_out.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)]
+        L.agx_test_poison.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
         L.agx_unit_load_files.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
         L.agx_reads_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p, ctypes.c_size_t]
         L.agx_reads_close.argtypes = [ctypes.c_void_p]

@@ -1255,4 +1255,31 @@ int agx_unit_bubbles(agx_unit *u, uint32_t pos_lo, uint32_t pos_hi, uint32_t min
     return answer(u, b, agx_bubbles_free, true, [&] { unit_bubbles(u, pos_lo, pos_hi, min_coverage, max_nodes, want_support != 0, b); });
 }
 
+// Test hook (behind the primitives' hooks): overwrites what the calls above must not trust.  what & 1: every byte of the export's scratch, taken as
+// Export::open() takes it, so that the call behind finds the buffer in place; what & 2: the edge counters, unless they hold the last build's counts (then they are state).
+// pattern 0, 1, 2: bytes 0x00, 0xFF, 0xA5; 3: 32-bit words of a host xorshift of `seed`.  Memsets and one upload on the export's own stream, waited for; no kernel.
+int agx_test_poison(agx_unit *u, uint32_t what, uint32_t pattern, uint64_t seed) {
+    if (!u || pattern > 3u || (what & ~3u)) return AGX_E_ARG;
+    return guarded(u, [&] {
+        export_check(u, false, "test poison", "only such units reserve the export's scratch", "is poisoned");
+        Export E(u);
+        if (what & 1u) E.open(); else E.open_stream();
+        uint64_t x = seed ? seed : 0x9E3779B97F4A7C15ull;
+        std::vector<agx_u32> junk;
+        auto poison = [&](void *p, size_t bytes) {
+            if (!p || !bytes) return;
+            if (pattern < 3u) { E.fill(p, pattern == 0u ? 0x00 : pattern == 1u ? 0xFF : 0xA5, bytes); return; }
+            junk.resize((bytes + 3) / 4);
+            for (agx_u32 &w : junk) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; w = (agx_u32)(x >> 16); }
+            E.write(p, junk.data(), bytes); E.sync();      // (junk is filled again for the next array)
+        };
+        if (what & 1u) poison(u->d_ut.p, u->d_ut.n);
+        if ((what & 2u) && (u->prm.flags & AGX_FLAG_EDGE_SUPPORT) && !u->support_valid) {
+            poison(u->d_e_cnt.p, u->d_e_cnt.n * 4); poison(u->d_ovf_cnt.p, u->d_ovf_cnt.n * 4); poison(u->d_sup_tot.p, u->d_sup_tot.n * 4);
+        }
+        E.sync();
+        HIP_OK(hipGetLastError());
+    });
+}
+
 }  // extern "C"

@@ -293,6 +293,13 @@ int agx_test_zero(int device, const uint32_t *len, uint32_t *words);
 /* agx_launch_copy_out of n_seg (1 .. 16) segments from device memory to registered host memory.  src: the segments one after the other, each padded to a multiple of
    16 bytes; dst: what the host buffer holds afterwards, each segment as (padded bytes | guard) */
 int agx_test_copy_out(int device, int n_seg, const uint64_t *bytes, const uint8_t *src, uint8_t *dst);
+/* Test hook of the on-request calls (agx_unit_unitigs and everything behind it in this file): overwrites what such a call must not trust, as a process that has answered
+   other questions about other units leaves it.  what & 1: every byte of the export's scratch, taken as any export takes it (agx_unit_hbm_needed and device_bytes are then
+   what they are after an export); what & 2: the edge counters of a unit with AGX_FLAG_EDGE_SUPPORT, unless they hold the last build's counts — valid counters are state
+   and stay.  pattern 0: bytes 0x00; 1: 0xFF; 2: 0xA5; 3: 32-bit words of a xorshift of seed, uploaded.  Memsets and copies on a stream of the call's own, waited for; no
+   kernel; nothing a build, walk or download reads is touched.  The preconditions of agx_unit_unitigs (AGX_E_ARG otherwise, also for other bits of `what` or pattern > 3,
+   and nothing is written). */
+int agx_test_poison(agx_unit *u, uint32_t what, uint32_t pattern, uint64_t seed);
 
 int agx_unit_create(const agx_params *p, agx_unit **out);
 void agx_unit_destroy(agx_unit *u);
