@@ -554,20 +554,7 @@ void stage_inputs(agx_unit *u) {
 // mapped and paged in where it is touched.  Valid for one BATCH size, one k and for exactly the five text files it was made from (size and
 // modification time of each are in the header): anything else and the loader falls back to the text.
 namespace cache {
-enum { S_HITS = 0, S_RUNS, S_CODES, S_SEGS, S_CHAIN_END, S_ROWS, S_REF, S_CM_CNT, S_CHAIN_STR, S_INITIAL, S_BASES, S_OTHER, S_SIDES, S_JUMP, S_OTHERB, S_N };
-struct Header {
-    char magic[8]; agx_u32 version, batch; unsigned long long stamp[6][2];      // (size, modification time) of the five text files and of tmp/_agx_pairs.<u>.bin
-    unsigned long long n_pos, n_ref, nh, n_runs, n_cm, n_segs, n_seg0, n_rows, n_chain_end, n_codes, pairs_in_file, sam_pairs;
-    agx_u32 stride, maxlen, n_slots, k;          // k: the staged hits name their left mate, which depends on it (agx_hit_left_is_mate2)
-    agx_u32 rows_in_reads;                       // 1: S_ROWS holds 64-bit offsets into tmp/_reads.fa (whose size and time are part of the stamp), S_BASES is empty; 0: S_ROWS holds the
-                                                 // read slot of every row and S_BASES the slots' bases (units that the general loader parsed); 2: both empty — the k-mer tails come out of
-                                                 // S_CODES (2-bit rows) and S_OTHER / S_OTHERB (units whose alignments were handed over staged: UnitView::codes2)
-    agx_u32 slot_stride;                         // bases per read slot in S_BASES (rows_in_reads == 0)
-    unsigned long long n_sides, n_jump;
-    agx_u32 sizes[5];                            // sizeof agx_whit, agx_wrun, agx_cmseg, Header, agx_wside: a file written by another layout is not this one
-    unsigned long long off[S_N], len[S_N];
-};
-const char MAGIC[8] = {'A', 'G', 'X', 'U', 'N', 'I', 'T', '7'};
+using namespace agx::cachefile;      // the header and the section numbers (agx_host.h)
 void stamps(const std::string &d, int unit, unsigned long long st[6][2]) {
     const std::string s = std::to_string(unit);
     const std::string f[6] = {d + "/_genome." + s + ".fa", d + "/_contigs.fa", d + "/_contigs_genome." + s + ".psl", d + "/_reads.fa", d + "/_reads_genome." + s + ".bowtie", pairsfile::path_of(d, unit)};
@@ -622,37 +609,11 @@ void save_cache(agx_unit *u, const std::string &dir, int unit) {
     if (!ok || rename(part.c_str(), path.c_str()) != 0) { (void)remove(part.c_str()); throw Error{E_IO, "cannot write " + path}; }
 }
 
-// The staged read alignments in u->s_* (read from a cache file or a staged-pairs file): everything the device and the walk index with must be in range — a file whose lengths
-// are intact but whose content is not is a reason to refuse it, not to read out of bounds.
-bool staged_pairs_fine(agx_unit *u, unsigned long long n_rows, agx_u32 stride, agx_u32 maxlen, unsigned long long n_runs, unsigned long long n_sides, unsigned threads) {
-    bool fine = true;
-    struct { unsigned long long n_rows, n_runs, n_sides; agx_u32 stride, maxlen; } H{n_rows, n_runs, n_sides, stride, maxlen};
-    {
-        const unsigned long long n_bases = H.n_rows * (unsigned long long)H.stride;
-        for (size_t i = 0; i < u->n_other && fine; i++) fine = u->s_other.p[i] < n_bases;
-        std::vector<int> bad2(threads, 0); std::vector<size_t> jumps(threads, 0);
-        on_threads(threads, [&](unsigned t) {
-            size_t nj = 0;
-            for (size_t i = u->nh * t / threads, hi = u->nh * (t + 1) / threads; i < hi; i++) {
-                const agx_whit &w = u->s_hits.p[i];
-                if (w.row >= H.n_rows || w.len == 0 || w.len > H.maxlen || w.back > i) { bad2[t] = 1; return; }
-                if (!(w.flags & (AGX_WF_RUNS1 | AGX_WF_RUNS2))) continue;                 // five hits in eight: nothing else to look at
-                if (((w.flags & AGX_WF_RUNS1) ? w.a : w.b) >= H.n_sides) { bad2[t] = 1; return; }
-                const agx_hit h = agx_unpack_hit(w, u->s_sides.p);
-                if ((h.nruns1 && (unsigned long long)h.runs1 + h.nruns1 > H.n_runs) || (h.nruns2 && (unsigned long long)h.runs2 + h.nruns2 > H.n_runs)) { bad2[t] = 1; return; }
-                nj += ((h.pad[0] & 1u) ? h.nruns2 : h.nruns1) >= 2;
-            }
-            jumps[t] = nj;
-        });
-        for (int b : bad2) fine = fine && !b;
-        { size_t want = 0; for (size_t v : jumps) want += v; fine = fine && want == u->n_jump; }      // pass J's list names exactly the hits whose left mate has several runs: as many, ...
-        for (size_t i = 0; i < u->n_jump && fine; i++) {      // ... ascending, each one of them
-            const agx_u32 h = u->s_jump.p[i];
-            fine = h < u->nh && (i == 0 || u->s_jump.p[i - 1] < h);
-            if (fine) { const agx_whit &w = u->s_hits.p[h]; fine = (w.flags & ((w.flags & AGX_WF_LEFT2) ? AGX_WF_RUNS2 : AGX_WF_RUNS1)) != 0; if (fine) { const agx_hit x = agx_unpack_hit(w, u->s_sides.p); fine = ((x.pad[0] & 1u) ? x.nruns2 : x.nruns1) >= 2; } }
-        }
-    }
-    return fine;
+// The staged read alignments in u->s_* (read from a cache file or a staged-pairs file) as the content rules look at them (agx_host.h: staged_pairs_rule).
+agx::StagedView staged_view(const agx_unit *u, unsigned long long n_rows, agx_u32 stride, agx_u32 maxlen, unsigned long long n_pos) {
+    agx::StagedView V; V.hits = u->s_hits.p; V.nh = u->nh; V.sides = u->s_sides.p; V.n_sides = u->n_sides; V.runs = u->s_runs.p; V.n_runs = u->n_runs; V.jump = u->s_jump.p; V.n_jump = u->n_jump;
+    V.other = u->s_other.p; V.n_other = u->n_other; V.n_rows = n_rows; V.stride = stride; V.maxlen = maxlen; V.n_pos = n_pos;
+    return V;
 }
 
 // A unit's read alignments out of tmp/_agx_pairs.<u>.bin (agx_host.h: pairsfile): the arrays into the pinned upload buffers, checked like a cache file's; the mapped file stays
@@ -660,7 +621,7 @@ bool staged_pairs_fine(agx_unit *u, unsigned long long n_rows, agx_u32 stride, a
 void load_staged_pairs(agx_unit *u, agx::PairsFile &F) {
     using namespace pairsfile;
     const Header &H = F.H;
-    if (H.k != u->prm.k || H.batch != u->prm.batch) throw Error{E_ARG, "tmp/_agx_pairs: staged for another k or another BATCH than this unit's"};
+    if (pairs_unit_rule(H, u->prm.k, u->prm.batch)) throw Error{E_ARG, "tmp/_agx_pairs: staged for another k or another BATCH than this unit's"};
     u->nh = H.nh; u->n_runs = H.n_runs; u->n_sides = H.n_sides; u->n_jump = H.n_jump; u->n_codes = H.n_codes; u->n_other = H.n_other; u->stride = H.stride; u->maxlen = H.maxlen; u->n_rows = H.n_rows;
     u->pairs_in_file = H.pairs_in_file; u->sam_pairs = H.sam_pairs; u->n_slots = 0; u->row_off.clear(); u->row_slot.clear(); u->reads_keep.reset(); u->reads_map.reset();
     alloc_pair_arrays(u);
@@ -669,9 +630,9 @@ void load_staged_pairs(agx_unit *u, agx::PairsFile &F) {
     cut(u->s_hits.p, S_HITS); cut(u->s_sides.p, S_SIDES); cut(u->s_jump.p, S_JUMP); cut(u->s_runs.p, S_RUNS); cut(u->s_codes.p, S_CODES); cut(u->s_other.p, S_OTHER);
     const unsigned threads = (unsigned)std::min<size_t>(std::min<unsigned>(8u, std::max(1u, usable_cpus())), pieces.size() ? pieces.size() : 1);
     move_pieces(pieces, threads, [&](char *mem, unsigned long long off, size_t n) { memcpy(mem, F.fv->p + off, n); return (ssize_t)n; });
-    bool fine = staged_pairs_fine(u, H.n_rows, H.stride, H.maxlen, H.n_runs, H.n_sides, threads);
-    for (size_t i = 1; i < u->n_other && fine; i++) fine = u->s_other.p[i - 1] < u->s_other.p[i];      // (the walk bisects the list)
-    if (!fine) throw Error{E_FORMAT, "tmp/_agx_pairs: the staged arrays are inconsistent"};
+    const char *rule = staged_pairs_rule(staged_view(u, H.n_rows, H.stride, H.maxlen, 0), threads);      // (the unit's positions are not known yet: agx_unit_load_files_shared)
+    if (!rule) rule = other_ascending_rule(u->s_other.p, u->n_other);      // (the walk bisects the list)
+    if (rule) throw Error{E_FORMAT, std::string("tmp/_agx_pairs: the staged arrays are inconsistent (") + rule + ")"};
     u->pairs_staged = true; u->pairs_file = std::move(F);
 }
 
@@ -686,16 +647,8 @@ bool load_cache(agx_unit *u, const std::string &dir, int unit) {
     Header H; struct stat sb;
     if (fstat(fd, &sb) != 0 || (size_t)sb.st_size < sizeof H || pread(fd, &H, sizeof H, 0) != (ssize_t)sizeof H) return false;
     unsigned long long st[6][2]; stamps(dir, unit, st);
-    if (memcmp(H.magic, MAGIC, 8) != 0 || H.version != 2 || H.batch != u->prm.batch || H.k != u->prm.k || memcmp(st, H.stamp, sizeof st) != 0) return false;
-    if (H.sizes[0] != sizeof(agx_whit) || H.sizes[1] != sizeof(agx_wrun) || H.sizes[2] != sizeof(agx_cmseg) || H.sizes[3] != sizeof(Header) || H.sizes[4] != sizeof(agx_wside)) return false;
-    for (int i = 0; i < S_N; i++) if (H.off[i] > (unsigned long long)sb.st_size || H.len[i] > (unsigned long long)sb.st_size - H.off[i]) return false;
+    if (cache_header_rule(H, (unsigned long long)sb.st_size, u->prm.batch, u->prm.k) || memcmp(st, H.stamp, sizeof st) != 0) return false;
     const bool in_reads = H.rows_in_reads == 1, from_codes = H.rows_in_reads == 2;
-    if (H.rows_in_reads > 2) return false;
-    if (H.n_pos == 0 || H.n_pos >= 0xFFFFFF00ull || H.n_ref > H.n_pos || H.len[S_REF] != H.n_pos || H.len[S_CM_CNT] != H.n_pos || H.len[S_HITS] != H.nh * sizeof(agx_whit) || H.len[S_RUNS] != H.n_runs * sizeof(agx_wrun) ||
-        H.len[S_SIDES] != H.n_sides * sizeof(agx_wside) || H.n_sides > H.nh || H.len[S_JUMP] != H.n_jump * 4 || H.n_jump > H.nh ||
-        H.len[S_CODES] != H.n_codes || H.len[S_SEGS] != H.n_segs * sizeof(agx_cmseg) || H.n_seg0 > H.n_segs || H.len[S_ROWS] != (from_codes ? 0ull : H.n_rows * (in_reads ? 8 : 4)) || (H.stride & 3u) || H.len[S_OTHERB] != (from_codes ? H.len[S_OTHER] / 8 : 0ull) ||
-        H.len[S_BASES] != ((in_reads || from_codes) ? 0ull : (unsigned long long)H.n_slots * H.slot_stride) || H.len[S_CHAIN_END] != H.n_chain_end * 4 || H.n_codes != H.n_rows * (H.stride / 4) || (H.len[S_OTHER] & 7u) ||
-        H.nh >= 0xFFFFFFFFull || H.n_runs >= 0xFFFFFFFFull || H.n_rows >= 0x7FFFFFFFull || H.maxlen > H.stride || (!in_reads && !from_codes && H.maxlen > H.slot_stride)) return false;
     HIP_OK(hipSetDevice(u->prm.device));
     const double t0 = now_ms();
     std::unique_ptr<FileView> reads_map;
@@ -716,28 +669,10 @@ bool load_cache(agx_unit *u, const std::string &dir, int unit) {
     bool fine = move_pieces(pieces, threads, [&](char *mem, unsigned long long off, size_t n) { return pread(fd, mem, n, (off_t)off); });
     // what the device and the walk index with must be in range: a file whose lengths are intact but whose content is not is a reason to parse the text again, not to read out of bounds
     if (fine) {
-        fine = staged_pairs_fine(u, H.n_rows, H.stride, H.maxlen, H.n_runs, H.n_sides, threads);
-        unsigned long long el = 0;
-        for (size_t i = 0; i < u->n_segs && fine; i++) { const agx_cmseg &g = u->s_segs.p[i]; fine = (unsigned long long)g.pos0 + g.len <= H.n_pos && g.hop_end < H.n_pos && (unsigned long long)g.hop_str0 + g.hop_len0 <= H.len[S_CHAIN_STR] + 1 && g.elem0 == el; el += g.len; }
-        fine = fine && el == H.n_cm;
-        if (fine) {      // the device derives cm_start from the counts and writes every run element at cm[cm_start[x] + rank] (agx_k_cm_fill): the counts must add up to the
-            // conti-mers, and every element's rank must lie below its position's count — or a file with intact lengths writes out of bounds in HBM
-            const agx_u8 *cc = (const agx_u8 *)(base + H.off[S_CM_CNT]);
-            std::vector<unsigned long long> part(threads, 0); std::vector<int> bad3(threads, 0);
-            on_threads(threads, [&](unsigned t) {
-                unsigned long long sum = 0;
-                for (size_t x = (size_t)H.n_pos * t / threads, hi = (size_t)H.n_pos * (t + 1) / threads; x < hi; x++) sum += cc[x];
-                part[t] = sum;
-                for (size_t i = u->n_segs * t / threads, hi = u->n_segs * (t + 1) / threads; i < hi; i++) { const agx_cmseg &g = u->s_segs.p[i]; if (g.rank > 254) { bad3[t] = 1; return; }
-                    for (agx_u32 j = 0; j < g.len; j++) if (cc[(size_t)g.pos0 + j] <= g.rank) { bad3[t] = 1; return; } }
-            });
-            unsigned long long total = 0; for (unsigned t = 0; t < threads; t++) { total += part[t]; fine = fine && !bad3[t]; }
-            fine = fine && total == H.n_cm;
-        }
-        for (size_t i = 0; i < u->n_chain_end && fine; i++) fine = u->s_chain_end.p[i] < H.n_pos;
-        if (fine && in_reads) { const uint64_t *ro = (const uint64_t *)(base + H.off[S_ROWS]); for (size_t r = 0; r < H.n_rows && fine; r++) fine = ro[r] + H.maxlen <= reads_map->n && ro[r] < reads_map->n; }      // (a row is read up to the longest read's length)
-        if (fine && !in_reads && !from_codes) { const agx_u32 *rs = (const agx_u32 *)(base + H.off[S_ROWS]); for (size_t r = 0; r < H.n_rows && fine; r++) fine = rs[r] < H.n_slots; }
-        for (size_t i = 1; i < u->n_other && fine && from_codes; i++) fine = u->s_other.p[i - 1] < u->s_other.p[i];      // (the walk bisects the list)
+        agx::CacheView C; C.segs = u->s_segs.p; C.n_segs = u->n_segs; C.cm_cnt = (const agx_u8 *)(base + H.off[S_CM_CNT]); C.chain_end = u->s_chain_end.p; C.n_chain_end = u->n_chain_end;
+        C.rows = base + H.off[S_ROWS]; C.n_pos = H.n_pos; C.n_cm = H.n_cm; C.n_rows = H.n_rows; C.chain_str_len = H.len[S_CHAIN_STR]; C.reads_size = in_reads ? reads_map->n : 0;
+        C.maxlen = H.maxlen; C.n_slots = H.n_slots; C.rows_in_reads = H.rows_in_reads;
+        fine = !staged_pairs_rule(staged_view(u, H.n_rows, H.stride, H.maxlen, H.n_pos), threads) && !cache_content_rule(C, threads) && !(from_codes && other_ascending_rule(u->s_other.p, u->n_other));
     }
     if (!fine) { u->cache_map.reset(); return false; }
     const double tv = now_ms();
@@ -1822,6 +1757,11 @@ int agx_unit_load_files_shared(agx_unit *u, const char *tmp_dir, int unit, const
         if (side_started) { side.join(); join.on = false; }
         if (thread_err) std::rethrow_exception(thread_err);
         if (pairs_err) std::rethrow_exception(pairs_err);
+        if (u->pairs_staged && u->pairs_file.fv)      // the rules of the staged-pairs file that need the unit's positions, now that the threading has said how many there are
+            if (const char *rule = staged_positions_rule(staged_view(u, u->n_rows, u->stride, u->maxlen, u->T.ref.size()), std::min(8u, std::max(1u, usable_cpus())))) {
+                u->pairs_staged = false; u->pairs_file = agx::PairsFile(); u->have_ref = u->have_threads = false;      // (nothing of the file stays with the unit)
+                throw Error{E_FORMAT, std::string("tmp/_agx_pairs: the staged arrays are inconsistent (") + rule + ")"};
+            }
         u->stats.ms_thread = ms_thread; u->stats.ms_parse = now_ms() - tp0;
         u->have_ref = u->have_threads = true;
         stage_inputs(u);

@@ -265,6 +265,18 @@ bool build_row_diffs(const agx_whit *hits, size_t nh, const agx_wside *sides, si
 // linked with the engine (or a generator of synthetic alignments: tools/agx_synth.cpp) writes where the reference's flow distributes SAM lines (AG:3545-3579).  The arrays are
 // exactly what the loaders + staging produce from the text (tests/test_staged_pairs.py compares them byte for byte); they depend on k (which mate is the left one) and on
 // BATCH (which line pairs the batch boundaries drop), both in the header.  agx_unit_load_files takes the file when it is there and does not look for the two text files.
+// The format's contract for a producer outside this tree — what the loader holds a file to besides the header's lengths (rule names as staged_pairs_rule returns them;
+// a file that breaks one is refused with AGX_E_FORMAT and the name):
+//   hit_row, hit_len    row < n_rows; 0 < len <= maxlen
+//   hit_back            back <= the hit's own number (the earlier hits of its pair)
+//   hit_flags           only the five bits REV1, REV2, LEFT2, RUNS1, RUNS2 (AGX_WF_DUP is the staging's)
+//   hit_side, side_runs a hit with RUNS1 / RUNS2 names a side record < n_sides in a (RUNS1) or b (RUNS2 only); a side's runs lie inside the pool: runs + nruns <= n_runs
+//   run_in_read         every run lies in its read: q + n <= len
+//   run_order           a mate's runs ascend and do not overlap, in the read and on the reference: q + n <= next q, t + n <= next t
+//   mate_in_unit        every aligned base of the mate that is NOT the left one lies inside the unit sequence (position + len, or t + n of each run, <= its length
+//                       with the positions contig threading appends); the left mate's span is checked on the device
+//   jump_*              S_JUMP lists exactly the hits whose LEFT mate has two runs or more: as many (jump_count), each < nh (jump_entry), ascending (jump_order), each one of them (jump_hit)
+//   other_in_rows, other_order   S_OTHER entries < n_rows * stride, strictly ascending; S_OTHERB[i] is the byte of entry i
 namespace pairsfile {
 enum { S_HITS = 0, S_SIDES, S_RUNS, S_CODES, S_OTHER, S_OTHERB, S_JUMP, S_N };
 struct Header {
@@ -282,6 +294,52 @@ std::vector<agx_u8> other_bytes_of(const Pairs &P, const StagedPairs &S);      /
 // maps and checks the header and the section lengths (not the content); false: no such file.  Throws Error{E_FORMAT} on a file that is not one.
 struct PairsFile { std::unique_ptr<FileView> fv; pairsfile::Header H; const char *sec(int i) const { return fv->p + H.off[i]; } };
 bool open_pairs_file(const std::string &path, PairsFile &F);
+
+// tmp/_agx_unit.<u>.bin — a unit's STAGED form (agx_engine.cpp "unit cache file" writes and loads it): its header and section numbers, here so that host-only code can
+// judge a header and a file's content without a device.
+namespace cachefile {
+enum { S_HITS = 0, S_RUNS, S_CODES, S_SEGS, S_CHAIN_END, S_ROWS, S_REF, S_CM_CNT, S_CHAIN_STR, S_INITIAL, S_BASES, S_OTHER, S_SIDES, S_JUMP, S_OTHERB, S_N };
+struct Header {
+    char magic[8]; agx_u32 version, batch; unsigned long long stamp[6][2];      // (size, modification time) of the five text files and of tmp/_agx_pairs.<u>.bin
+    unsigned long long n_pos, n_ref, nh, n_runs, n_cm, n_segs, n_seg0, n_rows, n_chain_end, n_codes, pairs_in_file, sam_pairs;
+    agx_u32 stride, maxlen, n_slots, k;          // k: the staged hits name their left mate, which depends on it (agx_hit_left_is_mate2)
+    agx_u32 rows_in_reads;                       // 1: S_ROWS holds 64-bit offsets into tmp/_reads.fa (whose size and time are part of the stamp), S_BASES is empty; 0: S_ROWS holds the
+                                                 // read slot of every row and S_BASES the slots' bases (units that the general loader parsed); 2: both empty — the k-mer tails come out of
+                                                 // S_CODES (2-bit rows) and S_OTHER / S_OTHERB (units whose alignments were handed over staged: UnitView::codes2)
+    agx_u32 slot_stride;                         // bases per read slot in S_BASES (rows_in_reads == 0)
+    unsigned long long n_sides, n_jump;
+    agx_u32 sizes[5];                            // sizeof agx_whit, agx_wrun, agx_cmseg, Header, agx_wside: a file written by another layout is not this one
+    unsigned long long off[S_N], len[S_N];
+};
+const char MAGIC[8] = {'A', 'G', 'X', 'U', 'N', 'I', 'T', '7'};
+}  // namespace cachefile
+
+// ---- what a staged-pairs file and a unit cache file must hold besides intact lengths (agx_load.cpp "content rules") ----
+// Everything the device and the walk index with must be in range: a file whose lengths are intact but whose content is not is a reason to refuse it, not to read out of
+// bounds.  Each check returns the NAME of the first rule that fails (short, stable: DESIGN.md "Rejected inputs" lists them with what each protects), or nullptr.
+// The staged read alignments, as both files hold them.  n_pos: the unit's positions, 0 where they are not known yet (the rules that need them are then left out:
+// staged_positions_rule applies them alone, later).
+struct StagedView {
+    const agx_whit *hits = nullptr; size_t nh = 0; const agx_wside *sides = nullptr; size_t n_sides = 0; const agx_wrun *runs = nullptr; size_t n_runs = 0;
+    const agx_u32 *jump = nullptr; size_t n_jump = 0; const unsigned long long *other = nullptr; size_t n_other = 0;
+    unsigned long long n_rows = 0; agx_u32 stride = 0, maxlen = 0; unsigned long long n_pos = 0;
+};
+const char *staged_pairs_rule(const StagedView &V, unsigned threads);
+const char *staged_positions_rule(const StagedView &V, unsigned threads);      // the rules of staged_pairs_rule that need V.n_pos, alone
+const char *other_ascending_rule(const unsigned long long *other, size_t n_other);      // the walk bisects the list (where it reads k-mer tails out of the 2-bit rows)
+// the header of a staged-pairs file of `file_size` bytes (open_pairs_file)
+const char *pairs_header_rule(const pairsfile::Header &H, unsigned long long file_size);
+const char *pairs_unit_rule(const pairsfile::Header &H, agx_u32 k, agx_u32 batch);      // the file was staged for this unit's k and BATCH
+// the header of a cache file of `file_size` bytes, for a unit of this BATCH and k (not the stamps: they are compared with the files beside it)
+const char *cache_header_rule(const cachefile::Header &H, unsigned long long file_size, agx_u32 batch, agx_u32 k);
+// what a cache file holds besides the staged read alignments: the conti-mer runs, the counts they fill, the chain ends, the rows' places.  reads_size: bytes of tmp/_reads.fa
+// (rows_in_reads == 1); rows: section S_ROWS
+struct CacheView {
+    const agx_cmseg *segs = nullptr; size_t n_segs = 0; const agx_u8 *cm_cnt = nullptr; const agx_u32 *chain_end = nullptr; size_t n_chain_end = 0; const void *rows = nullptr;
+    unsigned long long n_pos = 0, n_cm = 0, n_rows = 0, chain_str_len = 0, reads_size = 0; agx_u32 maxlen = 0, n_slots = 0, rows_in_reads = 0;
+};
+const char *cache_content_rule(const CacheView &C, unsigned threads);
+const char *const *content_rule_names(size_t *n);      // every name the checks above can return
 
 // agx_host.cpp
 void load_unit_reference(const std::string &path, std::string &ref);

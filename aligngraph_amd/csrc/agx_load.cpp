@@ -484,14 +484,191 @@ bool open_pairs_file(const std::string &path, PairsFile &F) {
     F.fv.reset(new FileView(path));
     if (F.fv->n < sizeof(Header)) throw Error{E_FORMAT, path + " is not a staged-pairs file"};
     memcpy(&F.H, F.fv->p, sizeof(Header));
-    const Header &H = F.H;
-    bool fine = memcmp(H.magic, MAGIC, 8) == 0 && H.version == 1 && H.sizes[0] == sizeof(agx_whit) && H.sizes[1] == sizeof(agx_wside) && H.sizes[2] == sizeof(agx_wrun);
-    for (int i = 0; i < S_N && fine; i++) fine = H.off[i] <= F.fv->n && H.len[i] <= F.fv->n - H.off[i];
-    fine = fine && H.len[S_HITS] == H.nh * sizeof(agx_whit) && H.len[S_SIDES] == H.n_sides * sizeof(agx_wside) && H.len[S_RUNS] == H.n_runs * sizeof(agx_wrun) && H.len[S_CODES] == H.n_codes &&
-           H.len[S_OTHER] == H.n_other * 8 && H.len[S_OTHERB] == H.n_other && H.len[S_JUMP] == H.n_jump * 4 && (H.stride & 3u) == 0 && H.maxlen <= H.stride &&
-           H.n_codes == (unsigned long long)H.n_rows * (H.stride / 4) && H.n_sides <= H.nh && H.n_jump <= H.nh && H.nh < 0xFFFFFFFFull && H.n_runs < 0xFFFFFFFFull && H.n_rows < 0x7FFFFFFFu;
-    if (!fine) throw Error{E_FORMAT, path + " is not a staged-pairs file of this layout"};
+    if (const char *rule = pairs_header_rule(F.H, F.fv->n)) throw Error{E_FORMAT, path + " is not a staged-pairs file of this layout (" + rule + ")"};
     return true;
+}
+
+// ---- content rules (agx_host.h) -----------------------------------------------------------------------------------------------------------------
+// Every rule has a name; a check returns the first one that fails.  RULE_NAMES lists them all (tests/test_damaged_inputs.py asks that each has a damaged input that
+// it refuses: a rule that arrives here arrives there).
+namespace {
+const char *const RULE_NAMES[] = {
+    // headers of both files
+    "magic", "version", "batch", "k", "sizes", "section_bounds", "count_limits", "rows_in_reads", "n_pos", "n_ref", "len_ref", "len_cm_cnt", "len_hits", "len_sides", "len_runs",
+    "len_codes", "len_other", "len_otherb", "len_jump", "len_segs", "len_rows", "len_bases", "len_chain_end", "stride_mod4", "maxlen_stride", "maxlen_slot_stride", "codes_rows",
+    "sides_hits", "jump_hits", "seg0_segs",
+    // staged read alignments
+    "other_in_rows", "other_order", "hit_row", "hit_len", "hit_back", "hit_side", "side_runs", "jump_count", "jump_entry", "jump_order", "jump_hit",
+    "hit_flags", "run_in_read", "run_order", "mate_in_unit",
+    // the rest of a cache file
+    "seg_span", "seg_hop_end", "seg_hop_str", "seg_elem0", "cm_total", "cm_sum", "seg_rank", "chain_end", "row_offset", "row_slot",
+};
+}  // namespace
+const char *const *content_rule_names(size_t *n) { *n = sizeof RULE_NAMES / sizeof RULE_NAMES[0]; return RULE_NAMES; }
+
+const char *pairs_header_rule(const pairsfile::Header &H, unsigned long long file_size) {
+    using namespace pairsfile;
+    if (memcmp(H.magic, MAGIC, 8) != 0) return "magic";
+    if (H.version != 1) return "version";
+    if (H.sizes[0] != sizeof(agx_whit) || H.sizes[1] != sizeof(agx_wside) || H.sizes[2] != sizeof(agx_wrun)) return "sizes";
+    for (int i = 0; i < S_N; i++) if (H.off[i] > file_size || H.len[i] > file_size - H.off[i]) return "section_bounds";
+    if (H.nh >= 0xFFFFFFFFull || H.n_runs >= 0xFFFFFFFFull || H.n_rows >= 0x7FFFFFFFu) return "count_limits";
+    if (H.len[S_HITS] != H.nh * sizeof(agx_whit)) return "len_hits";
+    if (H.len[S_SIDES] != H.n_sides * sizeof(agx_wside)) return "len_sides";
+    if (H.len[S_RUNS] != H.n_runs * sizeof(agx_wrun)) return "len_runs";
+    if (H.len[S_CODES] != H.n_codes) return "len_codes";
+    if (H.len[S_OTHER] != H.n_other * 8) return "len_other";
+    if (H.len[S_OTHERB] != H.n_other) return "len_otherb";
+    if (H.len[S_JUMP] != H.n_jump * 4) return "len_jump";
+    if (H.stride & 3u) return "stride_mod4";
+    if (H.maxlen > H.stride) return "maxlen_stride";
+    if (H.n_codes != (unsigned long long)H.n_rows * (H.stride / 4)) return "codes_rows";
+    if (H.n_sides > H.nh) return "sides_hits";
+    if (H.n_jump > H.nh) return "jump_hits";
+    return nullptr;
+}
+
+const char *pairs_unit_rule(const pairsfile::Header &H, agx_u32 k, agx_u32 batch) { return H.k != k ? "k" : H.batch != batch ? "batch" : nullptr; }
+
+const char *cache_header_rule(const cachefile::Header &H, unsigned long long file_size, agx_u32 batch, agx_u32 k) {
+    using namespace cachefile;
+    if (memcmp(H.magic, MAGIC, 8) != 0) return "magic";
+    if (H.version != 2) return "version";
+    if (H.batch != batch) return "batch";
+    if (H.k != k) return "k";
+    if (H.sizes[0] != sizeof(agx_whit) || H.sizes[1] != sizeof(agx_wrun) || H.sizes[2] != sizeof(agx_cmseg) || H.sizes[3] != sizeof(Header) || H.sizes[4] != sizeof(agx_wside)) return "sizes";
+    for (int i = 0; i < S_N; i++) if (H.off[i] > file_size || H.len[i] > file_size - H.off[i]) return "section_bounds";
+    if (H.rows_in_reads > 2) return "rows_in_reads";
+    const bool in_reads = H.rows_in_reads == 1, from_codes = H.rows_in_reads == 2;
+    if (H.n_pos == 0 || H.n_pos >= 0xFFFFFF00ull) return "n_pos";
+    if (H.nh >= 0xFFFFFFFFull || H.n_runs >= 0xFFFFFFFFull || H.n_rows >= 0x7FFFFFFFull) return "count_limits";
+    if (H.n_ref > H.n_pos) return "n_ref";
+    if (H.len[S_REF] != H.n_pos) return "len_ref";
+    if (H.len[S_CM_CNT] != H.n_pos) return "len_cm_cnt";
+    if (H.len[S_HITS] != H.nh * sizeof(agx_whit)) return "len_hits";
+    if (H.len[S_RUNS] != H.n_runs * sizeof(agx_wrun)) return "len_runs";
+    if (H.len[S_SIDES] != H.n_sides * sizeof(agx_wside)) return "len_sides";
+    if (H.n_sides > H.nh) return "sides_hits";
+    if (H.len[S_JUMP] != H.n_jump * 4) return "len_jump";
+    if (H.n_jump > H.nh) return "jump_hits";
+    if (H.len[S_CODES] != H.n_codes) return "len_codes";
+    if (H.len[S_SEGS] != H.n_segs * sizeof(agx_cmseg)) return "len_segs";
+    if (H.n_seg0 > H.n_segs) return "seg0_segs";
+    if (H.len[S_ROWS] != (from_codes ? 0ull : H.n_rows * (in_reads ? 8 : 4))) return "len_rows";
+    if (H.stride & 3u) return "stride_mod4";
+    if (H.len[S_OTHERB] != (from_codes ? H.len[S_OTHER] / 8 : 0ull)) return "len_otherb";
+    if (H.len[S_BASES] != ((in_reads || from_codes) ? 0ull : (unsigned long long)H.n_slots * H.slot_stride)) return "len_bases";
+    if (H.len[S_CHAIN_END] != H.n_chain_end * 4) return "len_chain_end";
+    if (H.n_codes != H.n_rows * (H.stride / 4)) return "codes_rows";
+    if (H.len[S_OTHER] & 7u) return "len_other";
+    if (H.maxlen > H.stride) return "maxlen_stride";
+    if (!in_reads && !from_codes && H.maxlen > H.slot_stride) return "maxlen_slot_stride";
+    return nullptr;
+}
+
+const char *other_ascending_rule(const unsigned long long *other, size_t n_other) {
+    for (size_t i = 1; i < n_other; i++) if (!(other[i - 1] < other[i])) return "other_order";
+    return nullptr;
+}
+
+// The staged read alignments (read from a cache file or a staged-pairs file): everything the device and the walk index with must be in range — a file whose lengths
+// are intact but whose content is not is a reason to refuse it, not to read out of bounds.
+const char *staged_pairs_rule(const StagedView &V, unsigned threads) {
+    threads = std::max(1u, threads);
+    const unsigned long long n_bases = V.n_rows * (unsigned long long)V.stride;
+    for (size_t i = 0; i < V.n_other; i++) if (!(V.other[i] < n_bases)) return "other_in_rows";
+    std::vector<const char *> bad(threads, nullptr); std::vector<size_t> jumps(threads, 0);
+    on_threads(threads, [&](unsigned t) {
+        size_t nj = 0;
+        for (size_t i = V.nh * t / threads, hi = V.nh * (t + 1) / threads; i < hi; i++) {
+            const agx_whit &w = V.hits[i];
+            if (w.row >= V.n_rows) { bad[t] = "hit_row"; return; }
+            if (w.len == 0 || w.len > V.maxlen) { bad[t] = "hit_len"; return; }
+            if (w.back > i) { bad[t] = "hit_back"; return; }
+            if (w.flags & ~31u) { bad[t] = "hit_flags"; return; }      // the five bits a loader writes; AGX_WF_DUP is the staging's to set, and a set bit there would drop the hit
+            if (!(w.flags & (AGX_WF_RUNS1 | AGX_WF_RUNS2))) continue;                 // five hits in eight: nothing else to look at
+            if (((w.flags & AGX_WF_RUNS1) ? w.a : w.b) >= V.n_sides) { bad[t] = "hit_side"; return; }
+            const agx_hit h = agx_unpack_hit(w, V.sides);
+            if ((h.nruns1 && (unsigned long long)h.runs1 + h.nruns1 > V.n_runs) || (h.nruns2 && (unsigned long long)h.runs2 + h.nruns2 > V.n_runs)) { bad[t] = "side_runs"; return; }
+            nj += ((h.pad[0] & 1u) ? h.nruns2 : h.nruns1) >= 2;
+            // the runs themselves: every run lies inside its read (the device reads the base of read index q at row * stride + q, or at len - 1 - q on the reverse strand), and a
+            // mate's runs ascend in the read and on the reference without overlapping, as the blocks of a CIGAR do (the tile pieces and lean records are cut on that)
+            for (int m = 0; m < 2; m++) {
+                const agx_u32 first = m ? h.runs2 : h.runs1, n = m ? h.nruns2 : h.nruns1;
+                for (agx_u32 j = 0; j < n; j++) {
+                    const agx_wrun &r = V.runs[first + j];
+                    if ((agx_u32)r.q + r.n > w.len) { bad[t] = "run_in_read"; return; }
+                    if (j + 1 < n) { const agx_wrun &x = V.runs[first + j + 1]; if ((agx_u32)r.q + r.n > x.q || (unsigned long long)r.t + r.n > x.t) { bad[t] = "run_order"; return; } }
+                }
+            }
+        }
+        jumps[t] = nj;
+    });
+    for (const char *b : bad) if (b) return b;      // (the first thread's hits come first)
+    { size_t want = 0; for (size_t v : jumps) want += v; if (want != V.n_jump) return "jump_count"; }      // pass J's list names exactly the hits whose left mate has several runs: as many, ...
+    for (size_t i = 0; i < V.n_jump; i++) {      // ... ascending, each one of them
+        const agx_u32 h = V.jump[i];
+        if (h >= V.nh) return "jump_entry";
+        if (i != 0 && !(V.jump[i - 1] < h)) return "jump_order";
+        const agx_whit &w = V.hits[h];
+        if ((w.flags & ((w.flags & AGX_WF_LEFT2) ? AGX_WF_RUNS2 : AGX_WF_RUNS1)) == 0) return "jump_hit";
+        const agx_hit x = agx_unpack_hit(w, V.sides);
+        if (((x.pad[0] & 1u) ? x.nruns2 : x.nruns1) < 2) return "jump_hit";
+    }
+    return V.n_pos ? staged_positions_rule(V, threads) : nullptr;
+}
+
+// The mate that is NOT the left one is never walked position by position: the device takes its reference offsets as they stand and loads the conti-mer head of each
+// (agx_arrival_fetch: cm_head[p0], n_pos + 1 entries; agx_for_candidates: cm_start[p0 + 1]).  The left mate's span is guarded where the hits are prepared
+// (agx_k_hit_prep: "read alignment beyond the end of the unit sequence"); nothing guards this one's, so every aligned base of it must lie inside the unit.
+const char *staged_positions_rule(const StagedView &V, unsigned threads) {
+    threads = std::max(1u, threads);
+    std::vector<const char *> bad(threads, nullptr);
+    on_threads(threads, [&](unsigned t) {
+        for (size_t i = V.nh * t / threads, hi = V.nh * (t + 1) / threads; i < hi; i++) {
+            const agx_whit &w = V.hits[i];
+            const bool b_is_1 = (w.flags & AGX_WF_LEFT2) != 0;      // the other mate is mate 1
+            if (!(w.flags & (b_is_1 ? AGX_WF_RUNS1 : AGX_WF_RUNS2))) { if ((unsigned long long)(b_is_1 ? w.a : w.b) + w.len > V.n_pos) { bad[t] = "mate_in_unit"; return; } continue; }
+            const agx_hit h = agx_unpack_hit(w, V.sides);
+            const agx_u32 first = b_is_1 ? h.runs1 : h.runs2, n = b_is_1 ? h.nruns1 : h.nruns2;
+            for (agx_u32 j = 0; j < n; j++) { const agx_wrun &r = V.runs[first + j]; if (r.n && (unsigned long long)r.t + r.n > V.n_pos) { bad[t] = "mate_in_unit"; return; } }
+        }
+    });
+    for (const char *b : bad) if (b) return b;
+    return nullptr;
+}
+
+// What a cache file holds besides the staged read alignments.  The device derives cm_start from the counts and writes every run element at cm[cm_start[x] + rank]
+// (agx_k_cm_fill): the counts must add up to the conti-mers, and every element's rank must lie below its position's count — or a file with intact lengths writes out of
+// bounds in HBM.
+const char *cache_content_rule(const CacheView &C, unsigned threads) {
+    threads = std::max(1u, threads);
+    unsigned long long el = 0;
+    for (size_t i = 0; i < C.n_segs; i++) {
+        const agx_cmseg &g = C.segs[i];
+        if ((unsigned long long)g.pos0 + g.len > C.n_pos) return "seg_span";
+        if (g.hop_end >= C.n_pos) return "seg_hop_end";
+        if ((unsigned long long)g.hop_str0 + g.hop_len0 > C.chain_str_len + 1) return "seg_hop_str";
+        if (g.elem0 != el) return "seg_elem0";
+        el += g.len;
+    }
+    if (el != C.n_cm) return "cm_total";
+    {
+        std::vector<unsigned long long> part(threads, 0); std::vector<int> bad(threads, 0);
+        on_threads(threads, [&](unsigned t) {
+            unsigned long long sum = 0;
+            for (size_t x = (size_t)C.n_pos * t / threads, hi = (size_t)C.n_pos * (t + 1) / threads; x < hi; x++) sum += C.cm_cnt[x];
+            part[t] = sum;
+            for (size_t i = C.n_segs * t / threads, hi = C.n_segs * (t + 1) / threads; i < hi; i++) { const agx_cmseg &g = C.segs[i]; if (g.rank > 254) { bad[t] = 1; return; }
+                for (agx_u32 j = 0; j < g.len; j++) if (C.cm_cnt[(size_t)g.pos0 + j] <= g.rank) { bad[t] = 1; return; } }
+        });
+        unsigned long long total = 0; for (unsigned t = 0; t < threads; t++) { total += part[t]; if (bad[t]) return "seg_rank"; }
+        if (total != C.n_cm) return "cm_sum";
+    }
+    for (size_t i = 0; i < C.n_chain_end; i++) if (C.chain_end[i] >= C.n_pos) return "chain_end";
+    if (C.rows_in_reads == 1) { const uint64_t *ro = (const uint64_t *)C.rows; for (size_t r = 0; r < C.n_rows; r++) if (!(ro[r] + C.maxlen <= C.reads_size && ro[r] < C.reads_size)) return "row_offset"; }      // (a row is read up to the longest read's length)
+    if (C.rows_in_reads == 0) { const agx_u32 *rs = (const agx_u32 *)C.rows; for (size_t r = 0; r < C.n_rows; r++) if (rs[r] >= C.n_slots) return "row_slot"; }
+    return nullptr;
 }
 
 void build_cm_layout(const agx_u8 *cm_cnt, size_t n_pos, const agx_cmseg *segs, size_t n_segs, CmLayout &L) {

@@ -43,7 +43,9 @@ struct SimGraph {
 // What a test may ask of the executor besides the graph: the lean record of every list entry (what pass 0 of the device's node sweep reads, made by the
 // same agx_lean_make_v from the same hits), and pass 0 on packed buckets (agx_bucket::packed: the device's layout, counters as 16-bit halves).
 // edges: which path of the edge build made each edge (SimEdges), with the slow list as the device makes it.
-struct SimOptions { bool packed = false, records = false, edges = false, front = false; };
+struct SimOptions { bool packed = false, records = false, edges = false, front = false;
+                    const agx_u8 *staged_left = nullptr; };      // not null: P.hits are STAGED hits (slot1 = the row of the left mate's bases, one row per slot of P.bases) and this is every hit's
+                                                                 // left mate as its record says it (tests/damaged_inputs_san.cpp); the span guard of agx_k_hit_prep then applies in full
 // front: what lies in front of the node sweep, whole — the expanded vote codes, the conti-mer keys and heads, the derived hit records in file order and the lean record of every
 // list entry with its slot and hit words (SimRecords::recs leaves those two out); the arrays the loaders own (T.ref, P.runs, T.cm_start) are copied by the caller
 struct SimFront { std::vector<agx_u8> vcodes; std::vector<agx_cmkey> cm; std::vector<agx_cmhead> cm_head; std::vector<agx_dhit> dhit; std::vector<agx_u32> tile_off; std::vector<agx_lrec> lrecs; };
@@ -71,8 +73,9 @@ void simulate(const Threads &T, const Pairs &P, agx_u32 k, int iv, int coverage,
     // hit_prep
     std::vector<agx_dhit> dh(P.hits.size());
     for (agx_u32 h = 0; h < P.hits.size(); h++)
-    {   const bool swap = agx_hit_left_is_mate2(P.hits[h], P.runs.data(), k);      // (the engine decides this when it stages the hits, and uploads only the a mates' bases)
-        if (agx_hit_prep(P.hits[h], agx_hit_dup(P.hits.data(), P.runs.data(), h), swap, P.hits[h].slot1 + (swap ? 1u : 0u), P.runs.data(), k, dh[h]) != 0) throw Error{E_ALIGNMENT, "BOWTIE ALIGNMENT ERROR"}; }
+    {   const bool swap = opt.staged_left ? opt.staged_left[h] != 0 : agx_hit_left_is_mate2(P.hits[h], P.runs.data(), k);      // (the engine decides this when it stages the hits, and uploads only the a mates' bases)
+        if (agx_hit_prep(P.hits[h], agx_hit_dup(P.hits.data(), P.runs.data(), h), swap, opt.staged_left ? P.hits[h].slot1 : P.hits[h].slot1 + (swap ? 1u : 0u), P.runs.data(), k, dh[h]) != 0) throw Error{E_ALIGNMENT, "BOWTIE ALIGNMENT ERROR"};
+        if (opt.staged_left && !(dh[h].flags & AGX_HF_SKIP) && dh[h].x_lo > dh[h].x_hi) throw Error{E_UNSUPPORTED, "read alignment beyond the end of the unit sequence"}; }
     // binning: (tile, hit) pairs in (tile, hit) order
     std::vector<std::vector<agx_u32> > lists(n_tiles);
     for (agx_u32 h = 0; h < dh.size(); h++) {
@@ -925,4 +928,134 @@ extern "C" int agx_hostsim_rowdiff_unit(const char *tmp_dir, int unit, int k, lo
         return 0;
     } catch (const Error &e) { say(e.msg); return 100 + e.code; }
     catch (const std::exception &e) { say(e.what()); return 99; }
+}
+
+// ---- damaged staged-pairs and cache files (tests/test_damaged_inputs.py, tests/damaged_inputs.py) -----------------------------------------------
+// The content rules of agx_host.h on the CPU.  A staged-pairs file is opened the way the engine opens it; a unit cache's arrays are made of the unit's text in memory
+// (the loaders, threading and staging are host code), handed to Python as plain pointers to damage one field of, and checked as load_cache checks a file's.
+extern "C" int agx_hostsim_rule_names(char *out, size_t out_len) {
+    size_t n = 0; const char *const *names = content_rule_names(&n); std::string all;
+    for (size_t i = 0; i < n; i++) { all += names[i]; all += '\n'; }
+    snprintf(out, out_len, "%s", all.c_str());
+    return all.size() < out_len ? (int)n : -1;
+}
+
+// 0: accepted; 1: the header is refused; 2: the content; `rule` = the rule's name.  n_pos: the unit's positions (0: not known, as where the engine first reads the file).
+// k, batch: the unit's (0: not compared).
+extern "C" int agx_hostsim_check_pairs_file(const char *path, unsigned long long n_pos, unsigned k, unsigned batch, int threads, char *rule, size_t rule_len) {
+    auto say = [&](const std::string &m) { if (rule && rule_len) snprintf(rule, rule_len, "%s", m.c_str()); };
+    say("");
+    try {
+        PairsFile F;
+        try { if (!open_pairs_file(path, F)) { say("no such file"); return -1; } }
+        catch (const Error &e) {
+            if (e.code != E_FORMAT) throw;
+            FileView fv(path); pairsfile::Header H;
+            if (fv.n < sizeof H) { say("short"); return 1; }
+            memcpy(&H, fv.p, sizeof H);
+            const char *r = pairs_header_rule(H, fv.n);
+            if (!r) { say("open_pairs_file refuses a header that pairs_header_rule accepts"); return -2; }
+            say(r); return 1;
+        }
+        using namespace pairsfile;
+        const Header &H = F.H;
+        if (k) if (const char *r = pairs_unit_rule(H, k, batch)) { say(r); return 1; }
+        StagedView V; V.hits = (const agx_whit *)F.sec(S_HITS); V.nh = H.nh; V.sides = (const agx_wside *)F.sec(S_SIDES); V.n_sides = H.n_sides; V.runs = (const agx_wrun *)F.sec(S_RUNS); V.n_runs = H.n_runs;
+        V.jump = (const agx_u32 *)F.sec(S_JUMP); V.n_jump = H.n_jump; V.other = (const unsigned long long *)F.sec(S_OTHER); V.n_other = H.n_other; V.n_rows = H.n_rows; V.stride = H.stride; V.maxlen = H.maxlen; V.n_pos = n_pos;
+        const char *r = staged_pairs_rule(V, (unsigned)threads);
+        if (!r) r = other_ascending_rule(V.other, V.n_other);
+        if (r) { say(r); return 2; }
+        return 0;
+    } catch (const Error &e) { say("unexpected: " + e.msg); return -99; }
+    catch (const std::exception &e) { say(std::string("unexpected: ") + e.what()); return -99; }
+}
+
+// the staged-pairs file of a unit's text (what tools/agx_synth.cpp --pairs-bin writes beside it), for units that exist as text only
+extern "C" int agx_hostsim_write_pairs_file(const char *tmp_dir, int unit, int k, long batch, int threads, const char *out_path, char *msg, size_t msg_len) {
+    try {
+        const std::string d = tmp_dir, s = std::to_string(unit);
+        VecSink A; Pairs P; StagedPairs S;
+        load_pairs_from_files(d + "/_reads.fa", d + "/_reads_genome." + s + ".bowtie", batch, (agx_u32)k, P, nullptr);
+        stage_pairs(P, (agx_u32)k, (unsigned)threads, A, S);
+        const std::vector<agx_u8> ob = other_bytes_of(P, S);
+        write_pairs_file(out_path, S, ob.data(), (agx_u32)k, (agx_u32)(batch <= 0 ? 1000000 : batch));
+        return 0;
+    } catch (const Error &e) { if (msg && msg_len) snprintf(msg, msg_len, "%s", e.msg.c_str()); return -1; }
+    catch (const std::exception &e) { if (msg && msg_len) snprintf(msg, msg_len, "%s", e.what()); return -1; }
+}
+
+extern "C" {
+typedef struct {
+    void *hits, *sides, *runs, *jump, *other, *segs, *cm_cnt, *chain_end, *rows, *header;
+    unsigned long long nh, n_sides, n_runs, n_jump, n_other, n_segs, n_pos, n_chain_end, n_rows, n_cm, chain_str_len, reads_size, file_size;
+    uint32_t stride, maxlen, n_slots, rows_in_reads, header_bytes, pad;
+} agx_sim_cache;
+}
+namespace {
+struct SimCache {
+    Threads T; Pairs P; StagedPairs S; VecSink sink; std::vector<agx_u32> chain_end; std::vector<agx_u32> jump; cachefile::Header H;
+    std::unique_ptr<ReadsIndex, void (*)(ReadsIndex *)> ri{nullptr, reads_index_close};
+};
+}
+// fast: the read alignments through the fast loader (rows_in_reads = 1: the rows are offsets into tmp/_reads.fa), else through the general one (0: read slots)
+extern "C" void *agx_hostsim_cache_arrays(const char *tmp_dir, int unit, int k, long batch, int threads, int fast, agx_sim_cache *out, char *msg, size_t msg_len) {
+    auto say = [&](const std::string &m) { if (msg && msg_len) snprintf(msg, msg_len, "%s", m.c_str()); };
+    say("");
+    try {
+        const std::string d = tmp_dir, s = std::to_string(unit);
+        std::unique_ptr<SimCache> c(new SimCache);
+        load_unit_reference(d + "/_genome." + s + ".fa", c->T.ref);
+        thread_contigs_from_files(d + "/_contigs.fa", d + "/_contigs_genome." + s + ".psl", c->T);
+        if (fast) {
+            c->ri.reset(reads_index_open(d + "/_reads.fa"));
+            if (!load_pairs_fast(*c->ri, d + "/_reads_genome." + s + ".bowtie", batch, (agx_u32)k, (unsigned)threads, c->sink, c->S)) { say("the fast loader declined"); return nullptr; }
+        } else {
+            load_pairs_from_files(d + "/_reads.fa", d + "/_reads_genome." + s + ".bowtie", batch, (agx_u32)k, c->P, nullptr);
+            stage_pairs(c->P, (agx_u32)k, (unsigned)threads, c->sink, c->S);
+        }
+        c->chain_end = c->T.chain_end_pos; std::sort(c->chain_end.begin(), c->chain_end.end()); c->chain_end.erase(std::unique(c->chain_end.begin(), c->chain_end.end()), c->chain_end.end());
+        c->chain_end.push_back(0);      // (one element of slack, as the engine's buffers have)
+        c->jump.assign(c->S.jump, c->S.jump + c->S.n_jump); c->jump.push_back(0);
+        const StagedPairs &S = c->S; const Threads &T = c->T;
+        agx_sim_cache &o = *out; memset(&o, 0, sizeof o);
+        o.hits = S.hits; o.sides = S.sides; o.runs = S.runs; o.jump = c->jump.data(); o.other = S.other; o.segs = c->T.segs.data(); o.cm_cnt = c->T.cm_cnt.data(); o.chain_end = c->chain_end.data();
+        o.rows = fast ? (void *)c->S.row_off.data() : (void *)c->S.row_slot.data();
+        o.nh = S.nh; o.n_sides = S.n_sides; o.n_runs = S.n_runs; o.n_jump = S.n_jump; o.n_other = S.n_other; o.n_segs = T.segs.size(); o.n_pos = T.ref.size(); o.n_chain_end = c->chain_end.size() - 1;
+        o.n_rows = S.n_rows; o.n_cm = T.n_cm; o.chain_str_len = T.chain_str.size(); o.reads_size = fast ? c->ri->fv.n : 0; o.stride = S.stride; o.maxlen = S.maxlen; o.n_slots = fast ? 0 : c->P.n_slots; o.rows_in_reads = fast ? 1u : 0u;
+        // the header save_cache would write for these arrays (stamps left zero: they are compared with the files, not judged)
+        using namespace cachefile;
+        Header &H = c->H; memset(&H, 0, sizeof H); memcpy(H.magic, MAGIC, 8); H.version = 2; H.batch = (agx_u32)(batch <= 0 ? 1000000 : batch);
+        H.n_pos = o.n_pos; H.n_ref = T.n_ref; H.nh = o.nh; H.n_runs = o.n_runs; H.n_cm = o.n_cm; H.n_segs = o.n_segs; H.n_seg0 = T.n_seg0; H.n_rows = o.n_rows; H.n_chain_end = o.n_chain_end; H.n_codes = S.n_codes;
+        H.pairs_in_file = S.n_pairs_in_file; H.sam_pairs = S.n_sam_pairs; H.stride = S.stride; H.maxlen = S.maxlen; H.n_slots = o.n_slots; H.k = (agx_u32)k; H.rows_in_reads = o.rows_in_reads;
+        H.slot_stride = fast ? S.stride : c->P.stride; H.n_sides = o.n_sides; H.n_jump = o.n_jump;
+        H.sizes[0] = sizeof(agx_whit); H.sizes[1] = sizeof(agx_wrun); H.sizes[2] = sizeof(agx_cmseg); H.sizes[3] = sizeof(Header); H.sizes[4] = sizeof(agx_wside);
+        const unsigned long long len[S_N] = {o.nh * sizeof(agx_whit), o.n_runs * sizeof(agx_wrun), S.n_codes, o.n_segs * sizeof(agx_cmseg), o.n_chain_end * 4, o.n_rows * (fast ? 8 : 4), o.n_pos, o.n_pos, o.chain_str_len,
+                                             T.initial_contigs.size(), fast ? 0ull : (unsigned long long)o.n_slots * c->P.stride, o.n_other * 8, o.n_sides * sizeof(agx_wside), o.n_jump * 4, 0ull};
+        unsigned long long at = (sizeof(Header) + 4095) & ~4095ull;
+        for (int i = 0; i < S_N; i++) { H.off[i] = at; H.len[i] = len[i]; at = (at + len[i] + 4095) & ~4095ull; }
+        o.file_size = at; o.header = &c->H; o.header_bytes = (uint32_t)sizeof(Header);
+        return c.release();
+    } catch (const Error &e) { say(e.msg); return nullptr; }
+    catch (const std::exception &e) { say(e.what()); return nullptr; }
+}
+extern "C" void agx_hostsim_cache_free(void *handle) { delete (SimCache *)handle; }
+// the content of a cache as load_cache judges it, with the counts c holds now; 0: accepted, 2: refused (`rule`)
+extern "C" int agx_hostsim_cache_check(const agx_sim_cache *c, int threads, char *rule, size_t rule_len) {
+    auto say = [&](const std::string &m) { if (rule && rule_len) snprintf(rule, rule_len, "%s", m.c_str()); };
+    say("");
+    StagedView V; V.hits = (const agx_whit *)c->hits; V.nh = c->nh; V.sides = (const agx_wside *)c->sides; V.n_sides = c->n_sides; V.runs = (const agx_wrun *)c->runs; V.n_runs = c->n_runs;
+    V.jump = (const agx_u32 *)c->jump; V.n_jump = c->n_jump; V.other = (const unsigned long long *)c->other; V.n_other = c->n_other; V.n_rows = c->n_rows; V.stride = c->stride; V.maxlen = c->maxlen; V.n_pos = c->n_pos;
+    CacheView C; C.segs = (const agx_cmseg *)c->segs; C.n_segs = c->n_segs; C.cm_cnt = (const agx_u8 *)c->cm_cnt; C.chain_end = (const agx_u32 *)c->chain_end; C.n_chain_end = c->n_chain_end; C.rows = c->rows;
+    C.n_pos = c->n_pos; C.n_cm = c->n_cm; C.n_rows = c->n_rows; C.chain_str_len = c->chain_str_len; C.reads_size = c->reads_size; C.maxlen = c->maxlen; C.n_slots = c->n_slots; C.rows_in_reads = c->rows_in_reads;
+    const char *r = staged_pairs_rule(V, (unsigned)threads);
+    if (!r) r = cache_content_rule(C, (unsigned)threads);
+    if (!r && c->rows_in_reads == 2) r = other_ascending_rule(V.other, V.n_other);
+    if (r) { say(r); return 2; }
+    return 0;
+}
+extern "C" int agx_hostsim_cache_header_check(const void *header, unsigned long long file_size, unsigned batch, unsigned k, char *rule, size_t rule_len) {
+    cachefile::Header H; memcpy(&H, header, sizeof H);
+    const char *r = cache_header_rule(H, file_size, batch, k);
+    if (rule && rule_len) snprintf(rule, rule_len, "%s", r ? r : "");
+    return r ? 1 : 0;
 }
