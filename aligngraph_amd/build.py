@@ -10,7 +10,7 @@ CLI = os.path.join(HERE, "AlignGraph_amd")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HOST_SRC = ["agx_engine.cpp", "agx_export.cpp", "agx_host.cpp", "agx_walk.cpp", "agx_load.cpp", "agx_gfa.cpp"]
 DEV_SRC = ["agx_kernels.hip", "agx_unitig.hip", "agx_evidence.hip", "agx_span.hip", "agx_links.hip", "agx_bubbles.hip"]
-HEADERS = ["agx_core.h", "agx_host.h", "agx_parse.h", "agx_mem.h", "agx_kargs.h", "agx_unit.h", os.path.join("..", "..", "include", "agx.h")]
+HEADERS = ["agx_core.h", "agx_host.h", "agx_forms.h", "agx_parse.h", "agx_mem.h", "agx_kargs.h", "agx_unit.h", os.path.join("..", "..", "include", "agx.h")]
 
 
 def _stale(out, deps):

@@ -789,7 +789,7 @@ AGX_HD agx_u32 agx_whit_side(const agx_whit &w) { const agx_u32 a = w.a, b = w.b
 AGX_HD agx_u32 agx_wside_left_first(const agx_whit &w, const agx_wside &sd) { const agx_u32 r1 = sd.runs1, r2 = sd.runs2, f = w.flags; return (f & AGX_WF_LEFT2) ? r2 : r1; }
 AGX_HD agx_u32 agx_wside_left_count(const agx_whit &w, const agx_wside &sd) { const agx_u32 n = sd.nruns, f = w.flags; return (f & AGX_WF_LEFT2) ? n >> 16 : n & 0xFFFFu; }
 // ---- hits in tile order (r05) ----------------------------------------------------------------------------------------------------------
-// The build walks a unit's hits in the order of the tile their first arrival falls in (the staging makes the permutation: stage_order in agx_engine.cpp): neighbouring
+// The build walks a unit's hits in the order of the tile their first arrival falls in (the staging makes the permutation: stage_order in agx_engine.cpp; gather_tiled in agx_forms.h applies it): neighbouring
 // lanes of agx_k_hit_prep then want the same tiles' counters, and a tile's list is a filter over a WINDOW of that order (agx_k_tile_fill) instead of a scatter of
 // 4-byte slot words all over HBM (r04: 893 MB written per 30 Mb unit where 250 were needed).  The key: the position of the left mate's first aligned base —
 // what agx_hit_prep calls x_lo for every hit it keeps (a hit it drops has no arrivals: where it stands in the order does not matter).

@@ -184,18 +184,18 @@ agx_cut_args stream_cuts(agx_u32 n_pos) {
 // upload that finds nothing staged).  The read bases cross PCIe as 2-bit classes plus a list of the few bases that are not A, C, G or T
 // (agx_pack_classes2): a quarter of the bytes of the largest array.  The read alignments are staged by stage_pairs() (agx_load.cpp) —
 // or were written into the staged buffers by the fast loader while it parsed (u->pairs_staged).
+// The arithmetic of every form is agx_forms.h, over plain arrays; what is here is the choice (u->choice, read once per entry: agx_unit.h), memory policy and the counts.
 // The file-order wire records and read rows of a unit that will upload their tile-ordered forms (stage_tiled) are only ever read by the host — the gather into those forms, the
 // cache file — so they live in ordinary memory: pinning a second copy of a unit's two largest arrays cost its load 0.2 ms per MB.  r05's forms (AGX_NO_TILED_UPLOAD) are uploaded
 // from them and keep them pinned.
-inline bool want_tiled() { return !getenv("AGX_NO_TILED_UPLOAD"); }
-template <class B> inline void alloc_file_order(B &buf, size_t count) { if (want_tiled()) buf.alloc_plain(count); else buf.alloc(count); }
+template <class B> inline void alloc_file_order(const agx_unit *u, B &buf, size_t count) { if (u->choice.tiled) buf.alloc_plain(count); else buf.alloc(count); }
 // One of the six arrays of a unit's staged read alignments, for `bytes` of content: an element of slack each; the packed rows are asked for with their 16 bytes of slack.
 void *alloc_pair_array(agx_unit *u, int which, size_t bytes) {
     switch (which) {
-    case SA_HITS:  alloc_file_order(u->s_hits, bytes / sizeof(agx_whit) + 1); return u->s_hits.p;
+    case SA_HITS:  alloc_file_order(u, u->s_hits, bytes / sizeof(agx_whit) + 1); return u->s_hits.p;
     case SA_SIDES: u->s_sides.alloc(bytes / sizeof(agx_wside) + 1); return u->s_sides.p;
     case SA_RUNS:  u->s_runs.alloc(bytes / sizeof(agx_wrun) + 1); return u->s_runs.p;
-    case SA_CODES: alloc_file_order(u->s_codes, bytes); return u->s_codes.p;
+    case SA_CODES: alloc_file_order(u, u->s_codes, bytes); return u->s_codes.p;
     case SA_JUMP:  u->s_jump.alloc(bytes / 4 + 1); return u->s_jump.p;
     default:       u->s_other.alloc(bytes / 8 + 1); return u->s_other.p;
     }
@@ -227,7 +227,7 @@ void stage_cm_layout(agx_unit *u, const agx_u8 *cm_cnt, size_t n_pos, const agx_
 void stage_reference(agx_unit *u, const char *ref, size_t n_pos, unsigned threads) {
     std::vector<agx_refx> others;
     u->s_ref.alloc((n_pos + 3) / 4 + 32);
-    u->ref_packed = getenv("AGX_REF_RAW") == nullptr && pack_reference(ref, n_pos, std::min(threads, 8u), u->s_ref.p, others);
+    u->ref_packed = !u->choice.ref_raw && pack_reference(ref, n_pos, std::min(threads, 8u), u->s_ref.p, others);
     if (u->ref_packed) { u->n_refx = others.size(); u->s_refx.alloc(u->n_refx + 1); if (u->n_refx) memcpy(u->s_refx.p, others.data(), u->n_refx * sizeof(agx_refx)); return; }
     u->n_refx = 0; u->s_ref.alloc(n_pos + 16);
     const unsigned T = std::max(1u, std::min(threads, 8u));
@@ -289,23 +289,21 @@ void adopt_row_diffs(agx_unit *u, const RowDiffs &D, unsigned threads) {
     memcpy(u->s_rowcnt.p, D.cnt.data(), u->n_rowcnt); memcpy(u->s_blockoff.p, D.block_off.data(), u->n_blockoff * 4); memcpy(u->s_blockfirst.p, D.block_first.data(), u->n_blockfirst * 4); memcpy(u->s_anchor.p, D.anchor_bits.data(), u->n_anchor * 4);
     u->rows_diffed = true;
 }
+void clear_row_diffs(agx_unit *u) { u->rows_diffed = false; u->n_units = u->n_rowcnt = u->n_blockoff = u->n_blockfirst = u->n_anchor = u->n_rows_explicit = 0; }
 // The read rows for the upload as differences against the reference (agx_core.h; build_row_diffs in agx_load.cpp): AGX_ROW_DIFF=1 asks for it.  It is NOT the default:
 // it takes 36-44 % off a unit's upload (66 -> 36 bytes per pair at 2x150) but no measured job is bound by its uploads — cfg3 36.4 against 36.5 ms, the 24-unit human
 // shapes 50.0 against 49.4 ms (1/16) and 187 against 183 ms (1/4) per job — while making the form costs the loader 30-60 ns per row (T_unit + 0.1 s at cfg3).  For hosts
 // whose ranks share a link or memory bandwidth.  Needs the packed reference.  The 2-bit rows stay where they are either way: the walk of a unit handed over staged reads
-// k-mer tails out of them, and a one-shot unit's download lands in their memory.
+// k-mer tails out of them, and a one-shot unit's download lands in their memory.  This one: over the file-order rows (the tile-ordered forms have their own: stage_rows_tiled).
 void stage_rows(agx_unit *u, unsigned threads) {
-    u->rows_diffed = false; u->n_units = u->n_rowcnt = u->n_blockoff = u->n_blockfirst = u->n_anchor = u->n_rows_explicit = 0;
-    const char *on = getenv("AGX_ROW_DIFF");
-    if (want_tiled()) return;      // (r06: the tile-ordered forms have their own: stage_rows_tiled)
-    if (!on || atoi(on) == 0 || !u->ref_packed || u->n_rows == 0 || u->nh == 0) return;
+    if (!u->ref_packed || u->n_rows == 0 || u->nh == 0) return;
     const double t0 = now_ms();
     RowDiffs D;
     if (!build_row_diffs(u->s_hits.p, u->nh, u->s_sides.p, u->n_sides, u->s_runs.p, u->n_runs, u->s_codes.p, u->n_rows, u->stride, (const agx_u32 *)u->s_ref.p, u->V.n_pos ? u->V.n_pos : u->T.ref.size(), threads, D)) return;
-    if (D.n_units * 2 + D.cnt.size() + (D.block_off.size() + D.block_first.size() + D.anchor_bits.size()) * 4 >= u->n_codes) return;      // nothing gained (reads that do not resemble the reference)
+    if (!row_diffs_gain(D, u->n_codes)) return;
     adopt_row_diffs(u, D, threads);
     if (getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] read rows against the reference: %.1f ms, %zu rows (%zu as they are), %.1f -> %.1f bytes per row\n", now_ms() - t0, (size_t)u->n_rows, u->n_rows_explicit,
-                                          (double)u->n_codes / u->n_rows, (double)(u->n_units * 2 + u->n_rowcnt + (u->n_blockoff + u->n_blockfirst + u->n_anchor) * 4) / u->n_rows);
+                                          (double)u->n_codes / u->n_rows, (double)row_diffs_bytes(D) / u->n_rows);
 }
 // The hits in the order of the tile their first arrival falls in (agx_core.h "hits in tile order"; order_hits in agx_load.cpp): 4 bytes per hit + 4 per tile more to upload.
 void stage_order(agx_unit *u, unsigned threads) {
@@ -316,158 +314,80 @@ void stage_order(agx_unit *u, unsigned threads) {
     order_hits(u->s_hits.p, u->nh, u->s_sides.p, u->s_runs.p, u->s_jump.p, u->n_jump, n_pos, threads, u->s_perm.p, u->s_tfirst.p, u->s_jump_at.p);
     if (getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] hits in tile order: %.1f ms (%zu hits, %zu tiles, window of %u tiles)\n", now_ms() - t0, u->nh, n_tiles, u->lookback);
 }
-// The hit and side records of the upload in their compact wire forms (agx_core.h "compact wire forms"): 16 -> about 9.5 bytes per hit and 12 -> 2 per side cross PCIe, in
-// front of everything else a unit sends, and the device makes d_whits / d_wsides of them at the head of the unit's first build (agx_k_expand_hits, agx_k_side_*).
-// AGX_WIRE_PLAIN=1: the records as they are (A/B, tests).
-inline bool want_compact() { const char *e = getenv("AGX_WIRE_PLAIN"); return !(e && atoi(e) != 0); }
-// The hits, a block at a time as its 64 records stand in the upload's order `hits` (tile order: stage_tiled writes them in its loop and hands each block over while it
-// is in the cache; r05's file order: stage_wire_hits).  Thread t of T packs the blocks [first(t), first(t + 1)); its escapes and extra words collect in lists of its own and
-// the headers hold places in those until finish() has put the lists behind one another.  Everything lands in ONE pinned buffer of the size the records would have taken
-// (s_wire: blocks, escapes, extra words — they are used only where they are fewer bytes): a unit pins what it pinned, and a one-shot unit's download finds the room it found.
-struct HitPacker {
-    agx_unit *u; unsigned T; size_t n_blocks; bool on; std::vector<std::vector<agx_whit>> esc; std::vector<std::vector<agx_u32>> ext;
-    HitPacker(agx_unit *unit, unsigned threads) : u(unit), T(threads), n_blocks((unit->nh + AGX_CH_BLOCK - 1) / AGX_CH_BLOCK), esc(threads), ext(threads) {
-        on = want_compact() && n_blocks * sizeof(agx_chit_block) < u->nh * sizeof(agx_whit);      // (a few dozen hits: the last block's empty slots outweigh the rest)
-        if (on) { u->s_wire.alloc((u->nh + 1) * sizeof(agx_whit)); for (unsigned t = 0; t < T; t++) { esc[t].reserve(u->nh / T / 8 + 64); ext[t].reserve(u->nh / T / 2 + 64); } }
-    }
-    agx_chit_block *blocks() const { return (agx_chit_block *)u->s_wire.p; }
-    size_t first(unsigned t) const { return n_blocks * t / T; }
-    void block(unsigned t, size_t b, const agx_whit *hits) {
-        const size_t lo = b * AGX_CH_BLOCK; const agx_u32 n = (agx_u32)std::min<size_t>(AGX_CH_BLOCK, u->nh - lo);
-        agx_whit e[AGX_CH_BLOCK]; agx_u32 x[AGX_CH_BLOCK], ne = 0, nx = 0;
-        agx_chit_block &B = blocks()[b];
-        agx_chit_pack_block(hits + lo, n, u->maxlen, B, e, ne, x, nx);
-        B.esc = (agx_u32)esc[t].size(); B.ext = (agx_u32)ext[t].size();
-        esc[t].insert(esc[t].end(), e, e + ne); ext[t].insert(ext[t].end(), x, x + nx);
-    }
-    bool finish(double t0) {      // false: the blocks would be no fewer bytes than the records (hits all over the unit: file order) — the unit sends its records
-        if (!on) return false;
-        size_t ne = 0, nx = 0;
-        for (unsigned t = 0; t < T; t++) { for (size_t b = first(t); b < first(t + 1); b++) { blocks()[b].esc += (agx_u32)ne; blocks()[b].ext += (agx_u32)nx; } ne += esc[t].size(); nx += ext[t].size(); }
-        const size_t bytes = n_blocks * sizeof(agx_chit_block) + ne * sizeof(agx_whit) + nx * 4;
-        const bool gain = bytes < u->nh * sizeof(agx_whit);
-        if (getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] compact hit records (with the forms they are made beside): %.1f ms, 16 -> %.2f bytes per hit, %.2f %% escaped, %.2f %% with an extra word%s\n", now_ms() - t0,
-                                              (double)bytes / u->nh, 100.0 * ne / u->nh, 100.0 * nx / u->nh, gain ? "" : ": not used");
-        if (!gain) return false;
-        agx_whit *e_at = (agx_whit *)(u->s_wire.p + n_blocks * sizeof(agx_chit_block)); agx_u32 *x_at = (agx_u32 *)(e_at + ne);      // (a block is a multiple of 16 bytes)
-        u->wire_esc = e_at; u->wire_ext = x_at;
-        for (unsigned t = 0; t < T; t++) {
-            if (!esc[t].empty()) memcpy(e_at, esc[t].data(), esc[t].size() * sizeof(agx_whit));
-            if (!ext[t].empty()) memcpy(x_at, ext[t].data(), ext[t].size() * 4);
-            e_at += esc[t].size(); x_at += ext[t].size();
-        }
-        u->n_cblocks = n_blocks; u->n_cesc = ne; u->n_cext = nx;
-        return true;
-    }
-};
+// The staged read alignments in u->s_* as the content rules (agx_host.h: staged_pairs_rule, on what was read from a cache file or a staged-pairs file) and the tile-ordered
+// gather look at them.
+agx::StagedView staged_view(const agx_unit *u, unsigned long long n_rows, agx_u32 stride, agx_u32 maxlen, unsigned long long n_pos) {
+    agx::StagedView V; V.hits = u->s_hits.p; V.nh = u->nh; V.sides = u->s_sides.p; V.n_sides = u->n_sides; V.runs = u->s_runs.p; V.n_runs = u->n_runs; V.jump = u->s_jump.p; V.n_jump = u->n_jump;
+    V.other = u->s_other.p; V.n_other = u->n_other; V.n_rows = n_rows; V.stride = stride; V.maxlen = maxlen; V.n_pos = n_pos;
+    return V;
+}
+// The hit and side records of the upload in their compact wire forms (agx_forms.h: HitPacker, plan_sides / fill_sides).  The blocks, escapes and extra words of the hits land in
+// ONE pinned buffer of the size the records would have taken (s_wire): a unit pins what it pinned, and a one-shot unit's download finds the room it found.
 void release_wire_hits(agx_unit *u) { u->hits_compact = false; u->n_cblocks = u->n_cesc = u->n_cext = 0; u->wire_esc = nullptr; u->wire_ext = nullptr; u->s_wire.release(); }
-// a unit that uploads r05's file-order forms: the same blocks over s_hits
+// what the packer made, noted in the unit; false: nothing gained (or the packer is off) — the unit sends its records
+bool adopt_wire_hits(agx_unit *u, const HitPacker &P, const HitWire &W, double t0) {
+    if (P.on && getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] compact hit records (with the forms they are made beside): %.1f ms, 16 -> %.2f bytes per hit, %.2f %% escaped, %.2f %% with an extra word%s\n", now_ms() - t0,
+                                                  (double)W.bytes / u->nh, 100.0 * W.n_esc / u->nh, 100.0 * W.n_ext / u->nh, W.gain ? "" : ": not used");
+    if (!W.gain) return false;
+    u->wire_esc = W.esc; u->wire_ext = W.ext; u->n_cblocks = W.n_blocks; u->n_cesc = W.n_esc; u->n_cext = W.n_ext;
+    return true;
+}
+// a unit that uploads r05's file-order forms: the blocks over s_hits
 void stage_wire_hits(agx_unit *u, unsigned threads) {
     release_wire_hits(u);
     if (u->nh == 0) return;
     const double t0 = now_ms();
-    const unsigned T = std::max(1u, std::min(threads, 16u));
-    HitPacker P(u, T);
-    if (P.on) on_threads(T, [&](unsigned t) { for (size_t b = P.first(t); b < P.first(t + 1); b++) P.block(t, b, u->s_hits.p); });
-    u->hits_compact = P.finish(t0);
+    HitPacker P(u->nh, u->maxlen, std::max(1u, std::min(threads, 16u)), u->choice.compact);
+    if (P.on) { u->s_wire.alloc((u->nh + 1) * sizeof(agx_whit)); P.into(u->s_wire.p); P.pack_blocks(u->s_hits.p); }
+    u->hits_compact = adopt_wire_hits(u, P, P.finish(), t0);
     if (!u->hits_compact) u->s_wire.release();
 }
-// The sides as their counts, the listed sides behind them in one pinned buffer.  The run pool lies in side order (both loaders write a hit's runs where the last hit's end) or
-// the unit sends the records themselves.
 void stage_wire_sides(agx_unit *u) {
     u->sides_compact = false; u->n_csesc = 0; u->side_first = 0; u->wire_listed = nullptr;
     const size_t n = u->n_sides;
     const double t0 = now_ms();
-    bool fine = want_compact() && n != 0;
+    bool fine = u->choice.compact && n != 0;
     if (fine) {
-        const agx_wside *sd = u->s_sides.p; size_t listed = 0;
-        u->side_first = agx_cside_first(sd, n); unsigned long long at = u->side_first;
-        for (size_t i = 0; i < n && fine; i++) { fine = agx_cside_in_order(sd[i], at); listed += agx_cside_pack(sd[i].nruns) == AGX_CS_ESC; }      // (agx_sides_consecutive)
-        const size_t counts_bytes = (n * 2 + 7) & ~(size_t)7, bytes = n * 2 + listed * sizeof(agx_cside_esc);
-        if (fine && bytes >= n * sizeof(agx_wside)) fine = false;
+        const SidePlan P = plan_sides(u->s_sides.p, n);
+        u->side_first = P.first; fine = P.fine;
         if (fine) {
-            u->s_csides.alloc(counts_bytes + (listed + 1) * sizeof(agx_cside_esc));
-            agx_u16 *c = (agx_u16 *)u->s_csides.p; agx_cside_esc *l = (agx_cside_esc *)(u->s_csides.p + counts_bytes);
-            u->wire_listed = l; u->n_csesc = listed;
-            for (size_t i = 0; i < n; i++) { const agx_u32 v = agx_cside_pack(sd[i].nruns); c[i] = (agx_u16)v; if (v == AGX_CS_ESC) *l++ = agx_cside_esc{(agx_u32)i, sd[i].nruns}; }
+            u->s_csides.alloc(P.counts_bytes + (P.listed + 1) * sizeof(agx_cside_esc));
+            agx_cside_esc *l = (agx_cside_esc *)(u->s_csides.p + P.counts_bytes);
+            u->wire_listed = l; u->n_csesc = P.listed;
+            fill_sides(u->s_sides.p, n, (agx_u16 *)u->s_csides.p, l);
         }
-        if (getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] compact side records: %.1f ms, 12 -> %.2f bytes per side, %.2f %% listed%s\n", now_ms() - t0, (double)bytes / n,
-                                              100.0 * listed / n, fine ? "" : ": not used (the run pool is not in side order, or nothing gained)");
+        if (getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] compact side records: %.1f ms, 12 -> %.2f bytes per side, %.2f %% listed%s\n", now_ms() - t0, (double)P.bytes / n,
+                                              100.0 * P.listed / n, fine ? "" : ": not used (the run pool is not in side order, or nothing gained)");
     }
     if (!fine) { u->s_csides.release(); return; }
     u->sides_compact = true;
 }
 
-// r06: what the device is sent of the read alignments, in the order of the hits' first tiles (stage_order's permutation applied on the host).
-//   * the wire records: s_hits_t[i] = hit perm[i], its `row` field carrying the hit's NUMBER (the key the tile lists are ranked by) — the 4 bytes per hit of the permutation no
-//     longer cross PCIe, the device reads the records in order instead of gathering them — and AGX_WF_DUP what the rule of AG:1650-1655 says about it (it needs the hit's FILE
-//     neighbours, which are not its neighbours here);
-//   * the read rows: row i = the left-mate row of the i-th hit (a pair with a second hit sends its row twice: 5 % of the rows), so the rows that a WINDOW of tiles reads are one
-//     contiguous piece of the upload, in front of which lie the rows of every earlier tile: the unit's first build sweeps window w when its piece has landed, beside the
-//     upload of the pieces behind it (do_upload / do_build) — chr1 of configs[4]: 22 ms of node sweep that used to wait for the last read row;
-//   * the list of the bases that are not A, C, G, T, re-indexed to those rows.
-// The k-mer string references of the nodes then name places in the tile order: slot_row maps them back for the walk (UnitView::slot_row).
-// Not when the rows cross as differences from the reference (their codec numbers the rows by their anchors' file order): AGX_ROW_DIFF units keep r05's forms.
+// r06: what the device is sent of the read alignments, in the order of the hits' first tiles (stage_order's permutation applied on the host; agx_forms.h: gather_tiled, with
+// the hits packed inside the gather), and the windows the unit's first build sweeps as their rows land (do_upload / do_build).
+void release_tiled(agx_unit *u) { u->tiled = false; u->n_other_t = 0; u->slot_row.clear(); u->n_win = 1; u->s_hits_t.release(); u->s_codes_t.release(); u->s_other_t.release(); }
 void stage_tiled(agx_unit *u, unsigned threads) {
-    u->tiled = false; u->n_other_t = 0; u->slot_row.clear(); u->n_win = 1;
     const size_t nh = u->nh, s4 = u->stride / 4;
-    // (rows that were to cross as differences and do not — nothing gained — cross tile-ordered)
-    if (u->rows_diffed || getenv("AGX_NO_TILED_UPLOAD") || nh == 0 || u->n_rows == 0) { u->s_hits_t.release(); u->s_codes_t.release(); u->s_other_t.release(); return; }
     const double t0 = now_ms();
     // (records that cross in their compact blocks are only ever read by the host: ordinary memory)
-    const bool compact = want_compact();
-    if (compact) u->s_hits_t.alloc_plain(nh + 1); else u->s_hits_t.alloc(nh + 1);
+    if (u->choice.compact) u->s_hits_t.alloc_plain(nh + 1); else u->s_hits_t.alloc(nh + 1);
     u->s_codes_t.alloc(nh * s4 + 16); u->slot_row.resize(nh);
-    const agx_whit *wh = u->s_hits.p; const agx_wside *sd = u->s_sides.p; const agx_wrun *wr = u->s_runs.p; const agx_u32 *perm = u->s_perm.p;
-    // rows that carry a listed base (few): one bit per row
-    const size_t n_rows = u->n_rows; std::vector<agx_u8> has_other((n_rows + 7) / 8, 0);
-    for (size_t j = 0; j < u->n_other; j++) { const size_t r = (size_t)(u->s_other.p[j] / u->stride); if (r < n_rows) has_other[r >> 3] |= (agx_u8)(1u << (r & 7)); }
-    auto idx0 = [&](const agx_whit &w) -> agx_u32 {      // positionSets[hit][0] of mate1 (agx_idx0_pos on the wire forms)
-        if (!(w.flags & AGX_WF_RUNS1)) return w.a;
-        const agx_wside &g = sd[w.a]; const agx_wrun &r = wr[g.runs1];
-        return r.q == 0 ? r.t : AGX_NONE;
-    };
     const unsigned T = std::max(1u, std::min(threads, 16u));
-    std::vector<std::vector<unsigned long long>> others(T);
     release_wire_hits(u);
-    HitPacker packer(u, T);
-    const size_t n_blocks = (nh + AGX_CH_BLOCK - 1) / AGX_CH_BLOCK;      // (a thread takes whole blocks of 64 hits)
-    on_threads(T, [&](unsigned t) {
-        // (two dependent random reads per hit — its record, then its row: asked for a few hits ahead, or every hit costs two cache misses in a row: 0.16 s of cfg3's load)
-        const size_t AHEAD = 48, NEAR = 24;
-        for (size_t i = (n_blocks * t / T) * AGX_CH_BLOCK, hi = std::min<size_t>(nh, (n_blocks * (t + 1) / T) * AGX_CH_BLOCK); i < hi; i++) {
-            if (i + AHEAD < hi) __builtin_prefetch(wh + perm[i + AHEAD]);
-            if (i + NEAR < hi) { const char *c = (const char *)(u->s_codes.p + (size_t)wh[perm[i + NEAR]].row * s4); __builtin_prefetch(c); if (s4 > 40) __builtin_prefetch(c + 64); }
-            const agx_u32 h = perm[i]; agx_whit w = wh[h];
-            const agx_u32 row = w.row;
-            u->slot_row[i] = row;
-            memcpy(u->s_codes_t.p + i * s4, u->s_codes.p + (size_t)row * s4, s4);
-            bool dup = false;
-            if (w.back) { const agx_u32 me = idx0(w); for (agx_u32 e = 1; e <= w.back && !dup; e++) dup = agx_absdiff(me, idx0(wh[h - e])) < (int)w.len; }      // agx_hit_dup_by
-            w.row = h; if (dup) w.flags |= (agx_u8)AGX_WF_DUP;
-            u->s_hits_t.p[i] = w;
-            if (packer.on && ((i & (AGX_CH_BLOCK - 1)) == AGX_CH_BLOCK - 1 || i + 1 == nh)) packer.block(t, i / AGX_CH_BLOCK, u->s_hits_t.p);
-            if (has_other[row >> 3] & (1u << (row & 7))) {
-                const unsigned long long lo = (unsigned long long)row * u->stride, *b = u->s_other.p, *e = b + u->n_other;
-                for (const unsigned long long *at = std::lower_bound(b, e, lo); at != e && *at < lo + u->stride; ++at) others[t].push_back((unsigned long long)i * u->stride + (*at - lo));
-            }
-        }
-    });
-    size_t no = 0; for (auto &v : others) no += v.size();
+    HitPacker packer(nh, u->maxlen, T, u->choice.compact);
+    if (packer.on) { u->s_wire.alloc((nh + 1) * sizeof(agx_whit)); packer.into(u->s_wire.p); }
+    const size_t n_pos = u->V.n_pos ? u->V.n_pos : u->T.ref.size(), n_tiles = (n_pos + AGX_TILE - 1) / AGX_TILE;
+    const std::vector<unsigned long long> others = gather_tiled(staged_view(u, u->n_rows, u->stride, u->maxlen, n_pos), u->s_codes.p, u->s_perm.p, T, packer, u->s_hits_t.p, u->s_codes_t.p, u->slot_row.data());
+    const size_t no = others.size();
     u->s_other_t.alloc(no + 1); u->n_other_t = no;
-    { size_t at = 0; for (auto &v : others) { if (!v.empty()) memcpy(u->s_other_t.p + at, v.data(), v.size() * 8); at += v.size(); } }
+    if (no) memcpy(u->s_other_t.p, others.data(), no * 8);
     u->tiled = true;
-    u->hits_compact = packer.finish(t0);
-    if (compact && !u->hits_compact) {      // nothing gained: the records into the pinned buffer that the blocks would have filled
+    u->hits_compact = adopt_wire_hits(u, packer, packer.finish(), t0);
+    if (u->choice.compact && !u->hits_compact) {      // nothing gained: the records into the pinned buffer that the blocks would have filled
         u->s_wire.alloc((nh + 1) * sizeof(agx_whit));
         on_threads(T, [&](unsigned t) { const size_t lo = nh * t / T, hi = nh * (t + 1) / T; if (hi > lo) memcpy(u->s_wire.p + lo * sizeof(agx_whit), u->s_hits_t.p + lo, (hi - lo) * sizeof(agx_whit)); });
     }
-    // windows of the first build's sweep: about 8 M positions each, eight at most (AGX_UPLOAD_WINDOWS forces a number: tests), cut at tiles
-    const size_t n_pos = u->V.n_pos ? u->V.n_pos : u->T.ref.size(), n_tiles = (n_pos + AGX_TILE - 1) / AGX_TILE;
-    size_t W = getenv("AGX_UPLOAD_WINDOWS") ? (size_t)atoi(getenv("AGX_UPLOAD_WINDOWS")) : n_pos / 8000000u;
-    W = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(W, 8), n_tiles));
-    u->n_win = (agx_u32)W;
-    for (size_t w = 0; w <= W; w++) u->win_tile[w] = (agx_u32)(n_tiles * w / W);
+    u->n_win = window_cuts(n_pos, n_tiles, u->choice.windows, u->win_tile);
     if (getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] tile-ordered upload forms: %.1f ms (%zu hits, %zu listed bases, %u windows)\n", now_ms() - t0, nh, no, u->n_win);
 }
 
@@ -480,35 +400,42 @@ void stage_tiled(agx_unit *u, unsigned threads) {
 // cfg3).  Since the windows, a unit's kernels run beside its upload and the two are about as long: with a third of the bytes gone the kernels bind, and they are the longer for
 // it — chr1 in the emulated rank is built at 66.9 ms instead of 61.9, the rank done at 132.6 instead of 128.7 ms; cfg3's builds end 0.6 ms later each.  It stays what it was
 // in r04/r05: an option for hosts whose link is scarcer than this one's (AGX_ROW_DIFF=1; =0 or unset: the 2-bit rows), parity-tested both ways in both upload forms.
+// Where the form does not apply (a raw reference, a stride beyond the codec's) or gains nothing, the unit's 2-bit rows cross tile-ordered.
 void stage_rows_tiled(agx_unit *u, unsigned threads) {
-    if (!u->tiled || !u->ref_packed || u->stride > AGX_ROW_MAXSTRIDE) return;
-    const char *env = getenv("AGX_ROW_DIFF");
+    if (!u->ref_packed || u->stride > AGX_ROW_MAXSTRIDE) return;
     const size_t n_pos = u->V.n_pos ? u->V.n_pos : u->T.ref.size();
-    if (!env || atoi(env) == 0) return;
     const double t0 = now_ms();
     RowDiffs D;
     if (!build_row_diffs(u->s_hits_t.p, u->nh, u->s_sides.p, u->n_sides, u->s_runs.p, u->n_runs, u->s_codes_t.p, u->nh, u->stride, (const agx_u32 *)u->s_ref.p, n_pos, threads, D, true)) return;
-    if (D.n_units * 2 + D.cnt.size() + (D.block_off.size() + D.block_first.size() + D.anchor_bits.size()) * 4 >= u->nh * (u->stride / 4)) return;      // nothing gained (reads that do not resemble the reference)
+    if (!row_diffs_gain(D, u->nh * (u->stride / 4))) return;
     adopt_row_diffs(u, D, threads);
     if (getenv("AGX_LOAD_TIMING")) fprintf(stderr, "[agx load] tile-ordered rows against the reference: %.1f ms, %zu rows (%zu as they are), %.1f -> %.1f bytes per row\n", now_ms() - t0, u->nh, u->n_rows_explicit,
-                                          (double)(u->stride / 4), (double)(u->n_units * 2 + u->n_rowcnt + (u->n_blockoff + u->n_blockfirst + u->n_anchor) * 4) / u->nh);
+                                          (double)(u->stride / 4), (double)row_diffs_bytes(D) / u->nh);
 }
 
 // The tail of staging, from the text (stage_inputs) and from the cache file (load_cache) alike, once the unit's view and its file-order arrays are there: the upload forms
-// of the rows and the hits, the landing room of a one-shot download; the unit is staged and nothing of an earlier upload counts any more.
+// of the rows and the hits by the unit's choice (DESIGN.md "Upload forms" has this as a table), the landing room of a one-shot download; the unit is staged and nothing of an
+// earlier upload counts any more.
 void finish_staging(agx_unit *u, unsigned threads_rows, unsigned threads) {
-    stage_rows(u, threads_rows);
-    stage_order(u, threads);
-    stage_tiled(u, threads);
-    if (!u->tiled) stage_wire_hits(u, threads);
+    clear_row_diffs(u);
+    if (u->choice.tiled && u->nh != 0 && u->n_rows != 0) {      // the tile-ordered forms, the hits packed inside the gather
+        stage_order(u, threads);
+        stage_tiled(u, threads);
+        if (u->choice.row_diff) stage_rows_tiled(u, threads);
+    } else {                                                    // the file-order forms, the hits packed over s_hits
+        release_tiled(u);
+        if (u->choice.row_diff) stage_rows(u, threads_rows);
+        stage_order(u, threads);
+        stage_wire_hits(u, threads);
+    }
     stage_wire_sides(u);
-    stage_rows_tiled(u, threads);
     u->V.slot_row = u->tiled ? u->slot_row.data() : nullptr;
     reserve_landing(u);
     u->staged = true; u->consumed = false; u->uploaded = false; u->built = false; u->downloaded = false;
 }
 
 void stage_inputs(agx_unit *u) {
+    u->choice = upload_choice();
     if (!u->have_ref || !u->have_threads) throw Error{E_ARG, "reference and contig threads must be set before upload"};
     // A one-shot unit's download lands in its staged buffers.  The general loader's pairs can be staged again from P; the fast loader wrote the hits, runs and
     // codes straight into those buffers and kept nothing else: after the download there is nothing to stage from, and clearing `consumed` would send the walk
@@ -607,13 +534,6 @@ void save_cache(agx_unit *u, const std::string &dir, int unit) {
     }
     ok = (close(fd) == 0) && ok;
     if (!ok || rename(part.c_str(), path.c_str()) != 0) { (void)remove(part.c_str()); throw Error{E_IO, "cannot write " + path}; }
-}
-
-// The staged read alignments in u->s_* (read from a cache file or a staged-pairs file) as the content rules look at them (agx_host.h: staged_pairs_rule).
-agx::StagedView staged_view(const agx_unit *u, unsigned long long n_rows, agx_u32 stride, agx_u32 maxlen, unsigned long long n_pos) {
-    agx::StagedView V; V.hits = u->s_hits.p; V.nh = u->nh; V.sides = u->s_sides.p; V.n_sides = u->n_sides; V.runs = u->s_runs.p; V.n_runs = u->n_runs; V.jump = u->s_jump.p; V.n_jump = u->n_jump;
-    V.other = u->s_other.p; V.n_other = u->n_other; V.n_rows = n_rows; V.stride = stride; V.maxlen = maxlen; V.n_pos = n_pos;
-    return V;
 }
 
 // A unit's read alignments out of tmp/_agx_pairs.<u>.bin (agx_host.h: pairsfile): the arrays into the pinned upload buffers, checked like a cache file's; the mapped file stays
@@ -791,29 +711,11 @@ void do_release(agx_unit *u);
 // Capacities of a unit's first build and the HBM they add up to (what do_upload reserves as one block; AlignGraph_amd admits a unit to a device by it:
 // agx_unit_hbm_needed).  From the staged counts: positions, hits, runs, conti-mers, read rows.
 struct Plan { agx_u32 pool_cap, list_cap, ovf_cap, sp_cap; size_t exact, total; };      // exact: what the five groups take; total: with the room to regrow in and the export's scratch
-// The read rows of windows [w_lo, w_hi) of a tile-ordered unit ((0, n_win): all of them), named ONCE for both sides of the upload: do_upload copies what a piece names and
-// records ev_rows[w]; the unit's first build expands the same piece into d_vcodes behind that event and records ev_win[w] (build_front).  File-order units have none.
-struct RowPiece { size_t r_lo, r_hi,      // the rows: those of the hits whose first tile lies in the windows (a tile's list also names hits that begin in earlier tiles: earlier pieces)
-    code_lo, code_hi,      // 2-bit rows: their bytes in s_codes_t / d_codes
-    cnt_lo, cnt_hi, blk_lo, blk_hi, unit_lo, unit_hi,      // rows as differences: count bytes (s_rowcnt / d_rowcnt), whole 64-row blocks (d_blockoff, d_blockfirst), their 16-bit units (s_units / d_units)
-    v_lo, v_hi, o_lo, o_hi; };      // the bases of d_vcodes they are expanded to; the listed bases among them: entries of s_other_t / d_other
+// The read rows of windows [w_lo, w_hi) of a tile-ordered unit ((0, n_win): all of them), named ONCE for both sides of the upload (agx_forms.h: row_piece): do_upload copies
+// what a piece names — bytes of s_codes_t / d_codes, or of s_rowcnt / s_units, entries of s_other_t / d_other — and records ev_rows[w]; the unit's first build expands the same
+// piece into d_vcodes behind that event and records ev_win[w] (build_front).  File-order units have none.
 RowPiece row_piece(const agx_unit *u, agx_u32 w_lo, agx_u32 w_hi) {
-    // a window's first row: the place in the tile order of the first hit of its first tile, rounded up to 16 rows — a piece then begins on a 16-byte boundary of the packed
-    // classes and on a multiple of 16 bases (agx_k_expand_codes takes 16 bases per thread) —, to 64 where the rows cross as differences (whole blocks of the stream); the few
-    // rows of the next window's hits that ride in this piece only arrive early
-    const size_t a = u->rows_diffed ? 63 : 15, s4 = u->stride / 4, nh = u->nh;
-    auto first_row = [&](agx_u32 w) { return w == 0 ? 0 : w >= u->n_win ? nh : std::min(nh, ((size_t)u->s_tfirst.p[u->win_tile[w]] + a) & ~a); };
-    const unsigned long long *ob = u->s_other_t.p, *oe = ob + u->n_other_t;
-    auto listed_at = [&](size_t row) { return (size_t)(std::lower_bound(ob, oe, (unsigned long long)row * u->stride) - ob); };
-    RowPiece p{}; p.r_lo = first_row(w_lo); p.r_hi = first_row(w_hi); p.o_lo = listed_at(p.r_lo); p.o_hi = listed_at(p.r_hi);
-    if (u->rows_diffed) {
-        p.blk_lo = p.r_lo / 64; p.blk_hi = (p.r_hi + 63) / 64; p.cnt_lo = p.r_lo; p.cnt_hi = std::min<size_t>(u->n_rowcnt, p.blk_hi * 64);
-        p.unit_lo = u->s_blockoff.p[p.blk_lo]; p.unit_hi = u->s_blockoff.p[p.blk_hi];
-    } else { p.code_lo = p.r_lo * s4; p.code_hi = p.r_hi * s4; }
-    // the piece that holds the LAST row — not always the last window's: a unit with few hits has windows without rows — is padded to whole 16-base groups like the whole array
-    // (r06's fuzz found the unpadded form: the last row's last bases stayed unexpanded where an earlier window already reached the last row)
-    p.v_lo = p.r_lo * s4 * 4; p.v_hi = p.r_hi == nh ? (codes_bytes(u) * 4 + 15) / 16 * 16 : p.r_hi * s4 * 4;
-    return p;
+    return row_piece(RowWindows{u->nh, u->stride, u->n_win, u->win_tile, u->s_tfirst.p, u->rows_diffed, u->n_rowcnt, u->s_blockoff.p, u->s_other_t.p, u->n_other_t}, w_lo, w_hi);
 }
 // Room behind the exact sum, in the same block: a group that proves too small on the device is taken again at its larger size, and while that fits here the unit stays
 // in ONE block — it holds no more HBM than it was admitted with, and agx_unit_trim can still give its tail back.  A 64th of the unit; the constant is what small units
@@ -1714,7 +1616,8 @@ int agx_unit_load_files_shared(agx_unit *u, const char *tmp_dir, int unit, const
     return guarded(u, [&] {
         const std::string d = tmp_dir, s = std::to_string(unit);
         u->stats.from_cache = 0;
-        if (load_cache(u, d, unit)) return;               // the unit's staged form, written when the alignments were distributed (agx_unit_cache_build)
+        u->choice = upload_choice();                      // (the loaders' buffers and the cache's staging follow it)
+        if (load_cache(u, d, unit)) return;              // the unit's staged form, written when the alignments were distributed (agx_unit_cache_build)
         const double t0 = now_ms();
         const bool fast = getenv("AGX_NO_FAST_LOAD") == nullptr;
         drop_outputs(u);

@@ -227,7 +227,7 @@ inline int walkers_for(size_t n) {
 struct ReadsIndex;
 enum { SA_HITS = 0, SA_SIDES, SA_RUNS, SA_CODES, SA_OTHER, SA_JUMP, SA_N };
 struct StageSink { virtual void *take(int which, size_t bytes) = 0; virtual ~StageSink() {} };      // where the staged arrays live (the engine: pinned memory)
-struct StagedPairs {        // what the upload wants of a unit's read alignments, in the wire formats of agx_core.h (agx_engine.cpp: stage)
+struct StagedPairs {        // what the upload wants of a unit's read alignments, in the wire formats of agx_core.h (agx_engine.cpp: staging; their upload forms: agx_forms.h)
     agx_whit *hits = nullptr; size_t nh = 0;             // row = ROW of the left mate's bases, AGX_WF_LEFT2 = which mate that is
     agx_wside *sides = nullptr; size_t n_sides = 0;      // one per hit with a multi-run mate
     agx_wrun *runs = nullptr; size_t n_runs = 0;

@@ -165,7 +165,7 @@ __global__ void __launch_bounds__(256) agx_k_patch_ref(const agx_refx *x, agx_u8
 }
 
 // ---- hit_prep: one thread per hit, hits in TILE order ------------------------------------------------------------------------------
-// Thread i takes hit perm[i]: the staging sorted the hits by the tile of their first arrival (stage_order, agx_engine.cpp; the SAM file's own order is random in
+// Thread i takes hit perm[i]: the staging sorted the hits by the tile of their first arrival (stage_order, agx_engine.cpp, and the gather into that order, gather_tiled, agx_forms.h; the SAM file's own order is random in
 // position).  Neighbouring lanes then want the same tiles: the histogram's device-scope atomics — the expensive part of binning on this chip (8 L2s: they are resolved
 // behind them) — collapse to one per run of equal tiles, and the derived records leave in the order the tile lists will read them.  r04 walked the hits in file order and
 // stored every (tile, hit) pair into a slot of the tile's own: 12.7 M scattered 4-byte stores per 30 Mb unit, 893 MB of write traffic for 250 MB of payload.

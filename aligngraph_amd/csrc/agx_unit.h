@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "agx_host.h"
+#include "agx_forms.h"
 #include "agx_mem.h"
 
 #include "agx_kargs.h"
@@ -112,6 +113,23 @@ struct UnitHelper {
     ~UnitHelper() { if (started) { { std::lock_guard<std::mutex> l(m); stop = true; } cv.notify_all(); th.join(); } }
 };
 
+// Which forms a unit's read alignments and its sequence cross PCIe in (agx_forms.h; DESIGN.md "Upload forms"), read from the environment ONCE per entry — where a unit's
+// files are loaded and where its inputs are staged — and kept in the unit: the loaders' buffers, the packers and the steps of finish_staging all see the same answer.
+//   tiled     tile-ordered records and rows (AGX_NO_TILED_UPLOAD, set at all: the file-order forms)
+//   row_diff  the read rows as differences from the reference (AGX_ROW_DIFF=1; it is NOT the default: agx_engine.cpp, stage_rows)
+//   compact   hit and side records in their compact wire forms (AGX_WIRE_PLAIN=1: the records as they are; A/B, tests)
+//   ref_raw   the unit sequence as its bytes (AGX_REF_RAW, set at all)
+//   windows   upload windows of the first build's sweep (AGX_UPLOAD_WINDOWS: tests); 0: by size
+struct UploadChoice { bool tiled = true, row_diff = false, compact = true, ref_raw = false; unsigned windows = 0; };
+inline UploadChoice upload_choice() {
+    UploadChoice c;
+    const char *diff = getenv("AGX_ROW_DIFF"), *plain = getenv("AGX_WIRE_PLAIN"), *win = getenv("AGX_UPLOAD_WINDOWS");
+    c.tiled = !getenv("AGX_NO_TILED_UPLOAD"); c.ref_raw = getenv("AGX_REF_RAW") != nullptr;
+    c.row_diff = diff && atoi(diff) != 0; c.compact = !(plain && atoi(plain) != 0);
+    c.windows = win ? std::max(1u, (unsigned)atoi(win)) : 0u;      // (a forced 0 was always one window)
+    return c;
+}
+
 // units of this process that are uploaded and not yet walked: the walk of the LAST one runs alone (the tail of a job) and may take every walker there is
 inline std::atomic<int> g_walks_pending{0};
 
@@ -120,6 +138,7 @@ inline std::atomic<int> g_walks_pending{0};
 struct agx_unit {
     agx_params prm{};
     std::string err;
+    UploadChoice choice;                // the upload forms this unit takes (read where its files are loaded and where its inputs are staged)
     Threads T; Pairs P;                 // what the loaders / the packed-array calls filled (empty when the unit came out of a cache file)
     UnitView V;                         // what everything downstream reads: into T / P, or into the mapped cache file
     size_t n_chain_str = 0;             // bytes behind V.chain_str (agx_unit_walk_graph hands them out)
@@ -144,9 +163,9 @@ struct agx_unit {
     PBuf<agx_whit> s_hits; PBuf<agx_wside> s_sides; PBuf<agx_wrun> s_runs; PBuf<agx_u8> s_codes; PBuf<unsigned long long> s_other; PBuf<agx_u32> s_jump; size_t n_other = 0, n_sides = 0, n_jump = 0;      // the read alignments in the wire formats of agx_core.h
     PBuf<agx_u8> s_ref; PBuf<agx_refx> s_refx; size_t n_refx = 0; bool ref_packed = false;      // the unit sequence: 2 bits per base + the stretches of other bytes (ref_packed), or the bytes as they are
     PBuf<agx_u32> s_chain_end, s_region_off; PBuf<agx_cmseg> s_segs; size_t n_segs = 0;
-    // r06, tile-ordered upload (stage_tiled): the wire records and the read rows in the order of the hits' first tiles — what the device is sent instead of s_hits / s_perm / s_codes / s_other
+    // r06, tile-ordered upload (stage_tiled; agx_forms.h: gather_tiled): the wire records and the read rows in the order of the hits' first tiles — what the device is sent instead of s_hits / s_perm / s_codes / s_other
     PBuf<agx_whit> s_hits_t; PBuf<agx_u8> s_codes_t; PBuf<unsigned long long> s_other_t; size_t n_other_t = 0; bool tiled = false; std::vector<agx_u32> slot_row;      // slot_row[i] = staged row of the i-th hit's left mate (the walk's k-mer tails)
-    // the hit and side records in their compact wire forms (agx_core.h; made at the end of staging: stage_wire_hits / stage_wire_sides).  hits_compact / sides_compact = false:
+    // the hit and side records in their compact wire forms (agx_core.h; made at the end of staging: stage_tiled or stage_wire_hits, stage_wire_sides; agx_forms.h).  hits_compact / sides_compact = false:
     // the unit sends the 16- and 12-byte records themselves (nothing gained, a run pool that is not in side order, AGX_WIRE_PLAIN=1)
     // s_wire: the hits' blocks, escapes and extra words in one pinned buffer of the records' size (or, tile-ordered with nothing gained, the records); s_csides: counts, then the listed sides
     PBuf<char> s_wire, s_csides; const agx_whit *wire_esc = nullptr; const agx_u32 *wire_ext = nullptr; const agx_cside_esc *wire_listed = nullptr; size_t n_cblocks = 0, n_cesc = 0, n_cext = 0, n_csesc = 0; agx_u32 side_first = 0; bool hits_compact = false, sides_compact = false;

@@ -7,7 +7,8 @@
 // and the header's counts, the value out of {0, 1, bound - 1, bound, bound + 1, all ones, a random word}.  Per mutant both doors' checks are applied.  A mutant that either
 // refuses is counted under the rule's name.  A mutant that both accept goes through everything that reads those arrays before and during a build, every array in a heap
 // block of its own of exactly the element count the engine gives its device buffer (agx_engine.cpp: fixed_bufs), so that an index past an array is a sanitizer report:
-//   * the host side: order_hits, the tile-ordered gather (the indexing of stage_tiled), the compact hit and side packers and their way back, build_row_diffs;
+//   * the host side: order_hits, the product's tile-ordered gather with the hits packed inside it (agx_forms.h: gather_tiled, HitPacker — what stage_tiled calls), the compact
+//     hit and side packers through tests/wire_shim.cpp and their way back, build_row_diffs;
 //   * the device's tables of the conti-mer runs the way its kernels fill them (agx_cm_layout_pos, agx_cm_fill_elem: agx_k_cm_fill's indexing) and the hop search over them;
 //   * the serial executor (tests/hostsim): hit preparation with the span guard of agx_k_hit_prep, tile lists, every arrival of every listed hit through agx_decode_arrival /
 //     agx_arrival_fetch (the vote-code and cm_head reads) inside the sweep's lane function, the edge lane functions, walk preparation, and the host walk with its k-mer tails.
@@ -132,31 +133,25 @@ void consume(const Arrays &M, const Base &B, agx_u32 k) {
     // ---- host: the tile order, the gather into it, the compact records, the rows against the reference
     Exact<agx_u32> perm(nh + 1), tile_first(n_tiles + 2), jump_at((size_t)c.n_jump + 1);
     order_hits(hits.get(), nh, sides.get(), runs.get(), jump.get(), (size_t)c.n_jump, n_pos, 2, perm.get(), tile_first.get(), jump_at.get());
-    Exact<agx_whit> hits_t(nh + 1); Exact<agx_u8> codes_t(nh * s4 + 16); Exact<agx_u32> slot_row(nh); std::vector<unsigned long long> others_t;
-    {   // (stage_tiled, agx_engine.cpp)
-        std::vector<agx_u8> has_other((n_rows + 7) / 8, 0);
-        for (size_t j = 0; j < c.n_other; j++) { const size_t r = (size_t)(other.get()[j] / c.stride); if (r < n_rows) has_other[r >> 3] |= (agx_u8)(1u << (r & 7)); }
-        const agx_whit *wh = hits.get(); const agx_wside *sd = sides.get(); const agx_wrun *wr = runs.get();
-        auto idx0 = [&](const agx_whit &w) -> agx_u32 { if (!(w.flags & AGX_WF_RUNS1)) return w.a; const agx_wside &g = sd[w.a]; const agx_wrun &r = wr[g.runs1]; return r.q == 0 ? r.t : AGX_NONE; };
-        for (size_t i = 0; i < nh; i++) {
-            const agx_u32 h = perm.get()[i]; agx_whit w = wh[h]; const agx_u32 row = w.row;
-            slot_row.get()[i] = row;
-            memcpy(codes_t.get() + i * s4, codes.get() + (size_t)row * s4, s4);
-            bool dup = false;
-            if (w.back) { const agx_u32 me = idx0(w); for (agx_u32 e = 1; e <= w.back && !dup; e++) dup = agx_absdiff(me, idx0(wh[h - e])) < (int)w.len; }
-            w.row = h; if (dup) w.flags |= (agx_u8)AGX_WF_DUP;
-            hits_t.get()[i] = w;
-            if (has_other[row >> 3] & (1u << (row & 7))) {
-                const unsigned long long lo = (unsigned long long)row * c.stride, *b = other.get(), *e = b + c.n_other;
-                for (const unsigned long long *at = std::lower_bound(b, e, lo); at != e && *at < lo + c.stride; ++at) others_t.push_back((unsigned long long)i * c.stride + (*at - lo));
-            }
-        }
+    Exact<agx_whit> hits_t(nh + 1); Exact<agx_u8> codes_t(nh * s4 + 16); Exact<agx_u32> slot_row(nh); Exact<char> wire((nh + 1) * sizeof(agx_whit));
+    HitWire fused{};      // what the packer inside the gather made, for the comparison below
+    {   // the product's gather with the hits packed inside it (agx_forms.h: gather_tiled, HitPacker), as stage_tiled runs it, into blocks of the engine's element counts
+        StagedView V; V.hits = hits.get(); V.nh = nh; V.sides = sides.get(); V.n_sides = (size_t)c.n_sides; V.runs = runs.get(); V.n_runs = (size_t)c.n_runs; V.other = other.get(); V.n_other = (size_t)c.n_other;
+        V.n_rows = c.n_rows; V.stride = c.stride; V.maxlen = c.maxlen; V.n_pos = c.n_pos;
+        HitPacker packer(nh, c.maxlen, 2, true);
+        if (packer.on) packer.into(wire.get());
+        (void)gather_tiled(V, codes.get(), perm.get(), 2, packer, hits_t.get(), codes_t.get(), slot_row.get());
+        fused = packer.finish();
     }
-    if (nh) {      // the compact records and the way back (HitPacker / stage_wire_sides; agx_k_expand_hits, agx_k_side_*)
+    if (nh) {      // the compact records and the way back (agx_forms.h: HitPacker, plan_sides / fill_sides; agx_k_expand_hits, agx_k_side_*)
         Exact<agx_chit_block> blocks(nh / 64 + 1); Exact<agx_whit> esc(nh + 1), back(nh + 1); Exact<uint32_t> ext(nh + 1); uint32_t counts[2];
-        agx_wire_pack_hits(hits_t.get(), (uint32_t)nh, c.maxlen, blocks.get(), esc.get(), ext.get(), counts);
+        agx_wire_pack_hits(hits_t.get(), (uint32_t)nh, c.maxlen, 2, blocks.get(), esc.get(), ext.get(), counts);
         agx_wire_unpack_hits(blocks.get(), (uint32_t)nh, c.maxlen, esc.get(), ext.get(), back.get());
         if (memcmp(back.get(), hits_t.get(), nh * sizeof(agx_whit)) != 0) throw Error{E_DEVICE, "compact hit records do not come back"};
+        // the blocks packed inside the gather (where they gained and were laid out) are the blocks packed over its finished array: both on two threads
+        if (fused.gain && (fused.n_esc != counts[0] || fused.n_ext != counts[1] || memcmp(wire.get(), blocks.get(), fused.n_blocks * sizeof(agx_chit_block)) != 0 ||
+                           memcmp(fused.esc, esc.get(), fused.n_esc * sizeof(agx_whit)) != 0 || memcmp(fused.ext, ext.get(), fused.n_ext * 4) != 0))
+            throw Error{E_DEVICE, "the blocks packed inside the gather differ from the blocks packed over its result"};
         const size_t ns = (size_t)c.n_sides;
         Exact<uint16_t> cc(ns + 4); Exact<agx_cside_esc> listed(ns + 1); Exact<agx_wside> sback(ns + 1); uint32_t n_listed = 0, first = 0;
         if (ns && agx_wire_pack_sides(sides.get(), (uint32_t)ns, cc.get(), listed.get(), &n_listed, &first)) {

@@ -5,6 +5,7 @@ that each case reaches what it is there for; the device runs the same cases in t
 import numpy as np
 import pytest
 
+import forms_shim
 import lean_units as LU
 import sweep_units as SU
 from conftest import graph_mismatch
@@ -66,5 +67,6 @@ def test_window_cases_have_deep_tiles_in_two_windows(swept, name):
     """The cases the device sweeps again under AGX_UPLOAD_WINDOWS=3: pass 0 fills mid_list from more than one launch."""
     ctx = swept(name)[4]
     n_tiles = len(ctx.tmax)
-    cuts = [n_tiles * w // 3 for w in range(4)]      # agx_engine.cpp: window w holds tiles n_tiles * w / W .. n_tiles * (w + 1) / W
+    cuts = [n_tiles * w // 3 for w in range(4)]      # window w holds tiles n_tiles * w / W .. n_tiles * (w + 1) / W: the model, held to the engine's own cuts (agx_forms.h)
+    assert forms_shim.window_cuts(n_tiles * 64, n_tiles, 3) == (3, cuts)
     assert sum(bool(((ctx.m["mid"] >= lo) & (ctx.m["mid"] < hi)).any()) for lo, hi in zip(cuts, cuts[1:])) >= 2

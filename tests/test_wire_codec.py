@@ -11,27 +11,17 @@ import subprocess
 import numpy as np
 import pytest
 
+import forms_shim
+from forms_shim import BLOCK, DUP, L, LEFT2, LISTED, REV1, REV2, RUNS1, RUNS2, WHIT, WSIDE, plain_hits  # noqa: F401  (the record types and hits shared with tests/test_stage_forms.py)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SHIM = os.path.join(HERE, "wire_shim.cpp")
-WHIT = np.dtype([("a", "<u4"), ("b", "<u4"), ("row", "<u4"), ("len", "<u2"), ("flags", "u1"), ("back", "u1")])
-WSIDE = np.dtype([("runs1", "<u4"), ("runs2", "<u4"), ("nruns", "<u4")])
-BLOCK = np.dtype([("base", "<u4"), ("esc", "<u4"), ("ext", "<u4"), ("pad", "<u4"), ("num", "<u4", 64), ("word", "<u4", 64)])
-LISTED = np.dtype([("side", "<u4"), ("nruns", "<u4")])
-REV1, REV2, LEFT2, RUNS1, RUNS2, DUP = 1, 2, 4, 8, 16, 32
-L = 150      # the unit's longest read in most cases
-P = ctypes.c_void_p
 
 
 @pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("wire_shim") / "libwire_shim.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared", "-o", so, SHIM])
-    lib = ctypes.CDLL(so)
-    lib.agx_wire_pack_hits.argtypes = [P, ctypes.c_uint32, ctypes.c_uint32, P, P, P, P]
-    lib.agx_wire_unpack_hits.argtypes = lib.agx_wire_unpack_hits_serial.argtypes = [P, ctypes.c_uint32, ctypes.c_uint32, P, P, P]
-    lib.agx_wire_pack_sides.argtypes = [P, ctypes.c_uint32, P, P, P, P]
-    lib.agx_wire_unpack_sides.argtypes = [P, ctypes.c_uint32, P, ctypes.c_uint32, ctypes.c_uint32, P]
-    return lib
+def shim():
+    return forms_shim.lib()      # (compiled alone with -Wall -Wextra -Werror; as a program of its own under the sanitizers: the last test)
+
 
 
 def hit(a, b, row=0, length=L, flags=0, back=0):
@@ -47,7 +37,7 @@ def round_trip(shim, hits, maxlen=L):
     n = len(hits)
     hits = np.ascontiguousarray(hits)
     blocks, esc, ext, counts = np.zeros(n // 64 + 1, BLOCK), np.zeros(n + 1, WHIT), np.zeros(n + 1, np.uint32), np.zeros(2, np.uint32)
-    shim.agx_wire_pack_hits(hits.ctypes.data, n, maxlen, blocks.ctypes.data, esc.ctypes.data, ext.ctypes.data, counts.ctypes.data)
+    shim.agx_wire_pack_hits(hits.ctypes.data, n, maxlen, 3, blocks.ctypes.data, esc.ctypes.data, ext.ctypes.data, counts.ctypes.data)      # (the product's packer, on three threads)
     for back in (shim.agx_wire_unpack_hits, shim.agx_wire_unpack_hits_serial):
         out = np.zeros(n + 1, WHIT)
         out[n] = (7, 7, 7, 7, 7, 7)
@@ -55,22 +45,6 @@ def round_trip(shim, hits, maxlen=L):
         assert out[:n].tobytes() == hits.tobytes()
         assert tuple(out[n]) == (7, 7, 7, 7, 7, 7), "a write behind the last record"
     return int(counts[0]), int(counts[1]), blocks
-
-
-def plain_hits(n, seed=1, start=50000):
-    """n hits as the loaders make them in tile order: positions that grow slowly, the other mate an insert size away, some with a side record."""
-    rnd = np.random.RandomState(seed)
-    h = np.zeros(n, WHIT)
-    at = start + np.cumsum(rnd.randint(0, 12, n)).astype(np.uint32)
-    flags = rnd.randint(0, 4, n) | (rnd.randint(0, 2, n) * DUP)
-    kind = rnd.randint(0, 8, n)      # 0: mate 1 has runs, 1: mate 2, 2: both
-    flags = flags | np.where(kind == 0, RUNS1, 0) | np.where(kind == 1, RUNS2, 0) | np.where(kind == 2, RUNS1 | RUNS2, 0)
-    side = rnd.randint(0, 1 << 31, n).astype(np.uint32)
-    other = at + 350 + rnd.randint(-40, 40, n).astype(np.uint32)
-    h["a"] = np.where(flags & RUNS1, side, at)
-    h["b"] = np.where(flags & RUNS2, np.where(flags & RUNS1, 0, side), other)
-    h["row"], h["len"], h["flags"] = rnd.randint(0, 1 << 32, n, dtype=np.uint64), L, flags
-    return h
 
 
 @pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 128, 129])
